@@ -2,7 +2,7 @@
 """bench.py -- the rModel draw path on MI355X: Mtris/s + ms/frame on the headline scene
 (1 000 000 triangles, 64 bones, 1920x1080; BASELINE.json `metric`).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one frame: clear (fused) -> geometry -> bin -> tile raster/shade -> framebuffer complete in
@@ -12,15 +12,17 @@ the 16x16-pixel bins over the ranks (bands of bin rows; a rank culls the geometr
 band) and exchanges colour with one all-gather.
 
 The timed region is EXACTLY `--steps` frames between two (barrier + synchronize) pairs, as the driver's
-contract says; it is repeated R = ceil(0.2 s / (steps x estimated frame time)) times and `ms_per_step` is
-the MEDIAN repetition (a 20-step region lasts 1 ms: one sample of it is mostly noise).
+contract says, after `--warmup` untimed frames; `ms_per_step` is its duration over `--steps`.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HBM-bound accounting, hipEvent
-timing on the library's own stream) and `cpu_baseline` (the CPU oracle -- kind "port": the
-reference has no CPU path at all -- on a bounded sample of the same workload, N = 1 only).  N > 1
-(or --configs) adds `configs`: BASELINE.json's multi-GPU configs C4 (128 instances, 3840x2160) and C5
-(1024 instances, 64 BC7 textures, 3840x2160) sharded over the N ranks, next to the same scene rendered
-unsharded in the same run, and efficiency = t1 / (N x tN).
+A plain run does only that and prints ONE JSON line (rank 0).  --dump-outputs DIR writes the framebuffer
+of the timed region's last frame as float32 .npy files (see dump_outputs).  --full adds everything else:
+the timed region repeated R = ceil(0.2 s / (steps x estimated frame time)) times (`repetitions`,
+`ms_per_step_median`), `latency`, `frame_stats`, `roofline` (dominant kernel, HBM-bound accounting,
+hipEvent timing on the library's own stream) and `cpu_baseline` (the CPU oracle -- kind "port": the
+reference has no CPU path at all -- on a bounded sample of the same workload, N = 1 only).  With --full,
+N > 1 (or --configs on) adds `configs`: BASELINE.json's multi-GPU configs C4 (128 instances, 3840x2160)
+and C5 (1024 instances, 64 BC7 textures, 3840x2160) sharded over the N ranks, next to the same scene
+rendered unsharded in the same run, and efficiency = t1 / (N x tN); --verify compares gathered frames.
 """
 import argparse
 import json
@@ -107,14 +109,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--verify", action="store_true", help="N > 1: compare every gathered frame (headline, C4, C5) with an unsharded render")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the framebuffer of the last timed frame to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: repeated timed regions, latency, "
+                         "roofline, CPU baseline, C4 / C5 configs, --verify")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline time budget")
+    ap.add_argument("--verify", action="store_true", help="--full, N > 1: compare every gathered frame (headline, C4, C5) with an unsharded render")
     ap.add_argument("--configs", choices=["auto", "on", "off"], default="auto",
-                    help="time BASELINE configs C4 / C5 too (auto: when N > 1, where they are defined)")
+                    help="--full: time BASELINE configs C4 / C5 too (auto: when N > 1, where they are defined)")
     ap.add_argument("--config-steps", type=int, default=100, help="frames per timed region of a C4 / C5 leg")
     ap.add_argument("--config-instances", type=int, default=0, help="rehearsals: C5 with this many instances instead of 1024 (C4: a quarter)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full and (args.verify or args.configs == "on"):
+        ap.error("--verify and --configs on belong to a --full run")
 
     # N > 1: more hardware queues than ROCm's default 4, so that the exchange (public stream + RCCL's stream) does not
     # share a queue with the library's three render streams; read by the HIP runtime when it starts, i.e. set it first
@@ -401,9 +412,8 @@ def main():
             ex.inline(fr)
             fr.close()
 
-    def time_leg(work, ex, shard_args, steps, warmup, ramp_frames, ramp_seconds, min_reps=1, budget_s=0.2):
-        """(ms per step: median repetition, every repetition's ms per step, repetitions).  A timed region = exactly `steps`
-        frames between two sync()s; max over the ranks per region."""
+    def warm_leg(work, ex, shard_args, warmup, ramp_frames, ramp_seconds):
+        """everything of a leg before its timed regions: (frame loop, estimated seconds per frame)"""
         loop = work.frame_loop(shard_args, ex is not None and ex.xthread)
         watchdog.arm(f"{work.name}: first frames + clock ramp", wd_seconds)
         # waited frames first: one that overflows the per-bin queue bound is re-run there and the bound doubles for the frames
@@ -426,18 +436,36 @@ def main():
                 n_ramp += 50
         sync(ex, f"{work.name} clock ramp")
         est = (time.perf_counter() - t_r0) / max(1, n_ramp)  # seconds per frame, roughly
+        watchdog.arm(f"{work.name}: warm-up", wd_seconds)
+        run_frames(work, ex, loop, warmup, shard_args)
+        sync(ex, f"{work.name} warm-up")
+        watchdog.disarm()
+        return loop, est
+
+    def auto_reps(steps, est, min_reps, budget_s):
+        """timed regions that fill about budget_s, the same count on every rank"""
         reps = max(min_reps, min(400, math.ceil(budget_s / max(1e-6, steps * est))))
-        if sharded:  # the same count on every rank
+        if sharded:
             t = torch.tensor([reps], dtype=torch.int32, device="cuda" if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             reps = int(t.item())
-        watchdog.arm(f"{work.name}: warm-up + {reps} timed regions of {steps} frames", wd_seconds)
-        run_frames(work, ex, loop, warmup, shard_args)
-        sync(ex, f"{work.name} warm-up")
-        dts = []
-        for _ in range(reps):
+        return reps
+
+    def timed_regions(work, ex, loop, shard_args, steps, reps, hold_last=False):
+        """(every region's ms per step, sorted; the held frame or None).  A timed region = exactly `steps` frames between
+        two sync()s; max over the ranks per region.  hold_last (unsharded): the last frame of the last region is issued
+        through api.Frame -- the same begin / draw / submit calls as the loop -- and returned submitted but not destroyed,
+        so that its framebuffer can be read once the clock has stopped (the caller closes it)."""
+        watchdog.arm(f"{work.name}: {reps} timed regions of {steps} frames", wd_seconds)
+        dts, held = [], None
+        for r in range(reps):
+            keep = hold_last and ex is None and r == reps - 1
             t0 = time.perf_counter()
-            run_frames(work, ex, loop, steps, shard_args)
+            run_frames(work, ex, loop, steps - 1 if keep else steps, shard_args)
+            if keep:
+                held = api.Frame(dev, work.w, work.h)
+                work.draw(held)
+                held.submit()
             fence(ex)  # barrier + synchronize: the end of the timed region
             dts.append(time.perf_counter() - t0)
             check(f"{work.name} timed region")
@@ -446,8 +474,33 @@ def main():
             t = torch.tensor(dts, dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dts = [float(v) for v in t.cpu()]
-        per_step = sorted(d * 1e3 / steps for d in dts)
-        return float(np.median(per_step)), per_step, reps
+        return sorted(d * 1e3 / steps for d in dts), held
+
+    def time_leg(work, ex, shard_args, steps, warmup, ramp_frames, ramp_seconds, min_reps=1, budget_s=0.2):
+        """(ms per step: median repetition, every repetition's ms per step, repetitions)"""
+        loop, est = warm_leg(work, ex, shard_args, warmup, ramp_frames, ramp_seconds)
+        per_step, _ = timed_regions(work, ex, loop, shard_args, steps, auto_reps(steps, est, min_reps, budget_s))
+        return float(np.median(per_step)), per_step, len(per_step)
+
+    def dump_outputs(out_dir, held, ex, w, h):
+        """What a caller of the timed path receives from its last frame, as float32 .npy: color.npy (h, w, 4) RGBA8 values and,
+        unsharded, depth.npy (h, w).  N > 1: the gathered colour buffer (depth is not exchanged).  Over 60 MB of pixels in all
+        (larger --width / --height: a dump stays under 64 MB), the same seeded sample of pixels from each array, in pixel order."""
+        if held is not None:
+            arrays = {"color": held.color(), "depth": held.depth()}
+        else:
+            torch.cuda.synchronize()
+            arrays = {"color": ex.final.cpu().numpy().reshape(h, w, 4)}
+        per_pixel = sum(a[0, 0].size for a in arrays.values()) * 4
+        keep = None
+        if w * h * per_pixel > 60_000_000:
+            keep = np.sort(np.random.default_rng(0).choice(w * h, 60_000_000 // per_pixel, replace=False))
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            a = a.astype(np.float32)
+            if keep is not None:
+                a = a.reshape((w * h,) + a.shape[2:])[keep]
+            np.save(os.path.join(out_dir, name + ".npy"), a)
 
     def verify_leg(work, ex):
         """the gathered frame(s) this rank holds == the same scene rendered unsharded on this rank, bit for bit"""
@@ -470,8 +523,19 @@ def main():
     ex = Exchange(headline, own) if sharded else None
     xthread = bool(ex and ex.xthread)
     lane2 = ex.lane2 if ex else None
-    ms_per_step, per_step, reps = time_leg(headline, ex, shard_args, args.steps, args.warmup,
-                                           (3000 if backend == "nccl" else 20) if sharded else 50, 0.3)
+    if args.dump_outputs and lane2 is not None:
+        sys.exit("bench.py: --dump-outputs takes one exchange lane (odd frames of a second lane land in a buffer of their own)")
+    loop, est = warm_leg(headline, ex, shard_args, args.warmup, (3000 if backend == "nccl" else 20) if sharded else 50, 0.3)
+    (ms_per_step,), held = timed_regions(headline, ex, loop, shard_args, args.steps, 1, hold_last=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, held, ex, W, H)
+    if held is not None:
+        held.close()
+    repeated = None
+    if args.full:  # the same region repeated for a spread: a 20-step region lasts 1 ms, one sample of it is mostly noise
+        per_step, _ = timed_regions(headline, ex, loop, shard_args, args.steps, auto_reps(args.steps, est, 1, 0.2))
+        repeated = {"repetitions": len(per_step), "ms_per_step_median": round(float(np.median(per_step)), 5),
+                    "ms_per_step_min_max": [round(per_step[0], 5), round(per_step[-1], 5)]}
     verified = {}
     if args.verify and sharded:
         verified["headline"] = verify_leg(headline, ex)
@@ -481,115 +545,116 @@ def main():
         ex.close()
     mtris = ntris / (ms_per_step * 1e-3) / 1e6
 
-    # ---- roofline: per-stage hipEvent timing on the library's streams, separate from the timed region ----
-    # (1) Same submission pattern as the timed region (frames in flight on the library's internal streams, nothing waited
-    # until several later frames are queued), with hipEvents around every kernel of every frame: the averages are the
-    # kernels' launch durations WHILE OVERLAPPING, which is what rocprofv3 --kernel-trace --stats reports for the
-    # same command (profiles/).  (2) The same kernels one frame at a time, nothing else on the GPU: 60 frames, of which
-    # the per-kernel stand-alone durations and the SURVEY 8(d) latency are the medians -- ms/frame from
-    # mtr_frame_begin (clear fused into the tile kernel) to the framebuffer complete in HBM, by the events that bracket
-    # the frame's first and last kernel, and by the host's clock around begin .. wait.
-    dev.set_profiling(True)
-    stage_ms = {k: 0.0 for k in api.STAGE_NAMES}
-    nprof = max(8, min(100, args.steps))
-    depth = 6
-    stats = None
-    inflight = []
+    roofline = latency = stats = None
+    if args.full:
+        # ---- roofline: per-stage hipEvent timing on the library's streams, separate from the timed region ----
+        # (1) Same submission pattern as the timed region (frames in flight on the library's internal streams, nothing waited
+        # until several later frames are queued), with hipEvents around every kernel of every frame: the averages are the
+        # kernels' launch durations WHILE OVERLAPPING, which is what rocprofv3 --kernel-trace --stats reports for the
+        # same command (profiles/).  (2) The same kernels one frame at a time, nothing else on the GPU: 60 frames, of which
+        # the per-kernel stand-alone durations and the SURVEY 8(d) latency are the medians -- ms/frame from
+        # mtr_frame_begin (clear fused into the tile kernel) to the framebuffer complete in HBM, by the events that bracket
+        # the frame's first and last kernel, and by the host's clock around begin .. wait.
+        dev.set_profiling(True)
+        stage_ms = {k: 0.0 for k in api.STAGE_NAMES}
+        nprof = max(8, min(100, args.steps))
+        depth = 6
+        inflight = []
 
-    def new_frame():
-        fr = api.Frame(dev, W, H)
-        if sharded:
-            fr.set_shard(*shard_args)
-        headline.draw(fr)
-        return fr
+        def new_frame():
+            fr = api.Frame(dev, W, H)
+            if sharded:
+                fr.set_shard(*shard_args)
+            headline.draw(fr)
+            return fr
 
-    def retire(fr):
-        nonlocal stats
-        fr.wait()
-        for k, v in fr.timings_ms().items():
-            stage_ms[k] += v / nprof
-        stats = fr.stats()
-        fr.close()
+        def retire(fr):
+            nonlocal stats
+            fr.wait()
+            for k, v in fr.timings_ms().items():
+                stage_ms[k] += v / nprof
+            stats = fr.stats()
+            fr.close()
 
-    for _ in range(nprof):
-        fr = new_frame()
-        fr.submit()
-        inflight.append(fr)
-        if len(inflight) > depth:
+        for _ in range(nprof):
+            fr = new_frame()
+            fr.submit()
+            inflight.append(fr)
+            if len(inflight) > depth:
+                retire(inflight.pop(0))
+        while inflight:
             retire(inflight.pop(0))
-    while inflight:
-        retire(inflight.pop(0))
-    serial = {k: [] for k in api.STAGE_NAMES}
-    lat_gpu, lat_host = [], []
-    for it in range(65):
-        t1 = time.perf_counter()
-        fr = new_frame()
-        fr.end()
-        t2 = time.perf_counter()
-        tm = fr.timings_ms()
-        fr.close()
-        if it >= 5:
-            for k, v in tm.items():
-                serial[k].append(v)
-            lat_gpu.append(sum(tm.values()))
-            lat_host.append((t2 - t1) * 1e3)
-    dev.set_profiling(False)
-    med = lambda xs: float(np.median(xs))
-    stage_ms_serial = {k: med(v) for k, v in serial.items()}
-    alg_frame, alg_geom, alg_tile = algorithmic_bytes(md, W, H, 1)
-    direct = stats["binning"] == 1
-    vis = stats["tile_kernel"] == 2
-    # kernel names as rocprofv3 prints them: k_geom<queue builder, culled launch, waves per SIMD it is built for (7: a draw of
-    # fewer than 65536 geometry waves)>, k_tile_vis<textured, waves per bin, order lists, quad walk>.  The timed region's frames
-    # share the GPU with their neighbours and run the <.., false> instantiation; a frame that has the GPU to itself (the latency
-    # figure, stage_ms_serial) runs <.., true>, which walks bboxes in 2 x 2 quads: shorter alone, slower among other kernels
-    vis_waves = 2 if stats["shard_bins"] > 4096 else (4 if stats["shard_bins"] > 1536 else 8)
-    names = {"geom": "k_geom<%d, %s, %d>" % (((2 if vis else 1) if direct else 0), "true" if sharded and own[0] != api.OWN_INTERLEAVED else "false",
-                                             7 if stats["chunks"] < 65536 else 8),
-             "scan": "k_scan", "fill": "k_fill", "tile": ("k_tile_vis<false, %d, false, false>" % vis_waves) if vis else "k_tile<false>"}
-    alg = {"geom": alg_geom, "tile": alg_tile}
-    traffic_by_kernel = pmc_traffic() if world == 1 else {}
-    kernels = {}
-    for st in ("geom", "tile"):
-        k = {"kernel": names[st], "algorithmic_bytes_per_launch": alg[st], "ms_overlapped": round(stage_ms[st], 5),
-             "ms_standalone": round(stage_ms_serial[st], 5), "traffic": traffic_by_kernel.get(names[st])}
-        if st == "tile" and vis:
-            k["kernel_standalone"] = "k_tile_vis<false, %d, false, true>" % vis_waves
-        k["frac_overlapped"] = round(alg[st] / (stage_ms[st] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-        k["frac_standalone"] = round(alg[st] / (stage_ms_serial[st] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-        kernels[st] = k
-    dom = max(("geom", "tile"), key=lambda k: stage_ms[k])
-    achieved = alg[dom] / (stage_ms[dom] * 1e-3) / 1e9
-    # achieved / frac: the dominant kernel's OWN algorithmic bytes over its average launch duration in the pipelined
-    # pattern of the timed region (what rocprofv3 --stats of this command reports); frac_standalone: the same bytes over
-    # the kernel's duration with nothing else on the GPU; `kernels` has both kernels; `frame_*`: the whole frame's
-    # algorithmic bytes over the measured ms_per_step
-    roofline = {"bound": "hbm", "kernel": names[dom], "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "frac_standalone": kernels[dom]["frac_standalone"],
-                "traffic": kernels[dom]["traffic"],
-                "algorithmic_bytes_per_launch": alg[dom], "kernel_ms": round(stage_ms[dom], 5), "kernel_ms_standalone": round(stage_ms_serial[dom], 5),
-                "note": "kernel_ms > ms_per_step is stream concurrency, not an inconsistency: three frames' kernels are co-resident "
-                        "on three streams, so a launch lasts longer than a step; frac uses that overlapped duration (what rocprofv3 "
-                        "--stats of this command reports), frac_standalone the kernel alone on the GPU (the visibility kernel then runs "
-                        "its quad-walk instantiation, kernels.tile.kernel_standalone)",
-                "kernels": kernels,
-                "stage_ms": {k: round(v, 5) for k, v in stage_ms.items()},
-                "stage_ms_serial": {k: round(v, 5) for k, v in stage_ms_serial.items()},
-                "frame_algorithmic_bytes": alg_frame,
-                "frame_gbps": round(alg_frame / (ms_per_step * 1e-3) / 1e9, 3),
-                "frame_frac": round(alg_frame / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                "residency_note": "the bench re-renders one frame whose ~80 MB of traffic fit the 256 MB Infinity Cache: `traffic` counts "
-                                  "fabric requests, not DRAM; FETCH_SIZE x2 (gfx950 correction for wide streaming reads) overstates 32-byte record gathers",
-                "traffic_source": ("profiles/pmc_traffic.json (kernel sources %s)" % kernel_source_hash()) if traffic_by_kernel else None}
-    if direct:  # single-pass binning: k_scan / k_fill are not launched at all
-        roofline["stage_note"] = "single-pass binning: no k_scan / k_fill launch (reported as 0)" + \
-                                 ("; sharded frames: the geom stage includes the culling kernels" if sharded else "")
-    latency = {"ms_per_frame_latency": round(med(lat_gpu), 5), "frames": len(lat_gpu), "definition": "SURVEY 8(d): one frame at a time, first kernel start to framebuffer complete in HBM (hipEvents on the frame's stream), median",
-               "ms_per_frame_latency_host_clock": round(med(lat_host), 5), "mtris_per_s_at_latency": round(ntris / (med(lat_gpu) * 1e-3) / 1e6, 2)}
+        serial = {k: [] for k in api.STAGE_NAMES}
+        lat_gpu, lat_host = [], []
+        for it in range(65):
+            t1 = time.perf_counter()
+            fr = new_frame()
+            fr.end()
+            t2 = time.perf_counter()
+            tm = fr.timings_ms()
+            fr.close()
+            if it >= 5:
+                for k, v in tm.items():
+                    serial[k].append(v)
+                lat_gpu.append(sum(tm.values()))
+                lat_host.append((t2 - t1) * 1e3)
+        dev.set_profiling(False)
+        med = lambda xs: float(np.median(xs))
+        stage_ms_serial = {k: med(v) for k, v in serial.items()}
+        alg_frame, alg_geom, alg_tile = algorithmic_bytes(md, W, H, 1)
+        direct = stats["binning"] == 1
+        vis = stats["tile_kernel"] == 2
+        # kernel names as rocprofv3 prints them: k_geom<queue builder, culled launch, waves per SIMD it is built for (7: a draw of
+        # fewer than 65536 geometry waves)>, k_tile_vis<textured, waves per bin, order lists, quad walk>.  The timed region's frames
+        # share the GPU with their neighbours and run the <.., false> instantiation; a frame that has the GPU to itself (the latency
+        # figure, stage_ms_serial) runs <.., true>, which walks bboxes in 2 x 2 quads: shorter alone, slower among other kernels
+        vis_waves = 2 if stats["shard_bins"] > 4096 else (4 if stats["shard_bins"] > 1536 else 8)
+        names = {"geom": "k_geom<%d, %s, %d>" % (((2 if vis else 1) if direct else 0), "true" if sharded and own[0] != api.OWN_INTERLEAVED else "false",
+                                                 7 if stats["chunks"] < 65536 else 8),
+                 "scan": "k_scan", "fill": "k_fill", "tile": ("k_tile_vis<false, %d, false, false>" % vis_waves) if vis else "k_tile<false>"}
+        alg = {"geom": alg_geom, "tile": alg_tile}
+        traffic_by_kernel = pmc_traffic() if world == 1 else {}
+        kernels = {}
+        for st in ("geom", "tile"):
+            k = {"kernel": names[st], "algorithmic_bytes_per_launch": alg[st], "ms_overlapped": round(stage_ms[st], 5),
+                 "ms_standalone": round(stage_ms_serial[st], 5), "traffic": traffic_by_kernel.get(names[st])}
+            if st == "tile" and vis:
+                k["kernel_standalone"] = "k_tile_vis<false, %d, false, true>" % vis_waves
+            k["frac_overlapped"] = round(alg[st] / (stage_ms[st] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+            k["frac_standalone"] = round(alg[st] / (stage_ms_serial[st] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+            kernels[st] = k
+        dom = max(("geom", "tile"), key=lambda k: stage_ms[k])
+        achieved = alg[dom] / (stage_ms[dom] * 1e-3) / 1e9
+        # achieved / frac: the dominant kernel's OWN algorithmic bytes over its average launch duration in the pipelined
+        # pattern of the timed region (what rocprofv3 --stats of this command reports); frac_standalone: the same bytes over
+        # the kernel's duration with nothing else on the GPU; `kernels` has both kernels; `frame_*`: the whole frame's
+        # algorithmic bytes over the measured ms_per_step
+        roofline = {"bound": "hbm", "kernel": names[dom], "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5), "frac_standalone": kernels[dom]["frac_standalone"],
+                    "traffic": kernels[dom]["traffic"],
+                    "algorithmic_bytes_per_launch": alg[dom], "kernel_ms": round(stage_ms[dom], 5), "kernel_ms_standalone": round(stage_ms_serial[dom], 5),
+                    "note": "kernel_ms > ms_per_step is stream concurrency, not an inconsistency: three frames' kernels are co-resident "
+                            "on three streams, so a launch lasts longer than a step; frac uses that overlapped duration (what rocprofv3 "
+                            "--stats of this command reports), frac_standalone the kernel alone on the GPU (the visibility kernel then runs "
+                            "its quad-walk instantiation, kernels.tile.kernel_standalone)",
+                    "kernels": kernels,
+                    "stage_ms": {k: round(v, 5) for k, v in stage_ms.items()},
+                    "stage_ms_serial": {k: round(v, 5) for k, v in stage_ms_serial.items()},
+                    "frame_algorithmic_bytes": alg_frame,
+                    "frame_gbps": round(alg_frame / (ms_per_step * 1e-3) / 1e9, 3),
+                    "frame_frac": round(alg_frame / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                    "residency_note": "the bench re-renders one frame whose ~80 MB of traffic fit the 256 MB Infinity Cache: `traffic` counts "
+                                      "fabric requests, not DRAM; FETCH_SIZE x2 (gfx950 correction for wide streaming reads) overstates 32-byte record gathers",
+                    "traffic_source": ("profiles/pmc_traffic.json (kernel sources %s)" % kernel_source_hash()) if traffic_by_kernel else None}
+        if direct:  # single-pass binning: k_scan / k_fill are not launched at all
+            roofline["stage_note"] = "single-pass binning: no k_scan / k_fill launch (reported as 0)" + \
+                                     ("; sharded frames: the geom stage includes the culling kernels" if sharded else "")
+        latency = {"ms_per_frame_latency": round(med(lat_gpu), 5), "frames": len(lat_gpu), "definition": "SURVEY 8(d): one frame at a time, first kernel start to framebuffer complete in HBM (hipEvents on the frame's stream), median",
+                   "ms_per_frame_latency_host_clock": round(med(lat_host), 5), "mtris_per_s_at_latency": round(ntris / (med(lat_gpu) * 1e-3) / 1e6, 2)}
 
     # ---- BASELINE configs C4 / C5: multi-GPU by definition ("sharded across 2/4/8 GPUs", "8 GPUs") ----
     configs = None
-    if args.configs == "on" or (args.configs == "auto" and sharded):
+    if args.full and (args.configs == "on" or (args.configs == "auto" and sharded)):
         configs = {}
         n5 = args.config_instances or 1024
         n4 = max(2, n5 // 8)
@@ -643,7 +708,7 @@ def main():
             configs["note"] = "rehearsal backend (gloo through host memory, every rank on one GPU): plumbing only, the times mean nothing"
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as orc
         om = orc.OracleModel(md)
         # the GPU box gives one-GPU jobs a 16-CPU share; more OpenMP threads than that only spin
@@ -667,8 +732,7 @@ def main():
         out = {
             "metric": "Mtris/sec, 1M-tri 64-bone skinned scene @1920x1080", "value": round(mtris, 2), "unit": "Mtris/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5),
-            "repetitions": reps, "ms_per_step_min_max": [round(per_step[0], 5), round(per_step[-1], 5)],
-            "ms_per_step_is": "the median of `repetitions` timed regions of exactly `steps` frames each (every region bracketed by barrier + synchronize)",
+            "ms_per_step_is": "one timed region of exactly `steps` frames (bracketed by barrier + synchronize) over `steps`",
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "headline: 20 x mesh50k primitives = 1,000,000 strip triangles, 506,520 vertices x 24 B, "
                                    "64-bone palette, debug-id shader, %dx%d" % (W, H),
@@ -676,10 +740,11 @@ def main():
                        "sharding": ({api.OWN_INTERLEAVED: "bins %% %d" % world, api.OWN_BANDS: "bands of bin rows %s over %d ranks, geometry culled per rank" % (list(map(int, own[2])) if own[2] is not None else "equal", world),
                                      api.OWN_SUPERTILES: "super-tiles of %d x %d bins over %d ranks, geometry culled per rank" % (1 << own[1], 1 << own[1], world)}[own[0]]) if sharded else "none",
                        "collective": ((("ncclAllGather (exchange thread, 2 lanes)" if lane2 is not None else "ncclAllGather (exchange thread)") if xthread else "ncclAllGather (ctypes)") if rc is not None else "torch.distributed all_gather_into_tensor") if sharded else "none"},
-            "value_is": "pipelined throughput: frames submitted back to back, three in flight on the library's streams; the per-frame latency is in `latency`",
-            "latency": latency,
-            "frame_stats": stats, "roofline": roofline, "cpu_baseline": cpu_baseline,
+            "value_is": "pipelined throughput: frames submitted back to back, three in flight on the library's streams; the per-frame latency is in `latency` (--full)",
         }
+        if args.full:
+            out.update(repeated)
+            out.update({"latency": latency, "frame_stats": stats, "roofline": roofline, "cpu_baseline": cpu_baseline})
         if configs is not None:
             out["configs"] = configs
         if verified:

@@ -10,7 +10,7 @@ if [ "$1" = build ]; then
 else
   for n in 4 5 6 7 8; do
     export MTR_LIB_PATH=$PWD/mt_renderer_amd/libmtr_gocc$n.so
-    echo "GEOM_OCC=$n $(python bench.py --steps 500 --warmup 50 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['roofline']['stage_ms_serial'], d['latency']['ms_per_frame_latency'])")"
+    echo "GEOM_OCC=$n $(python bench.py --full --steps 500 --warmup 50 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['roofline']['stage_ms_serial'], d['latency']['ms_per_frame_latency'])")"
     python tools/bench_configs.py "C3" 2>&1 | grep -v amdgpu | cut -c1-60; python tools/bench_configs.py "opaque" 2>&1 | grep -v amdgpu | cut -c1-60
   done
 fi

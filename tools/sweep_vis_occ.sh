@@ -10,7 +10,7 @@ if [ "$1" = build ]; then
 else
   for rep in 1 2; do for n in 4 5 6 7 8; do
     export MTR_LIB_PATH=$PWD/mt_renderer_amd/libmtr_vocc$n.so
-    echo "rep $rep VIS_OCC=$n $(python bench.py --steps 2000 --warmup 100 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['roofline']['stage_ms_serial'], d['latency']['ms_per_frame_latency'])")"
+    echo "rep $rep VIS_OCC=$n $(python bench.py --full --steps 2000 --warmup 100 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['roofline']['stage_ms_serial'], d['latency']['ms_per_frame_latency'])")"
   done; done
   for n in 4 5 6 7 8; do export MTR_LIB_PATH=$PWD/mt_renderer_amd/libmtr_vocc$n.so; echo "VIS_OCC=$n"; python tools/bench_configs.py "C" 2>&1 | grep -v amdgpu | cut -c1-70; done
 fi
