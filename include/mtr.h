@@ -177,6 +177,17 @@ int32_t mtr_model_set_prim_states(mtr_model *model, const mtr_prim_state *states
 int32_t mtr_model_set_parts_disp(mtr_model *model, const uint8_t *parts_disp, size_t n);
 /* bone palette for linear-blend skinning (build extension; n x 16 f32 column-major, n <= 256) */
 int32_t mtr_model_set_palette(mtr_model *model, const float *mats, size_t n);
+/* Skeletal poses (build extension, SPEC.md section 12): palettes formed on the GPU (k_pose) from one local matrix per joint,
+ *     world_j = local_j (parent 255 or j: a root), else world_parent(j) * local_j;   palette_j = world_j * imat_j
+ * bit for bit what mtr_rmodel_palette forms on the host.  mtr_model_create_from_files sets the file's skeleton (JointInfo
+ * parent bytes, imats) when it is valid.  Every call below that fails (no skeleton, njoints not the skeleton's, ...)
+ * returns MTR_E_INVALID and changes nothing: frames drawn afterwards render the previous state. */
+/* parents[j]: 255 or j = a root, else < njoints; no cycles; 1 <= njoints <= 256; imats njoints x 16.  parents == NULL
+ * clears it.  Set-up, not per frame: replacing a skeleton waits for the device. */
+int32_t mtr_model_set_skeleton(mtr_model *model, const uint8_t *parents, const float *imats, size_t njoints);
+/* palette formed on the GPU from a pose (njoints x 16, host memory, free on return); same frame semantics as
+ * mtr_model_set_palette */
+int32_t mtr_model_set_pose(mtr_model *model, const float *local_mats, size_t njoints);
 
 /* ---- instance batch ("scheduler" submission): n instances of one model, each
  * with its own model matrix and (optionally) palette and albedo override, resident in HBM ---- */
@@ -184,6 +195,23 @@ int32_t mtr_batch_create(mtr_device *dev, mtr_model *model, size_t n, const floa
                          const float *palettes /* n * npal * 16 or NULL */, size_t npal,
                          const int32_t *texture_override /* n entries or NULL */, mtr_batch **out);
 void mtr_batch_destroy(mtr_batch *batch);
+/* In-place updates.  A draw uses the matrices and palettes that were current when it was RECORDED, also when its frame is
+ * re-run after a bin-queue overflow; every update writes a fresh version of the batch's buffers (a small ring that grows
+ * only while frames hold every version: no allocation and no device-wide sync in steady state) and frames drawn afterwards
+ * wait for that write.  The instance count and texture overrides are fixed at creation. */
+/* new instance matrices (n x 16) and/or palettes (n x npal x 16, 1 <= npal <= 256) from host memory; NULL keeps that part */
+int32_t mtr_batch_update(mtr_batch *batch, const float *model_mats, const float *palettes, size_t npal);
+/* one pose per instance (n x njoints x 16 local matrices, host memory, free on return) through the model's skeleton;
+ * afterwards the batch has npal = njoints */
+int32_t mtr_batch_set_poses(mtr_batch *batch, const float *local_mats, size_t njoints);
+/* the same from device memory (16-byte aligned): k_pose reads local_mats_dev in stream order on hip_stream (NULL = the
+ * device's stream, which is NOT ordered with HIP's legacy null stream: a host whose work runs there passes a stream that
+ * waits for it, as api.py does for torch's default stream); frames drawn afterwards wait for it; the caller may overwrite
+ * the buffer with work queued later on that stream */
+int32_t mtr_batch_set_poses_device(mtr_batch *batch, const float *local_mats_dev, size_t njoints, void *hip_stream);
+/* test / debug hook: the batch's current palettes (n x npal x 16 floats; count = room in floats), after its pending
+ * update has completed */
+int32_t mtr_batch_read_palettes(mtr_batch *batch, float *out, size_t count);
 
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],

@@ -105,6 +105,9 @@ class Model {
         dev_.check(mtr_model_set_parts_disp(h_, parts_disp.data(), parts_disp.size()));
     }
     void set_palette(const float* mats, size_t n) { dev_.check(mtr_model_set_palette(h_, mats, n)); }
+    // skeletal poses (SPEC.md section 12): parents == nullptr clears the skeleton; set_pose forms the palette on the GPU
+    void set_skeleton(const uint8_t* parents, const float* imats, size_t njoints) { dev_.check(mtr_model_set_skeleton(h_, parents, imats, njoints)); }
+    void set_pose(const float* local_mats, size_t njoints) { dev_.check(mtr_model_set_pose(h_, local_mats, njoints)); }
     // the state objects a material names (src/rmaterial.rs:211-230), applied per primitive; default = src/model.rs:240-262
     void set_prim_states(const std::vector<mtr_prim_state>& states) { dev_.check(mtr_model_set_prim_states(h_, states.data(), states.size())); }
     // joint positions for the per-joint debug cubes of Model::render (src/model.rs:309-315)
@@ -117,6 +120,39 @@ class Model {
   private:
     const Device& dev_;
     mtr_model* h_ = nullptr;
+};
+
+// n instances of one model resident in HBM, updatable in place (frames use what was current when they were recorded)
+class Batch {
+  public:
+    Batch(const Device& dev, const Model& model, size_t n, const float* model_mats, const float* palettes = nullptr, size_t npal = 0,
+          const int32_t* texture_override = nullptr)
+        : dev_(dev), n_(n), npal_(palettes ? npal : 0) {
+        dev.check(mtr_batch_create(dev.handle(), model.handle(), n, model_mats, palettes, npal, texture_override, &h_));
+    }
+    Batch(const Batch&) = delete;
+    ~Batch() { mtr_batch_destroy(h_); }
+    // nullptr keeps that part
+    void update(const float* model_mats, const float* palettes = nullptr, size_t npal = 0) {
+        dev_.check(mtr_batch_update(h_, model_mats, palettes, npal));
+        if (palettes) npal_ = npal;
+    }
+    void set_poses(const float* local_mats, size_t njoints) { dev_.check(mtr_batch_set_poses(h_, local_mats, njoints)); npal_ = njoints; }
+    void set_poses_device(const float* local_mats_dev, size_t njoints, void* hip_stream = nullptr) {
+        dev_.check(mtr_batch_set_poses_device(h_, local_mats_dev, njoints, hip_stream));
+        npal_ = njoints;
+    }
+    std::vector<float> read_palettes() const {
+        std::vector<float> out(n_ * npal_ * 16);
+        dev_.check(mtr_batch_read_palettes(h_, out.data(), out.size()));
+        return out;
+    }
+    mtr_batch* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    size_t n_, npal_;
+    mtr_batch* h_ = nullptr;
 };
 
 class Frame {

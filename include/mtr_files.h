@@ -243,7 +243,8 @@ int32_t mtr_rarchive_extract(const mtr_rarchive_view *a, uint32_t i, void *out, 
  * albedo texture index -> textures[] (the caller loads rmaterial texture i into textures[i]; NULL = could not be
  * loaded, an error only if a primitive needs it: "no texture found!", src/model.rs:167), the debug id from the
  * primitive's boundary joint.  `mat` may be NULL (every primitive untextured).  The joints' offsets become the model's
- * joint positions (src/model.rs:283-291) for mtr_frame_draw_model_joints. */
+ * joint positions (src/model.rs:283-291) for mtr_frame_draw_model_joints; the JointInfo parents and imats become its
+ * skeleton (mtr_model_set_skeleton) when they form a valid one, otherwise the model has none. */
 int32_t mtr_model_create_from_files(mtr_device *dev, const mtr_rmodel_view *model, const mtr_rshader2 *sh,
                                     const mtr_rmaterial *mat, mtr_texture *const *textures, size_t ntextures,
                                     mtr_model **out);

@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = [
     "mtr_frame_unpack_color_shards_on_stream", "mtr_device_exchange_start", "mtr_device_exchange_add_lane", "mtr_frame_submit_exchange", "mtr_device_exchange_drain", "mtr_device_exchange_stop",
     "mtr_group_create", "mtr_group_destroy", "mtr_group_size", "mtr_group_device", "mtr_group_last_error", "mtr_group_frame_begin",
     "mtr_group_frame_part", "mtr_group_frame_end", "mtr_group_frame_read_color", "mtr_group_frame_color_devptr", "mtr_group_frame_destroy",
+    "mtr_model_set_skeleton", "mtr_model_set_pose", "mtr_batch_update", "mtr_batch_set_poses", "mtr_batch_set_poses_device",
+    "mtr_batch_read_palettes",
 ]
 
 
@@ -158,6 +160,12 @@ def _load() -> C.CDLL:
         "mtr_group_frame_read_color": (i32, [vp, vp, sz]),
         "mtr_group_frame_color_devptr": (vp, [vp]),
         "mtr_group_frame_destroy": (None, [vp]),
+        "mtr_model_set_skeleton": (i32, [vp, vp, vp, sz]),
+        "mtr_model_set_pose": (i32, [vp, vp, sz]),
+        "mtr_batch_update": (i32, [vp, vp, vp, sz]),
+        "mtr_batch_set_poses": (i32, [vp, vp, sz]),
+        "mtr_batch_set_poses_device": (i32, [vp, vp, sz, vp]),
+        "mtr_batch_read_palettes": (i32, [vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -197,6 +205,7 @@ class Device:
         if rc:
             raise MtrError(rc, (lib.mtr_last_error(None) or b"").decode())
         self._h = h
+        self.hip_device = hip_device
 
     def check(self, rc: int):
         if rc:
@@ -351,6 +360,26 @@ class Model:
             m = _f32(mats, (-1, 16))
             self.dev.check(lib.mtr_model_set_palette(self._h, _p(m), m.shape[0]))
 
+    def set_skeleton(self, parents: Optional[Sequence[int]], imats: Optional[np.ndarray] = None):
+        """skeleton for set_pose / Batch.set_poses (include/mtr.h): parents[j] = 255 or j for a root, else its parent;
+        imats [njoints, 16] inverse bind matrices.  None clears it."""
+        if parents is None:
+            self.dev.check(lib.mtr_model_set_skeleton(self._h, None, None, 0))
+            return
+        par = np.ascontiguousarray(parents, dtype=np.uint8)
+        im = _f32(imats, (-1, 16))
+        if im.shape[0] != par.size:
+            raise MtrError(MTR_E_INVALID, "one inverse bind matrix per joint")
+        n = par.size
+        if n == 0:  # not NULL (which clears the skeleton): the library rejects a skeleton of no joints
+            par, im = np.zeros(1, dtype=np.uint8), np.zeros((1, 16), dtype=np.float32)
+        self.dev.check(lib.mtr_model_set_skeleton(self._h, _p(par), _p(im), n))
+
+    def set_pose(self, local_mats: np.ndarray):
+        """palette formed on the GPU from one local matrix per joint of the skeleton ([njoints, 16])"""
+        lm = _f32(local_mats, (-1, 16))
+        self.dev.check(lib.mtr_model_set_pose(self._h, _p(lm), lm.shape[0]))
+
     def render(self, frame: "Frame", view_proj: np.ndarray, joints: bool = False):
         """Model::render(rpass, queue, transform_bind_group, debug_overlay) -- src/model.rs:299-305; the
         transform uniform (src/bin/modelviewer.rs:217-221) is passed directly.  joints: also the per-joint debug cubes the
@@ -383,6 +412,17 @@ class Model:
         self.textures = []
 
 
+_POSE_STREAMS = {}
+
+
+def _pose_stream(device):
+    """per device: the torch stream Batch.set_poses orders a pose on when the current stream is the legacy default one"""
+    import torch
+    if device.index not in _POSE_STREAMS:
+        _POSE_STREAMS[device.index] = torch.cuda.Stream(device)
+    return _POSE_STREAMS[device.index]
+
+
 class Batch:
     """n instances of one Model resident in HBM (the build's scheduler submission)."""
 
@@ -397,7 +437,57 @@ class Batch:
         to = None if texture_override is None else np.ascontiguousarray(texture_override, dtype=np.int32)
         h = C.c_void_p()
         dev.check(lib.mtr_batch_create(dev._h, model._h, n, _p(mm), _p(pal), npal, _p(to), C.byref(h)))
-        self.dev, self._h, self.n, self.model = dev, h, n, model
+        self.dev, self._h, self.n, self.model, self.npal = dev, h, n, model, npal
+
+    def update(self, model_mats: Optional[np.ndarray] = None, palettes: Optional[np.ndarray] = None):
+        """new instance matrices [n, 16] and / or palettes [n, npal, 16] for frames drawn afterwards; None keeps that part"""
+        mm = None if model_mats is None else _f32(model_mats, (self.n, 16))
+        pal, npal = None, 0
+        if palettes is not None:
+            pal = _f32(palettes).reshape(self.n, -1, 16)
+            npal = pal.shape[1]
+        self.dev.check(lib.mtr_batch_update(self._h, _p(mm), _p(pal), npal))
+        if pal is not None:
+            self.npal = npal
+
+    def set_poses(self, local_mats):
+        """one pose per instance, [n, njoints, 16] local matrices, through the model's skeleton (k_pose).  A numpy array is
+        copied in; a torch tensor on the batch's device is read in stream order on torch.cuda.current_stream()."""
+        if isinstance(local_mats, np.ndarray):
+            lm = _f32(local_mats).reshape(self.n, -1, 16)
+            self.dev.check(lib.mtr_batch_set_poses(self._h, _p(lm), lm.shape[1]))
+            self.npal = lm.shape[1]
+            return
+        import torch
+        t = local_mats
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise MtrError(MTR_E_INVALID, "set_poses: a numpy array or a float32 tensor on the GPU")
+        if t.get_device() != self.dev.hip_device:
+            raise MtrError(MTR_E_INVALID, f"set_poses: the tensor is on cuda:{t.get_device()}, the batch on cuda:{self.dev.hip_device}")
+        cur = torch.cuda.current_stream(t.device)
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            t = t.contiguous().clone()
+        nj = t.numel() // (self.n * 16)
+        if nj * self.n * 16 != t.numel():
+            raise MtrError(MTR_E_INVALID, "set_poses: n x njoints x 16 local matrices")
+        if cur.cuda_stream != 0:
+            self.dev.check(lib.mtr_batch_set_poses_device(self._h, C.c_void_p(t.data_ptr()), nj, C.c_void_p(cur.cuda_stream)))
+        else:
+            # torch's legacy default stream: its handle, 0, would name the device's own stream to the library (include/mtr.h),
+            # which is not ordered with it.  Run on a helper stream that follows the current one, and make the current one
+            # (and the allocator, for the input's block) wait for it.
+            side = _pose_stream(t.device)
+            side.wait_stream(cur)
+            self.dev.check(lib.mtr_batch_set_poses_device(self._h, C.c_void_p(t.data_ptr()), nj, C.c_void_p(side.cuda_stream)))
+            t.record_stream(side)
+            cur.wait_stream(side)
+        self.npal = nj
+
+    def read_palettes(self) -> np.ndarray:
+        """the batch's current palettes [n, npal, 16], after its pending update has completed"""
+        out = np.zeros((self.n, self.npal, 16), dtype=np.float32)
+        self.dev.check(lib.mtr_batch_read_palettes(self._h, _p(out), out.size))
+        return out
 
     def close(self):
         if self._h:
@@ -577,7 +667,7 @@ class Group:
         self.devices = []
         for r in range(lib.mtr_group_size(h)):
             d = Device.__new__(Device)
-            d._h, d._borrowed = C.c_void_p(lib.mtr_group_device(h, r)), True
+            d._h, d._borrowed, d.hip_device = C.c_void_p(lib.mtr_group_device(h, r)), True, int(ids[r])
             self.devices.append(d)
 
     def __len__(self):

@@ -19,6 +19,10 @@
 #include <utility>
 #include <vector>
 
+// k_pose.hip.  Weak: the host-only builds of this file (tests/cpp, over the HIP stub runtime) link no kernels and never
+// form a pose; libmtr.so links k_pose.o.
+void mtr_launch_pose(const PoseParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+
 namespace {
 
 thread_local std::string g_create_error = "";
@@ -110,8 +114,14 @@ struct mtr_device {
     hipEvent_t inflight[kMaxInflight] = {};
     uint32_t max_inflight = 16;
     uint64_t frames_submitted = 0;  // index of the next frame; frame i records inflight[i % max_inflight]
-    struct Garbage { void* p; uint64_t last_frame; };
-    std::vector<Garbage> garbage;   // device buffers of destroyed batches whose last frame may still be in flight
+    // device buffers of destroyed batches (and retired batch versions) whose last frame may still be in flight; ev, when
+    // set, is the last write into the buffer (a pose kernel or copy no frame has waited for), owned by the entry
+    struct Garbage { void* p; uint64_t last_frame; hipEvent_t ev = nullptr; };
+    std::vector<Garbage> garbage;
+    // host poses (mtr_model_set_pose, mtr_batch_set_poses): the local matrices are copied here on s_copy and read there by
+    // k_pose, so the stream orders every reuse; grown (after a sync of s_copy) only while the largest pose grows
+    float* pose_stage = nullptr;
+    size_t pose_stage_cap = 0;  // floats
     // Everything a frame submission touches (slots, the in-flight ring, frames_submitted, garbage, the models' chunk
     // tables and palette rings) is guarded by submit_mu: the render thread submits, but the exchange thread re-runs a
     // frame whose bin queues overflowed and destroys frames (which may own batches).  Uncontended in steady state.
@@ -232,6 +242,9 @@ struct mtr_model {
     DPrim* d_prims = nullptr;
     std::shared_ptr<const ChunkTable> table;  // for the current parts_disp; rebuilt by the next draw when chunks_dirty (submit_mu)
     float* d_palette = nullptr;   // the current palette: one buffer of pal_ring
+    // skeleton of mtr_model_set_skeleton (what k_pose needs): immutable once uploaded; replacing it waits for the device
+    struct Skeleton { uint32_t njoints = 0, path_bytes = 0; float* d = nullptr; /* imats (njoints * 16 f32), paths (njoints u32), path bytes */ };
+    Skeleton skel;
     uint32_t npal = 0;
     // mtr_model_set_palette does not wait for frames in flight: every call uploads into the next buffer of a ring
     // (max_inflight + 1 of them) on the copy stream and records an event; a frame captures pointer + event when the
@@ -273,11 +286,17 @@ struct mtr_batch {
     mtr_device* dev;
     mtr_model* model;
     uint32_t n = 0;
-    float* d_model_mats = nullptr;
-    float* d_palettes = nullptr;
-    uint32_t npal = 0;
+    // Versions of the instance data.  mtr_batch_create writes the first; every mtr_batch_update / _set_poses writes a fresh
+    // one (never the current one, nor one a frame may still read) and makes it current.  A draw records the current version
+    // and pins it until its frame can no longer (re-)run, like the model's palette ring; the ring grows while every version
+    // is held or in flight (up to max_inflight + 1 before it waits for a frame), so the steady state allocates nothing.
+    // d: n model matrices, then n * npal palette matrices (cap floats); ready: the last write into d (copy stream, or the
+    // caller's stream of mtr_batch_set_poses_device); frames that draw the version wait on it.
+    struct Ver { float* d = nullptr; size_t cap = 0; uint32_t npal = 0; hipEvent_t ready = nullptr; uint64_t last_frame = 0; bool used = false; uint32_t pinned = 0; };
+    std::vector<Ver> vers;
+    int cur = 0;
+    uint32_t refs = 1;           // the handle + every recorded draw (submit_mu): the last one parks the versions
     std::vector<int32_t> tex_override;
-    hipEvent_t ready = nullptr;  // the uploads (copy stream); frames that draw the batch wait on it
     uint64_t last_frame = 0;     // last frame that drew it: its buffers are freed only once that frame has left the GPU
     bool used = false;
     int hint_slot = -1;          // mtr_device::hint_host slot, or -1
@@ -303,6 +322,8 @@ struct Draw {
     uint32_t const_rgba8;
     bool blend;
     bool pal_pinned = false;  // holds a pin on the model's palette ring buffer pal_slot until the frame is submitted
+    int batch_ver = -1;       // version of `batch` the draw recorded, pinned while ver_pinned; the draw holds a batch ref
+    bool ver_pinned = false;
     std::unique_ptr<mtr_batch, BatchDeleter> owned_batch;
 };
 
@@ -829,7 +850,12 @@ void mtr_device_destroy(mtr_device* d) {
         if (sl.stream) (void)hipStreamSynchronize(sl.stream);
     for (hipEvent_t e : d->inflight)
         if (e) (void)hipEventDestroy(e);
-    for (auto& g : d->garbage) (void)hipFree(g.p);
+    for (auto& g : d->garbage) {
+        if (g.ev) { (void)hipEventSynchronize(g.ev); (void)hipEventDestroy(g.ev); }
+        if (g.p) (void)hipFree(g.p);
+    }
+    if (d->s_copy) (void)hipStreamSynchronize(d->s_copy);
+    if (d->pose_stage) (void)hipFree(d->pose_stage);
     if (d->s_copy) (void)hipStreamDestroy(d->s_copy);
     if (d->cube) mtr_model_destroy(d->cube);
     for (auto& t : d->own_tables) {
@@ -1109,7 +1135,8 @@ void mtr_model_destroy(mtr_model* m) {
         if (pb.d) (void)hipFree(pb.d);
         if (pb.ready) (void)hipEventDestroy(pb.ready);
     }
-    void* ptrs[] = {m->d_vbuf, m->d_ibuf, m->d_prims, m->d_boxes, m->d_inst_boxes};
+    if (m->skel.d) (void)hipDeviceSynchronize();  // a pose kernel on a caller's stream may still read the skeleton
+    void* ptrs[] = {m->d_vbuf, m->d_ibuf, m->d_prims, m->d_boxes, m->d_inst_boxes, m->skel.d};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete m;
@@ -1148,6 +1175,102 @@ int32_t mtr_model_set_parts_disp(mtr_model* m, const uint8_t* parts_disp, size_t
     return MTR_OK;
 }
 
+namespace {
+
+// The next buffer of the model's palette ring for an n-matrix palette, made current (see mtr_model::PalBuf).  submit_mu held.
+int32_t next_palette_buffer(mtr_model* m, size_t n, mtr_model::PalBuf** out) {
+    mtr_device* d = m->dev;
+    int32_t rc = MTR_OK;
+    if (m->pal_ring.size() < (size_t)d->max_inflight + 1)  // first use (the bound is fixed at device creation)
+        m->pal_ring.resize((size_t)d->max_inflight + 1);
+    size_t slot = m->pal_next++ % m->pal_ring.size();
+    for (size_t tries = 0; m->pal_ring[slot].pinned && tries < m->pal_ring.size(); tries++) slot = m->pal_next++ % m->pal_ring.size();
+    if (m->pal_ring[slot].pinned) {
+        // every buffer is held by a live frame that may still (re-)run: the host keeps more un-waited frames alive than
+        // the ring has buffers.  The ring grows by one (indices held by recorded draws stay valid).
+        if (m->pal_ring.size() >= 4096) return fail(d, MTR_E_NOMEM, "more than 4096 live frames hold a palette of this model");
+        m->pal_ring.emplace_back();
+        slot = m->pal_ring.size() - 1;
+    }
+    mtr_model::PalBuf& pb = m->pal_ring[slot];
+    // the last frame that read this buffer: finished for sure once max_inflight later frames have been submitted
+    if (pb.used && d->frames_submitted < pb.last_frame + 1 + d->max_inflight && d->inflight[pb.last_frame % d->max_inflight])
+        HIPCHK(d, hipEventSynchronize(d->inflight[pb.last_frame % d->max_inflight]));
+    if (pb.cap < n) {  // grow: nothing in flight may still read the old buffer
+        if ((rc = drain_all(d))) return rc;
+        if (pb.d) (void)hipFree(pb.d);
+        pb.d = nullptr; pb.cap = 0;
+        if ((rc = dev_alloc(d, &pb.d, std::max<size_t>(n, 64) * 16))) return rc;
+        pb.cap = (uint32_t)std::max<size_t>(n, 64);
+    }
+    if (!pb.ready) HIPCHK(d, hipEventCreateWithFlags(&pb.ready, hipEventDisableTiming));
+    m->npal = (uint32_t)n;
+    m->d_palette = pb.d;
+    m->pal_ready = pb.ready;
+    m->pal_slot = (int)slot;
+    *out = &pb;
+    return MTR_OK;
+}
+
+// The k_pose path table of a skeleton: paths[j] = offset | length << 16 of joint j's path in `bytes`, the joints from its
+// root down to j (a root's path is itself).  false: a parent out of range or a cycle.
+bool pose_paths(const uint8_t* parents, size_t n, std::vector<uint32_t>& paths, std::vector<uint8_t>& bytes) {
+    std::vector<uint8_t> state(n, 0);  // 0 new, 1 on the walk, 2 checked
+    for (size_t j0 = 0; j0 < n; j0++) {
+        std::vector<size_t> walk;
+        size_t j = j0;
+        while (state[j] != 2) {
+            if (state[j] == 1) return false;  // its own ancestor
+            state[j] = 1;
+            walk.push_back(j);
+            const uint32_t p = parents[j];
+            if (p == 255 || p == j) break;
+            if (p >= n) return false;
+            j = p;
+        }
+        for (size_t c : walk) state[c] = 2;
+    }
+    paths.assign(n, 0);
+    bytes.clear();
+    std::vector<uint8_t> up;
+    for (size_t j = 0; j < n; j++) {
+        up.clear();
+        for (size_t k = j;; k = parents[k]) {
+            up.push_back((uint8_t)k);
+            if (parents[k] == 255 || parents[k] == k) break;
+        }
+        paths[j] = (uint32_t)bytes.size() | ((uint32_t)up.size() << 16);
+        bytes.insert(bytes.end(), up.rbegin(), up.rend());
+    }
+    bytes.resize((bytes.size() + 3) & ~size_t(3), 0);
+    return true;
+}
+
+// host local matrices -> the device's staging buffer, on s_copy (the render thread only)
+int32_t stage_pose(mtr_device* d, const float* local_mats, size_t count) {
+    if (count > d->pose_stage_cap) {
+        HIPCHK(d, hipStreamSynchronize(d->s_copy));  // a queued pose kernel may still read the old buffer
+        if (d->pose_stage) (void)hipFree(d->pose_stage);
+        d->pose_stage = nullptr; d->pose_stage_cap = 0;
+        int32_t rc = dev_alloc(d, &d->pose_stage, count);
+        if (rc) return rc;
+        d->pose_stage_cap = count;
+    }
+    HIPCHK(d, hipMemcpyAsync(d->pose_stage, local_mats, count * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
+    return MTR_OK;
+}
+
+PoseParams pose_params(const mtr_model::Skeleton& sk, const float* locals, float* out) {
+    PoseParams pp{};
+    pp.locals = locals; pp.out = out; pp.imats = sk.d;
+    pp.paths = reinterpret_cast<const uint32_t*>(sk.d + (size_t)sk.njoints * 16);
+    pp.path_words = reinterpret_cast<const uint32_t*>(sk.d + (size_t)sk.njoints * 17);
+    pp.njoints = sk.njoints; pp.path_bytes = sk.path_bytes;
+    return pp;
+}
+
+}  // namespace
+
 int32_t mtr_model_set_palette(mtr_model* m, const float* mats, size_t n) {
     if (!m) return MTR_E_INVALID;
     mtr_device* d = m->dev;
@@ -1160,41 +1283,216 @@ int32_t mtr_model_set_palette(mtr_model* m, const float* mats, size_t n) {
     m->pal_ready = nullptr;
     m->pal_slot = -1;
     if (n) {
-        if (m->pal_ring.size() < (size_t)d->max_inflight + 1)  // first use (the bound is fixed at device creation)
-            m->pal_ring.resize((size_t)d->max_inflight + 1);
-        size_t slot = m->pal_next++ % m->pal_ring.size();
-        for (size_t tries = 0; m->pal_ring[slot].pinned && tries < m->pal_ring.size(); tries++) slot = m->pal_next++ % m->pal_ring.size();
-        if (m->pal_ring[slot].pinned) {
-            // every buffer is held by a live frame that may still (re-)run: the host keeps more un-waited frames alive than
-            // the ring has buffers.  The ring grows by one (indices held by recorded draws stay valid).
-            if (m->pal_ring.size() >= 4096) return fail(d, MTR_E_NOMEM, "more than 4096 live frames hold a palette of this model");
-            m->pal_ring.emplace_back();
-            slot = m->pal_ring.size() - 1;
-        }
-        mtr_model::PalBuf& pb = m->pal_ring[slot];
-        // the last frame that read this buffer: finished for sure once max_inflight later frames have been submitted
-        if (pb.used && d->frames_submitted < pb.last_frame + 1 + d->max_inflight && d->inflight[pb.last_frame % d->max_inflight])
-            HIPCHK(d, hipEventSynchronize(d->inflight[pb.last_frame % d->max_inflight]));
-        if (pb.cap < n) {  // grow: nothing in flight may still read the old buffer
-            if ((rc = drain_all(d))) return rc;
-            if (pb.d) (void)hipFree(pb.d);
-            pb.d = nullptr; pb.cap = 0;
-            if ((rc = dev_alloc(d, &pb.d, std::max<size_t>(n, 64) * 16))) return rc;
-            pb.cap = (uint32_t)std::max<size_t>(n, 64);
-        }
-        if (!pb.ready) HIPCHK(d, hipEventCreateWithFlags(&pb.ready, hipEventDisableTiming));
-        HIPCHK(d, hipMemcpyAsync(pb.d, mats, n * 64, hipMemcpyHostToDevice, d->s_copy));
-        HIPCHK(d, hipEventRecord(pb.ready, d->s_copy));
-        m->d_palette = pb.d;
-        m->pal_ready = pb.ready;
-        m->pal_slot = (int)slot;
+        mtr_model::PalBuf* pb = nullptr;
+        if ((rc = next_palette_buffer(m, n, &pb))) return rc;
+        HIPCHK(d, hipMemcpyAsync(pb->d, mats, n * 64, hipMemcpyHostToDevice, d->s_copy));
+        HIPCHK(d, hipEventRecord(pb->ready, d->s_copy));
     }
+    return MTR_OK;
+}
+
+int32_t mtr_model_set_skeleton(mtr_model* m, const uint8_t* parents, const float* imats, size_t njoints) {
+    if (!m) return MTR_E_INVALID;
+    mtr_device* d = m->dev;
+    mtr_model::Skeleton sk{};
+    if (parents) {
+        if (!imats || njoints == 0 || njoints > MTR_POSE_MAX_JOINTS) return fail(d, MTR_E_INVALID, "skeleton: 1 to 256 joints and their inverse bind matrices");
+        std::vector<uint32_t> paths;
+        std::vector<uint8_t> bytes;
+        if (!pose_paths(parents, njoints, paths, bytes)) return fail(d, MTR_E_INVALID, "skeleton: a parent out of range or a cycle");
+        int32_t rc = set_device(d);
+        if (rc) return rc;
+        std::vector<float> img(njoints * 17 + bytes.size() / 4);  // imats, the path table, the paths (bytes padded to words)
+        memcpy(img.data(), imats, njoints * 64);
+        memcpy(img.data() + njoints * 16, paths.data(), njoints * 4);
+        memcpy(img.data() + njoints * 17, bytes.data(), bytes.size());
+        sk.path_bytes = (uint32_t)bytes.size();
+        if ((rc = dev_alloc(d, &sk.d, img.size()))) return rc;
+        const hipError_t e = hipMemcpy(sk.d, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(sk.d); return fail(d, MTR_E_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
+        sk.njoints = (uint32_t)njoints;
+    }
+    mtr_model::Skeleton old;
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        old = m->skel;
+        m->skel = sk;
+    }
+    if (old.d) {  // a pose kernel (on s_copy or a caller's stream) may still read it; skeletons change at set-up, not per frame
+        (void)hipDeviceSynchronize();
+        (void)hipFree(old.d);
+    }
+    return MTR_OK;
+}
+
+int32_t mtr_model_set_pose(mtr_model* m, const float* local_mats, size_t njoints) {
+    if (!m) return MTR_E_INVALID;
+    mtr_device* d = m->dev;
+    if (!m->skel.d) return fail(d, MTR_E_INVALID, "pose: the model has no skeleton");
+    if (!local_mats || njoints != m->skel.njoints) return fail(d, MTR_E_INVALID, "pose: one local matrix per joint of the skeleton");
+    if (!mtr_launch_pose) return fail(d, MTR_E_UNSUPPORTED, "pose: built without k_pose");
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, local_mats, njoints * 16))) return rc;
+    std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+    mtr_model::PalBuf* pb = nullptr;
+    if ((rc = next_palette_buffer(m, njoints, &pb))) return rc;
+    mtr_launch_pose(pose_params(m->skel, d->pose_stage, pb->d), 1, d->s_copy);
+    HIPCHK(d, hipGetLastError());
+    HIPCHK(d, hipEventRecord(pb->ready, d->s_copy));
     return MTR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // instance batches
 // ---------------------------------------------------------------------------------------------
+namespace {
+
+// frame `f` has left the GPU (or certainly will have before anything queued after this call runs)
+bool frame_done(mtr_device* d, uint64_t f) {
+    if (d->frames_submitted >= f + 1 + d->max_inflight) return true;  // frame f + max_inflight waited for it
+    hipEvent_t e = d->inflight[f % d->max_inflight];
+    const bool done = !e || hipEventQuery(e) == hipSuccess;
+    (void)hipGetLastError();  // hipEventQuery reports "not ready" as an error code
+    return done;
+}
+
+// Buffers and events nobody can use any more, collected under submit_mu and released after it (release_now).
+struct FreeList {
+    std::vector<void*> bufs;
+    std::vector<hipEvent_t> events;
+};
+
+void release_now(FreeList& fl) {
+    for (void* p : fl.bufs) (void)hipFree(p);
+    for (hipEvent_t e : fl.events) (void)hipEventDestroy(e);
+    fl.bufs.clear();
+    fl.events.clear();
+}
+
+// Retires the buffer of a version nobody will draw again: into `now` (released after the lock) when no frame in flight
+// reads it and its last write has completed, otherwise -- or when now is nullptr -- parked in d->garbage with the event of
+// that write, collected by a later submit.  submit_mu held.
+void retire_version(mtr_device* d, mtr_batch::Ver& v, FreeList* now) {
+    if (v.d) {
+        const bool read_in_flight = v.used && !frame_done(d, v.last_frame);
+        bool written = true;
+        if (v.ready) { written = hipEventQuery(v.ready) == hipSuccess; (void)hipGetLastError(); }
+        if (read_in_flight || !written || !now) {
+            d->garbage.push_back({v.d, v.used ? v.last_frame : 0, v.ready});
+            v.ready = nullptr;
+        } else {
+            now->bufs.push_back(v.d);
+        }
+    }
+    if (v.ready) {
+        if (now) now->events.push_back(v.ready);
+        else d->garbage.push_back({nullptr, 0, v.ready});
+    }
+    v = mtr_batch::Ver{};
+}
+
+// drops one reference of the batch; the last one retires every version and frees the handle.  submit_mu held.
+void batch_unref(mtr_batch* b, FreeList& fl) {
+    if (--b->refs) return;
+    mtr_device* d = b->dev;
+    if (b->hint_slot >= 0) { d->hint_used[b->hint_slot] = false; d->hint_host[2 * b->hint_slot] = d->hint_host[2 * b->hint_slot + 1] = 0u; }
+    for (auto& v : b->vers) retire_version(d, v, &fl);
+    delete b;
+}
+
+// A version the next update may write: not the current one, held by no frame that may still (re-)run, and preferably read
+// by no frame still on the GPU.  Once the ring has max_inflight + 1 versions the one read longest ago is taken and
+// *frame_ev is the completion event of the frame that read it: the writing stream must wait on it.  A version too small
+// for npal palettes per instance is emptied (its buffer parked in d->garbage) for the caller to allocate.  No allocation,
+// free or host wait here.  submit_mu held.
+int32_t batch_next_version(mtr_batch* b, uint32_t npal, int* out, hipEvent_t* frame_ev) {
+    mtr_device* d = b->dev;
+    int pick = -1, oldest = -1;
+    *frame_ev = nullptr;
+    for (size_t i = 0; i < b->vers.size() && pick < 0; i++) {
+        const mtr_batch::Ver& v = b->vers[i];
+        if ((int)i == b->cur || v.pinned) continue;
+        if (!v.used || frame_done(d, v.last_frame)) pick = (int)i;
+        else if (oldest < 0 || v.last_frame < b->vers[(size_t)oldest].last_frame) oldest = (int)i;
+    }
+    if (pick < 0 && (oldest < 0 || b->vers.size() < (size_t)d->max_inflight + 1)) {
+        if (b->vers.size() >= 4096) return fail(d, MTR_E_NOMEM, "more than 4096 live frames hold a version of this batch");
+        b->vers.emplace_back();
+        pick = (int)b->vers.size() - 1;
+    }
+    if (pick < 0) {
+        // not done, so its frame is one of the last max_inflight: the ring event still holds that frame's record
+        pick = oldest;
+        *frame_ev = d->inflight[b->vers[(size_t)pick].last_frame % d->max_inflight];
+    }
+    mtr_batch::Ver& v = b->vers[(size_t)pick];
+    if (v.cap < (size_t)b->n * 16 * (1 + (size_t)npal)) retire_version(d, v, nullptr);
+    v.used = false; v.last_frame = 0;
+    *out = pick;
+    return MTR_OK;
+}
+
+// What an update writes into a fresh version.  mats / pals: host arrays, or nullptr = keep the current version's (device
+// copy); locals (device, k_pose input) replaces the palettes with the pose's.  Enqueued on `s`, the version made current.
+int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, uint32_t npal_new, const float* locals, hipStream_t s) {
+    mtr_device* d = b->dev;
+    const size_t n = b->n;
+    int vi = -1;
+    mtr_batch::Ver cur{}, v{};
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        cur = b->vers[(size_t)b->cur];
+        const uint32_t npal = (pals || locals) ? npal_new : cur.npal;
+        hipEvent_t frame_ev = nullptr;
+        int32_t rc = batch_next_version(b, npal, &vi, &frame_ev);
+        if (rc) return rc;
+        mtr_batch::Ver& nv = b->vers[(size_t)vi];
+        nv.npal = npal;
+        nv.pinned++;  // nobody else takes it while it is being written
+        v = nv;
+        // a frame still on the GPU reads it: the write waits for that frame on the device (the enqueue happens under the
+        // lock, before any later frame can record the same ring event)
+        if (frame_ev) {
+            const hipError_t e = hipStreamWaitEvent(s, frame_ev, 0);
+            if (e != hipSuccess) { nv.pinned--; return fail(d, MTR_E_HIP, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e)); }
+        }
+    }
+    // only this thread touches the version's buffer and event while it is pinned
+    int32_t rc = MTR_OK;
+    const size_t need = n * 16 * (1 + (size_t)v.npal);
+    if (!v.d) {
+        if (!(rc = dev_alloc(d, &v.d, need))) v.cap = need;
+    }
+    if (!rc && !v.ready && hipEventCreateWithFlags(&v.ready, hipEventDisableTiming) != hipSuccess) rc = fail(d, MTR_E_HIP, "hipEventCreate failed");
+    auto enqueue = [&]() -> int32_t {
+        HIPCHK(d, hipStreamWaitEvent(s, v.ready, 0));    // its previous write (a version may be rewritten before any draw)
+        if (cur.ready) HIPCHK(d, hipStreamWaitEvent(s, cur.ready, 0));
+        if (mats) HIPCHK(d, hipMemcpyAsync(v.d, mats, n * 64, hipMemcpyHostToDevice, s));
+        else HIPCHK(d, hipMemcpyAsync(v.d, cur.d, n * 64, hipMemcpyDeviceToDevice, s));
+        float* vp = v.d + n * 16;
+        if (locals) {
+            mtr_launch_pose(pose_params(b->model->skel, locals, vp), (uint32_t)n, s);
+            HIPCHK(d, hipGetLastError());
+        } else if (pals) {
+            HIPCHK(d, hipMemcpyAsync(vp, pals, n * v.npal * 64, hipMemcpyHostToDevice, s));
+        } else if (v.npal) {
+            HIPCHK(d, hipMemcpyAsync(vp, cur.d + n * 16, n * v.npal * 64, hipMemcpyDeviceToDevice, s));
+        }
+        HIPCHK(d, hipEventRecord(v.ready, s));
+        return MTR_OK;
+    };
+    if (!rc) rc = enqueue();
+    std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+    mtr_batch::Ver& nv = b->vers[(size_t)vi];
+    nv.d = v.d; nv.cap = v.cap; nv.ready = v.ready;
+    nv.pinned--;
+    if (!rc) b->cur = vi;
+    return rc;
+}
+
+}  // namespace
+
 int32_t mtr_batch_create(mtr_device* d, mtr_model* model, size_t n, const float* model_mats, const float* palettes,
                          size_t npal, const int32_t* texture_override, mtr_batch** out) {
     if (!d || !out) return MTR_E_INVALID;
@@ -1202,8 +1500,11 @@ int32_t mtr_batch_create(mtr_device* d, mtr_model* model, size_t n, const float*
     if (!model || model->dev != d || !model_mats || n == 0 || n > 0xFFFFu)
         return fail(d, MTR_E_INVALID, "bad batch arguments");
     if (npal > 256 || (npal && !palettes)) return fail(d, MTR_E_INVALID, "palette: at most 256 matrices");
-    auto b = std::make_unique<mtr_batch>();
-    b->dev = d; b->model = model; b->n = (uint32_t)n; b->npal = palettes ? (uint32_t)npal : 0;
+    auto b = std::unique_ptr<mtr_batch, BatchDeleter>(new mtr_batch());
+    b->dev = d; b->model = model; b->n = (uint32_t)n;
+    b->vers.emplace_back();
+    mtr_batch::Ver& v = b->vers[0];
+    v.npal = palettes ? (uint32_t)npal : 0;
     if (texture_override) {
         b->tex_override.assign(texture_override, texture_override + n);
         for (int32_t t : b->tex_override)
@@ -1211,15 +1512,13 @@ int32_t mtr_batch_create(mtr_device* d, mtr_model* model, size_t n, const float*
     }
     int32_t rc = set_device(d);
     if (rc) return rc;
-    if ((rc = dev_alloc(d, &b->d_model_mats, n * 16))) return rc;
+    v.cap = n * 16 * (1 + (size_t)v.npal);
+    if ((rc = dev_alloc(d, &v.d, v.cap))) return rc;
     // uploads go through the copy stream and an event: creating a batch does not wait for frames in flight
-    HIPCHK(d, hipMemcpyAsync(b->d_model_mats, model_mats, n * 64, hipMemcpyHostToDevice, d->s_copy));
-    if (b->npal) {
-        if ((rc = dev_alloc(d, &b->d_palettes, n * npal * 16))) return rc;
-        HIPCHK(d, hipMemcpyAsync(b->d_palettes, palettes, n * npal * 64, hipMemcpyHostToDevice, d->s_copy));
-    }
-    HIPCHK(d, hipEventCreateWithFlags(&b->ready, hipEventDisableTiming));
-    HIPCHK(d, hipEventRecord(b->ready, d->s_copy));
+    HIPCHK(d, hipMemcpyAsync(v.d, model_mats, n * 64, hipMemcpyHostToDevice, d->s_copy));
+    if (v.npal) HIPCHK(d, hipMemcpyAsync(v.d + n * 16, palettes, n * npal * 64, hipMemcpyHostToDevice, d->s_copy));
+    HIPCHK(d, hipEventCreateWithFlags(&v.ready, hipEventDisableTiming));
+    HIPCHK(d, hipEventRecord(v.ready, d->s_copy));
     *out = b.release();
     return MTR_OK;
 }
@@ -1228,19 +1527,72 @@ void mtr_batch_destroy(mtr_batch* b) {
     if (!b) return;
     mtr_device* d = b->dev;
     (void)hipSetDevice(d->hip_dev);
-    // a frame that drew the batch may still be in flight: park the buffers until that frame has left the GPU
-    // (collected at a later submit); otherwise free them now.  No stream is drained either way.  The exchange thread
-    // destroys the batches its frames own while the render thread submits: submit_mu guards the list and the index.
-    std::lock_guard<std::mutex> submit_lock(d->submit_mu);
-    const bool busy = b->used && d->frames_submitted <= b->last_frame + d->max_inflight;
-    if (b->hint_slot >= 0) { d->hint_used[b->hint_slot] = false; d->hint_host[2 * b->hint_slot] = d->hint_host[2 * b->hint_slot + 1] = 0u; }
-    for (void* p : {(void*)b->d_model_mats, (void*)b->d_palettes})
-        if (p) {
-            if (busy) d->garbage.push_back({p, b->last_frame});
-            else (void)hipFree(p);
-        }
-    if (b->ready) (void)hipEventDestroy(b->ready);
-    delete b;
+    // a frame that drew the batch may still be in flight, or be re-run: the versions its draws recorded stay until those
+    // frames are destroyed (their references), then they are parked until that frame has left the GPU (collected at a
+    // later submit), as is a version a pose kernel or copy may still be writing.  No stream is drained either way.  The
+    // exchange thread destroys the batches its frames own while the render thread submits: submit_mu guards the list.
+    FreeList fl;
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        batch_unref(b, fl);
+    }
+    release_now(fl);
+}
+
+int32_t mtr_batch_update(mtr_batch* b, const float* model_mats, const float* palettes, size_t npal) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (palettes && (npal == 0 || npal > 256)) return fail(d, MTR_E_INVALID, "batch update: 1 to 256 palette matrices per instance");
+    if (!model_mats && !palettes) return MTR_OK;
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    return batch_write_version(b, model_mats, palettes, (uint32_t)npal, nullptr, d->s_copy);
+}
+
+static int32_t check_batch_pose(mtr_batch* b, size_t njoints) {
+    mtr_device* d = b->dev;
+    if (!b->model->skel.d) return fail(d, MTR_E_INVALID, "pose: the batch's model has no skeleton");
+    if (njoints != b->model->skel.njoints) return fail(d, MTR_E_INVALID, "pose: one local matrix per joint of the skeleton");
+    if (!mtr_launch_pose) return fail(d, MTR_E_UNSUPPORTED, "pose: built without k_pose");
+    return set_device(d);
+}
+
+int32_t mtr_batch_set_poses(mtr_batch* b, const float* local_mats, size_t njoints) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!local_mats) return fail(d, MTR_E_INVALID, "pose: no local matrices");
+    int32_t rc = check_batch_pose(b, njoints);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, local_mats, (size_t)b->n * njoints * 16))) return rc;
+    return batch_write_version(b, nullptr, nullptr, (uint32_t)njoints, d->pose_stage, d->s_copy);
+}
+
+int32_t mtr_batch_set_poses_device(mtr_batch* b, const float* local_mats_dev, size_t njoints, void* hip_stream) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!local_mats_dev || ((uintptr_t)local_mats_dev & 15u)) return fail(d, MTR_E_INVALID, "pose: device matrices must be 16-byte aligned");
+    int32_t rc = check_batch_pose(b, njoints);
+    if (rc) return rc;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    return batch_write_version(b, nullptr, nullptr, (uint32_t)njoints, local_mats_dev, s);
+}
+
+int32_t mtr_batch_read_palettes(mtr_batch* b, float* out, size_t count) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    mtr_batch::Ver v{};
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        v = b->vers[(size_t)b->cur];
+    }
+    const size_t need = (size_t)b->n * v.npal * 16;
+    if ((!out && need) || count < need) return fail(d, MTR_E_INVALID, "read_palettes: room for n * npal * 16 floats needed");
+    int32_t rc = set_device(d);
+    if (rc || !need) return rc;
+    HIPCHK(d, hipStreamWaitEvent(d->s_copy, v.ready, 0));
+    HIPCHK(d, hipMemcpyAsync(out, v.d + (size_t)b->n * 16, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
+    HIPCHK(d, hipStreamSynchronize(d->s_copy));
+    return MTR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1326,8 +1678,14 @@ void mtr_frame_destroy(mtr_frame* f) {
         const_cast<OwnTable*>(f->own)->refs--;
     }
     {
-        std::lock_guard<std::mutex> g(d->submit_mu);
-        release_palette_pins(f);  // drawn and never submitted, or submitted and never waited for
+        FreeList fl;
+        {
+            std::lock_guard<std::mutex> g(d->submit_mu);
+            release_palette_pins(f);  // drawn and never submitted, or submitted and never waited for
+            for (Draw& dr : f->draws)
+                if (dr.batch) { batch_unref(dr.batch, fl); dr.batch = nullptr; }  // the batch may have been destroyed since
+        }
+        release_now(fl);
     }
     if (f->submitted && !f->flags_checked && f->status_idx >= 0) {
         // nobody looked at this frame's overflow flags: they are examined when its status word is polled or recycled,
@@ -1422,11 +1780,21 @@ int32_t mtr_frame_draw_batch(mtr_frame* f, mtr_batch* b, const float view_proj[1
     if (rc) return rc;
     Draw dr{};
     dr.table = std::move(table);
-    dr.model = b->model; dr.d_model_mats = b->d_model_mats; dr.batch = b; dr.pal_ready = b->ready; dr.pal_slot = -1;
-    dr.d_palettes = b->npal ? b->d_palettes : nullptr;
-    dr.npal = b->npal; dr.pal_stride = b->npal * 16; dr.ninst = b->n;
+    dr.model = b->model; dr.batch = b; dr.pal_slot = -1; dr.ninst = b->n;
     dr.tex_override = b->tex_override; dr.shader_override = -1; dr.blend = true;
     memcpy(dr.vp, view_proj, sizeof dr.vp);
+    {
+        // the draw uses the version that is current now, whatever later updates write, for as long as its frame may run
+        std::lock_guard<std::mutex> submit_lock(f->dev->submit_mu);
+        mtr_batch::Ver& v = b->vers[(size_t)b->cur];
+        dr.d_model_mats = v.d; dr.pal_ready = v.ready;
+        dr.d_palettes = v.npal ? v.d + (size_t)b->n * 16 : nullptr;
+        dr.npal = v.npal; dr.pal_stride = v.npal * 16;
+        dr.batch_ver = b->cur;
+        v.pinned++;
+        dr.ver_pinned = true;
+        b->refs++;
+    }
     f->draws.push_back(std::move(dr));
     return MTR_OK;
 }
@@ -1497,13 +1865,18 @@ int32_t mtr_frame_draw_overlay_cubes(mtr_frame* f, const float camera[16], const
     return MTR_OK;
 }
 
-// the frame can no longer (re-)run: its draws let go of the palette ring buffers they hold.  submit_mu held.
+// the frame can no longer (re-)run: its draws let go of the palette ring buffers and batch versions they hold.  submit_mu held.
 static void release_palette_pins(mtr_frame* f) {
-    for (Draw& dr : f->draws)
+    for (Draw& dr : f->draws) {
         if (dr.pal_pinned && dr.pal_slot >= 0 && (size_t)dr.pal_slot < dr.model->pal_ring.size()) {
             dr.model->pal_ring[(size_t)dr.pal_slot].pinned--;
             dr.pal_pinned = false;
         }
+        if (dr.ver_pinned && dr.batch) {
+            dr.batch->vers[(size_t)dr.batch_ver].pinned--;
+            dr.ver_pinned = false;
+        }
+    }
 }
 
 // Enqueues every kernel of the frame.  The caller holds d->submit_mu.
@@ -1538,9 +1911,14 @@ static int32_t run_frame(mtr_frame* f) {
     if (!d->garbage.empty()) {
         size_t keep = 0;
         for (auto& g : d->garbage) {
-            if (g.last_frame + d->max_inflight <= this_frame) (void)hipFree(g.p);
-            else d->garbage[keep++] = g;
+            if (g.last_frame + d->max_inflight <= this_frame && (!g.ev || hipEventQuery(g.ev) == hipSuccess)) {
+                if (g.ev) (void)hipEventDestroy(g.ev);
+                if (g.p) (void)hipFree(g.p);
+            } else {
+                d->garbage[keep++] = g;
+            }
         }
+        (void)hipGetLastError();  // hipEventQuery reports "not ready" as an error code
         d->garbage.resize(keep);
     }
     f->slot = (int)(d->frame_counter++ % d->nslots);
@@ -1758,7 +2136,11 @@ static int32_t run_frame(mtr_frame* f) {
         gp.vbuf = m->d_vbuf; gp.ibuf = m->d_ibuf; gp.prims = m->d_prims; gp.chunks = dr.table->d_chunks;
         gp.boxes = m->d_boxes;
         gp.nchunks = (uint32_t)dr.table->chunks.size(); gp.ninst = dr.ninst;
-        if (dr.batch) { dr.batch->last_frame = this_frame; dr.batch->used = true; }
+        if (dr.batch) {
+            dr.batch->last_frame = this_frame; dr.batch->used = true;
+            mtr_batch::Ver& v = dr.batch->vers[(size_t)dr.batch_ver];
+            v.last_frame = this_frame; v.used = true;  // protects the version while this run's kernels are in flight
+        }
         if (dr.pal_ready) {  // uploads of a model palette (ring) or of a batch, made on the copy stream
             HIPCHK(d, hipStreamWaitEvent(sg, dr.pal_ready, 0));
             if (dr.pal_slot >= 0 && (size_t)dr.pal_slot < m->pal_ring.size()) {

@@ -796,6 +796,10 @@ int32_t mtr_rscheduler_apply(const mtr_rscheduler* s, uint32_t frame, const mtr_
     return MTR_OK;
 }
 
+// mtr_api.cpp.  Weak: the parser fuzz build (tests/cpp/files_fuzz.cpp) compiles this file alone, with stand-ins for the few
+// entry points of mtr.h it calls; libmtr.so always has it.
+extern "C" int32_t mtr_model_set_skeleton(mtr_model* model, const uint8_t* parents, const float* imats, size_t njoints) __attribute__((weak));
+
 // -------------------------------------------------------------------------------------------- skin palette
 int32_t mtr_rmodel_joint_index(const mtr_rmodel_view* m, uint32_t no) {
     if (!m || !m->joint_table || no > 255) return -1;
@@ -957,6 +961,17 @@ int32_t mtr_model_create_from_files(mtr_device* dev, const mtr_rmodel_view* mode
             mtr_rmodel_joint(model, j, &no, &parent, &sym, &pos[(size_t)j * 3]);
         }
         mtr_model_set_joint_positions(*out, pos.data(), model->jnt_num);
+        if (model->imats && model->jnt_num <= 256) {  // the skeleton of mtr_model_set_pose; an invalid one is left unset
+            std::vector<uint8_t> parents(model->jnt_num);
+            std::vector<float> imats((size_t)model->jnt_num * 16);
+            memcpy(imats.data(), model->imats, imats.size() * 4);  // the file's array may be unaligned
+            for (uint32_t j = 0; j < model->jnt_num; j++) {
+                uint32_t no, parent, sym;
+                mtr_rmodel_joint(model, j, &no, &parent, &sym, nullptr);
+                parents[j] = (uint8_t)parent;
+            }
+            if (mtr_model_set_skeleton) (void)mtr_model_set_skeleton(*out, parents.data(), imats.data(), model->jnt_num);
+        }
     }
     return rc;
 }

@@ -400,3 +400,15 @@ struct ChunkCullParams {
     uint32_t keep_all;           // timing ablation (MTR_CULL_DEBUG=3): run the tests, keep everything
 };
 void mtr_launch_cull_chunks(const ChunkCullParams& p, hipStream_t s);
+// skin palettes from skeletal poses (k_pose.hip): out[inst][j] = world_j * imat_j for ninst instances of njoints joints
+#define MTR_POSE_MAX_JOINTS 256
+#define MTR_POSE_MAX_PATH_BYTES (MTR_POSE_MAX_JOINTS * (MTR_POSE_MAX_JOINTS + 1) / 2)  // a 256-deep chain
+struct PoseParams {
+    const float* locals;        // ninst * njoints * 16, 16-byte aligned
+    float* out;                 // ninst * njoints * 16, 16-byte aligned
+    const float* imats;         // njoints * 16
+    const uint32_t* paths;      // njoints: offset of joint j's path in path_words (bytes) | its length << 16
+    const uint32_t* path_words; // path_bytes / 4 words of joint ids: each path from its root down to the joint itself
+    uint32_t njoints, path_bytes;
+};
+void mtr_launch_pose(const PoseParams& p, uint32_t ninst, hipStream_t s);

@@ -206,6 +206,13 @@ class ModelFile:
     def imats(self) -> np.ndarray:
         return self._arr(self.v.imats, self.v.jnt_num * 64, np.float32).reshape(-1, 16)
 
+    def skeleton(self):
+        """(parents uint8 [jnt_num], imats f32 [jnt_num, 16]): the JointInfo parent bytes and inverse bind matrices, what
+        Model.set_skeleton takes (model_from_files sets them when they are valid)"""
+        n = self.v.jnt_num
+        parents = np.array([self.joint(j)["parent"] for j in range(n)], dtype=np.uint8)
+        return parents, self.imats().copy()
+
     def palette(self, local_mats: Optional[np.ndarray] = None) -> np.ndarray:
         """skin palette of the skeleton (include/mtr_files.h: mtr_rmodel_palette): [jnt_num, 16] f32 for Model.set_palette;
         local_mats None = the file's bind pose"""

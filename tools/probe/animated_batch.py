@@ -1,0 +1,88 @@
+"""Animated instance batches: ms per frame for C3 (128 instances of mesh50k, 1080p) and a C5-size batch (1 024 instances x
+64 joints, 4K, untextured), each static, with host poses before every frame (Batch.set_poses(numpy): copy + k_pose on the
+copy stream) and with device poses before every frame (Batch.set_poses(torch tensor): k_pose on torch's current stream).
+Frames are submitted without waiting, through api.FrameLoop; a timed region is `--frames` frames bracketed by a device
+synchronise, repeated `--reps` times per mode with the modes alternating, and the median is reported.
+Extra modes: device_side_stream (device poses from a non-default torch stream), poses_only (device poses, no frames).
+    python tools/probe/animated_batch.py [--only c3|c5] [--frames N] [--reps R] [--modes static,host,device] [--json OUT]"""
+import argparse, json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import numpy as np
+import torch
+from mt_renderer_amd import api, scene
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--only", default="")
+ap.add_argument("--frames", type=int, default=300)
+ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--modes", default="static,host,device,device_side_stream,poses_only")
+ap.add_argument("--json", default=None)
+args = ap.parse_args()
+modes = args.modes.split(",")
+CHAIN = [255] + list(range(63))  # mesh50k's 64 bones run along the capsule: a chain
+
+
+def poses(rng, n, k):
+    """k pose sets [n, 64, 16]: small bends about z per joint (column-major local matrices)"""
+    out = np.zeros((k, n, 64, 16), dtype=np.float32)
+    a = rng.uniform(-0.04, 0.04, size=(k, n, 64))
+    c, s = np.cos(a), np.sin(a)
+    out[..., 0], out[..., 1], out[..., 4], out[..., 5] = c, s, -s, c
+    out[..., 10] = out[..., 15] = 1.0
+    return out
+
+
+dev = api.Device(0)
+results = []
+for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)):
+    if args.only and args.only != name:
+        continue
+    md = scene.mesh50k()
+    mats, pals = scene.instance_lattice(nx, ny)
+    n = nx * ny
+    model = api.Model.new(dev, md)
+    model.set_skeleton(CHAIN, np.tile(np.eye(4, dtype=np.float32).reshape(16), (64, 1)))
+    batch = api.Batch(dev, model, mats, pals)
+    host = poses(np.random.default_rng(1), n, 8)
+    devp = [torch.tensor(p, device="cuda:0") for p in host]
+    loop = api.FrameLoop(dev, W, H, batch=batch, view_proj=scene.to_f32_colmajor(scene.reference_view_proj(W, H)))
+
+    side = torch.cuda.Stream()
+
+    def region(mode, nframes):
+        for k in range(nframes):
+            if mode == "host":
+                batch.set_poses(host[k % 8])
+            elif mode == "device":
+                batch.set_poses(devp[k % 8])
+            elif mode == "device_side_stream":  # the same from a non-default torch stream
+                with torch.cuda.stream(side):
+                    batch.set_poses(devp[k % 8])
+            elif mode == "poses_only":  # device poses and no frames: k_pose alone on the GPU
+                batch.set_poses(devp[k % 8])
+                continue
+            loop.run(1)
+
+    def timed(mode):
+        dev.synchronize(); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        region(mode, args.frames)
+        dev.synchronize(); torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.frames * 1e3
+
+    for mode in modes:
+        region(mode, 30)  # warm-up: code objects, the batch's version ring, the staging buffer
+    ms = {m: [] for m in modes}
+    for _ in range(args.reps):
+        for mode in modes:
+            ms[mode].append(timed(mode))
+    for mode in modes:
+        r = dict(config=name, instances=n, joints=64, width=W, height=H, mode=mode, frames=args.frames,
+                 ms_per_frame=round(float(np.median(ms[mode])), 4), ms_all=[round(v, 4) for v in ms[mode]])
+        results.append(r)
+        print(json.dumps(r), flush=True)
+    batch.close()
+    model.close()
+dev.close()
+if args.json:
+    json.dump(results, open(args.json, "w"), indent=1)
