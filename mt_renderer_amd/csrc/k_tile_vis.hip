@@ -6,7 +6,9 @@
 // in submission order among equals.  So each pixel keeps one 64-bit key  (~bits(z) : order+1)  in
 // LDS and every fragment is an order-independent, fire-and-forget `ds_max_u64`:
 //   * 64 triangles are set up per pass, one per lane;
-//   * the (triangle, pixel-of-bbox) pairs of every i32-edge-class triangle are FLATTENED over the wave, in rounds of
+//   * a pass whose boxes are mostly larger than four pixels flattens (triangle, bbox row) items instead, and each row walks
+//     only the run of columns its triangle covers (span_row.h; see the walk below);
+//   * otherwise the (triangle, pixel-of-bbox) pairs of every i32-edge-class triangle are FLATTENED over the wave, in rounds of
 //     <= 4096 pairs: a pass costs sum(bbox pixels)/64 iterations whatever the mix of 1-pixel slivers and bin-filling
 //     triangles (a lane = triangle walk ran max(bbox pixels) iterations at 29 % lane efficiency on the headline scene).
 //     The pair -> triangle map needs no search: triangle t sets bit (prefix_t mod 64) of a 64-bit start mask per
@@ -109,9 +111,6 @@ __device__ __forceinline__ void setup_tri(const RecA& a, uint32_t ord, int32_t b
     s.chi = make_int4(Chi[0], Chi[1], Chi[2], 0);
 }
 
-#ifndef MTR_QUAD_WALK
-#define MTR_QUAD_WALK 1
-#endif
 #define STAIR_K 8u  // submission orders kept per pixel (STAIR)
 
 // one fragment that passed coverage and the z range.  STAIR: also remember its order unless the key it meets proves it
@@ -191,6 +190,8 @@ __device__ __forceinline__ float z_at(const RecA& a, int32_t px, int32_t py) {
 // VIS_WAVES: 2 for unsharded frames (see above); a sharded rank has few bins and the frame then takes as long as its
 // heaviest bin (629 triangles = 183 batches of 64 pairs on the headline scene: 23 us with two waves), so the host
 // gives such frames 4 or 8 waves per bin (mtr_launch_tile_vis).
+// QW: always false.  It selected a 2 x 2 quad walk for frames alone on the GPU until the span walk below replaced it; the
+// parameter stays so that the kernel keeps the name bench.py and profiles/ refer to it by (k_tile_vis<false, 2, false, false>).
 template <bool TEX, int VIS_WAVES, bool STAIR, bool QW>
 __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams P) {
     __shared__ unsigned long long s_key[MTR_BIN * MTR_BIN];
@@ -201,9 +202,9 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
     __shared__ uint32_t s_cnt[STAIR ? MTR_BIN * MTR_BIN : 1];                      // STAIR: orders listed per pixel
     __shared__ __align__(16) uint32_t s_list[STAIR ? MTR_BIN * MTR_BIN * STAIR_K : 4];  // STAIR: the orders (+ 1)
 
+    static_assert(!QW, "the quad walk is retired");
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t magic_lut = (65536u + (lane & 15u)) / ((lane & 15u) + 1u);  // lane i: ceil(65536 / (i + 1)), fetched by __shfl per pass
     const uint32_t ovf = tile_prologue(P);
     uint32_t bin;
     if (!block_to_bin(P.fb, bin, P.xcd_run)) return;  // uniform over the workgroup, before any barrier
@@ -280,19 +281,10 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
         Setup s = {};
         if (valid) setup_tri(a_cur, ord_cur, binx0, biny0, vw, vh, s);
         const bool large = (s.t.flags & 1u) != 0;
-        // The wave's work item is a (triangle, pixel of its bbox) pair, or -- when a good part of the pass's triangles have a bbox
-        // of more than four pixels -- a (triangle, 2 x 2 quad) pair: one staged record read and one index decode per four pixels,
-        // the three edge functions stepped by an add.  A pass of one-pixel boxes (the instanced configs) is cheaper pixel by pixel,
-        // a pass of the headline model's 10-pixel boxes in quads: 9 % fewer VALU and 29 % fewer LDS instructions, the kernel alone
-        // 50.4 -> 45.3 us -- and frames in flight 1.3 % SLOWER (paired builds, three runs each), so the host asks for quads only
-        // for a frame that has the GPU to itself (TileParams::quad_walk -> the QW instantiation: latency, not throughput).  Uniform
-        // over the wave.
-        const bool quads = QW && (uint32_t)__popcll(__ballot(!large && s.npx > 4)) * 4u >= (uint32_t)__popcll(__ballot(!large && s.npx > 0));
-        const uint32_t bwm1_l = (s.t.box >> 8) & 15u;
-        const uint32_t iw = (quads && !large) ? (bwm1_l >> 1) + 1u : bwm1_l + 1u, ih = (quads && !large) ? (s.bhm1 >> 1) + 1u : s.bhm1 + 1u;
-        const uint32_t npx = s.npx ? iw * ih : 0u;
-        // k / iw = k * magic >> 16, exact for k < 256 and iw <= 16: magic = ceil(65536 / iw), from the lanes' table (QW) or divided out
-        s.t.box |= (QW ? (uint32_t)__shfl((int)magic_lut, (int)(iw - 1u)) : (65536u + iw - 1u) / iw) << 12;
+        const uint32_t iw = ((s.t.box >> 8) & 15u) + 1u;  // bbox width
+        const uint32_t npx = (uint32_t)s.npx;
+        // k / iw = k * magic >> 16, exact for k < 256 and iw <= 16: magic = ceil(65536 / iw)
+        s.t.box |= ((65536u + iw - 1u) / iw) << 12;
         // ---- lane = pixel of the bbox: triangles that need 64-bit edge functions (more than 64 px across: rare),
         //      broadcast one at a time with v_readlane ----
         for (uint64_t mb = __ballot(npx != 0 && large); mb; mb &= mb - 1) {
@@ -325,10 +317,75 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
             }
         }
 
+        // ---- lane = (triangle, bbox row), 64 rows per step, for every i32-class triangle of a pass whose boxes are mostly
+        //      larger than four pixels.  A row finds the exact run of columns its triangle covers (span_row.h: three
+        //      zero crossings, each estimated in f32 and settled by one integer evaluation of its edge) and walks just
+        //      that run: no (eb0 | eb1 | eb2) test, and the pairs of the bbox that cover no pixel centre -- 78 % of them on
+        //      the headline scene (tools/span_stats.py) -- are never visited.  The headline's covered runs are one pixel
+        //      long on average, so the run is walked by its own lane rather than flattened a second time.  A pass holds
+        //      at most 64 x 16 rows: one round, at most 16 start masks, the pair walk's scheme.  Uniform over the wave;
+        //      passes of one-pixel boxes (the instanced configs) keep the pair walk below. ----
+        const uint32_t ncand = (uint32_t)__popcll(__ballot(npx != 0 && !large));
+        const bool spans = zlim_ok && ncand != 0u && (uint32_t)__popcll(__ballot(!large && npx > 4)) * 2u >= ncand;
+        if (spans) {
+            const bool cand = npx != 0 && !large;
+            const uint64_t cm = __ballot(cand);
+            const uint32_t rows = cand ? s.bhm1 + 1u : 0u;
+            const uint32_t inc = wave_incl_scan_u32(rows);
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);  // <= 64 x 16
+            const uint32_t pre = inc - rows;
+            s_start[wv][lane] = 0ull;
+            wave_lds_sync();
+            if (cand) {
+                // the pair walk's record, with the triangle's first row item in place of its first pair
+                uint4* dst = &s_flat[wv][__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u)) * 4];
+                const int32_t ox = (int32_t)(s.t.box & 15u), oy = (int32_t)((s.t.box >> 4) & 15u);
+                const int32_t c0 = s.t.C0 + __mul24(s.t.A0, ox) + __mul24(s.t.B0, oy);
+                const int32_t c1 = s.t.C1 + __mul24(s.t.A1, ox) + __mul24(s.t.B1, oy);
+                const int32_t c2 = s.t.C2 + __mul24(s.t.A2, ox) + __mul24(s.t.B2, oy);
+                dst[0] = make_uint4((uint32_t)s.t.A0, (uint32_t)s.t.B0, (uint32_t)c0, (uint32_t)s.t.A1);
+                dst[1] = make_uint4((uint32_t)s.t.B1, (uint32_t)c1, (uint32_t)s.t.A2, (uint32_t)s.t.B2);
+                dst[2] = make_uint4((uint32_t)c2, pre, __float_as_uint(s.t.z0), __float_as_uint(s.t.dz1));
+                dst[3] = make_uint4(__float_as_uint(s.t.dz2), __float_as_uint(s.t.rcpA), s.t.ordk, s.t.box | ((s.t.flags & 0x60u) << 24));
+                atomicOr(&s_start[wv][pre >> 6], 1ull << (pre & 63u));
+            }
+            wave_lds_sync();
+            const unsigned long long my_start = s_start[wv][lane];
+            const uint32_t nb = (total + 63u) >> 6;
+            uint32_t base = 0;
+            for (uint32_t b = 0; b < nb; b++) {
+                const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_start, b);
+                const uint32_t mhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(my_start >> 32), b);
+                const uint64_t m = ((uint64_t)mhi << 32) | mlo;
+                const uint32_t tri = base + __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u)) + (uint32_t)((m >> lane) & 1ull) - 1u;
+                base += (uint32_t)__popcll(m);
+                const uint32_t p = b * 64u + lane;
+                if (p < total) {
+                    const uint4* src = &s_flat[wv][tri * 4];
+                    const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+                    const uint32_t box = q3.w;
+                    const int32_t row = (int32_t)(p - q2.y);
+                    const int32_t A1 = (int32_t)q0.w, A2 = (int32_t)q1.z;
+                    int32_t e1 = (int32_t)q1.y + __mul24((int32_t)q1.x, row), e2 = (int32_t)q2.x + __mul24((int32_t)q1.w, row);
+                    int32_t lo, hi;
+                    span_of_row((int32_t)q0.z + __mul24((int32_t)q0.y, row), e1, e2, (int32_t)q0.x, A1, A2, (int32_t)((box >> 8) & 15u), lo, hi);
+                    // eb1 / eb2 of the run's first pixel, + (1 - tl): the pair walk's integers, stepped along the row
+                    e1 += __mul24(A1, lo) + (int32_t)((box >> 29) & 1u);
+                    e2 += __mul24(A2, lo) + (int32_t)((box >> 30) & 1u);
+                    const float rcp = __uint_as_float(q3.y), dz1 = __uint_as_float(q2.w), dz2 = __uint_as_float(q3.x), z0 = __uint_as_float(q2.z);
+                    uint32_t pix = (box & 0xffu) + (uint32_t)(row * MTR_BIN + lo);
+                    for (int32_t c = lo; c <= hi; c++, pix++, e1 += A1, e2 += A2) {
+                        const float b1 = (float)e1 * rcp, b2 = (float)e2 * rcp;
+                        const float z = fmaf(b2, dz2, fmaf(b1, dz1, z0));
+                        if (__float_as_uint(z) <= zlim) put_fragment<STAIR>(s_key, s_cnt, s_list, pix, make_key(z, q3.z));
+                    }
+                }
+            }
+        }
         // ---- lane = (triangle, pixel) pair, 64 pairs per step, for every i32-class triangle.  A round stages a
         //      prefix of the remaining triangles holding <= 4096 pairs (64 start masks, one per lane); one round
         //      is the rule, a pass of 64 bin-filling triangles takes four. ----
-        for (uint64_t todo = zlim_ok ? __ballot(npx != 0 && !large) : 0ull; todo;) {
+        for (uint64_t todo = (zlim_ok && !spans) ? __ballot(npx != 0 && !large) : 0ull; todo;) {
             const bool cand = (todo >> lane) & 1ull;
             const uint32_t mine = cand ? npx : 0u;
             const uint32_t inc = wave_incl_scan_u32(mine);
@@ -349,7 +406,7 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
                 const int32_t c2 = s.t.C2 + __mul24(s.t.A2, ox) + __mul24(s.t.B2, oy);
                 dst[0] = make_uint4((uint32_t)s.t.A0, (uint32_t)s.t.B0, (uint32_t)c0, (uint32_t)s.t.A1);
                 dst[1] = make_uint4((uint32_t)s.t.B1, (uint32_t)c1, (uint32_t)s.t.A2, (uint32_t)s.t.B2);
-                dst[2] = make_uint4((uint32_t)c2, pre | (s.bhm1 << 16), __float_as_uint(s.t.z0), __float_as_uint(s.t.dz1));
+                dst[2] = make_uint4((uint32_t)c2, pre, __float_as_uint(s.t.z0), __float_as_uint(s.t.dz1));
                 // box bits 29 / 30: 1 - tl of edges 1 / 2 (flags bits 5 / 6)
                 dst[3] = make_uint4(__float_as_uint(s.t.dz2), __float_as_uint(s.t.rcpA), s.t.ordk, s.t.box | ((s.t.flags & 0x60u) << 24));
                 atomicOr(&s_start[wv][pre >> 6], 1ull << (pre & 63u));
@@ -366,10 +423,10 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
                 const uint32_t tri = base + __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u)) + (uint32_t)((m >> lane) & 1ull) - 1u;
                 base += (uint32_t)__popcll(m);
                 const uint32_t p = b * 64u + lane;
-                if (p < total && (!QW || !quads)) {
+                if (p < total) {
                     const uint4* src = &s_flat[wv][tri * 4];
                     const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-                    const uint32_t box = q3.w, k = p - (q2.y & 0xFFFFu);
+                    const uint32_t box = q3.w, k = p - q2.y;
                     const int32_t row = (int32_t)((k * ((box >> 12) & 0x1ffffu)) >> 16);
                     const int32_t col = (int32_t)k - __mul24(row, (int32_t)((box >> 8) & 15u) + 1);
                     const int32_t eb0 = (int32_t)q0.z + __mul24((int32_t)q0.x, col) + __mul24((int32_t)q0.y, row);
@@ -382,35 +439,6 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
                     // negative and NaN patterns are above every non-negative bound)
                     if ((eb0 | eb1 | eb2) >= 0 && __float_as_uint(z) <= zlim)
                         put_fragment<STAIR>(s_key, s_cnt, s_list, (box & 0xffu) + (uint32_t)(row * MTR_BIN + col), make_key(z, q3.z));
-                }
-                if (QW && p < total && quads) {
-                    const uint4* src = &s_flat[wv][tri * 4];
-                    const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-                    const uint32_t box = q3.w, k = p - (q2.y & 0xFFFFu);
-                    const uint32_t bwm1 = (box >> 8) & 15u, bhm1 = q2.y >> 16;
-                    const int32_t qr = (int32_t)((k * ((box >> 12) & 0x1ffffu)) >> 16);
-                    const int32_t qc = (int32_t)k - __mul24(qr, (int32_t)(bwm1 >> 1) + 1);
-                    const int32_t col = qc * 2, row = qr * 2;  // the quad's first pixel in the bbox
-                    const int32_t A0 = (int32_t)q0.x, B0 = (int32_t)q0.y, A1 = (int32_t)q0.w, B1 = (int32_t)q1.x, A2 = (int32_t)q1.z, B2 = (int32_t)q1.w;
-                    const int32_t e0 = (int32_t)q0.z + __mul24(A0, col) + __mul24(B0, row);
-                    const int32_t e1 = (int32_t)q1.y + __mul24(A1, col) + __mul24(B1, row);
-                    const int32_t e2 = (int32_t)q2.x + __mul24(A2, col) + __mul24(B2, row);
-                    const int32_t f1 = (int32_t)((box >> 29) & 1u), f2 = (int32_t)((box >> 30) & 1u);
-                    const float rcp = __uint_as_float(q3.y), dz1 = __uint_as_float(q2.w), dz2 = __uint_as_float(q3.x), z0 = __uint_as_float(q2.z);
-                    const uint32_t pix0 = (box & 0xffu) + (uint32_t)(row * MTR_BIN + col), ordk = q3.z;
-                    // a pixel past the bbox's last column / row belongs to the neighbouring bin (or lies off the target): not ours
-                    const bool vx = (uint32_t)col < bwm1, vy = (uint32_t)row < bhm1;
-                    auto fragment = [&](int32_t a0, int32_t a1, int32_t a2, bool ok, uint32_t pix) {
-                        if (ok && (a0 | a1 | a2) >= 0) {
-                            const float b1 = (float)(a1 + f1) * rcp, b2 = (float)(a2 + f2) * rcp;
-                            const float z = fmaf(b2, dz2, fmaf(b1, dz1, z0));
-                            if (__float_as_uint(z) <= zlim) put_fragment<STAIR>(s_key, s_cnt, s_list, pix, make_key(z, ordk));
-                        }
-                    };
-                    fragment(e0, e1, e2, true, pix0);
-                    fragment(e0 + A0, e1 + A1, e2 + A2, vx, pix0 + 1u);
-                    fragment(e0 + B0, e1 + B1, e2 + B2, vy, pix0 + MTR_BIN);
-                    fragment(e0 + A0 + B0, e1 + A1 + B1, e2 + A2 + B2, vx && vy, pix0 + MTR_BIN + 1u);
                 }
             }
         }
@@ -521,13 +549,7 @@ void mtr_launch_tile_vis(const TileParams& p, bool textured, hipStream_t s) {
     if (p.vis_waves) waves = (int)p.vis_waves;
     else if (mine <= 1536) waves = 8;   // 256 CUs: every bin is resident at once, the heaviest bin bounds the frame
     else if (mine <= 4096) waves = 4;
-// QW (2 x 2 quad walk where a pass's boxes are large enough): all-opaque frames that have the GPU to themselves (latency);
-// its own instantiation, so that the kernel of frames in flight keeps its registers and code
-#define MTR_LAUNCH_VIS(T, W, S)                                                                                         \
-    do {                                                                                                                \
-        if (!S && p.quad_walk && MTR_QUAD_WALK) hipLaunchKernelGGL((mtr::k_tile_vis<T, W, false, true>), dim3(grid), dim3(64 * W), 0, s, p);  \
-        else hipLaunchKernelGGL((mtr::k_tile_vis<T, W, S, false>), dim3(grid), dim3(64 * W), 0, s, p);                  \
-    } while (0)
+#define MTR_LAUNCH_VIS(T, W, S) hipLaunchKernelGGL((mtr::k_tile_vis<T, W, S, false>), dim3(grid), dim3(64 * W), 0, s, p)
 #define MTR_LAUNCH_VIS_W(T, S) do { if (waves >= 8) MTR_LAUNCH_VIS(T, 8, S); else if (waves >= 4) MTR_LAUNCH_VIS(T, 4, S); else MTR_LAUNCH_VIS(T, 2, S); } while (0)
     // frames with translucent materials keep per-pixel order lists (STAIR); all-opaque frames need only the key
     if (p.mixed) { if (textured) MTR_LAUNCH_VIS_W(true, true); else MTR_LAUNCH_VIS_W(false, true); }

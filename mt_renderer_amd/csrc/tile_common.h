@@ -3,6 +3,7 @@
 #pragma once
 #include "bc_sample.h"
 #include "mtr_internal.h"
+#include "span_row.h"
 
 namespace mtr {
 
