@@ -9,7 +9,8 @@ from oracle import oracle as orc
 
 
 def render_oracle(w, h, draws, clear=(1.0, 1.0, 1.0, 1.0), clear_depth=1.0, nthreads=1):
-    """draws: list of dicts {md, M | (vp, model_mats, palettes, tex_override), palette}"""
+    """draws: list of dicts {md, M | (vp, model_mats, palettes, tex_override), palette}; a batch that also has
+    (skeleton, poses) is posed on the GPU by render_gpu, while the oracle takes its palettes"""
     f = orc.OracleFrame(w, h, clear, clear_depth)
     cache = {}
     for d in draws:
@@ -58,7 +59,12 @@ def render_gpu(dev, w, h, draws, clear=(1.0, 1.0, 1.0, 1.0), clear_depth=1.0, sh
                 models[id(md)] = d["make_model"](dev) if "make_model" in d else api.Model.new(dev, md)
             m = models[id(md)]
             if "model_mats" in d:
-                b = api.Batch(dev, m, d["model_mats"], d.get("palettes"), d.get("tex_override"))
+                if "poses" in d:  # the palettes are formed on the GPU (k_pose) from one pose per instance
+                    m.set_skeleton(*d["skeleton"])
+                    b = api.Batch(dev, m, d["model_mats"], None, d.get("tex_override"))
+                    b.set_poses(d["poses"])
+                else:
+                    b = api.Batch(dev, m, d["model_mats"], d.get("palettes"), d.get("tex_override"))
                 batches.append(b)
                 fr.draw_batch(b, d["vp"])
             else:
