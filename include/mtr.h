@@ -213,6 +213,39 @@ int32_t mtr_batch_set_poses_device(mtr_batch *batch, const float *local_mats_dev
  * update has completed */
 int32_t mtr_batch_read_palettes(mtr_batch *batch, float *out, size_t count);
 
+/* ---- animation clips (build extension, SPEC.md section 14): palettes formed on the GPU (k_anim) from keyframes ----
+ * An animation set belongs to a joint count and holds nclips >= 1 clips of uniformly spaced keys; a key is, per joint, a
+ * translation, a rotation quaternion (x, y, z, w) and a scale.  keys: clip after clip, inside a clip key after key, inside
+ * a key joint after joint (sum(nkeys) * njoints entries); flags: MTR_CLIP_* per clip, NULL = 0 for all.  The library copies.
+ * An animation state says, for one instance: clip A at position x_a cross-faded by w (0 = A alone .. 1 = B alone) with clip
+ * B at x_b.  Positions are in KEYS (seconds times the clip's key rate; the library defines no clock); a LOOP clip wraps
+ * them (the last key interpolates towards the first), any other clip holds its first / last key.  Clip indices are
+ * clamped to nclips - 1, never rejected (device states cannot be validated; host and device paths agree); with w == 0
+ * clip B is not read.  The local matrix of a joint is from_scale_rotation_translation of the interpolated key, the
+ * palette is the skeleton's of section 12: bit for bit a binary32 model of section 14 followed by mtr_rmodel_palette.
+ * Errors: MTR_E_INVALID, and nothing changes, for a NULL handle, njoints outside 1..256, nclips == 0, a clip without
+ * keys (or more than 2^24), a model without skeleton, an animation set whose njoints is not the skeleton's or that
+ * belongs to another device, a misaligned device pointer; MTR_E_UNSUPPORTED when the library was built without k_anim. */
+#define MTR_CLIP_LOOP 1u
+typedef struct mtr_anim mtr_anim;
+typedef struct mtr_anim_key   { float t[3], pad0, q[4], s[3], pad1; } mtr_anim_key;      /* 48 bytes */
+typedef struct mtr_anim_state { uint32_t clip_a, clip_b; float x_a, x_b, w; uint32_t pad; } mtr_anim_state; /* 24 bytes */
+int32_t mtr_anim_create(mtr_device *dev, size_t njoints, size_t nclips, const uint32_t *nkeys, const uint32_t *flags,
+                        const mtr_anim_key *keys /* sum(nkeys) * njoints, clip after clip */, mtr_anim **out);
+/* may follow an animate call directly: the clip set is parked until the last kernel that reads it has run (no wait) */
+void mtr_anim_destroy(mtr_anim *anim);
+/* the model's palette from one state (host memory, free on return); same frame semantics as mtr_model_set_pose */
+int32_t mtr_model_animate(mtr_model *model, mtr_anim *anim, const mtr_anim_state *state /* one, host */);
+/* one state per instance (host memory, free on return); same frame semantics as mtr_batch_set_poses; afterwards the
+ * batch has npal = njoints */
+int32_t mtr_batch_animate(mtr_batch *batch, mtr_anim *anim, const mtr_anim_state *states /* n, host */);
+/* the same from device memory: k_anim reads states_dev in stream order on hip_stream, with the rules of
+ * mtr_batch_set_poses_device (NULL = the device's stream; the caller may overwrite the buffer with work queued later) */
+int32_t mtr_batch_animate_device(mtr_batch *batch, mtr_anim *anim, const mtr_anim_state *states_dev /* 8-byte aligned */,
+                                 void *hip_stream /* as mtr_batch_set_poses_device */);
+/* test / debug hook: the local matrices of section 14 for n states, n * njoints * 16 floats to host memory */
+int32_t mtr_anim_sample(mtr_anim *anim, const mtr_anim_state *states, size_t n, float *out_locals, size_t count);
+
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],
                         float clear_depth, mtr_frame **out);

@@ -83,6 +83,33 @@ class Texture {
 
 class Frame;
 
+// An animation set (include/mtr.h, SPEC.md section 14): clips of uniformly spaced keys, resident in HBM.  keys: clip after
+// clip, sum(nkeys) * njoints entries; flags: MTR_CLIP_* per clip (empty = 0 for all).
+class Anim {
+  public:
+    Anim(const Device& dev, size_t njoints, const std::vector<uint32_t>& nkeys, const std::vector<uint32_t>& flags, const mtr_anim_key* keys)
+        : dev_(dev), njoints_(njoints) {
+        if (!flags.empty() && flags.size() != nkeys.size()) throw Error(MTR_E_INVALID, "one flag word per clip");
+        dev.check(mtr_anim_create(dev.handle(), njoints, nkeys.size(), nkeys.data(), flags.empty() ? nullptr : flags.data(), keys, &h_));
+    }
+    Anim(Anim&& o) noexcept : dev_(o.dev_), njoints_(o.njoints_), h_(std::exchange(o.h_, nullptr)) {}
+    Anim(const Anim&) = delete;
+    ~Anim() { mtr_anim_destroy(h_); }
+    size_t njoints() const { return njoints_; }
+    // test / debug hook: the local matrices of n states, n * njoints * 16 floats
+    std::vector<float> sample(const mtr_anim_state* states, size_t n) const {
+        std::vector<float> out(n * njoints_ * 16);
+        dev_.check(mtr_anim_sample(h_, states, n, out.data(), out.size()));
+        return out;
+    }
+    mtr_anim* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    size_t njoints_;
+    mtr_anim* h_ = nullptr;
+};
+
 class Model {
   public:
     // Model::new(model_file, material_file, shader2, resource_manager, device, queue, ..) -- src/model.rs:36-45
@@ -108,6 +135,8 @@ class Model {
     // skeletal poses (SPEC.md section 12): parents == nullptr clears the skeleton; set_pose forms the palette on the GPU
     void set_skeleton(const uint8_t* parents, const float* imats, size_t njoints) { dev_.check(mtr_model_set_skeleton(h_, parents, imats, njoints)); }
     void set_pose(const float* local_mats, size_t njoints) { dev_.check(mtr_model_set_pose(h_, local_mats, njoints)); }
+    // the palette from one animation state through the skeleton (SPEC.md section 14)
+    void animate(const Anim& anim, const mtr_anim_state& state) { dev_.check(mtr_model_animate(h_, anim.handle(), &state)); }
     // the state objects a material names (src/rmaterial.rs:211-230), applied per primitive; default = src/model.rs:240-262
     void set_prim_states(const std::vector<mtr_prim_state>& states) { dev_.check(mtr_model_set_prim_states(h_, states.data(), states.size())); }
     // joint positions for the per-joint debug cubes of Model::render (src/model.rs:309-315)
@@ -141,6 +170,12 @@ class Batch {
     void set_poses_device(const float* local_mats_dev, size_t njoints, void* hip_stream = nullptr) {
         dev_.check(mtr_batch_set_poses_device(h_, local_mats_dev, njoints, hip_stream));
         npal_ = njoints;
+    }
+    // one animation state per instance (SPEC.md section 14): host memory, or device memory read in stream order
+    void animate(const Anim& anim, const mtr_anim_state* states) { dev_.check(mtr_batch_animate(h_, anim.handle(), states)); npal_ = anim.njoints(); }
+    void animate_device(const Anim& anim, const mtr_anim_state* states_dev, void* hip_stream = nullptr) {
+        dev_.check(mtr_batch_animate_device(h_, anim.handle(), states_dev, hip_stream));
+        npal_ = anim.njoints();
     }
     std::vector<float> read_palettes() const {
         std::vector<float> out(n_ * npal_ * 16);

@@ -44,7 +44,13 @@ EXPORTED_SYMBOLS = [
     "mtr_group_frame_part", "mtr_group_frame_end", "mtr_group_frame_read_color", "mtr_group_frame_color_devptr", "mtr_group_frame_destroy",
     "mtr_model_set_skeleton", "mtr_model_set_pose", "mtr_batch_update", "mtr_batch_set_poses", "mtr_batch_set_poses_device",
     "mtr_batch_read_palettes",
+    "mtr_anim_create", "mtr_anim_destroy", "mtr_model_animate", "mtr_batch_animate", "mtr_batch_animate_device", "mtr_anim_sample",
 ]
+
+CLIP_LOOP = 1
+# mtr_anim_key / mtr_anim_state (include/mtr.h; SPEC.md section 14)
+ANIM_KEY = np.dtype([("t", "<f4", 3), ("pad0", "<f4"), ("q", "<f4", 4), ("s", "<f4", 3), ("pad1", "<f4")])
+ANIM_STATE = np.dtype([("clip_a", "<u4"), ("clip_b", "<u4"), ("x_a", "<f4"), ("x_b", "<f4"), ("w", "<f4"), ("pad", "<u4")])
 
 
 class MtrError(RuntimeError):
@@ -166,6 +172,12 @@ def _load() -> C.CDLL:
         "mtr_batch_set_poses": (i32, [vp, vp, sz]),
         "mtr_batch_set_poses_device": (i32, [vp, vp, sz, vp]),
         "mtr_batch_read_palettes": (i32, [vp, vp, sz]),
+        "mtr_anim_create": (i32, [vp, sz, sz, vp, vp, vp, vp]),
+        "mtr_anim_destroy": (None, [vp]),
+        "mtr_model_animate": (i32, [vp, vp, vp]),
+        "mtr_batch_animate": (i32, [vp, vp, vp]),
+        "mtr_batch_animate_device": (i32, [vp, vp, vp, vp]),
+        "mtr_anim_sample": (i32, [vp, vp, sz, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -380,6 +392,11 @@ class Model:
         lm = _f32(local_mats, (-1, 16))
         self.dev.check(lib.mtr_model_set_pose(self._h, _p(lm), lm.shape[0]))
 
+    def animate(self, anim: "Anim", state):
+        """palette formed on the GPU (k_anim) from one animation state (an ANIM_STATE record or a dict of its fields)"""
+        st = anim_states(state, 1)
+        self.dev.check(lib.mtr_model_animate(self._h, anim._h, _p(st)))
+
     def render(self, frame: "Frame", view_proj: np.ndarray, joints: bool = False):
         """Model::render(rpass, queue, transform_bind_group, debug_overlay) -- src/model.rs:299-305; the
         transform uniform (src/bin/modelviewer.rs:217-221) is passed directly.  joints: also the per-joint debug cubes the
@@ -410,6 +427,65 @@ class Model:
         for t in self.textures:
             t.close()
         self.textures = []
+
+
+def anim_states(states, n: Optional[int] = None) -> np.ndarray:
+    """animation states as a contiguous ANIM_STATE array: from a structured array of that dtype, or from a dict of
+    clip_a, clip_b, x_a, x_b, w (arrays or scalars; a missing clip_b / x_b / w is 0)"""
+    if isinstance(states, dict):
+        unknown = set(states) - set(ANIM_STATE.names)
+        if unknown or "clip_a" not in states or "x_a" not in states:
+            raise MtrError(MTR_E_INVALID, "animation states: clip_a and x_a, optionally clip_b, x_b and w")
+        cols = {k: np.atleast_1d(np.asarray(v)) for k, v in states.items()}
+        st = np.zeros(max(c.size for c in cols.values()) if n is None else n, dtype=ANIM_STATE)
+        for k, v in cols.items():
+            st[k] = v
+    else:
+        a = np.asarray(states)
+        if a.dtype != ANIM_STATE:
+            raise MtrError(MTR_E_INVALID, "animation states: an array of dtype ANIM_STATE or a dict of its fields")
+        st = np.ascontiguousarray(a).reshape(-1)
+    if n is not None and st.size != n:
+        raise MtrError(MTR_E_INVALID, f"animation states: {n} expected, {st.size} given")
+    return st
+
+
+class Anim:
+    """An animation set (include/mtr.h, SPEC.md section 14): clips of uniformly spaced keys for ``njoints`` joints, resident
+    in HBM.  clips: a list of (keys, flags); keys is [nkeys, njoints, 12] float32 (t.xyz 0 | q.xyzw | s.xyz 0) or an
+    ANIM_KEY array [nkeys, njoints]; flags 0 or CLIP_LOOP."""
+
+    def __init__(self, dev: Device, njoints: int, clips):
+        if not 1 <= njoints <= 256:
+            raise MtrError(MTR_E_INVALID, "anim: 1 to 256 joints")
+        blocks, nkeys, flags = [], [], []
+        for keys, fl in clips:
+            k = np.asarray(keys)
+            k = k.view(np.float32) if k.dtype == ANIM_KEY else _f32(k)
+            if k.size % (njoints * 12):
+                raise MtrError(MTR_E_INVALID, "anim: keys are [nkeys, njoints, 12] float32")
+            k = np.ascontiguousarray(k).reshape(k.size // (njoints * 12), njoints, 12)
+            blocks.append(k.reshape(-1, 12))
+            nkeys.append(k.shape[0])
+            flags.append(int(fl))
+        allk = np.ascontiguousarray(np.concatenate(blocks)) if blocks else np.zeros((1, 12), dtype=np.float32)
+        nk = np.asarray(nkeys if nkeys else [0], dtype=np.uint32)
+        fl = np.asarray(flags if flags else [0], dtype=np.uint32)
+        h = C.c_void_p()
+        dev.check(lib.mtr_anim_create(dev._h, njoints, len(nkeys), _p(nk), _p(fl), _p(allk), C.byref(h)))
+        self.dev, self._h, self.njoints, self.nclips = dev, h, njoints, len(nkeys)
+
+    def sample(self, states) -> np.ndarray:
+        """the local matrices [n, njoints, 16] of the given states, formed on the GPU (test / debug hook)"""
+        st = anim_states(states)
+        out = np.zeros((st.size, self.njoints, 16), dtype=np.float32)
+        self.dev.check(lib.mtr_anim_sample(self._h, _p(st), st.size, _p(out), out.size))
+        return out
+
+    def close(self):
+        if self._h:
+            lib.mtr_anim_destroy(self._h)
+            self._h = None
 
 
 _POSE_STREAMS = {}
@@ -482,6 +558,36 @@ class Batch:
             t.record_stream(side)
             cur.wait_stream(side)
         self.npal = nj
+
+    def animate(self, anim: Anim, states):
+        """one animation state per instance through ``anim`` and the model's skeleton (k_anim).  A structured numpy array
+        (ANIM_STATE) or a dict of its fields is copied in; a torch uint8 [n, 24] / int32 [n, 6] tensor on the batch's device
+        holding ANIM_STATE records is read in stream order on torch.cuda.current_stream()."""
+        if isinstance(states, (np.ndarray, dict)):
+            st = anim_states(states, self.n)
+            self.dev.check(lib.mtr_batch_animate(self._h, anim._h, _p(st)))
+            self.npal = anim.njoints
+            return
+        import torch
+        t = states
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32):
+            raise MtrError(MTR_E_INVALID, "animate: a numpy ANIM_STATE array, a dict, or a uint8 / int32 tensor on the GPU")
+        if t.get_device() != self.dev.hip_device:
+            raise MtrError(MTR_E_INVALID, f"animate: the tensor is on cuda:{t.get_device()}, the batch on cuda:{self.dev.hip_device}")
+        if t.numel() * t.element_size() != self.n * ANIM_STATE.itemsize:
+            raise MtrError(MTR_E_INVALID, "animate: n states of 24 bytes")
+        cur = torch.cuda.current_stream(t.device)
+        if not t.is_contiguous() or t.data_ptr() % 8:
+            t = t.contiguous().clone()
+        if cur.cuda_stream != 0:
+            self.dev.check(lib.mtr_batch_animate_device(self._h, anim._h, C.c_void_p(t.data_ptr()), C.c_void_p(cur.cuda_stream)))
+        else:  # torch's legacy default stream: as set_poses
+            side = _pose_stream(t.device)
+            side.wait_stream(cur)
+            self.dev.check(lib.mtr_batch_animate_device(self._h, anim._h, C.c_void_p(t.data_ptr()), C.c_void_p(side.cuda_stream)))
+            t.record_stream(side)
+            cur.wait_stream(side)
+        self.npal = anim.njoints
 
     def read_palettes(self) -> np.ndarray:
         """the batch's current palettes [n, npal, 16], after its pending update has completed"""

@@ -1,0 +1,151 @@
+// k_anim.hip -- skin palettes from animation clips (SPEC.md section 14).  For every instance: sample one or two clips at
+// the instance's key positions, cross-fade them, turn each joint's (translation, quaternion, scale) into its local matrix
+// and fold the skeleton as k_pose does (section 12).  The local matrices exist in LDS only.
+//
+// Same shape as k_pose: one workgroup per instance, one thread per joint.  The 24-byte state is the same for the whole
+// workgroup; thread j reads its joint's keys (3 x 16 bytes each: 2 keys, or 4 with a cross-fade) with every load issued
+// before the first use.  Section 14 has no fused multiply-add: every operator below is one rounded operation (the file
+// is compiled with -ffp-contract=off), so a plain binary32 model reproduces the local matrices bit for bit.
+#include "pose_common.h"
+
+namespace mtr {
+
+struct AnimPos {
+    uint32_t i0, i1;  // key indices inside the clip
+    float a;          // fraction towards i1
+};
+
+// Position -> keys: nkeys >= 1 keys at uniform spacing, x in keys
+__device__ __forceinline__ AnimPos anim_position(float x, uint32_t nkeys, uint32_t flags) {
+    AnimPos r;
+    float pos;
+    if (flags & 1u) {  // MTR_CLIP_LOOP
+        const float nf = (float)nkeys;
+        pos = x - floorf(x / nf) * nf;
+        if (!(pos >= 0.0f && pos < nf)) pos = 0.0f;  // NaN, +-inf, huge x, and pos == nf for a tiny negative x
+        r.i0 = (uint32_t)floorf(pos);
+        r.i1 = r.i0 + 1u == nkeys ? 0u : r.i0 + 1u;
+    } else {
+        const float last = (float)(nkeys - 1u);
+        pos = x >= 0.0f ? x : 0.0f;  // NaN -> 0
+        if (pos > last) pos = last;
+        r.i0 = (uint32_t)floorf(pos);
+        r.i1 = r.i0 + 1u < nkeys ? r.i0 + 1u : nkeys - 1u;
+    }
+    r.a = pos - (float)r.i0;
+    return r;
+}
+
+__device__ __forceinline__ float anim_lerp(float v0, float v1, float a) { return v0 + a * (v1 - v0); }
+
+__device__ __forceinline__ float4 anim_lerp4(const float4& v0, const float4& v1, float a) {
+    return make_float4(anim_lerp(v0.x, v1.x, a), anim_lerp(v0.y, v1.y, a), anim_lerp(v0.z, v1.z, a), anim_lerp(v0.w, v1.w, a));
+}
+
+__device__ __forceinline__ float anim_dot(const float4& p, const float4& q) { return ((p.x * q.x + p.y * q.y) + p.z * q.z) + p.w * q.w; }
+
+__device__ __forceinline__ float4 anim_nlerp(const float4& q0, float4 q1, float a) {
+    if (anim_dot(q0, q1) < 0.0f) q1 = make_float4(-q1.x, -q1.y, -q1.z, -q1.w);  // the shortest path; NaN compares false
+    const float4 q = anim_lerp4(q0, q1, a);
+    const float n2 = anim_dot(q, q);
+    const float rn = 1.0f / sqrtf(n2);
+    if (n2 == 0.0f || !(fabsf(rn) <= 3.402823466e38f)) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    return make_float4(q.x * rn, q.y * rn, q.z * rn, q.w * rn);
+}
+
+struct AnimKey {
+    float4 t, q, s;
+};
+
+__device__ __forceinline__ AnimKey anim_load_key(const float4* keys, uint32_t key, uint32_t J, uint32_t j) {
+    const float4* k = keys + ((size_t)key * J + j) * 3;
+    AnimKey r;
+    r.t = k[0]; r.q = k[1]; r.s = k[2];
+    return r;
+}
+
+__device__ __forceinline__ AnimKey anim_mix(const AnimKey& k0, const AnimKey& k1, float a) {
+    AnimKey r;
+    r.t = anim_lerp4(k0.t, k1.t, a);
+    r.q = anim_nlerp(k0.q, k1.q, a);
+    r.s = anim_lerp4(k0.s, k1.s, a);
+    return r;
+}
+
+// The local matrix of joint j of instance inst (column-major)
+__device__ __forceinline__ void anim_local(const AnimParams& p, uint32_t inst, uint32_t j, float4 (&M)[4]) {
+    const uint32_t J = p.pose.njoints;
+    const uint2* st = reinterpret_cast<const uint2*>(p.states + (size_t)inst * 6);
+    const uint2 sc = st[0], sx = st[1], sw = st[2];
+    float w = __uint_as_float(sw.x);
+    w = w > 0.0f ? w : 0.0f;  // NaN -> 0
+    w = w > 1.0f ? 1.0f : w;
+    const uint4* clips = reinterpret_cast<const uint4*>(p.clips);
+    const float4* keys = reinterpret_cast<const float4*>(p.keys);
+    const uint4 ca = clips[sc.x < p.nclips ? sc.x : p.nclips - 1u];
+    const AnimPos pa = anim_position(__uint_as_float(sx.x), ca.y, ca.z);
+    AnimKey r;
+    if (w == 0.0f) {  // clip B is not read
+        const AnimKey a0 = anim_load_key(keys, ca.x + pa.i0, J, j), a1 = anim_load_key(keys, ca.x + pa.i1, J, j);
+        r = anim_mix(a0, a1, pa.a);
+    } else {
+        const uint4 cb = clips[sc.y < p.nclips ? sc.y : p.nclips - 1u];
+        const AnimPos pb = anim_position(__uint_as_float(sx.y), cb.y, cb.z);
+        const AnimKey a0 = anim_load_key(keys, ca.x + pa.i0, J, j), a1 = anim_load_key(keys, ca.x + pa.i1, J, j);
+        const AnimKey b0 = anim_load_key(keys, cb.x + pb.i0, J, j), b1 = anim_load_key(keys, cb.x + pb.i1, J, j);
+        r = anim_mix(anim_mix(a0, a1, pa.a), anim_mix(b0, b1, pb.a), w);
+    }
+    const float x = r.q.x, y = r.q.y, z = r.q.z, qw = r.q.w;
+    const float x2 = x + x, y2 = y + y, z2 = z + z;
+    const float xx = x * x2, yy = y * y2, zz = z * z2, xy = x * y2, xz = x * z2, yz = y * z2;
+    const float wx = qw * x2, wy = qw * y2, wz = qw * z2;
+    M[0] = make_float4((1.0f - (yy + zz)) * r.s.x, (xy + wz) * r.s.x, (xz - wy) * r.s.x, 0.0f);
+    M[1] = make_float4((xy - wz) * r.s.y, (1.0f - (xx + zz)) * r.s.y, (yz + wx) * r.s.y, 0.0f);
+    M[2] = make_float4((xz + wy) * r.s.z, (yz - wx) * r.s.z, (1.0f - (xx + yy)) * r.s.z, 0.0f);
+    M[3] = make_float4(r.t.x, r.t.y, r.t.z, 1.0f);
+}
+
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim(AnimParams p) {
+    __shared__ float4 loc[MTR_POSE_MAX_JOINTS * 4];
+    extern __shared__ uint32_t path_lds[];  // p.pose.path_bytes / 4 words
+    const uint32_t inst = blockIdx.x, t = threadIdx.x, J = p.pose.njoints;
+    if (t < J) {
+        float4 M[4];
+        anim_local(p, inst, t, M);
+#pragma unroll
+        for (int c = 0; c < 4; c++) loc[t * 4 + c] = M[c];
+    }
+    for (uint32_t i = t; i < p.pose.path_bytes / 4; i += blockDim.x) path_lds[i] = p.pose.path_words[i];
+    __syncthreads();
+    if (t >= J) return;
+    pose_fold_store(p.pose, loc, path_lds, inst, t);
+}
+
+// the local matrices themselves (mtr_anim_sample): the same sampling function, stored instead of folded
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_sample(AnimParams p) {
+    const uint32_t inst = blockIdx.x, t = threadIdx.x, J = p.pose.njoints;
+    if (t >= J) return;
+    float4 M[4];
+    anim_local(p, inst, t, M);
+    float4* out = reinterpret_cast<float4*>(p.pose.out + ((size_t)inst * J + t) * 16);
+#pragma unroll
+    for (int c = 0; c < 4; c++) out[c] = M[c];
+}
+
+}  // namespace mtr
+
+static bool anim_launchable(const AnimParams& p, uint32_t ninst) {
+    return ninst != 0 && p.nclips != 0 && p.pose.njoints != 0 && p.pose.njoints <= MTR_POSE_MAX_JOINTS;
+}
+
+void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_launchable(p, ninst) || p.pose.path_bytes > MTR_POSE_MAX_PATH_BYTES) return;
+    const uint32_t threads = (p.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim, dim3(ninst), dim3(threads), p.pose.path_bytes, s, p);
+}
+
+void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_launchable(p, ninst)) return;
+    const uint32_t threads = (p.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_sample, dim3(ninst), dim3(threads), 0, s, p);
+}

@@ -22,6 +22,9 @@
 // k_pose.hip.  Weak: the host-only builds of this file (tests/cpp, over the HIP stub runtime) link no kernels and never
 // form a pose; libmtr.so links k_pose.o.
 void mtr_launch_pose(const PoseParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+// k_anim.hip, weak for the same reason
+void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 
 namespace {
 
@@ -301,6 +304,18 @@ struct mtr_batch {
     bool used = false;
     int hint_slot = -1;          // mtr_device::hint_host slot, or -1
     uint64_t hint_key = 0;       // the ownership (table, rank) the slot's numbers were reported under
+};
+
+// An animation set (SPEC.md section 14): immutable once uploaded.  d: the clip table (nclips x 4 words: first key, key count,
+// flags, 0), then the keys.  `last` is recorded behind every kernel that reads d; a kernel queued on another stream than
+// the one before first waits for it, so the one event always covers every reader and mtr_anim_destroy can park d behind it.
+struct mtr_anim {
+    mtr_device* dev;
+    uint32_t njoints = 0, nclips = 0;
+    uint32_t* d = nullptr;
+    hipEvent_t last = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool recorded = false;
 };
 
 struct BatchDeleter {
@@ -1269,6 +1284,27 @@ PoseParams pose_params(const mtr_model::Skeleton& sk, const float* locals, float
     return pp;
 }
 
+AnimParams anim_params(const mtr_anim* a, const mtr_model::Skeleton& sk, const void* states_dev, float* out) {
+    AnimParams ap{};
+    ap.pose = pose_params(sk, nullptr, out);
+    ap.clips = a->d;
+    ap.keys = reinterpret_cast<const float*>(a->d + (size_t)a->nclips * 4);
+    ap.states = static_cast<const uint32_t*>(states_dev);
+    ap.nclips = a->nclips;
+    return ap;
+}
+
+// around a kernel on `s` that reads the clip set: see mtr_anim::last
+int32_t anim_before(mtr_anim* a, hipStream_t s) {
+    if (a->recorded && a->last_stream != s) HIPCHK(a->dev, hipStreamWaitEvent(s, a->last, 0));
+    return MTR_OK;
+}
+int32_t anim_after(mtr_anim* a, hipStream_t s) {
+    HIPCHK(a->dev, hipEventRecord(a->last, s));
+    a->last_stream = s; a->recorded = true;
+    return MTR_OK;
+}
+
 }  // namespace
 
 int32_t mtr_model_set_palette(mtr_model* m, const float* mats, size_t n) {
@@ -1433,9 +1469,17 @@ int32_t batch_next_version(mtr_batch* b, uint32_t npal, int* out, hipEvent_t* fr
     return MTR_OK;
 }
 
+// Where the palettes of a pose come from: local matrices (k_pose), or animation states over a clip set (k_anim); device memory
+struct PoseSrc {
+    const float* locals = nullptr;
+    mtr_anim* anim = nullptr;
+    const void* states = nullptr;
+    explicit operator bool() const { return locals || anim; }
+};
+
 // What an update writes into a fresh version.  mats / pals: host arrays, or nullptr = keep the current version's (device
-// copy); locals (device, k_pose input) replaces the palettes with the pose's.  Enqueued on `s`, the version made current.
-int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, uint32_t npal_new, const float* locals, hipStream_t s) {
+// copy); a pose source replaces the palettes with the pose's.  Enqueued on `s`, the version made current.
+int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, uint32_t npal_new, const PoseSrc& src, hipStream_t s) {
     mtr_device* d = b->dev;
     const size_t n = b->n;
     int vi = -1;
@@ -1443,7 +1487,7 @@ int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, 
     {
         std::lock_guard<std::mutex> submit_lock(d->submit_mu);
         cur = b->vers[(size_t)b->cur];
-        const uint32_t npal = (pals || locals) ? npal_new : cur.npal;
+        const uint32_t npal = (pals || src) ? npal_new : cur.npal;
         hipEvent_t frame_ev = nullptr;
         int32_t rc = batch_next_version(b, npal, &vi, &frame_ev);
         if (rc) return rc;
@@ -1471,8 +1515,14 @@ int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, 
         if (mats) HIPCHK(d, hipMemcpyAsync(v.d, mats, n * 64, hipMemcpyHostToDevice, s));
         else HIPCHK(d, hipMemcpyAsync(v.d, cur.d, n * 64, hipMemcpyDeviceToDevice, s));
         float* vp = v.d + n * 16;
-        if (locals) {
-            mtr_launch_pose(pose_params(b->model->skel, locals, vp), (uint32_t)n, s);
+        if (src.anim) {
+            int32_t arc = anim_before(src.anim, s);
+            if (arc) return arc;
+            mtr_launch_anim(anim_params(src.anim, b->model->skel, src.states, vp), (uint32_t)n, s);
+            HIPCHK(d, hipGetLastError());
+            if ((arc = anim_after(src.anim, s))) return arc;
+        } else if (src.locals) {
+            mtr_launch_pose(pose_params(b->model->skel, src.locals, vp), (uint32_t)n, s);
             HIPCHK(d, hipGetLastError());
         } else if (pals) {
             HIPCHK(d, hipMemcpyAsync(vp, pals, n * v.npal * 64, hipMemcpyHostToDevice, s));
@@ -1546,7 +1596,7 @@ int32_t mtr_batch_update(mtr_batch* b, const float* model_mats, const float* pal
     if (!model_mats && !palettes) return MTR_OK;
     int32_t rc = set_device(d);
     if (rc) return rc;
-    return batch_write_version(b, model_mats, palettes, (uint32_t)npal, nullptr, d->s_copy);
+    return batch_write_version(b, model_mats, palettes, (uint32_t)npal, PoseSrc{}, d->s_copy);
 }
 
 static int32_t check_batch_pose(mtr_batch* b, size_t njoints) {
@@ -1564,7 +1614,9 @@ int32_t mtr_batch_set_poses(mtr_batch* b, const float* local_mats, size_t njoint
     int32_t rc = check_batch_pose(b, njoints);
     if (rc) return rc;
     if ((rc = stage_pose(d, local_mats, (size_t)b->n * njoints * 16))) return rc;
-    return batch_write_version(b, nullptr, nullptr, (uint32_t)njoints, d->pose_stage, d->s_copy);
+    PoseSrc src;
+    src.locals = d->pose_stage;
+    return batch_write_version(b, nullptr, nullptr, (uint32_t)njoints, src, d->s_copy);
 }
 
 int32_t mtr_batch_set_poses_device(mtr_batch* b, const float* local_mats_dev, size_t njoints, void* hip_stream) {
@@ -1574,7 +1626,132 @@ int32_t mtr_batch_set_poses_device(mtr_batch* b, const float* local_mats_dev, si
     int32_t rc = check_batch_pose(b, njoints);
     if (rc) return rc;
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
-    return batch_write_version(b, nullptr, nullptr, (uint32_t)njoints, local_mats_dev, s);
+    PoseSrc src;
+    src.locals = local_mats_dev;
+    return batch_write_version(b, nullptr, nullptr, (uint32_t)njoints, src, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// animation clips (SPEC.md section 14)
+// ---------------------------------------------------------------------------------------------
+int32_t mtr_anim_create(mtr_device* d, size_t njoints, size_t nclips, const uint32_t* nkeys, const uint32_t* flags,
+                        const mtr_anim_key* keys, mtr_anim** out) {
+    if (!d || !out) return MTR_E_INVALID;
+    *out = nullptr;
+    if (njoints == 0 || njoints > MTR_POSE_MAX_JOINTS) return fail(d, MTR_E_INVALID, "anim: 1 to 256 joints");
+    if (nclips == 0 || nclips > 0xFFFFFFu || !nkeys || !keys) return fail(d, MTR_E_INVALID, "anim: at least one clip, its key counts and keys");
+    std::vector<uint32_t> table(nclips * 4);
+    uint64_t total = 0;
+    for (size_t c = 0; c < nclips; c++) {
+        // key counts are exact in binary32 (the position arithmetic of section 14)
+        if (nkeys[c] == 0 || nkeys[c] > (1u << 24)) return fail(d, MTR_E_INVALID, "anim: a clip has 1 to 16 777 216 keys");
+        table[c * 4 + 0] = (uint32_t)total;
+        table[c * 4 + 1] = nkeys[c];
+        table[c * 4 + 2] = flags ? flags[c] : 0u;
+        table[c * 4 + 3] = 0u;
+        total += nkeys[c];
+        if (total * njoints > 0x3FFFFFFu) return fail(d, MTR_E_INVALID, "anim: more than 2^26 joint keys");
+    }
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    auto a = std::make_unique<mtr_anim>();
+    a->dev = d; a->njoints = (uint32_t)njoints; a->nclips = (uint32_t)nclips;
+    const size_t key_words = (size_t)total * njoints * 12;
+    if ((rc = dev_alloc(d, &a->d, table.size() + key_words))) return rc;
+    hipError_t e = hipMemcpy(a->d, table.data(), table.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(a->d + table.size(), keys, key_words * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&a->last, hipEventDisableTiming);
+    if (e != hipSuccess) { (void)hipFree(a->d); return fail(d, MTR_E_HIP, std::string("anim upload: ") + hipGetErrorString(e)); }
+    *out = a.release();
+    return MTR_OK;
+}
+
+void mtr_anim_destroy(mtr_anim* a) {
+    if (!a) return;
+    mtr_device* d = a->dev;
+    {
+        // a kernel may still read the clip set: parked behind the event of the last one, collected by a later submit
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        d->garbage.push_back({a->d, 0, a->last});
+    }
+    delete a;
+}
+
+static int32_t check_anim(mtr_device* d, const mtr_model* m, const mtr_anim* a) {
+    if (!a) return fail(d, MTR_E_INVALID, "animate: no animation set");
+    if (a->dev != d) return fail(d, MTR_E_INVALID, "animate: the animation set belongs to another device");
+    if (!m->skel.d) return fail(d, MTR_E_INVALID, "animate: the model has no skeleton");
+    if (a->njoints != m->skel.njoints) return fail(d, MTR_E_INVALID, "animate: the animation set's joint count is not the skeleton's");
+    if (!mtr_launch_anim) return fail(d, MTR_E_UNSUPPORTED, "animate: built without k_anim");
+    return set_device(d);
+}
+
+int32_t mtr_model_animate(mtr_model* m, mtr_anim* a, const mtr_anim_state* state) {
+    if (!m) return MTR_E_INVALID;
+    mtr_device* d = m->dev;
+    if (!state) return fail(d, MTR_E_INVALID, "animate: no state");
+    int32_t rc = check_anim(d, m, a);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, reinterpret_cast<const float*>(state), sizeof(mtr_anim_state) / sizeof(float)))) return rc;
+    std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+    mtr_model::PalBuf* pb = nullptr;
+    if ((rc = next_palette_buffer(m, a->njoints, &pb))) return rc;
+    if ((rc = anim_before(a, d->s_copy))) return rc;
+    mtr_launch_anim(anim_params(a, m->skel, d->pose_stage, pb->d), 1, d->s_copy);
+    HIPCHK(d, hipGetLastError());
+    if ((rc = anim_after(a, d->s_copy))) return rc;
+    HIPCHK(d, hipEventRecord(pb->ready, d->s_copy));
+    return MTR_OK;
+}
+
+int32_t mtr_batch_animate(mtr_batch* b, mtr_anim* a, const mtr_anim_state* states) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!states) return fail(d, MTR_E_INVALID, "animate: no states");
+    int32_t rc = check_anim(d, b->model, a);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, reinterpret_cast<const float*>(states), (size_t)b->n * (sizeof(mtr_anim_state) / sizeof(float))))) return rc;
+    PoseSrc src;
+    src.anim = a; src.states = d->pose_stage;
+    return batch_write_version(b, nullptr, nullptr, a->njoints, src, d->s_copy);
+}
+
+int32_t mtr_batch_animate_device(mtr_batch* b, mtr_anim* a, const mtr_anim_state* states_dev, void* hip_stream) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!states_dev || ((uintptr_t)states_dev & 7u)) return fail(d, MTR_E_INVALID, "animate: device states must be 8-byte aligned");
+    int32_t rc = check_anim(d, b->model, a);
+    if (rc) return rc;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    PoseSrc src;
+    src.anim = a; src.states = states_dev;
+    return batch_write_version(b, nullptr, nullptr, a->njoints, src, s);
+}
+
+int32_t mtr_anim_sample(mtr_anim* a, const mtr_anim_state* states, size_t n, float* out_locals, size_t count) {
+    if (!a) return MTR_E_INVALID;
+    mtr_device* d = a->dev;
+    const size_t need = n * a->njoints * 16;
+    if (n > 0xFFFFFFu || (n && (!states || !out_locals)) || count < need) return fail(d, MTR_E_INVALID, "anim sample: n states and room for n * njoints * 16 floats");
+    if (!mtr_launch_anim_sample) return fail(d, MTR_E_UNSUPPORTED, "anim sample: built without k_anim");
+    int32_t rc = set_device(d);
+    if (rc || !n) return rc;
+    float* tmp = nullptr;  // the local matrices, then the states
+    if ((rc = dev_alloc(d, &tmp, need + n * 6))) return rc;
+    auto run = [&]() -> int32_t {
+        HIPCHK(d, hipMemcpyAsync(tmp + need, states, n * sizeof(mtr_anim_state), hipMemcpyHostToDevice, d->s_copy));
+        AnimParams ap = anim_params(a, mtr_model::Skeleton{}, tmp + need, tmp);
+        ap.pose.njoints = a->njoints;
+        mtr_launch_anim_sample(ap, (uint32_t)n, d->s_copy);
+        HIPCHK(d, hipGetLastError());
+        HIPCHK(d, hipMemcpyAsync(out_locals, tmp, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
+        return MTR_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(d->s_copy);  // also when a step failed: the buffer is freed next
+    (void)hipFree(tmp);
+    if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
 }
 
 int32_t mtr_batch_read_palettes(mtr_batch* b, float* out, size_t count) {

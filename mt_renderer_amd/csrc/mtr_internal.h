@@ -411,3 +411,14 @@ struct PoseParams {
     uint32_t njoints, path_bytes;
 };
 void mtr_launch_pose(const PoseParams& p, uint32_t ninst, hipStream_t s);
+// animation clips (k_anim.hip, SPEC.md section 14): the local matrices of every instance are sampled from a clip set and
+// folded into its palette in one kernel; the locals live in LDS only
+struct AnimParams {
+    PoseParams pose;            // locals unused; out: the palettes (k_anim) or the local matrices (k_anim_sample)
+    const uint32_t* clips;      // nclips x 4 words: first key, key count (>= 1), flags (MTR_CLIP_LOOP), 0
+    const float* keys;          // (total keys) x njoints x 12 f32, key-major, joint fastest; 16-byte aligned
+    const uint32_t* states;     // ninst x 6 words: clip_a, clip_b, x_a, x_b, w (f32 bits), pad; 8-byte aligned
+    uint32_t nclips;            // >= 1
+};
+void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s);

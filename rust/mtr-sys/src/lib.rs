@@ -70,7 +70,30 @@ pub const MTR_OWN_SUPERTILES: u32 = 2;
 pub const MTR_TEXRES_DECODED: u32 = 0;
 pub const MTR_TEXRES_BLOCKS: u32 = 1;
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame);
+opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim);
+
+/// animation clips (mtr.h, SPEC.md section 14): one key of one joint, 48 bytes
+pub const MTR_CLIP_LOOP: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_anim_key {
+    pub t: [f32; 3],
+    pub pad0: f32,
+    pub q: [f32; 4], // x, y, z, w
+    pub s: [f32; 3],
+    pub pad1: f32,
+}
+/// what one instance plays: clip A at x_a cross-faded by w with clip B at x_b, positions in keys; 24 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_anim_state {
+    pub clip_a: u32,
+    pub clip_b: u32,
+    pub x_a: f32,
+    pub x_b: f32,
+    pub w: f32,
+    pub pad: u32,
+}
 
 pub type mtr_allgather_fn = Option<unsafe extern "C" fn(send: *const c_void, recv: *mut c_void, count: usize, datatype: i32,
                                                          comm: *mut c_void, stream: *mut c_void) -> i32>;
@@ -149,5 +172,14 @@ extern "C" {
     pub fn mtr_frame_shard_bytes(frame: *mut mtr_frame) -> usize;
     pub fn mtr_frame_unpack_color_shards_on_stream(frame: *mut mtr_frame, gathered_dev: *const c_void, dst_dev: *mut c_void,
                                                    hip_stream: *mut c_void) -> i32;
+    // animation clips
+    pub fn mtr_anim_create(dev: *mut mtr_device, njoints: usize, nclips: usize, nkeys: *const u32, flags: *const u32,
+                           keys: *const mtr_anim_key, out: *mut *mut mtr_anim) -> i32;
+    pub fn mtr_anim_destroy(anim: *mut mtr_anim);
+    pub fn mtr_model_animate(model: *mut mtr_model, anim: *mut mtr_anim, state: *const mtr_anim_state) -> i32;
+    pub fn mtr_batch_animate(batch: *mut mtr_batch, anim: *mut mtr_anim, states: *const mtr_anim_state) -> i32;
+    pub fn mtr_batch_animate_device(batch: *mut mtr_batch, anim: *mut mtr_anim, states_dev: *const mtr_anim_state,
+                                    hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_sample(anim: *mut mtr_anim, states: *const mtr_anim_state, n: usize, out_locals: *mut f32, count: usize) -> i32;
 }
 pub mod files;

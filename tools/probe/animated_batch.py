@@ -3,8 +3,11 @@
 copy stream) and with device poses before every frame (Batch.set_poses(torch tensor): k_pose on torch's current stream).
 Frames are submitted without waiting, through api.FrameLoop; a timed region is `--frames` frames bracketed by a device
 synchronise, repeated `--reps` times per mode with the modes alternating, and the median is reported.
-Extra modes: device_side_stream (device poses from a non-default torch stream), poses_only (device poses, no frames).
-    python tools/probe/animated_batch.py [--only c3|c5] [--frames N] [--reps R] [--modes static,host,device] [--json OUT]"""
+Extra modes: device_side_stream (device poses from a non-default torch stream), poses_only (device poses, no frames);
+anim (host animation states before every frame: Batch.animate(numpy), 24 bytes per instance + k_anim on the copy stream),
+anim_device (states in a torch tensor: k_anim on torch's current stream), anim_only (device states, no frames).  The clip
+set (four clips of 120 / 60 / 31 / 2 keys, small bends about z) and the states are generated from --seed.
+    python tools/probe/animated_batch.py [--only c3|c5] [--frames N] [--reps R] [--modes static,host,anim] [--seed S] [--json OUT]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
@@ -16,6 +19,7 @@ ap.add_argument("--only", default="")
 ap.add_argument("--frames", type=int, default=300)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--modes", default="static,host,device,device_side_stream,poses_only")
+ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--json", default=None)
 args = ap.parse_args()
 modes = args.modes.split(",")
@@ -32,6 +36,28 @@ def poses(rng, n, k):
     return out
 
 
+def clips(rng):
+    """(keys [nkeys, 64, 12], flags) per clip: rotations about z within +-0.04 rad, small translations, unit scale"""
+    out = []
+    for nk, fl in ((120, api.CLIP_LOOP), (60, api.CLIP_LOOP), (31, 0), (2, api.CLIP_LOOP)):
+        a = rng.uniform(-0.04, 0.04, size=(nk, 64))
+        k = np.zeros((nk, 64, 12), dtype=np.float32)
+        k[..., 0:3] = rng.uniform(-0.01, 0.01, size=(nk, 64, 3))
+        k[..., 6], k[..., 7] = np.sin(a / 2), np.cos(a / 2)
+        k[..., 8:11] = 1.0
+        out.append((k, fl))
+    return out
+
+
+def states(rng, n, k):
+    """k state sets [n]: every instance somewhere in some clip, three quarters of them cross-fading into another"""
+    st = np.zeros((k, n), dtype=api.ANIM_STATE)
+    st["clip_a"], st["clip_b"] = rng.integers(0, 4, (k, n)), rng.integers(0, 4, (k, n))
+    st["x_a"], st["x_b"] = rng.uniform(0, 240, (k, n)), rng.uniform(0, 240, (k, n))
+    st["w"] = np.where(rng.random((k, n)) < 0.25, 0.0, rng.uniform(0, 1, (k, n)))
+    return st
+
+
 dev = api.Device(0)
 results = []
 for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)):
@@ -43,8 +69,12 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
     model = api.Model.new(dev, md)
     model.set_skeleton(CHAIN, np.tile(np.eye(4, dtype=np.float32).reshape(16), (64, 1)))
     batch = api.Batch(dev, model, mats, pals)
-    host = poses(np.random.default_rng(1), n, 8)
+    rng = np.random.default_rng(args.seed)
+    host = poses(rng, n, 8)
     devp = [torch.tensor(p, device="cuda:0") for p in host]
+    anim = api.Anim(dev, 64, clips(rng))
+    host_st = states(rng, n, 8)
+    dev_st = [torch.from_numpy(s.view(np.uint8).reshape(n, 24).copy()).to("cuda:0") for s in host_st]
     loop = api.FrameLoop(dev, W, H, batch=batch, view_proj=scene.to_f32_colmajor(scene.reference_view_proj(W, H)))
 
     side = torch.cuda.Stream()
@@ -58,6 +88,13 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
             elif mode == "device_side_stream":  # the same from a non-default torch stream
                 with torch.cuda.stream(side):
                     batch.set_poses(devp[k % 8])
+            elif mode == "anim":
+                batch.animate(anim, host_st[k % 8])
+            elif mode == "anim_device":
+                batch.animate(anim, dev_st[k % 8])
+            elif mode == "anim_only":  # device states and no frames: k_anim alone on the GPU
+                batch.animate(anim, dev_st[k % 8])
+                continue
             elif mode == "poses_only":  # device poses and no frames: k_pose alone on the GPU
                 batch.set_poses(devp[k % 8])
                 continue
@@ -82,6 +119,7 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
         results.append(r)
         print(json.dumps(r), flush=True)
     batch.close()
+    anim.close()
     model.close()
 dev.close()
 if args.json:
