@@ -436,6 +436,24 @@ int32_t dev_grow(mtr_device* d, T** p, uint32_t* cap, size_t need) {
     return MTR_OK;
 }
 
+// Grows the buffers of a slot that share the capacity *cap to `need` elements, if `need` exceeds it or any of them is null
+// (an earlier growth that ran out of memory): waits for the slot's stream (and for `also`, if another stream reads the
+// buffers) once, grows every pointer, and commits the capacity only when all of them succeeded, so that a failure leaves a
+// state the next frame grows again.  *grew (optional): whether it did.  The only place that pairs a sync with dev_grow.
+template <class... T>
+int32_t grow_slot(mtr_device* d, Slot& sl, hipStream_t also, bool* grew, size_t need, uint32_t* cap, T**... ptrs) {
+    const bool grow = need > *cap || (!*ptrs || ...);
+    if (grew) *grew = grow;
+    if (!grow) return MTR_OK;
+    HIPCHK(d, hipStreamSynchronize(sl.stream));
+    if (also) HIPCHK(d, hipStreamSynchronize(also));
+    int32_t rc = MTR_OK;
+    auto one = [&](auto** p) { uint32_t c = *cap; if (!rc) rc = dev_grow(d, p, &c, need); };
+    (one(ptrs), ...);
+    if (!rc) *cap = (uint32_t)need;
+    return rc;
+}
+
 int32_t set_device(mtr_device* d) {
     HIPCHK(d, hipSetDevice(d->hip_dev));
     return MTR_OK;
@@ -2056,117 +2074,123 @@ static void release_palette_pins(mtr_frame* f) {
     }
 }
 
-// Enqueues every kernel of the frame.  The caller holds d->submit_mu.
-static int32_t run_frame(mtr_frame* f) {
-    mtr_device* d = f->dev;
-    int32_t rc = set_device(d);
-    if (rc) return rc;
-    const uint32_t nbx = (f->w + MTR_BIN - 1) / MTR_BIN, nby = (f->h + MTR_BIN - 1) / MTR_BIN, nbins = nbx * nby;
-    // ---- chunk tables, capacities ----
+namespace {
+
+// run_frame's phases, in the order it calls them.  They run under d->submit_mu, which run_frame's caller holds: none takes
+// a lock.  FrameRun is what they hand to each other during one run, on run_frame's stack.
+struct FrameRun {
+    uint32_t nbins = 0;
     uint64_t total_chunks = 0, nmats = 0, tris_in = 0;
+    uint64_t this_frame = 0; int sidx = 0;               // index of this run in submission order, its status word
+    std::vector<uint32_t> mat_base, mat_stride;          // per draw: its materials in the frame's table
+    std::vector<uint32_t> inst_off, work_off, comp_off;  // per draw: its share of the slot's culling buffers (prepare_stream)
+    uint32_t strad_base = 0;   // the second half of inst_list: the slots of the instances that straddle the rank's border
+    uint32_t chunk_base = 0;   // global chunk id of the next draw's first chunk
+    uint32_t nhint = 0;        // batch draws whose culling counters this frame's tile kernel reports to the host (launch sizing)
+    uint16_t hint_word[4] = {}, hint_slot[4] = {};
+    bool use_vis = false, prof = false;
+    FrameBuffers fb{};
+};
+
+// Phase 1, the work of the frame: reads the draws; writes r.nbins and the totals; rejects a frame with too many chunks.
+int32_t count_work(mtr_frame* f, FrameRun& r) {
+    r.nbins = ((f->w + MTR_BIN - 1) / MTR_BIN) * ((f->h + MTR_BIN - 1) / MTR_BIN);
     for (auto& dr : f->draws) {
-        mtr_model* m = dr.model;
-        total_chunks += (uint64_t)dr.table->chunks.size() * dr.ninst;
-        nmats += (uint64_t)m->prims.size() * (dr.tex_override.empty() ? 1 : dr.ninst);
-        tris_in += dr.table->ntris_visible * dr.ninst;
+        r.total_chunks += (uint64_t)dr.table->chunks.size() * dr.ninst;
+        r.nmats += (uint64_t)dr.model->prims.size() * (dr.tex_override.empty() ? 1 : dr.ninst);
+        r.tris_in += dr.table->ntris_visible * dr.ninst;
     }
     // a (triangle, bin) entry is the 32-bit submission order chunk * 128 + slot, and the visibility key stores order + 1:
     // fewer than 2^25 - 1 chunks (2 G triangles) per frame
-    if (total_chunks >= (1ull << 25) - 1) return fail(d, MTR_E_OVERFLOW, "too many geometry chunks in one frame");
+    if (r.total_chunks >= (1ull << 25) - 1) return fail(f->dev, MTR_E_OVERFLOW, "too many geometry chunks in one frame");
+    return MTR_OK;
+}
+
+// Frees what only frames up to this_frame - max_inflight could still read (they have all been waited for): d->garbage.
+void collect_garbage(mtr_device* d, uint64_t this_frame) {
+    if (d->garbage.empty()) return;
+    size_t keep = 0;
+    for (auto& g : d->garbage) {
+        if (g.last_frame + d->max_inflight <= this_frame && (!g.ev || hipEventQuery(g.ev) == hipSuccess)) {
+            if (g.ev) (void)hipEventDestroy(g.ev);
+            if (g.p) (void)hipFree(g.p);
+        } else {
+            d->garbage[keep++] = g;
+        }
+    }
+    (void)hipGetLastError();  // hipEventQuery reports "not ready" as an error code
+    d->garbage.resize(keep);
+}
+
+// Phase 2, the frame's place in the device: takes the next frame index (d->frames_submitted) and waits for the frame that
+// held its place in the in-flight ring, recycles that frame's status word (examining it if nobody has), collects garbage
+// and picks the slot (d->frame_counter).  Writes r.this_frame, r.sidx, and f->status_idx, frame_index, slot and flags.
+int32_t claim_frame(mtr_device* d, mtr_frame* f, FrameRun& r) {
     // this frame's slot: the other slots may still be feeding earlier frames' tile kernels
-    const uint64_t this_frame = d->frames_submitted++;
+    const uint64_t this_frame = r.this_frame = d->frames_submitted++;
     hipEvent_t& ring = d->inflight[this_frame % d->max_inflight];
     if (ring) HIPCHK(d, hipEventSynchronize(ring));  // frame (i - max_inflight) has left the GPU
     else HIPCHK(d, hipEventCreateWithFlags(&ring, hipEventDisableTiming));
     // its status word is recycled for this frame: if nobody looked at that frame's overflow flags, do it now
-    const int sidx = (int)(this_frame % d->max_inflight);
+    const int sidx = r.sidx = (int)(this_frame % d->max_inflight);
     examine_status(d, sidx, true);
     __atomic_store_n(&d->status_host[sidx], 0u, __ATOMIC_RELEASE);
     d->status_checked[sidx] = false; d->status_released[sidx] = false; d->status_owner[sidx] = this_frame;
     f->status_idx = sidx; f->frame_index = this_frame; f->flags_checked = false; f->stats_valid = false;
-    // every frame up to this_frame - max_inflight has been waited for: collect what only they could still read
-    if (!d->garbage.empty()) {
-        size_t keep = 0;
-        for (auto& g : d->garbage) {
-            if (g.last_frame + d->max_inflight <= this_frame && (!g.ev || hipEventQuery(g.ev) == hipSuccess)) {
-                if (g.ev) (void)hipEventDestroy(g.ev);
-                if (g.p) (void)hipFree(g.p);
-            } else {
-                d->garbage[keep++] = g;
-            }
-        }
-        (void)hipGetLastError();  // hipEventQuery reports "not ready" as an error code
-        d->garbage.resize(keep);
-    }
+    collect_garbage(d, this_frame);
     f->slot = (int)(d->frame_counter++ % d->nslots);
     d->status_slot_of[sidx] = f->slot;
-    Slot& sl = d->slots[f->slot];
-    const uint64_t rec_need = total_chunks * MTR_CHUNK_SLOTS;
+    return MTR_OK;
+}
+
+// Phase 3, room in the slot for everything but culling: reads r's totals and the frame's queue demands (min_entries,
+// min_segs, force_two_pass); grows the slot's record, chunk, bin, queue buffers (grow-only); may halve d->qcap for a huge
+// bin grid; writes f->ran_direct and sl.bin_fill_dirty.
+int32_t reserve_slot_buffers(mtr_device* d, mtr_frame* f, Slot& sl, const FrameRun& r) {
+    int32_t rc;
+    const uint32_t nbins = r.nbins;
+    const uint64_t rec_need = r.total_chunks * MTR_CHUNK_SLOTS;
     if (rec_need > 0xFFFFFFF0ull) return fail(d, MTR_E_OVERFLOW, "too many triangles in one frame");
-    if (rec_need > sl.rec_cap || !sl.rec_a) {
-        HIPCHK(d, hipStreamSynchronize(sl.stream));
-        uint32_t c0 = sl.rec_cap, c1 = sl.rec_cap, c2 = sl.rec_cap;
-        if ((rc = dev_grow(d, &sl.rec_hdr, &c0, rec_need))) return rc;
-        if ((rc = dev_grow(d, &sl.rec_a, &c1, rec_need))) return rc;
-        { uint32_t c3 = sl.rec_cap; if ((rc = dev_grow(d, &sl.rec_l, &c3, rec_need))) return rc; }
-        if ((rc = dev_grow(d, &sl.rec_b, &c2, rec_need))) return rc;
-        sl.rec_cap = c0;
+    if ((rc = grow_slot(d, sl, nullptr, nullptr, rec_need, &sl.rec_cap, &sl.rec_hdr, &sl.rec_a, &sl.rec_l, &sl.rec_b))) return rc;
+    if ((rc = grow_slot(d, sl, nullptr, nullptr, r.total_chunks, &sl.chunk_cap, &sl.chunk_info))) return rc;
+    bool grew;  // mtr_frame_read_bin_counts copies from the bin arrays on the public stream
+    if ((rc = grow_slot(d, sl, d->stream, &grew, nbins + 1, &sl.bin_cap, &sl.bin_count, &sl.bin_fill, &sl.bin_start, &sl.seg_start, &sl.bin_flag))) return rc;
+    if (grew) sl.bin_fill_dirty = true;
+    // direct mode: nbins bounded queues; the bound shrinks if the bin grid is so large that the queues would not
+    // be addressable with 32 bits
+    while ((uint64_t)nbins * d->qcap > 0xF0000000ull && d->qcap > 64) d->qcap /= 2;
+    f->ran_direct = d->direct_enabled && !f->force_two_pass;
+    uint64_t e_need = std::max<uint64_t>(1u << 20, rec_need / 2) * d->queue_scale, s_need = std::max<uint64_t>(1u << 18, r.total_chunks * 8) * d->queue_scale;
+    e_need = std::max<uint64_t>(e_need, f->min_entries);
+    s_need = std::max<uint64_t>(s_need, f->min_segs);
+    if (f->ran_direct) {
+        e_need = std::max<uint64_t>(e_need, (uint64_t)nbins * d->qcap);
+        s_need = std::max<uint64_t>(s_need, (uint64_t)nbins * d->scap);
     }
-    if (total_chunks > sl.chunk_cap || !sl.chunk_info) {
-        HIPCHK(d, hipStreamSynchronize(sl.stream));
-        if ((rc = dev_grow(d, &sl.chunk_info, &sl.chunk_cap, total_chunks))) return rc;
-    }
-    if (nbins + 1 > sl.bin_cap || !sl.bin_count) {
-        HIPCHK(d, hipStreamSynchronize(sl.stream));
-        HIPCHK(d, hipStreamSynchronize(d->stream));  // mtr_frame_read_bin_counts copies from them on the public stream
-        uint32_t c0 = sl.bin_cap, c1 = sl.bin_cap, c2 = sl.bin_cap, c3 = sl.bin_cap;
-        if ((rc = dev_grow(d, &sl.bin_count, &c0, nbins + 1))) return rc;
-        if ((rc = dev_grow(d, &sl.bin_fill, &c1, nbins + 1))) return rc;
-        if ((rc = dev_grow(d, &sl.bin_start, &c2, nbins + 1))) return rc;
-        if ((rc = dev_grow(d, &sl.seg_start, &c3, nbins + 1))) return rc;
-        uint32_t c4 = sl.bin_cap;
-        if ((rc = dev_grow(d, &sl.bin_flag, &c4, nbins + 1))) return rc;
-        sl.bin_cap = c0;
-        sl.bin_fill_dirty = true;
-    }
-    {
-        // direct mode: nbins bounded queues; the bound shrinks if the bin grid is so large that the queues would not
-        // be addressable with 32 bits
-        while ((uint64_t)nbins * d->qcap > 0xF0000000ull && d->qcap > 64) d->qcap /= 2;
-        f->ran_direct = d->direct_enabled && !f->force_two_pass;
-        uint64_t e_need = std::max<uint64_t>(1u << 20, rec_need / 2) * d->queue_scale, s_need = std::max<uint64_t>(1u << 18, total_chunks * 8) * d->queue_scale;
-        e_need = std::max<uint64_t>(e_need, f->min_entries);
-        s_need = std::max<uint64_t>(s_need, f->min_segs);
-        if (f->ran_direct) {
-            e_need = std::max<uint64_t>(e_need, (uint64_t)nbins * d->qcap);
-            s_need = std::max<uint64_t>(s_need, (uint64_t)nbins * d->scap);
-        }
-        if (e_need > sl.entry_cap || !sl.entries) {
-            HIPCHK(d, hipStreamSynchronize(sl.stream));
-            if ((rc = dev_grow(d, &sl.entries, &sl.entry_cap, std::min<uint64_t>(e_need, 0xFFFFFFF0ull)))) return rc;
-        }
-        if (s_need > sl.seg_cap || !sl.segs) {
-            HIPCHK(d, hipStreamSynchronize(sl.stream));
-            if ((rc = dev_grow(d, &sl.segs, &sl.seg_cap, std::min<uint64_t>(s_need, 0xFFFFFFF0ull)))) return rc;
-        }
-    }
-    // ---- material table ----
+    if ((rc = grow_slot(d, sl, nullptr, nullptr, std::min<uint64_t>(e_need, 0xFFFFFFF0ull), &sl.entry_cap, &sl.entries))) return rc;
+    return grow_slot(d, sl, nullptr, nullptr, std::min<uint64_t>(s_need, 0xFFFFFFF0ull), &sl.seg_cap, &sl.segs);
+}
+
+// Phase 4, the material table: reads the draws' models, states and textures; rebuilds f->mats_host and f->all_opaque,
+// writes r.mat_base / r.mat_stride; grows sl.mats and uploads the table on the slot's stream when it differs from what the
+// slot holds (sl.mats_uploaded).
+int32_t upload_materials(mtr_device* d, mtr_frame* f, Slot& sl, FrameRun& r) {
     std::vector<DMat>& mats = f->mats_host;
     mats.clear();
     f->all_opaque = true;
-    mats.reserve(nmats);
-    std::vector<uint32_t> mat_base(f->draws.size()), mat_stride(f->draws.size());
+    mats.reserve(r.nmats);
+    r.mat_base.resize(f->draws.size()); r.mat_stride.resize(f->draws.size());
     for (size_t di = 0; di < f->draws.size(); di++) {
         Draw& dr = f->draws[di];
         mtr_model* m = dr.model;
-        mat_base[di] = (uint32_t)mats.size();
-        mat_stride[di] = dr.tex_override.empty() ? 0 : (uint32_t)m->prims.size();
+        r.mat_base[di] = (uint32_t)mats.size();
+        r.mat_stride[di] = dr.tex_override.empty() ? 0 : (uint32_t)m->prims.size();
         const uint32_t reps = dr.tex_override.empty() ? 1 : dr.ninst;
-        for (uint32_t r = 0; r < reps; r++)
+        for (uint32_t rep = 0; rep < reps; rep++)
             for (size_t p = 0; p < m->prims.size(); p++) {
                 DMat dm{};
                 int32_t tex = m->prim_to_texture[p];
-                if (tex >= 0 && !dr.tex_override.empty() && dr.tex_override[r] >= 0) tex = dr.tex_override[r];
+                if (tex >= 0 && !dr.tex_override.empty() && dr.tex_override[rep] >= 0) tex = dr.tex_override[rep];
                 dm.blend = dr.blend ? MTR_DB_ALPHA : MTR_DB_OFF;
                 dm.dstate = 3u;  // depth write | depth test << 1
                 dm.tlevels = 1;
@@ -2192,25 +2216,30 @@ static int32_t run_frame(mtr_frame* f) {
             }
     }
     if (mats.size() >= MTR_MAX_TEXTURED_MATERIALS) return fail(d, MTR_E_OVERFLOW, "too many materials in one frame (a record holds a 24-bit material id)");
-    if (mats.size() > sl.mat_cap || !sl.mats) {
-        HIPCHK(d, hipStreamSynchronize(sl.stream));
-        if ((rc = dev_grow(d, &sl.mats, &sl.mat_cap, std::max<size_t>(mats.size(), 64)))) return rc;
-        sl.mats_uploaded.clear();
-    }
+    bool grew;
+    int32_t rc = grow_slot(d, sl, nullptr, &grew, std::max<size_t>(mats.size(), 64), &sl.mat_cap, &sl.mats);
+    if (rc) return rc;
+    if (grew) sl.mats_uploaded.clear();
     // the material table is tiny; the copy is ordered on the stream before the kernels that read it
     if (mats.size() != sl.mats_uploaded.size() ||
         (!mats.empty() && memcmp(mats.data(), sl.mats_uploaded.data(), mats.size() * sizeof(DMat)) != 0)) {
         HIPCHK(d, hipMemcpyAsync(sl.mats, mats.data(), mats.size() * sizeof(DMat), hipMemcpyHostToDevice, sl.stream));
         sl.mats_uploaded = mats;
     }
+    return MTR_OK;
+}
 
-    FrameBuffers fb{};
+// Phase 5, what every kernel of the frame is handed: reads the slot's buffers and capacities, the frame's size, ownership
+// table and f->all_opaque / ran_direct, the device's culling, queue and tile-mode settings; writes r.fb (ownership record
+// included) and r.use_vis.  Mutates nothing else.
+void fill_frame_buffers(const mtr_device* d, const mtr_frame* f, const Slot& sl, FrameRun& r) {
+    FrameBuffers& fb = r.fb;
     fb.rec_hdr = sl.rec_hdr; fb.rec_a = sl.rec_a; fb.rec_l = sl.rec_l; fb.rec_b = sl.rec_b; fb.chunk_info = sl.chunk_info;
     fb.bin_count = sl.bin_count; fb.bin_fill = sl.bin_fill; fb.bin_start = sl.bin_start; fb.seg_start = sl.seg_start;
     fb.entries = sl.entries; fb.segs = sl.segs; fb.counters = f->fb.live();
     fb.rec_cap = sl.rec_cap; fb.entry_cap = sl.entry_cap; fb.seg_cap = sl.seg_cap;
-    fb.W = f->w; fb.H = f->h; fb.nbx = nbx; fb.nby = nby;
-    fb.own.map = MTR_OWN_INTERLEAVED; fb.own.rank = 0; fb.own.world = 1; fb.own.own_count = nbins; fb.own.own_list = nullptr;
+    fb.W = f->w; fb.H = f->h; fb.nbx = (f->w + MTR_BIN - 1) / MTR_BIN; fb.nby = (f->h + MTR_BIN - 1) / MTR_BIN;
+    fb.own.map = MTR_OWN_INTERLEAVED; fb.own.rank = 0; fb.own.world = 1; fb.own.own_count = r.nbins; fb.own.own_list = nullptr;
     if (f->own && f->shard_world > 1) {
         const OwnTable& t = *f->own;
         fb.own.map = t.map; fb.own.rank = f->shard_rank; fb.own.world = f->shard_world;
@@ -2229,233 +2258,267 @@ static int32_t run_frame(mtr_frame* f) {
     fb.direct = f->ran_direct ? 1u : 0u; fb.qcap = d->qcap; fb.scap = d->scap;
     // every material opaque (debug / overlay colours have a == 1; opaque textures sample a == 1): the frame is a
     // per-pixel (min z, latest) reduction and the visibility-key kernel applies; otherwise blend order matters
-    const bool use_vis = f->all_opaque && d->tile_mode != MTR_TILE_ORDERED;
-    fb.unordered = (f->ran_direct && use_vis) ? 1u : 0u;
+    r.use_vis = f->all_opaque && d->tile_mode != MTR_TILE_ORDERED;
+    fb.unordered = (f->ran_direct && r.use_vis) ? 1u : 0u;
+}
 
+// Phase 6, what is queued ahead of the draws.  Creates the frame's profiling events once (f->ev, r.prof), orders the run
+// behind the last frame that used the colour / depth / counter set, zeroes what this run counts into: the frame's counter
+// block (f->fb.ctr_dirty) and the slot's bin_count or bin_fill (sl.bin_fill_dirty).  Then plans the culling of a sharded
+// frame (r.fb.own.cull): k_cull_instances compacts the instance list of a batch draw to the instances that may reach this
+// rank's bins, k_cull_chunks bounds every chunk of the survivors and writes the work list of k_geom.  Reads the draws; writes
+// each draw's offsets into the slot's four culling buffers (r.inst_off, work_off, comp_off, strad_base), grows those, and
+// zeroes the culling counters when no tile kernel has (sl.cull_counts_dirty, ctr_clean_draws).
+int32_t prepare_stream(mtr_device* d, mtr_frame* f, Slot& sl, FrameRun& r) {
     if (d->profiling && !f->have_events) {
         for (auto& e : f->ev) HIPCHK(d, hipEventCreate(&e));
         f->have_events = true;
     }
-    const bool prof = d->profiling && f->have_events;
-    // one stream per slot: the slot's previous frame is ordered before this one by the stream itself
-    hipStream_t sg = sl.stream, st = sl.stream;
-    // recycled colour / depth / counter buffers: their last frame may have run on another slot's stream
+    r.prof = d->profiling && f->have_events;
+    // one stream per slot: the slot's previous frame is ordered before this one by the stream itself; recycled colour /
+    // depth / counter buffers: their last frame may have run on another slot's stream
+    hipStream_t sg = sl.stream;
     if (f->fb.used) HIPCHK(d, hipStreamWaitEvent(sg, f->fb.done, 0));
     if (f->fb.ctr_dirty) HIPCHK(d, hipMemsetAsync(f->fb.live(), 0, CTR_NUM * sizeof(uint32_t), sg));
     f->fb.ctr_dirty = true;  // a second run of this frame (queue overflow) starts from a fill again
-    if (!fb.direct) {
-        HIPCHK(d, hipMemsetAsync(sl.bin_count, 0, (size_t)(nbins + 1) * sizeof(unsigned long long), sg));
+    if (!r.fb.direct) {
+        HIPCHK(d, hipMemsetAsync(sl.bin_count, 0, (size_t)(r.nbins + 1) * sizeof(unsigned long long), sg));
         sl.bin_fill_dirty = true;
     } else if (sl.bin_fill_dirty) {
         HIPCHK(d, hipMemsetAsync(sl.bin_fill, 0, (size_t)sl.bin_cap * sizeof(unsigned long long), sg));
         sl.bin_fill_dirty = false;
     }
-    // sharded draws: k_cull_instances compacts the instance list of a batch draw to the instances that may reach this
-    // rank's bins, k_cull_chunks then bounds every chunk of the surviving instances and writes the work list of k_geom
+    if (!r.fb.own.cull) return MTR_OK;
     const size_t ndraws = f->draws.size();
-    std::vector<uint32_t> inst_off(ndraws, 0xFFFFFFFFu), work_off(ndraws, 0u), comp_off(ndraws, 0u);
-    uint32_t strad_base = 0;
+    r.inst_off.assign(ndraws, 0xFFFFFFFFu); r.work_off.assign(ndraws, 0u); r.comp_off.assign(ndraws, 0u);
+    uint64_t ninst_total = 0, work_total = 0, comp_total = 0;
+    for (size_t di = 0; di < ndraws; di++) {
+        const Draw& dr = f->draws[di];
+        const mtr_model* m = dr.model;
+        const bool sk = dr.d_palettes && dr.npal;
+        // one 16-bit mask per (instance slot, group of 16 chunks)
+        const uint64_t nx = ((uint64_t)dr.table->chunks.size() + 15) / 16;
+        // one-dimensional launch of nx * 4 * slots workgroups of 256 threads: HIP rejects 2^32 threads or more per dimension
+        if (nx * 4 * dr.ninst > 0xFFFFFFull) return fail(d, MTR_E_OVERFLOW, "too many geometry chunks in one sharded draw");
+        r.work_off[di] = (uint32_t)work_total;
+        work_total += (nx * dr.ninst + 1) & ~1ull;  // even: k_geom reads a mask through the aligned dword that holds it
+        if (!dr.d_model_mats) continue;  // a single model: chunk culling only
+        if (sk ? (!m->inst_skinned_boundable || m->n_inst_skinned == 0) : (m->n_inst_unskinned == 0)) continue;
+        r.inst_off[di] = (uint32_t)ninst_total;
+        ninst_total += dr.ninst;
+        r.comp_off[di] = (uint32_t)comp_total;
+        comp_total += (uint64_t)dr.ninst * (sk ? dr.npal + 1u : 1u);
+    }
+    if (work_total > 0xFFFFFFF0ull || comp_total > 0xFFFFFFF0ull) return fail(d, MTR_E_OVERFLOW, "too many geometry chunks in one sharded frame");
+    int32_t rc;
+    if ((rc = grow_slot(d, sl, nullptr, nullptr, std::max<uint64_t>(comp_total, 64), &sl.comp_cap, &sl.comp))) return rc;
+    if ((rc = grow_slot(d, sl, nullptr, nullptr, std::max<uint64_t>(work_total, 64), &sl.work_cap, &sl.work_mask))) return rc;
+    r.strad_base = (uint32_t)ninst_total;
+    if ((rc = grow_slot(d, sl, nullptr, nullptr, std::max<uint64_t>(2 * ninst_total, 64), &sl.inst_cap, &sl.inst_list))) return rc;
+    bool grew;
+    uint32_t words = sl.draw_cap * MTR_CULL_CTR_WORDS;  // inst_count is sized in words, its capacity kept in draws
+    if ((rc = grow_slot(d, sl, nullptr, &grew, (size_t)MTR_CULL_CTR_WORDS * std::max<size_t>(ndraws, 4), &words, &sl.inst_count))) return rc;
+    if (grew) { sl.draw_cap = words / MTR_CULL_CTR_WORDS; sl.cull_counts_dirty = true; }
+    // the counters start from zero: the tile kernel of the slot's previous frame cleared them (TileParams::zero_words)
+    if (sl.cull_counts_dirty || ndraws > sl.ctr_clean_draws)
+        HIPCHK(d, hipMemsetAsync(sl.inst_count, 0, (size_t)sl.draw_cap * MTR_CULL_CTR_WORDS * sizeof(uint32_t), sg));
+    sl.cull_counts_dirty = true;  // until a tile kernel that clears them has been queued (record_tiles)
+    // the exact two-pass fill walks every chunk's run descriptor: culled chunks write none
+    if (!r.fb.direct) HIPCHK(d, hipMemsetAsync(sl.chunk_info, 0, r.total_chunks * sizeof(ChunkInfo), sg));
+    return MTR_OK;
+}
+
+// Launch sizes of a culled batch draw from what a recent frame of this batch kept under the same ownership (k_geom.hip); a
+// camera that moves changes the count gradually: the margin and the second geometry launch take what the hint misses.
+// Gives the batch a hint slot at its first culled draw (d->hint_used, b->hint_slot / hint_key), and books the draw's
+// counters for this frame's tile kernel to report (r.nhint, hint_word, hint_slot).
+void pick_launch_hints(mtr_device* d, const mtr_frame* f, FrameRun& r, mtr_batch* b, size_t di, uint32_t* slots_hint, uint32_t* strad_hint) {
+    if (b->hint_slot < 0)
+        for (uint32_t i = 0; i < mtr_device::kHintSlots; i++)
+            if (!d->hint_used[i]) { d->hint_used[i] = true; b->hint_slot = (int)i; b->hint_key = 0; break; }
+    if (b->hint_slot < 0) return;
+    uint64_t key = 0xcbf29ce484222325ull;  // FNV-1a over what the kept set depends on
+    auto mix = [&](const void* p, size_t n) { for (size_t i = 0; i < n; i++) key = (key ^ static_cast<const uint8_t*>(p)[i]) * 0x100000001b3ull; };
+    const void* own_id = f->own;
+    mix(&own_id, sizeof own_id); mix(&f->shard_rank, sizeof f->shard_rank); mix(&r.fb.own.cull, sizeof r.fb.own.cull);
+    volatile uint32_t* hw = d->hint_host + 2 * b->hint_slot;
+    if (key != b->hint_key) { b->hint_key = key; hw[0] = hw[1] = 0u; }  // other bands, another rank: start over
+    *slots_hint = hw[0]; *strad_hint = hw[1];
+    if (r.nhint < 4 && di * MTR_CULL_CTR_WORDS < 0xFFFFu) { r.hint_word[r.nhint] = (uint16_t)(di * MTR_CULL_CTR_WORDS); r.hint_slot[r.nhint++] = (uint16_t)b->hint_slot; }
+}
+
+// Phase 7, one draw: stamps the batch, its version and the palette ring buffer the draw reads with r.this_frame (before
+// the first launch: they protect the buffers while this run's kernels are in flight), orders the slot's stream behind
+// their upload, then launches the draw's cull kernels (sharded frames) and k_geom.  Advances r.chunk_base.
+int32_t record_draw(mtr_device* d, mtr_frame* f, Slot& sl, FrameRun& r, size_t di) {
+    const FrameBuffers& fb = r.fb; hipStream_t sg = sl.stream;
+    Draw& dr = f->draws[di];
+    mtr_model* m = dr.model;
+    GeomParams gp{};
+    gp.vbuf = m->d_vbuf; gp.ibuf = m->d_ibuf; gp.prims = m->d_prims; gp.chunks = dr.table->d_chunks;
+    gp.boxes = m->d_boxes;
+    gp.nchunks = (uint32_t)dr.table->chunks.size(); gp.ninst = dr.ninst;
+    if (dr.batch) {
+        dr.batch->last_frame = r.this_frame; dr.batch->used = true;
+        mtr_batch::Ver& v = dr.batch->vers[(size_t)dr.batch_ver];
+        v.last_frame = r.this_frame; v.used = true;  // protects the version while this run's kernels are in flight
+    }
+    if (dr.pal_ready) {  // uploads of a model palette (ring) or of a batch, made on the copy stream
+        HIPCHK(d, hipStreamWaitEvent(sg, dr.pal_ready, 0));
+        if (dr.pal_slot >= 0 && (size_t)dr.pal_slot < m->pal_ring.size()) {
+            mtr_model::PalBuf& pb = m->pal_ring[(size_t)dr.pal_slot];
+            pb.last_frame = r.this_frame;  // protects the buffer while this run's kernels are in flight
+            pb.used = true;
+            // the pin stays: until the frame's overflow flags have been looked at it may be re-run (settle_frame, by
+            // mtr_frame_wait or the exchange thread, several submits later) and must then skin with the SAME palette
+        }
+    }
+    gp.model_mats = dr.d_model_mats; gp.palettes = dr.d_palettes; gp.npal = dr.d_palettes ? dr.npal : 0;
+    gp.pal_stride = dr.pal_stride;
+    memcpy(gp.vp, dr.vp, sizeof gp.vp);
+    gp.chunk_base = r.chunk_base; gp.mat_base = r.mat_base[di]; gp.mat_inst_stride = r.mat_stride[di];
+    gp.fb = fb;
+    gp.mats = sl.mats;
     if (fb.own.cull) {
-        uint64_t ninst_total = 0, work_total = 0, comp_total = 0;
-        for (size_t di = 0; di < ndraws; di++) {
-            const Draw& dr = f->draws[di];
-            const mtr_model* m = dr.model;
-            const bool sk = dr.d_palettes && dr.npal;
-            // one 16-bit mask per (instance slot, group of 16 chunks)
-            const uint64_t nx = ((uint64_t)dr.table->chunks.size() + 15) / 16;
-            // one-dimensional launch of nx * 4 * slots workgroups of 256 threads: HIP rejects 2^32 threads or more per dimension
-            if (nx * 4 * dr.ninst > 0xFFFFFFull) return fail(d, MTR_E_OVERFLOW, "too many geometry chunks in one sharded draw");
-            work_off[di] = (uint32_t)work_total;
-            work_total += (nx * dr.ninst + 1) & ~1ull;  // even: k_geom reads a mask through the aligned dword that holds it
-            if (!dr.d_model_mats) continue;  // a single model: chunk culling only
-            if (sk ? (!m->inst_skinned_boundable || m->n_inst_skinned == 0) : (m->n_inst_unskinned == 0)) continue;
-            inst_off[di] = (uint32_t)ninst_total;
-            ninst_total += dr.ninst;
-            comp_off[di] = (uint32_t)comp_total;
-            comp_total += (uint64_t)dr.ninst * (sk ? dr.npal + 1u : 1u);
+        const bool sk = dr.d_palettes && dr.npal;
+        const uint32_t inst_off = r.inst_off[di];
+        uint32_t* inst_cnt = nullptr;
+        if (inst_off != 0xFFFFFFFFu) {
+            CullParams cp{};
+            cp.boxes = m->d_inst_boxes + (sk ? m->n_inst_unskinned : 0); cp.nboxes = sk ? m->n_inst_skinned : m->n_inst_unskinned;
+            cp.ninst = dr.ninst; cp.model_mats = dr.d_model_mats; cp.palettes = gp.palettes; cp.npal = gp.npal; cp.pal_stride = gp.pal_stride;
+            memcpy(cp.vp, dr.vp, sizeof cp.vp);
+            cp.W = f->w; cp.H = f->h; cp.nbx = fb.nbx; cp.nby = fb.nby; cp.own = fb.own;
+            cp.list = sl.inst_list + inst_off; cp.count = inst_cnt = sl.inst_count + di * MTR_CULL_CTR_WORDS;
+            cp.comp = sl.comp + r.comp_off[di]; cp.ncomp = sk ? dr.npal + 1u : 1u;
+            cp.work_mask = sl.work_mask + r.work_off[di]; cp.strad = sl.inst_list + r.strad_base + inst_off; cp.nchunks = gp.nchunks;
+            cp.counters = fb.counters;
+            mtr_launch_cull_instances(cp, sg);
+            HIPCHK(d, hipGetLastError());  // a rejected launch must not pass as an empty frame (a later successful call clears the error)
         }
-        if (work_total > 0xFFFFFFF0ull || comp_total > 0xFFFFFFF0ull) return fail(d, MTR_E_OVERFLOW, "too many geometry chunks in one sharded frame");
-        if (comp_total > sl.comp_cap || !sl.comp) {
-            HIPCHK(d, hipStreamSynchronize(sl.stream));
-            if ((rc = dev_grow(d, &sl.comp, &sl.comp_cap, std::max<uint64_t>(comp_total, 64)))) return rc;
-        }
-        if (work_total > sl.work_cap || !sl.work_mask) {
-            HIPCHK(d, hipStreamSynchronize(sl.stream));
-            if ((rc = dev_grow(d, &sl.work_mask, &sl.work_cap, std::max<uint64_t>(work_total, 64)))) return rc;
-        }
-        strad_base = (uint32_t)ninst_total;  // the second half of inst_list: the slots of the instances that straddle the rank's border
-        if (2 * ninst_total > sl.inst_cap || !sl.inst_list) {
-            HIPCHK(d, hipStreamSynchronize(sl.stream));
-            if ((rc = dev_grow(d, &sl.inst_list, &sl.inst_cap, std::max<uint64_t>(2 * ninst_total, 64)))) return rc;
-        }
-        if (ndraws > sl.draw_cap || !sl.inst_count) {
-            HIPCHK(d, hipStreamSynchronize(sl.stream));
-            uint32_t words = sl.draw_cap * MTR_CULL_CTR_WORDS;
-            if ((rc = dev_grow(d, &sl.inst_count, &words, (size_t)MTR_CULL_CTR_WORDS * std::max<size_t>(ndraws, 4)))) return rc;
-            sl.draw_cap = words / MTR_CULL_CTR_WORDS;
-            sl.cull_counts_dirty = true;
-        }
-        // the counters start from zero: the tile kernel of the slot's previous frame cleared them (TileParams::zero_words)
-        if (sl.cull_counts_dirty || ndraws > sl.ctr_clean_draws)
-            HIPCHK(d, hipMemsetAsync(sl.inst_count, 0, (size_t)sl.draw_cap * MTR_CULL_CTR_WORDS * sizeof(uint32_t), sg));
-        sl.cull_counts_dirty = true;  // until a tile kernel that clears them has been queued (below)
-        // the exact two-pass fill walks every chunk's run descriptor: culled chunks write none
-        if (!fb.direct) HIPCHK(d, hipMemsetAsync(sl.chunk_info, 0, total_chunks * sizeof(ChunkInfo), sg));
-    }
-    if (prof) HIPCHK(d, hipEventRecord(f->ev[0], sg));
-    uint32_t nhint = 0;  // batch draws whose culling counters this frame's tile kernel reports to the host (launch sizing)
-    uint16_t hint_word[4] = {}, hint_slot[4] = {};
-    uint32_t chunk_base = 0;
-    for (size_t di = 0; di < f->draws.size(); di++) {
-        Draw& dr = f->draws[di];
-        mtr_model* m = dr.model;
-        GeomParams gp{};
-        gp.vbuf = m->d_vbuf; gp.ibuf = m->d_ibuf; gp.prims = m->d_prims; gp.chunks = dr.table->d_chunks;
-        gp.boxes = m->d_boxes;
-        gp.nchunks = (uint32_t)dr.table->chunks.size(); gp.ninst = dr.ninst;
-        if (dr.batch) {
-            dr.batch->last_frame = this_frame; dr.batch->used = true;
-            mtr_batch::Ver& v = dr.batch->vers[(size_t)dr.batch_ver];
-            v.last_frame = this_frame; v.used = true;  // protects the version while this run's kernels are in flight
-        }
-        if (dr.pal_ready) {  // uploads of a model palette (ring) or of a batch, made on the copy stream
-            HIPCHK(d, hipStreamWaitEvent(sg, dr.pal_ready, 0));
-            if (dr.pal_slot >= 0 && (size_t)dr.pal_slot < m->pal_ring.size()) {
-                mtr_model::PalBuf& pb = m->pal_ring[(size_t)dr.pal_slot];
-                pb.last_frame = this_frame;  // protects the buffer while this run's kernels are in flight
-                pb.used = true;
-                // the pin stays: until the frame's overflow flags have been looked at it may be re-run (settle_frame, by
-                // mtr_frame_wait or the exchange thread, several submits later) and must then skin with the SAME palette
-            }
-        }
-        gp.model_mats = dr.d_model_mats; gp.palettes = dr.d_palettes; gp.npal = dr.d_palettes ? dr.npal : 0;
-        gp.pal_stride = dr.pal_stride;
-        memcpy(gp.vp, dr.vp, sizeof gp.vp);
-        gp.chunk_base = chunk_base; gp.mat_base = mat_base[di]; gp.mat_inst_stride = mat_stride[di];
-        gp.fb = fb;
-        gp.mats = sl.mats;
-        if (fb.own.cull) {
-            const bool sk = dr.d_palettes && dr.npal;
-            uint32_t* inst_cnt = nullptr;
-            if (inst_off[di] != 0xFFFFFFFFu) {
-                CullParams cp{};
-                cp.boxes = m->d_inst_boxes + (sk ? m->n_inst_unskinned : 0); cp.nboxes = sk ? m->n_inst_skinned : m->n_inst_unskinned;
-                cp.ninst = dr.ninst; cp.model_mats = dr.d_model_mats; cp.palettes = gp.palettes; cp.npal = gp.npal; cp.pal_stride = gp.pal_stride;
-                memcpy(cp.vp, dr.vp, sizeof cp.vp);
-                cp.W = f->w; cp.H = f->h; cp.nbx = nbx; cp.nby = nby; cp.own = fb.own;
-                cp.list = sl.inst_list + inst_off[di]; cp.count = inst_cnt = sl.inst_count + di * MTR_CULL_CTR_WORDS;
-                cp.comp = sl.comp + comp_off[di]; cp.ncomp = sk ? dr.npal + 1u : 1u;
-                cp.work_mask = sl.work_mask + work_off[di]; cp.strad = sl.inst_list + strad_base + inst_off[di]; cp.nchunks = gp.nchunks;
-                cp.counters = fb.counters;
-                mtr_launch_cull_instances(cp, sg);
-                HIPCHK(d, hipGetLastError());  // a rejected launch must not pass as an empty frame (a later successful call clears the error)
-            }
-            ChunkCullParams cc{};
-            cc.chunks = dr.table->d_chunks; cc.boxes = m->d_boxes; cc.nchunks = gp.nchunks; cc.ninst = dr.ninst;
-            cc.inst_list = inst_cnt ? sl.inst_list + inst_off[di] : nullptr; cc.inst_count = inst_cnt;
-            cc.strad = inst_cnt ? sl.inst_list + strad_base + inst_off[di] : nullptr;
-            cc.model_mats = dr.d_model_mats; cc.palettes = gp.palettes; cc.npal = gp.npal; cc.pal_stride = gp.pal_stride;
-            memcpy(cc.vp, dr.vp, sizeof cc.vp);
-            cc.fb = fb;
-            cc.comp = inst_cnt ? sl.comp + comp_off[di] : nullptr;
-            cc.work_mask = sl.work_mask + work_off[di];
-            cc.keep_all = (fb.own.cull == 3u || fb.own.cull == 4u) ? 1u : 0u;
-            if (inst_cnt && dr.batch && !dr.owned_batch) {
-                // launch sizes from what a recent frame of this batch kept under the same ownership (k_geom.hip); a camera that
-                // moves changes the count gradually: the margin and the second geometry launch take what the hint misses
-                mtr_batch* b = dr.batch;
-                if (b->hint_slot < 0)
-                    for (uint32_t i = 0; i < mtr_device::kHintSlots; i++)
-                        if (!d->hint_used[i]) { d->hint_used[i] = true; b->hint_slot = (int)i; b->hint_key = 0; break; }
-                if (b->hint_slot >= 0) {
-                    uint64_t key = 0xcbf29ce484222325ull;  // FNV-1a over what the kept set depends on
-                    auto mix = [&](const void* p, size_t n) { for (size_t i = 0; i < n; i++) key = (key ^ static_cast<const uint8_t*>(p)[i]) * 0x100000001b3ull; };
-                    const void* own_id = f->own;
-                    mix(&own_id, sizeof own_id); mix(&f->shard_rank, sizeof f->shard_rank); mix(&fb.own.cull, sizeof fb.own.cull);
-                    volatile uint32_t* hw = d->hint_host + 2 * b->hint_slot;
-                    if (key != b->hint_key) { b->hint_key = key; hw[0] = hw[1] = 0u; }  // other bands, another rank: start over
-                    gp.slots_hint = hw[0]; cc.strad_hint = hw[1];
-                    if (nhint < 4 && di * MTR_CULL_CTR_WORDS < 0xFFFFu) { hint_word[nhint] = (uint16_t)(di * MTR_CULL_CTR_WORDS); hint_slot[nhint++] = (uint16_t)b->hint_slot; }
-                }
-            }
-            mtr_launch_cull_chunks(cc, sg);
-            HIPCHK(d, hipGetLastError());
-            gp.work_mask = cc.work_mask; gp.work_nx = (gp.nchunks + 15u) / 16u;
-            gp.inst_list = cc.inst_list; gp.inst_count = cc.inst_count;
-        }
-        gp.slots_override = d->geom_slots;
-        // a draw of fewer than ~64 k geometry waves (the headline model: 16 k) overlaps with the neighbouring frames' tile
-        // kernels for most of its life: the build that leaves them a wave slot per SIMD (k_geom.hip: GEOM_OCC_SMALL)
-        gp.small_draw = ((uint64_t)gp.nchunks * dr.ninst < 65536u) ? 1u : 0u;
-        mtr_launch_geom(gp, sg);
+        ChunkCullParams cc{};
+        cc.chunks = dr.table->d_chunks; cc.boxes = m->d_boxes; cc.nchunks = gp.nchunks; cc.ninst = dr.ninst;
+        cc.inst_list = inst_cnt ? sl.inst_list + inst_off : nullptr; cc.inst_count = inst_cnt;
+        cc.strad = inst_cnt ? sl.inst_list + r.strad_base + inst_off : nullptr;
+        cc.model_mats = dr.d_model_mats; cc.palettes = gp.palettes; cc.npal = gp.npal; cc.pal_stride = gp.pal_stride;
+        memcpy(cc.vp, dr.vp, sizeof cc.vp);
+        cc.fb = fb;
+        cc.comp = inst_cnt ? sl.comp + r.comp_off[di] : nullptr;
+        cc.work_mask = sl.work_mask + r.work_off[di];
+        cc.keep_all = (fb.own.cull == 3u || fb.own.cull == 4u) ? 1u : 0u;
+        if (inst_cnt && dr.batch && !dr.owned_batch) pick_launch_hints(d, f, r, dr.batch, di, &gp.slots_hint, &cc.strad_hint);
+        mtr_launch_cull_chunks(cc, sg);
         HIPCHK(d, hipGetLastError());
-        chunk_base += gp.nchunks * dr.ninst;
+        gp.work_mask = cc.work_mask; gp.work_nx = (gp.nchunks + 15u) / 16u;
+        gp.inst_list = cc.inst_list; gp.inst_count = cc.inst_count;
     }
-    if (prof) HIPCHK(d, hipEventRecord(f->ev[1], sg));
+    gp.slots_override = d->geom_slots;
+    // a draw of fewer than ~64 k geometry waves (the headline model: 16 k) overlaps with the neighbouring frames' tile
+    // kernels for most of its life: the build that leaves them a wave slot per SIMD (k_geom.hip: GEOM_OCC_SMALL)
+    gp.small_draw = ((uint64_t)gp.nchunks * dr.ninst < 65536u) ? 1u : 0u;
+    mtr_launch_geom(gp, sg);
+    HIPCHK(d, hipGetLastError());
+    r.chunk_base += gp.nchunks * dr.ninst;
+    return MTR_OK;
+}
+
+// Phase 8, binning and the tile kernels: scan and fill for the two-pass queues (with their profiling events), then the
+// visibility kernel, the ordered kernel, or both (a mixed frame).  Reads f->mats_host, r.use_vis, the hints; hands the tile
+// kernel the frame's other counter block and the slot's culling counters to zero for the next frame (f->fb.next_zeroed,
+// sl.cull_counts_dirty, ctr_clean_draws), writes f->stats.tile_kernel, publishes the status word of a rank without a bin.
+int32_t record_tiles(mtr_device* d, mtr_frame* f, Slot& sl, FrameRun& r) {
+    const FrameBuffers& fb = r.fb; hipStream_t st = sl.stream;
     // single-pass binning launches neither kernel: no event either (an event costs the stream ~5 us, which would count
     // as frame latency); mtr_frame_wait reports both stages as 0
-    if (!fb.direct) { mtr_launch_scan(fb, sg); HIPCHK(d, hipGetLastError()); }
-    if (prof && !fb.direct) HIPCHK(d, hipEventRecord(f->ev[2], sg));
-    if (!fb.direct) { mtr_launch_fill(fb, (uint32_t)total_chunks, sg); HIPCHK(d, hipGetLastError()); }
-    if (prof && !fb.direct) HIPCHK(d, hipEventRecord(f->ev[3], st));
+    if (!fb.direct) { mtr_launch_scan(fb, st); HIPCHK(d, hipGetLastError()); }
+    if (r.prof && !fb.direct) HIPCHK(d, hipEventRecord(f->ev[2], st));
+    if (!fb.direct) { mtr_launch_fill(fb, (uint32_t)r.total_chunks, st); HIPCHK(d, hipGetLastError()); }
+    if (r.prof && !fb.direct) HIPCHK(d, hipEventRecord(f->ev[3], st));
     TileParams tp{};
     tp.fb = fb; tp.mats = sl.mats; tp.color = f->fb.color; tp.depth = f->fb.depth;
     tp.clear_rgba8 = f->clear_rgba8; tp.clear_depth = f->clear_depth;
     bool any_textured = false;
-    for (const DMat& dm : mats) any_textured = any_textured || dm.shader == MTR_SH_TEXTURED;
+    for (const DMat& dm : f->mats_host) any_textured = any_textured || dm.shader == MTR_SH_TEXTURED;
     // some material translucent, some not: the visibility kernel takes the bins whose queue holds only opaque
     // triangles (order-free), flags the others, and the ordered kernel renders those in submission order
     // ... and also the bins whose translucent triangles are merely alpha-blended in the default depth state (prefix minima
     // of z, k_tile_vis.hip: STAIR).  Only when every material is HARD order-dependent (additive blend, depth write / test
     // off) is there nothing for it to do.
     bool any_soft = false;
-    for (const DMat& dm : mats) any_soft = any_soft || !dm.translucent || !(dm.blend == MTR_DB_ADD || dm.dstate != 3u);
-    const bool mixed = !use_vis && d->tile_mode == MTR_TILE_AUTO && any_soft;
+    for (const DMat& dm : f->mats_host) any_soft = any_soft || !dm.translucent || !(dm.blend == MTR_DB_ADD || dm.dstate != 3u);
+    const bool use_vis = r.use_vis, mixed = !use_vis && d->tile_mode == MTR_TILE_AUTO && any_soft;
     tp.bin_flag = sl.bin_flag; tp.mixed = mixed ? 1u : 0u;
     tp.zero_next = f->fb.other();
     f->fb.next_zeroed = fb.own.own_count != 0;  // a rank without a bin launches no tile workgroup
-    tp.host_status = d->status_dev + sidx;
+    tp.host_status = d->status_dev + r.sidx;
     tp.vis_waves = d->vis_waves;
-    {
-        // the previous frame still on the GPU: this one will share it, balance across the XCDs wins; otherwise the frame
-        // has the GPU to itself and the contiguous order's locality gives the shorter kernel (latency)
-        bool shared = false;
-        if (this_frame > 0) {
-            hipEvent_t prev = d->inflight[(this_frame - 1) % d->max_inflight];
-            shared = prev && hipEventQuery(prev) == hipErrorNotReady;
-        }
-        tp.xcd_run = d->xcd_run != mtr_device::kXcdRunAuto ? d->xcd_run : ((fb.own.world <= 1 && shared) ? std::max(16u, nbx / 4u) : 0u);
+    // the previous frame still on the GPU: this one will share it, balance across the XCDs wins; otherwise the frame
+    // has the GPU to itself and the contiguous order's locality gives the shorter kernel (latency)
+    bool shared = false;
+    if (r.this_frame > 0) {
+        hipEvent_t prev = d->inflight[(r.this_frame - 1) % d->max_inflight];
+        shared = prev && hipEventQuery(prev) == hipErrorNotReady;
     }
+    tp.xcd_run = d->xcd_run != mtr_device::kXcdRunAuto ? d->xcd_run : ((fb.own.world <= 1 && shared) ? std::max(16u, fb.nbx / 4u) : 0u);
     if (fb.own.cull && fb.own.own_count) {  // this frame's tile kernel clears the slot's culling counters for the next one
-        tp.zero_words = sl.inst_count; tp.zero_nwords = (uint32_t)ndraws * MTR_CULL_CTR_WORDS;
-        tp.hint_out = d->hint_dev; tp.nhint = nhint;
-        for (uint32_t k = 0; k < nhint; k++) { tp.hint_word[k] = hint_word[k]; tp.hint_slot[k] = hint_slot[k]; }
+        const uint32_t ndraws = (uint32_t)f->draws.size();
+        tp.zero_words = sl.inst_count; tp.zero_nwords = ndraws * MTR_CULL_CTR_WORDS;
+        tp.hint_out = d->hint_dev; tp.nhint = r.nhint;
+        for (uint32_t k = 0; k < r.nhint; k++) { tp.hint_word[k] = r.hint_word[k]; tp.hint_slot[k] = r.hint_slot[k]; }
         sl.cull_counts_dirty = false;
-        sl.ctr_clean_draws = (uint32_t)ndraws;  // what a frame with more draws than this one finds beyond is stale
+        sl.ctr_clean_draws = ndraws;  // what a frame with more draws than this one finds beyond is stale
     }
     f->stats.tile_kernel = use_vis ? MTR_TILE_VISIBILITY : (mixed ? MTR_TILE_MIXED : MTR_TILE_ORDERED);
     if (use_vis || mixed) { mtr_launch_tile_vis(tp, any_textured, st); HIPCHK(d, hipGetLastError()); }
     if (mixed) tp.nhint = 0;  // the visibility kernel of a mixed frame has reported (and cleared) the counters: the second kernel would report zeros
     if (!use_vis) { mtr_launch_tile(tp, any_textured, st); HIPCHK(d, hipGetLastError()); }
     // a rank without a bin launches no tile workgroup: nobody else would publish the (clean) status
-    if (fb.own.own_count == 0) __atomic_store_n(&d->status_host[sidx], 0x80000000u, __ATOMIC_RELEASE);
-    if (prof) HIPCHK(d, hipEventRecord(f->ev[4], st));
-    HIPCHK(d, hipEventRecord(f->fb.done, st));
-    HIPCHK(d, hipEventRecord(ring, st));
+    if (fb.own.own_count == 0) __atomic_store_n(&d->status_host[r.sidx], 0x80000000u, __ATOMIC_RELEASE);
+    return MTR_OK;
+}
+
+// Phase 9, the end of a successful run: records the last profiling event, the framebuffer's and the in-flight ring's
+// events behind the tile kernel, makes the public stream wait for the frame (unless the exchange thread consumes it),
+// and only then resets f->stats (keeping the tile kernel chosen) and f->total_chunks.
+int32_t finish_frame(mtr_device* d, mtr_frame* f, Slot& sl, const FrameRun& r) {
+    if (r.prof) HIPCHK(d, hipEventRecord(f->ev[4], sl.stream));
+    HIPCHK(d, hipEventRecord(f->fb.done, sl.stream));
+    HIPCHK(d, hipEventRecord(d->inflight[r.this_frame % d->max_inflight], sl.stream));
     f->fb.used = true;
     // the device's public stream (read-backs, shard packing, the caller's own work) sees the framebuffer complete
     if (!f->for_exchange) HIPCHK(d, hipStreamWaitEvent(d->stream, f->fb.done, 0));
     HIPCHK(d, hipGetLastError());
-    {
-        const uint32_t tk = f->stats.tile_kernel;
-        f->stats = mtr_frame_stats{};
-        f->stats.tile_kernel = tk;
-        f->stats.binning = f->ran_direct ? 1u : 2u;
-    }
-    f->stats.tris_in = tris_in;
-    f->total_chunks = total_chunks;
-    f->stats.width = f->w; f->stats.height = f->h; f->stats.nbins = nbins; f->stats.ndraws = (uint32_t)f->draws.size();
+    const uint32_t tk = f->stats.tile_kernel;
+    f->stats = mtr_frame_stats{};
+    f->stats.tile_kernel = tk;
+    f->stats.binning = f->ran_direct ? 1u : 2u;
+    f->stats.tris_in = r.tris_in;
+    f->total_chunks = r.total_chunks;
+    f->stats.width = f->w; f->stats.height = f->h; f->stats.nbins = r.nbins; f->stats.ndraws = (uint32_t)f->draws.size();
     return MTR_OK;
+}
+
+}  // namespace
+
+// Enqueues every kernel of the frame.  The caller holds d->submit_mu.
+static int32_t run_frame(mtr_frame* f) {
+    mtr_device* d = f->dev;
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    FrameRun r;
+    if ((rc = count_work(f, r))) return rc;
+    if ((rc = claim_frame(d, f, r))) return rc;
+    Slot& sl = d->slots[f->slot];
+    if ((rc = reserve_slot_buffers(d, f, sl, r))) return rc;
+    if ((rc = upload_materials(d, f, sl, r))) return rc;
+    fill_frame_buffers(d, f, sl, r);
+    if ((rc = prepare_stream(d, f, sl, r))) return rc;
+    if (r.prof) HIPCHK(d, hipEventRecord(f->ev[0], sl.stream));
+    for (size_t di = 0; di < f->draws.size(); di++)
+        if ((rc = record_draw(d, f, sl, r, di))) return rc;
+    if (r.prof) HIPCHK(d, hipEventRecord(f->ev[1], sl.stream));
+    if ((rc = record_tiles(d, f, sl, r))) return rc;
+    return finish_frame(d, f, sl, r);
 }
 
 int32_t mtr_frame_submit(mtr_frame* f) {

@@ -1,0 +1,35 @@
+"""CPU: the launch sequence of a frame.  The host side of libmtr.so (csrc/mtr_api.cpp) compiled by g++ with AddressSanitizer
+and UBSan over the stand-in HIP runtime (tests/cpp/hip_stub), with kernel launchers that log what they are asked to launch
+and a trace hook that logs the memsets, uploads, waits, event records and stream syncs in between; the expected logs --
+which kernels run in which order for direct / two-pass binning, visibility / mixed / ordered tile kernels, sharded draws,
+overflow re-runs, an empty band, profiling -- are written out in tests/cpp/frame_launch_log.cpp."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def launch_log_exe(tmp_path_factory):
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path_factory.mktemp("frame_launch_log") / "frame_launch_log")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "frame_launch_log.cpp"), "-o", exe])
+    return exe
+
+
+def test_launch_sequences(launch_log_exe):
+    r = subprocess.run([launch_log_exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "failed=0" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-6000:])
+
+
+def test_a_failed_allocation_never_leaves_a_null_buffer(launch_log_exe):
+    """hipMalloc fails at each allocation of a submit in turn, on a fresh slot and on one that has already served a smaller
+    frame: MTR_E_NOMEM, and the frame submitted next succeeds or fails the same way without a launcher seeing a null buffer."""
+    r = subprocess.run([launch_log_exe, "nomem"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "first_frame_bad=0 grown_slot_bad=0:" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-6000:])

@@ -152,3 +152,36 @@ def test_prim_state_errors(gpu_device):
     m.set_prim_states(np.array([(1, 0, 0, 2)], dtype=np.uint8))
     m.set_prim_states(None)
     m.close()
+
+
+def test_stage_timings_follow_the_binning_mode():
+    """mtr_frame_get_timings: single-pass binning runs (and times) no scan and no fill; the two-pass queues time all four
+    stages.  Sign and finiteness only: no claim about how long a stage takes."""
+    from mt_renderer_amd import api
+    dev = api.Device(0)
+    try:
+        dev.set_profiling(True)
+        m = api.Model.new(dev, scene.cube_model())
+        M = scene.cube_transform(64, 64)
+
+        def frame():
+            fr = api.Frame(dev, 64, 64)
+            try:
+                m.render(fr, M)
+                fr.end()
+                return fr.timings_ms(), fr.stats()
+            finally:
+                fr.close()
+
+        ms, st = frame()
+        assert st["binning"] == 1
+        assert ms["scan"] == 0.0 and ms["fill"] == 0.0, ms
+        assert np.isfinite(ms["geom"]) and np.isfinite(ms["tile"]) and ms["tile"] > 0.0, ms
+        dev.set_binning(False)
+        ms, st = frame()
+        assert st["binning"] == 2
+        assert all(np.isfinite(ms[k]) and ms[k] >= 0.0 for k in ("geom", "scan", "fill", "tile")), ms
+        assert ms["tile"] > 0.0, ms
+        m.close()
+    finally:
+        dev.close()
