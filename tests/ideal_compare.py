@@ -13,15 +13,41 @@ exact arithmetic").  Every tolerance is derived from the rules, none from what t
 * uv (256 x 256 ramp texture R = x, G = y): ``|R - clamp(256 u - 0.5, 0, 255)| <= 0.5 + 0.5 + 256 (|grad u| sqrt(2)/512 +
   rounding terms) + 2^-10``: half a texel between the nearest and the linear filter, half a step for the store;
 * ``tris_in`` is the ideal's count of assembled triangles.
+
+The fragment rule (scenes rendered with ``fragments=True``; SPEC 7, 8 and 10) replaces identity and uv on them:
+
+* ``E_u = |grad u| sqrt(2)/512 + err_u + gamma_11 (1 + 2 sum|beta_i|) iw_max (max|u_i| + |u|) / iw`` at a pixel: snapping, the vertex
+  stage's rounding carried to the pixel, and the 11 rounded operations of ``u = u'/iw`` (``1/w``, ``u iw``, a difference, two
+  conversions, a reciprocal and a product for ``b``, two fmas, the division) on the absolute values of the interpolation
+  written as SPEC 7 writes it; ``beta`` the screen-space barycentrics, ``iw_max`` the largest ``1/w`` of the visible part;
+* a quad difference is uncertain by the sum over its two ends, a product by that sum times ``Wt`` plus two roundings;
+* a pixel is *decision-ambiguous* (left out; at most 2 % of the textured pixels) when the products do not settle linear
+  against nearest (every product + margin <= 1, or one product - margin > 1), when the interval of ``m`` reaches across a level
+  threshold below ``L - 1``, or when its nearest sample has more than four candidate texels;
+* a source is an exact colour, a set of up to four candidate texels ``floor((u +- E_u) W_l) x floor((v +- E_v) H_l)``, or the
+  bilinear value +- ``Lx Wt E_u + Ly Ht E_v + 3 gamma_8`` with ``Lx, Ly`` the largest texel-to-texel differences over the 3 x 3
+  texels that hold every cell the uncertainty box touches (bilinear interpolation is continuous across cells);
+* the blend is linear in each of ``s``, ``a`` and ``d``: its extremes over a box are at the box's corners, so the interval of a
+  layer is the hull of the rule at the 8 corners of every candidate, widened by ``255 x 2 gamma_6`` for the binary32 blend
+  and store, and stored as ``[rint(lo), rint(hi)]``; the stored bytes are what the next layer reads.  The frame's byte
+  must lie in the last interval, per channel, alpha included;
+* a pixel whose chain holds a translucent or state-changed fragment and a depth decision within the two ``tol`` is left out
+  as a near tie; depth is compared with the last fragment that wrote it.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from tests.ideal_renderer import PALETTE, SNAP
+from tests import ideal_renderer as ir
+from tests.ideal_renderer import PALETTE, SNAP, gamma
 
 AMBIGUOUS_CAP = 0.02
 NEAR_TIE_CAP = 0.01
+DECISION_CAP = 0.02          # of a scene's textured pixels
+SINGLE_CANDIDATE_FLOOR = 0.9
+EXACT_BYTE_FLOOR = 0.9
+T_ROUND = 255.0 * 2.0 * gamma(6)   # SPEC 7 blend and store in binary32: d / 255, 1 - a, d (1 - a), the fma, x 255; |terms| <= 2
+T_LINEAR = 3.0 * gamma(8)          # SPEC 7 bilinear: byte / 255, two differences, three fmas; |terms| <= 3
 
 
 def ramp_texture():
@@ -32,11 +58,19 @@ def ramp_texture():
     return scene.TextureData(256, 256, scene.TEX_RGBA8, img.tobytes())
 
 
+def near_ties(ideal):
+    """pixels whose depth (and colour) may legally be that of either of two fragments"""
+    tie = ideal.covered & (ideal.gap <= 2.0 * ideal.tol)
+    if ideal.fragments:
+        # where the order or a state matters, every depth decision of the chain counts, and the pixel is left out
+        tie = np.where(ideal.special, ideal.decision_tie, tie)
+    return tie & ~ideal.ambiguous
+
+
 def scene_shares(ideal):
     """(ambiguous share, near-tie share) of a scene -- from the ideal alone"""
     n = ideal.w * ideal.h
-    tie = ideal.covered & ~ideal.ambiguous & (ideal.gap <= 2.0 * ideal.tol)
-    return float(ideal.ambiguous.sum()) / n, float(tie.sum()) / n
+    return float(ideal.ambiguous.sum()) / n, float(near_ties(ideal).sum()) / n
 
 
 def assert_scene_caps(ideal, what=""):
@@ -44,6 +78,130 @@ def assert_scene_caps(ideal, what=""):
     assert amb <= AMBIGUOUS_CAP, f"{what}: {100 * amb:.2f} % of the pixels are ambiguous (cap 2 %): the scene is unfit"
     assert tie <= NEAR_TIE_CAP, f"{what}: {100 * tie:.2f} % of the pixels are near ties (cap 1 %): the scene is unfit"
     assert ideal.covered.mean() > 0.02, f"{what}: the scene covers next to nothing"
+    if ideal.fragments:
+        x = expected(ideal)
+        assert x.decision_share <= DECISION_CAP, \
+            f"{what}: {100 * x.decision_share:.2f} % of the textured pixels are decision-ambiguous (cap 2 %): the scene is unfit"
+        assert x.single_share >= SINGLE_CANDIDATE_FLOOR, \
+            f"{what}: only {100 * x.single_share:.1f} % of the nearest samples have one candidate texel (floor 90 %)"
+        assert x.exact_share >= EXACT_BYTE_FLOOR, \
+            f"{what}: only {100 * x.exact_share:.1f} % of the bytes from exact sources have a one-byte interval (floor 90 %)"
+        assert x.compare.mean() > 0.02, f"{what}: the fragment rule compares next to nothing"
+
+
+class Expected:
+    """what the fragment rule expects of a frame: lo, hi [H, W, 4] byte intervals, compare [H, W] and the scene's shares"""
+
+
+def _sources(ideal, i):
+    """the sources of fragments ``i``: up to four candidates with an interval each -> (lo [4, n, 4], hi [4, n, 4] in
+    [0, 1], decision-ambiguous [n], single candidate [n])"""
+    F = ideal.frags
+    n = i.size
+    lo, hi = np.ones((4, n, 4)), np.ones((4, n, 4))
+    amb = F.decision_ambiguous[i].copy()
+    single = np.ones(n, dtype=bool)
+    flat = F.kind[i] == 0
+    lo[:, flat, :3] = hi[:, flat, :3] = PALETTE[F.did[i[flat]] % 20] / 255.0
+    W = np.array([T.W for T in ideal.textures] + [1], dtype=np.float64)[F.tex[i]]
+    H = np.array([T.H for T in ideal.textures] + [1], dtype=np.float64)[F.tex[i]]
+    u, v = F.u[i], F.v[i]
+    k = np.nonzero(F.kind[i] == 2)[0]
+    if k.size:
+        j = i[k]
+        eu = F.Eu[j] + gamma(1) * np.abs(u[k])    # and the rounded product u W_l
+        ev = F.Ev[j] + gamma(1) * np.abs(v[k])
+        x0, y0 = ir.nearest_index(ideal, j, u[k] - eu, v[k] - ev)
+        x1, y1 = ir.nearest_index(ideal, j, u[k] + eu, v[k] + ev)
+        amb[k] |= (x1 - x0 > 1) | (y1 - y0 > 1)        # more than four candidate texels
+        single[k] = (x1 == x0) & (y1 == y0)
+        for c, (su, sv) in enumerate(((-1, -1), (1, -1), (-1, 1), (1, 1))):
+            lo[c, k] = hi[c, k] = ir.nearest_at(ideal, j, u[k] + su * eu, v[k] + sv * ev)
+    k = np.nonzero(F.kind[i] == 1)[0]
+    if k.size:
+        j = i[k]
+        mid = ir.linear_at(ideal, j, u[k], v[k])
+        # the uncertainty box in texel units, with the roundings of x = u Wt - 0.5
+        x, y = u[k] * W[k] - 0.5, v[k] * H[k] - 0.5
+        ex = W[k] * F.Eu[j] + gamma(2) * (np.abs(u[k]) * W[k] + 0.5)
+        ey = H[k] * F.Ev[j] + gamma(2) * (np.abs(v[k]) * H[k] + 0.5)
+        xa, ya = np.floor(x - ex), np.floor(y - ey)
+        amb[k] |= (np.floor(x + ex) + 1 - xa > 2) | (np.floor(y + ey) + 1 - ya > 2)   # the box is wider than a cell
+        # the largest texel-to-texel differences over the 3 x 3 texels that hold every cell the box touches
+        zero = np.zeros(k.size, dtype=np.int64)
+        t = [[ir.texels(ideal, F.tex[j], zero, ir._clampi(xa + c, W[k]), ir._clampi(ya + r, H[k])) for c in range(3)]
+             for r in range(3)]
+        Lx = np.max([np.abs(t[r][c + 1] - t[r][c]) for r in range(3) for c in range(2)], axis=0)
+        Ly = np.max([np.abs(t[r + 1][c] - t[r][c]) for r in range(2) for c in range(3)], axis=0)
+        rad = Lx * ex[:, None] + Ly * ey[:, None] + T_LINEAR
+        lo[:, k] = np.clip(mid - rad, 0.0, 1.0)
+        hi[:, k] = np.clip(mid + rad, 0.0, 1.0)
+    return lo, hi, amb, single
+
+
+def expected(ideal) -> Expected:
+    """SPEC 13, fragment rule: the colour chain of every pixel propagated as intervals -- from the ideal alone"""
+    if getattr(ideal, "_expected", None) is not None:
+        return ideal._expected
+    F = ideal.frags
+    w, h = ideal.w, ideal.h
+    P = w * h
+    clear = np.rint(np.clip(np.array(ideal.clear), 0.0, 1.0) * 255.0)
+    b_lo, b_hi = np.tile(clear, (P, 1)), np.tile(clear, (P, 1))
+    d_lo, d_hi = b_lo / 255.0, b_hi / 255.0
+    r_lo, r_hi = b_lo.copy(), b_hi.copy()         # the real interval ahead of the last store
+    amb, inexact, textured = np.zeros(P, dtype=bool), np.zeros(P, dtype=bool), np.zeros(P, dtype=bool)
+    n_nearest, n_single = np.zeros(P), np.zeros(P)
+    multi = np.zeros(P, dtype=bool)               # a candidate set with more than one colour in the live chain
+    for r in range(F.layers):
+        i = np.nonzero((F.rank == r) & F.passes)[0]
+        if not i.size:
+            continue
+        p = F.pix[i]
+        s_lo, s_hi, a_own, single = _sources(ideal, i)
+        mode = F.blend[i]
+        o_lo, o_hi = np.full((i.size, 4), np.inf), np.full((i.size, 4), -np.inf)
+        # the blend is linear in each of s, a and d with the others fixed: its extremes over a box are at the corners
+        for c in range(4):
+            for rgb in (s_lo[c], s_hi[c]):
+                for a in (s_lo[c][:, 3], s_hi[c][:, 3]):
+                    s = rgb.copy()
+                    s[:, 3] = a
+                    for d in (d_lo[p], d_hi[p]):
+                        out = ir.blend(ideal, mode, s, d)
+                        o_lo, o_hi = np.minimum(o_lo, out), np.maximum(o_hi, out)
+        x_lo = np.clip(np.clip(o_lo, 0.0, 1.0) * 255.0 - T_ROUND, 0.0, 255.0)
+        x_hi = np.clip(np.clip(o_hi, 0.0, 1.0) * 255.0 + T_ROUND, 0.0, 255.0)
+        b_lo[p], b_hi[p] = ir.store(ideal, x_lo), ir.store(ideal, x_hi)
+        r_lo[p], r_hi[p] = x_lo, x_hi
+        d_lo[p], d_hi[p] = ir.carried(ideal, b_lo[p], x_lo), ir.carried(ideal, b_hi[p], x_hi)
+        # a fragment that replaces what lies under it (OFF, or ALPHA with alpha exactly 1) starts the chain afresh
+        h_lo, h_hi = s_lo.min(axis=0), s_hi.max(axis=0)
+        fresh = (mode == ir.BLEND_OFF) | ((mode == ir.BLEND_ALPHA) & (h_lo[:, 3] == 1.0))
+        wide = (h_hi - h_lo).max(axis=1) > 1e-9
+        tex = F.kind[i] != 0
+        near = F.kind[i] == 2
+        amb[p] = np.where(fresh, a_own, amb[p] | a_own)
+        inexact[p] = np.where(fresh, wide, inexact[p] | wide)
+        textured[p] = np.where(fresh, tex, textured[p] | tex)
+        multi[p] = np.where(fresh, near & wide, multi[p] | (near & wide))
+        n_nearest[p] = np.where(fresh, 0, n_nearest[p]) + near
+        n_single[p] = np.where(fresh, 0, n_single[p]) + (near & single)
+    x = ideal._expected = Expected()
+    sh = (h, w)
+    amb, inexact, textured = amb.reshape(sh), inexact.reshape(sh), textured.reshape(sh)
+    rest = ~ideal.ambiguous & ~near_ties(ideal)
+    x.lo, x.hi = b_lo.reshape(h, w, 4), b_hi.reshape(h, w, 4)
+    x.real_lo, x.real_hi = r_lo.reshape(h, w, 4), r_hi.reshape(h, w, 4)
+    x.compare = rest & ~amb
+    x.inexact, x.textured, x.multi = inexact, textured, multi.reshape(sh)
+    x.textured_compared = int((x.compare & textured).sum())
+    x.decision_share = float((rest & amb & textured).sum()) / max(1, int((rest & textured).sum()))
+    nn = float(n_nearest.reshape(sh)[x.compare].sum())
+    x.single_share = float(n_single.reshape(sh)[x.compare].sum()) / nn if nn else 1.0
+    ex = x.compare & ~inexact
+    x.exact_share = float((x.lo == x.hi)[ex].mean()) if ex.any() else 1.0
+    return x
 
 
 class Report:
@@ -52,6 +210,11 @@ class Report:
         self.coverage_wrong = self.identity_wrong = 0
         self.depth_ratio = self.uv_ratio = 0.0
         self.compared = 0
+        # the fragment rule
+        self.blend_wrong = self.textured_compared = 0
+        self.decision_share = 0.0
+        self.single_share = self.exact_share = 1.0
+        self.linear_ratio = self.blend_ratio = 0.0   # share of its margin the worst byte uses: inexact / exact sources
 
     @property
     def ok(self):
@@ -60,6 +223,12 @@ class Report:
     def line(self):
         return (f"compared {self.compared} px, coverage wrong {self.coverage_wrong}, identity wrong {self.identity_wrong}, "
                 f"depth err/tol {self.depth_ratio:.3f}, uv err/bound {self.uv_ratio:.3f}")
+
+    def fragment_line(self):
+        return (f"blend / texel wrong {self.blend_wrong} px; textured compared {self.textured_compared} px, "
+                f"decision-ambiguous {100 * self.decision_share:.2f} %, single-candidate {100 * self.single_share:.1f} %, "
+                f"exact-byte {100 * self.exact_share:.1f} %, bilinear err/bound {self.linear_ratio:.3f}, "
+                f"blend err/bound {self.blend_ratio:.3f}")
 
 
 def compare(frame, ideal) -> Report:
@@ -73,7 +242,10 @@ def compare(frame, ideal) -> Report:
         r.failures.append(f"coverage: {r.coverage_wrong} unambiguous pixels disagree")
     both = ok & got & ideal.covered
     r.compared = int(both.sum())
-    tie = both & (ideal.gap <= 2.0 * ideal.tol)
+    tie = both & near_ties(ideal)
+    if ideal.fragments:
+        both = both & ~(ideal.special & ideal.decision_tie)   # left out: the chain's depth decisions are uncertain
+        tie = tie & both
     clear = both & ~tie
     err = np.abs(depth - ideal.depth)
     err_tie = np.minimum(err, np.abs(depth - ideal.depth2))
@@ -85,6 +257,9 @@ def compare(frame, ideal) -> Report:
     tri = np.where(clear, ideal.tri, 0)
     table = np.array([(t[3], t[4]) for t in ideal.tris] or [(0, 0)], dtype=np.int64)
     did, textured = table[tri, 0], table[tri, 1].astype(bool)
+    if ideal.fragments:
+        _compare_fragments(r, color, ideal)
+        clear = clear & False          # the chain rule speaks for every pixel of such a scene
     flat = clear & ~textured
     want = PALETTE[did % 20]
     wrong = flat & ((color[..., :3] != want).any(axis=-1) | (color[..., 3] != 255))
@@ -105,6 +280,28 @@ def compare(frame, ideal) -> Report:
     if stats["tris_in"] != ideal.tris_in:
         r.failures.append(f"tris_in {stats['tris_in']} != {ideal.tris_in}")
     return r
+
+
+def _compare_fragments(r, color, ideal):
+    x = expected(ideal)
+    c = color.astype(np.float64)
+    bad = x.compare & ((c < x.lo) | (c > x.hi)).any(axis=-1)
+    r.blend_wrong = int(bad.sum())
+    r.textured_compared, r.decision_share = x.textured_compared, x.decision_share
+    r.single_share, r.exact_share = x.single_share, x.exact_share
+    # how much of its margin a byte uses: the distance from the centre of the real interval to the values that round to
+    # the byte, over the interval's radius
+    half = (x.real_hi - x.real_lo) / 2.0
+    with np.errstate(all="ignore"):
+        q = np.where(half > 0, np.maximum(0.0, np.abs(c - (x.real_lo + x.real_hi) / 2.0) - 0.5) / half, 0.0)
+    q = np.where(bad[..., None], 0.0, q)
+    lin = x.compare & x.inexact & ~x.multi
+    r.linear_ratio = float(q[lin].max()) if lin.any() else 0.0
+    r.blend_ratio = float(q[x.compare & ~x.inexact].max()) if (x.compare & ~x.inexact).any() else 0.0
+    if r.blend_wrong:
+        yy, xx = np.nonzero(bad)
+        r.failures.append(f"blend / texel: {r.blend_wrong} pixels outside their interval, first ({xx[0]}, {yy[0]}) "
+                          f"{color[yy[0], xx[0]].tolist()} not in {x.lo[yy[0], xx[0]].tolist()} .. {x.hi[yy[0], xx[0]].tolist()}")
 
 
 def vertex_stage_ratio(got_clip, got_uv, clip, uv, e_clip, e_uv):

@@ -23,8 +23,29 @@ def test_gpu_frame_against_exact_arithmetic(gpu_device, name):
     cmp.assert_scene_caps(ideal, name)
     rep = cmp.compare(render_gpu(gpu_device, w, h, draws), ideal)
     print(f"{name}: {rep.line()}")
+    if name in scenes.FRAGMENT_SCENES:
+        print(f"{name}: {rep.fragment_line()}")
     assert rep.ok, (name, rep.failures)
     assert rep.compared > 0.02 * w * h
+
+
+def test_gpu_block_resident_textures_against_exact_arithmetic(gpu_device):
+    """the block-compressed chains once more with the blocks resident in memory and decoded per fetch (csrc/bc_sample.h),
+    as tests/test_gpu_texture_blocks.py selects it; the test above rendered them decoded at upload"""
+    from mt_renderer_amd import api
+    name = "frag_bc_chains"
+    w, h, draws = scenes.scene_of(name)
+    ideal = scenes.ideal_of(name)
+    try:
+        gpu_device.set_texture_residency(api.TEXRES_BLOCKS)
+        frame = render_gpu(gpu_device, w, h, draws)
+    finally:
+        gpu_device.set_texture_residency(api.TEXRES_DECODED)
+    rep = cmp.compare(frame, ideal)
+    print(f"{name} (blocks resident): {rep.line()}")
+    print(f"{name} (blocks resident): {rep.fragment_line()}")
+    assert rep.ok, (name, rep.failures)
+    assert rep.textured_compared > 0.02 * w * h
 
 
 def _posed_batch(dev, name):
