@@ -16,6 +16,8 @@
 //      src/shaders/textured.wgsl + sampler src/texture.rs:33-42) and the blend
 //      (src/model.rs:240-247) in submission order,
 //   4. colour + depth leave the CU once (clear is fused: no separate clear pass).
+// Set-up and edge evaluation: tri_setup.h; flattened walk and plane-equation quad derivatives: tile_common.h (the functions
+// k_tile_vis.hip uses); both paths of step 3 shade through resolve_fragment below.
 #include "tile_common.h"
 
 namespace mtr {
@@ -42,9 +44,7 @@ struct TriC {
     uint32_t pad;    // bbox inside the bin (fragment-list path), see setup_entry
 };
 struct TriX {
-    float iw0, diw1, diw2, up0;
-    float dup1, dup2, vp0, dvp1;
-    float dvp2;
+    UVPlanes p;
     uint32_t tw, th, tlevels;
     const uint8_t* tex;
     uint64_t pad2;
@@ -63,26 +63,9 @@ __device__ __forceinline__ void setup_entry(const TileParams& P, uint32_t r, int
     if (!solid) mat = P.mats[a.mat];
     const uint32_t mshader = solid ? (uint32_t)MTR_SH_DEBUG : mat.shader;
     const int32_t X[3] = {a.X0, a.X1, a.X2}, Y[3] = {a.Y0, a.Y1, a.Y2};
-    const long long A2 = (long long)(X[2] - X[0]) * (long long)(Y[1] - Y[0]) - (long long)(X[1] - X[0]) * (long long)(Y[2] - Y[0]);
-    const int32_t xmin = min(X[0], min(X[1], X[2])), xmax = max(X[0], max(X[1], X[2]));
-    const int32_t ymin = min(Y[0], min(Y[1], Y[2])), ymax = max(Y[0], max(Y[1], Y[2]));
-    const bool large = (xmax - xmin) > 16384 || (ymax - ymin) > 16384;
-    const long long Px = (long long)binx0 * 256 + 128, Py = (long long)biny0 * 256 + 128;
-    // edge 0: v1->v2, edge 1: v2->v0, edge 2: v0->v1;  E = dy*(Px-Xa) - dx*(Py-Ya)
-    int32_t A[3], B[3], Clo[3], Chi[3];
-    uint32_t flags = large ? TF_LARGE : 0u;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        const int ia = (i + 1) % 3, ib = (i + 2) % 3;
-        const int32_t dx = X[ib] - X[ia], dy = Y[ib] - Y[ia];
-        const int32_t tl = (dy > 0 || (dy == 0 && dx < 0)) ? 1 : 0;
-        const long long C = (long long)dy * (Px - X[ia]) - (long long)dx * (Py - Y[ia]) + (tl - 1);
-        flags |= (uint32_t)(1 - tl) << (4 + i);
-        A[i] = large ? dy : dy * 256;
-        B[i] = large ? -dx : -dx * 256;
-        Clo[i] = (int32_t)(uint32_t)(unsigned long long)C;
-        Chi[i] = (int32_t)(C >> 32);
-    }
+    TriSetup g;
+    tri_setup(X, Y, a.z0, a.z1, a.z2, binx0, biny0, g);
+    uint32_t flags = g.flags;  // TF_LARGE and the (1 - tl) bits
     if (TEX && mshader == MTR_SH_TEXTURED) flags |= TF_TEX;
     if (!solid) {
         if (mat.blend == MTR_DB_ALPHA) flags |= TF_BLEND;
@@ -91,35 +74,57 @@ __device__ __forceinline__ void setup_entry(const TileParams& P, uint32_t r, int
         if (!(mat.dstate & 2u)) flags |= TF_NODT;
         if (mshader != MTR_SH_TEXTURED && mat.blend == MTR_DB_ADD) flags |= TF_BLENDSOLID;
     }
-    t.A0 = A[0]; t.B0 = B[0]; t.C0 = Clo[0];
-    t.A1 = A[1]; t.B1 = B[1]; t.C1 = Clo[1];
-    t.A2 = A[2]; t.B2 = B[2]; t.C2 = Clo[2];
+    t.A0 = g.A[0]; t.B0 = g.B[0]; t.C0 = g.Clo[0];
+    t.A1 = g.A[1]; t.B1 = g.B[1]; t.C1 = g.Clo[1];
+    t.A2 = g.A[2]; t.B2 = g.B[2]; t.C2 = g.Clo[2];
     t.flags = flags;
-    t.z0 = a.z0; t.dz1 = a.z1 - a.z0; t.dz2 = a.z2 - a.z0;
-    t.rcpA = 1.0f / (float)A2;
+    t.z0 = g.z0; t.dz1 = g.dz1; t.dz2 = g.dz2; t.rcpA = g.rcpA;
     t.rgba8 = solid ? a.pad0 : mat.rgba8;
-    chi = make_int4(Chi[0], Chi[1], Chi[2], 0);
-    // sub-tiles (8x8 px) of this bin touched by the pixel-centre bbox: bit = sy*2 + sx
-    int32_t px0 = ((xmin + 127) >> 8) - binx0, px1 = ((xmax - 128) >> 8) - binx0;
-    int32_t py0 = ((ymin + 127) >> 8) - biny0, py1 = ((ymax - 128) >> 8) - biny0;
+    chi = make_int4(g.Chi[0], g.Chi[1], g.Chi[2], 0);
+    // sub-tiles (8x8 px) of this bin touched by the pixel-centre bbox: bit = sy*2 + sx.  A bbox that misses the bin gives
+    // submask == 0 and pad == 0: such a triangle's coefficients (meaningless, tri_setup.h) are never read
     uint32_t sm = 0;
-    if (px0 <= 15 && px1 >= 0 && py0 <= 15 && py1 >= 0) {
-        const uint32_t colbits = (px0 <= 7 ? 1u : 0u) | (px1 >= 8 ? 2u : 0u);
-        if (py0 <= 7) sm |= colbits;
-        if (py1 >= 8) sm |= colbits << 2;
+    if (g.px0 <= 15 && g.px1 >= 0 && g.py0 <= 15 && g.py1 >= 0) {
+        const uint32_t colbits = (g.px0 <= 7 ? 1u : 0u) | (g.px1 >= 8 ? 2u : 0u);
+        if (g.py0 <= 7) sm |= colbits;
+        if (g.py1 >= 8) sm |= colbits << 2;
     }
     submask = sm;
     // bbox clipped to the bin, for the fragment-list path: px0 | py0 << 4 | (w-1) << 8 | (h-1) << 12 | non-empty << 16
-    {
-        const int32_t cx0 = max(px0, 0), cx1 = min(px1, MTR_BIN - 1), cy0 = max(py0, 0), cy1 = min(py1, MTR_BIN - 1);
-        t.pad = (cx0 <= cx1 && cy0 <= cy1) ? ((uint32_t)cx0 | ((uint32_t)cy0 << 4) | ((uint32_t)(cx1 - cx0) << 8) | ((uint32_t)(cy1 - cy0) << 12) | (1u << 16)) : 0u;
-    }
+    const int32_t cx0 = max(g.px0, 0), cx1 = min(g.px1, MTR_BIN - 1), cy0 = max(g.py0, 0), cy1 = min(g.py1, MTR_BIN - 1);
+    t.pad = (cx0 <= cx1 && cy0 <= cy1) ? ((uint32_t)cx0 | ((uint32_t)cy0 << 4) | ((uint32_t)(cx1 - cx0) << 8) | ((uint32_t)(cy1 - cy0) << 12) | (1u << 16)) : 0u;
     if (TEX && mshader == MTR_SH_TEXTURED) {
-        const RecB b = P.fb.rec_b[r];
-        x->iw0 = b.iw0; x->diw1 = b.iw1 - b.iw0; x->diw2 = b.iw2 - b.iw0;
-        x->up0 = b.up0; x->dup1 = b.up1 - b.up0; x->dup2 = b.up2 - b.up0;
-        x->vp0 = b.vp0; x->dvp1 = b.vp1 - b.vp0; x->dvp2 = b.vp2 - b.vp0;
+        x->p = uv_planes(P.fb.rec_b[r]);
         x->tex = mat.tex; x->tw = mat.tw; x->th = mat.th; x->tlevels = mat.tlevels;
+    }
+}
+
+// One fragment of the triangle whose record words 8..15 are (q2, q3), at a pixel holding dep / col: z from the
+// barycentrics, the depth test (LessEqual unless off) and write (unless off), the fragment shader -- solid, solid through
+// the blend, textured -- and the blend.  quad() yields (u, v) and their quad derivatives; it is called only for a
+// textured fragment that passes.
+template <bool TEX, typename Q>
+__device__ __forceinline__ void resolve_fragment(const int4 q2, const int4 q3, const TriX& Xt, bool covered, float b1, float b2, float& dep,
+                                                 uint32_t& col, Q&& quad) {
+    const uint32_t flags = (uint32_t)q2.y;
+    const float z = tri_depth(b1, b2, __int_as_float(q2.z), __int_as_float(q2.w), __int_as_float(q3.x));
+    if (!(covered && z >= 0.0f && z <= 1.0f && ((flags & TF_NODT) || z <= dep))) return;
+    if (!(flags & TF_NODW)) dep = z;
+    const uint32_t bmode = (flags & TF_ADD) ? 2u : ((flags & TF_BLEND) ? 1u : 0u);
+    if (!TEX || !(flags & TF_TEX)) {
+        if (flags & TF_BLENDSOLID) {
+            const uint32_t c8 = (uint32_t)q3.z;
+            const float src[4] = {unorm8f(c8), unorm8f(c8 >> 8), unorm8f(c8 >> 16), unorm8f(c8 >> 24)};
+            col = blend_store(col, src, bmode);
+        } else {
+            col = (uint32_t)q3.z;
+        }
+    } else {
+        const QuadUV q = quad();
+        const TexRef tr = {Xt.tex, Xt.tw, Xt.th, Xt.tlevels};
+        float src[4];
+        sample_texture(tr, q.u, q.v, filter_select(q.dudx, q.dvdx, q.dudy, q.dvdy, tr.tw, tr.th, tr.levels), src);
+        col = blend_store(col, src, bmode);
     }
 }
 
@@ -262,46 +267,30 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
                     const uint32_t inc = wave_incl_scan_u32(mine);
                     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
                     if (!__ballot(large) && total != 0 && total <= 2048u) {
-                        const uint64_t nzm = __ballot(mine != 0);
-                        const uint32_t cidx = __builtin_amdgcn_mbcnt_hi((uint32_t)(nzm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nzm, 0u));
-                        const uint32_t pre = inc - mine;
-                        if (lane < 32) s_start[lane] = 0ull;
-                        wave_lds_sync();
+                        const uint32_t pre = inc - mine, cidx = lane_rank(__ballot(mine != 0));
+                        flat_stage_starts(s_start, 32, lane, mine, pre);
                         if (mine) {
                             s_tmap[cidx] = (uint8_t)lane;
                             s_pm[lane] = pre | (((65536u + bw - 1u) / bw) << 12);  // exact k / bw for k < 256, bw <= 16
-                            atomicOr(&s_start[pre >> 6], 1ull << (pre & 63u));
                         }
                         wave_lds_sync();
-                        const unsigned long long my_start = lane < 32 ? s_start[lane] : 0ull;
-                        const uint32_t nbat = (total + 63u) >> 6;
-                        uint32_t base = 0;
-                        for (uint32_t b = 0; b < nbat; b++) {
-                            const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_start, b);
-                            const uint32_t mhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(my_start >> 32), b);
-                            const uint64_t mm = ((uint64_t)mhi << 32) | mlo;
-                            const uint32_t ci = base + __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u)) + (uint32_t)((mm >> lane) & 1ull) - 1u;
-                            base += (uint32_t)__popcll(mm);
-                            const uint32_t pidx = b * 64u + lane;
-                            if (pidx < total) {
-                                const uint32_t t = s_tmap[ci];
-                                const int4* tc = reinterpret_cast<const int4*>(&s_tc[t]);
-                                const int4 q0 = tc[0], q1 = tc[1], q2 = tc[2], q3 = tc[3];
-                                const uint32_t tb = (uint32_t)q3.w, pm = s_pm[t];
-                                const uint32_t k = pidx - (pm & 0xfffu);
-                                const uint32_t row = (k * (pm >> 12)) >> 16;
-                                const int32_t lx = (int32_t)((tb & 15u) + (k - row * (((tb >> 8) & 15u) + 1u)));
-                                const int32_t ly = (int32_t)(((tb >> 4) & 15u) + row);
-                                const int32_t eb0 = q0.z + __mul24(q0.x, lx) + __mul24(q0.y, ly);
-                                const int32_t eb1 = q1.y + __mul24(q0.w, lx) + __mul24(q1.x, ly);
-                                const int32_t eb2 = q2.x + __mul24(q1.z, lx) + __mul24(q1.w, ly);
-                                if ((eb0 | eb1 | eb2) >= 0) {
-                                    const uint32_t pix = (uint32_t)(ly * MTR_BIN + lx);
-                                    const uint32_t slot = atomicAdd(&s_cnt[pix], 1u);
-                                    if (slot < FRAG_K) s_frag[pix * FRAG_K + slot] = (uint8_t)t;
-                                }
+                        flat_for_each(s_start, 32, lane, total, [&](uint32_t pidx, uint32_t ci) {
+                            const uint32_t t = s_tmap[ci];
+                            const int4* tc = reinterpret_cast<const int4*>(&s_tc[t]);
+                            const int4 q0 = tc[0], q1 = tc[1], q2 = tc[2], q3 = tc[3];
+                            const TriEdges E = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x};
+                            const uint32_t tb = (uint32_t)q3.w, pm = s_pm[t];
+                            const uint32_t k = pidx - (pm & 0xfffu);
+                            const uint32_t row = (k * (pm >> 12)) >> 16;
+                            const int32_t lx = (int32_t)((tb & 15u) + (k - row * (((tb >> 8) & 15u) + 1u)));
+                            const int32_t ly = (int32_t)(((tb >> 4) & 15u) + row);
+                            int32_t e1, e2;
+                            if (tri_inside(E, lx, ly, e1, e2)) {
+                                const uint32_t pix = (uint32_t)(ly * MTR_BIN + lx);
+                                const uint32_t slot = atomicAdd(&s_cnt[pix], 1u);
+                                if (slot < FRAG_K) s_frag[pix * FRAG_K + slot] = (uint8_t)t;
                             }
-                        }
+                        });
                         wave_lds_sync();
                         uint32_t cn[4];
                         bool over = false;
@@ -338,53 +327,16 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
                                     const int4* tc = reinterpret_cast<const int4*>(&s_tc[best]);
                                     const int4 q0 = tc[0], q1 = tc[1], q2 = tc[2], q3 = tc[3];
                                     const uint32_t flags = (uint32_t)q2.y;
-                                    const float z0 = __int_as_float(q2.z), dz1 = __int_as_float(q2.w), dz2 = __int_as_float(q3.x),
-                                                rcpA = __int_as_float(q3.y);
+                                    const float rcpA = __int_as_float(q3.y);
                                     // barycentrics at pixel (x, y) of the bin: the arithmetic of the loop below, lane by lane
                                     auto bary = [&](int32_t x, int32_t y, float& b1, float& b2) {
-                                        const int32_t e1 = q1.y + __mul24(q0.w, x) + __mul24(q1.x, y);
-                                        const int32_t e2 = q2.x + __mul24(q1.z, x) + __mul24(q1.w, y);
-                                        b1 = (float)(e1 + (int32_t)((flags >> 5) & 1u)) * rcpA;
-                                        b2 = (float)(e2 + (int32_t)((flags >> 6) & 1u)) * rcpA;
+                                        b1 = tri_bary(tri_edge(q1.y, q0.w, q1.x, x, y), (flags >> 5) & 1u, rcpA);
+                                        b2 = tri_bary(tri_edge(q2.x, q1.z, q1.w, x, y), (flags >> 6) & 1u, rcpA);
                                     };
                                     float b1, b2;
                                     bary(lx, ly, b1, b2);
-                                    const float z = fmaf(b2, dz2, fmaf(b1, dz1, z0));
-                                    if (!(z >= 0.0f && z <= 1.0f && ((flags & TF_NODT) || z <= dep[i]))) continue;
-                                    if (!(flags & TF_NODW)) dep[i] = z;
-                                    const uint32_t bmode = (flags & TF_ADD) ? 2u : ((flags & TF_BLEND) ? 1u : 0u);
-                                    if (!TEX || !(flags & TF_TEX)) {
-                                        if (flags & TF_BLENDSOLID) {
-                                            const uint32_t c8 = (uint32_t)q3.z;
-                                            const float src[4] = {unorm8f(c8), unorm8f(c8 >> 8), unorm8f(c8 >> 16), unorm8f(c8 >> 24)};
-                                            col[i] = blend_store(col[i], src, bmode);
-                                        } else {
-                                            col[i] = (uint32_t)q3.z;
-                                        }
-                                    } else {
-                                        const TriX& Xt = s_tx[TEX ? best : 0];
-                                        auto uv_at = [&](int32_t x, int32_t y, float& u, float& v) {
-                                            float c1, c2;
-                                            bary(x, y, c1, c2);
-                                            const float iw = fmaf(c2, Xt.diw2, fmaf(c1, Xt.diw1, Xt.iw0));
-                                            const float up = fmaf(c2, Xt.dup2, fmaf(c1, Xt.dup1, Xt.up0));
-                                            const float vp = fmaf(c2, Xt.dvp2, fmaf(c1, Xt.dvp1, Xt.vp0));
-                                            u = up / iw;
-                                            v = vp / iw;
-                                        };
-                                        // fine quad differences: (odd position) - (even position) along each axis; this
-                                        // pixel is one end of both, so two more evaluations give all four derivatives
-                                        float u, v, uh, vh, uw, vw;
-                                        uv_at(lx, ly, u, v);
-                                        uv_at(lx ^ 1, ly, uh, vh);
-                                        uv_at(lx, ly ^ 1, uw, vw);
-                                        const float dudx = (lx & 1) ? u - uh : uh - u, dvdx = (lx & 1) ? v - vh : vh - v;
-                                        const float dudy = (ly & 1) ? u - uw : uw - u, dvdy = (ly & 1) ? v - vw : vw - v;
-                                        const TexRef tr = {Xt.tex, Xt.tw, Xt.th, Xt.tlevels};
-                                        float src[4];
-                                        sample_texture(tr, u, v, filter_select(dudx, dvdx, dudy, dvdy, tr.tw, tr.th, tr.levels), src);
-                                        col[i] = blend_store(col[i], src, bmode);
-                                    }
+                                    const TriX& Xt = s_tx[TEX ? best : 0];
+                                    resolve_fragment<TEX>(q2, q3, Xt, true, b1, b2, dep[i], col[i], [&] { return quad_uv(Xt.p, lx, ly, bary); });
                                 }
                             }
                         }
@@ -401,67 +353,31 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
                         m &= m - 1;
                         const int4* tc = reinterpret_cast<const int4*>(&s_tc[t]);
                         const int4 q0 = tc[0], q1 = tc[1], q2 = tc[2], q3 = tc[3];
-                        const int32_t A0 = q0.x, B0 = q0.y, C0 = q0.z, A1 = q0.w, B1 = q1.x, C1 = q1.y, A2 = q1.z, B2 = q1.w, C2 = q2.x;
+                        const TriEdges E = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x};
                         const uint32_t flags = (uint32_t)q2.y;
-                        const float z0 = __int_as_float(q2.z), dz1 = __int_as_float(q2.w), dz2 = __int_as_float(q3.x),
-                                    rcpA = __int_as_float(q3.y);
+                        const float rcpA = __int_as_float(q3.y);
                         bool inside;
-                        float e1f, e2f;
+                        float b1, b2;
                         if (!(flags & TF_LARGE)) {
-                            const int32_t eb0 = C0 + __mul24(A0, lx) + __mul24(B0, ly);
-                            const int32_t eb1 = C1 + __mul24(A1, lx) + __mul24(B1, ly);
-                            const int32_t eb2 = C2 + __mul24(A2, lx) + __mul24(B2, ly);
-                            inside = (eb0 | eb1 | eb2) >= 0;
-                            e1f = (float)(eb1 + (int32_t)((flags >> 5) & 1u));
-                            e2f = (float)(eb2 + (int32_t)((flags >> 6) & 1u));
+                            int32_t e1, e2;
+                            inside = tri_inside(E, lx, ly, e1, e2);
+                            b1 = tri_bary(e1, (flags >> 5) & 1u, rcpA);
+                            b2 = tri_bary(e2, (flags >> 6) & 1u, rcpA);
                         } else {
                             const int4 ch = s_chi[t];
-                            const long long Xp = (long long)lx * 256, Yp = (long long)ly * 256;
-                            const long long c0 = ((long long)ch.x << 32) | (unsigned long long)(uint32_t)C0;
-                            const long long c1 = ((long long)ch.y << 32) | (unsigned long long)(uint32_t)C1;
-                            const long long c2 = ((long long)ch.z << 32) | (unsigned long long)(uint32_t)C2;
-                            const long long eb0 = c0 + (long long)A0 * Xp + (long long)B0 * Yp;
-                            const long long eb1 = c1 + (long long)A1 * Xp + (long long)B1 * Yp;
-                            const long long eb2 = c2 + (long long)A2 * Xp + (long long)B2 * Yp;
-                            inside = (eb0 | eb1 | eb2) >= 0;
-                            e1f = (float)(eb1 + (long long)((flags >> 5) & 1u));
-                            e2f = (float)(eb2 + (long long)((flags >> 6) & 1u));
+                            inside = tri_inside_large(E, ch.x, ch.y, ch.z, flags, rcpA, lx, ly, b1, b2);
                         }
-                        const float b1 = e1f * rcpA, b2 = e2f * rcpA;
-                        const float z = fmaf(b2, dz2, fmaf(b1, dz1, z0));
-                        const bool pass = inside && in_vp && z >= 0.0f && z <= 1.0f && ((flags & TF_NODT) || z <= dep[i]);
-                        const uint32_t bmode = (flags & TF_ADD) ? 2u : ((flags & TF_BLEND) ? 1u : 0u);
-                        if (!TEX || !(flags & TF_TEX)) {
-                            if (pass) {
-                                if (!(flags & TF_NODW)) dep[i] = z;
-                                if (flags & TF_BLENDSOLID) {
-                                    const uint32_t c8 = (uint32_t)q3.z;
-                                    const float src[4] = {unorm8f(c8), unorm8f(c8 >> 8), unorm8f(c8 >> 16), unorm8f(c8 >> 24)};
-                                    col[i] = blend_store(col[i], src, bmode);
-                                } else {
-                                    col[i] = (uint32_t)q3.z;
-                                }
-                            }
-                        } else {
-                            // every lane evaluates (u,v) so quad differences exist for helper pixels too
-                            const TriX& Xt = s_tx[TEX ? t : 0];
-                            const float iw = fmaf(b2, Xt.diw2, fmaf(b1, Xt.diw1, Xt.iw0));
-                            const float up = fmaf(b2, Xt.dup2, fmaf(b1, Xt.dup1, Xt.up0));
-                            const float vp = fmaf(b2, Xt.dvp2, fmaf(b1, Xt.dvp1, Xt.vp0));
-                            const float u = up / iw, v = vp / iw;
-                            const float dudx = __shfl(u, (int)(lane | 1)) - __shfl(u, (int)(lane & ~1u));
-                            const float dvdx = __shfl(v, (int)(lane | 1)) - __shfl(v, (int)(lane & ~1u));
-                            const float dudy = __shfl(u, (int)(lane | 8)) - __shfl(u, (int)(lane & ~8u));
-                            const float dvdy = __shfl(v, (int)(lane | 8)) - __shfl(v, (int)(lane & ~8u));
-                            const TexRef tr = {Xt.tex, Xt.tw, Xt.th, Xt.tlevels};
-                            const int flt = filter_select(dudx, dvdx, dudy, dvdy, tr.tw, tr.th, tr.levels);
-                            if (pass) {
-                                if (!(flags & TF_NODW)) dep[i] = z;
-                                float src[4];
-                                sample_texture(tr, u, v, flt, src);
-                                col[i] = blend_store(col[i], src, bmode);
-                            }
+                        // a textured triangle: every lane evaluates (u,v), before the depth test, so quad differences
+                        // exist for helper pixels too
+                        const TriX& Xt = s_tx[TEX ? t : 0];
+                        QuadUV q = {};
+                        if (TEX && (flags & TF_TEX)) {
+                            uv_at_bary(Xt.p, b1, b2, q.u, q.v);
+                            auto across = [&](float a, uint32_t bit) { return __shfl(a, (int)(lane | bit)) - __shfl(a, (int)(lane & ~bit)); };
+                            q.dudx = across(q.u, 1u); q.dvdx = across(q.v, 1u);
+                            q.dudy = across(q.u, 8u); q.dvdy = across(q.v, 8u);
                         }
+                        resolve_fragment<TEX>(q2, q3, Xt, inside && in_vp, b1, b2, dep[i], col[i], [&] { return q; });
                     }
                 }
                 wave_lds_sync();

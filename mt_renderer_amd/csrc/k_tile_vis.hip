@@ -11,15 +11,14 @@
 //   * otherwise the (triangle, pixel-of-bbox) pairs of every i32-edge-class triangle are FLATTENED over the wave, in rounds of
 //     <= 4096 pairs: a pass costs sum(bbox pixels)/64 iterations whatever the mix of 1-pixel slivers and bin-filling
 //     triangles (a lane = triangle walk ran max(bbox pixels) iterations at 29 % lane efficiency on the headline scene).
-//     The pair -> triangle map needs no search: triangle t sets bit (prefix_t mod 64) of a 64-bit start mask per
-//     batch of 64 pairs (one ds_or_b64), and pair p's triangle is  #starts before its batch + popcount(mask bits
-//     <= p) - 1  (v_mbcnt).  Triangles over 64 px across (64-bit edge functions) are rasterised by the whole wave, one
-//     at a time (v_readlane);
+//     The pair -> triangle map needs no search (start masks, tile_common.h).  Triangles over 64 px across (64-bit edge
+//     functions) are rasterised by the whole wave, one at a time (v_readlane);
 //   * shading is deferred: the winner's record is addressable from its order (chunk runs live at
 //     chunk * MTR_CHUNK_SLOTS), so the resolve does one colour lookup -- or one texture sample with the
 //     quad derivatives evaluated from the winner's plane equations exactly as SPEC.md section 7
 //     defines them -- per pixel, then the only framebuffer write of the frame.
-// Same arithmetic per fragment as k_tile.hip, bit for bit; the host picks this kernel only when the
+// Same arithmetic per fragment as k_tile.hip, bit for bit: the set-up, the edge evaluation and the absolute-coordinate
+// barycentrics are tri_setup.h's functions in both kernels, the flattened walk tile_common.h's; the host picks this kernel only when the
 // frame is eligible (mtr_api.cpp); tests run both kernels on the same scenes.
 // VIS_WAVES waves per 16x16 bin (passes dealt round-robin, two workgroup barriers in total), no segment
 // sort (the submission order rides in the entry).
@@ -59,56 +58,36 @@ struct Setup {
     uint32_t bhm1; // bbox height - 1
 };
 
+// the shared set-up (tri_setup.h) plus this kernel's own: the bbox clipped to the bin and the viewport, and the order.
+// A triangle whose bbox misses the bin gets npx == 0: its coefficients (meaningless, tri_setup.h) are never read
 __device__ __forceinline__ void setup_tri(const RecA& a, uint32_t ord, int32_t binx0, int32_t biny0, int32_t vw, int32_t vh, Setup& s) {
-    const int32_t xmin = min(a.X0, min(a.X1, a.X2)), xmax = max(a.X0, max(a.X1, a.X2));
-    const int32_t ymin = min(a.Y0, min(a.Y1, a.Y2)), ymax = max(a.Y0, max(a.Y1, a.Y2));
-    const bool large = (xmax - xmin) > 16384 || (ymax - ymin) > 16384;
     const int32_t X[3] = {a.X0, a.X1, a.X2}, Y[3] = {a.Y0, a.Y1, a.Y2};
-    int32_t A[3], B[3], Clo[3], Chi[3] = {0, 0, 0};
-    uint32_t flags = large ? 1u : 0u;
-    float fA2;
-    if (!large) {
-        // the bin overlaps the bbox, so every operand is < 2^16 and every product < 2^31: 24-bit multiplies
-        const int32_t Px = binx0 * 256 + 128, Py = biny0 * 256 + 128;
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const int ia = (i + 1) % 3, ib = (i + 2) % 3;
-            const int32_t dx = X[ib] - X[ia], dy = Y[ib] - Y[ia];
-            const int32_t tl = (dy > 0 || (dy == 0 && dx < 0)) ? 1 : 0;
-            flags |= (uint32_t)(1 - tl) << (4 + i);
-            A[i] = dy * 256; B[i] = -dx * 256;
-            Clo[i] = __mul24(dy, Px - X[ia]) - __mul24(dx, Py - Y[ia]) + (tl - 1);
-        }
-        fA2 = (float)(__mul24(X[2] - X[0], Y[1] - Y[0]) - __mul24(X[1] - X[0], Y[2] - Y[0]));
-    } else {
-        const long long Px = (long long)binx0 * 256 + 128, Py = (long long)biny0 * 256 + 128;
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const int ia = (i + 1) % 3, ib = (i + 2) % 3;
-            const int32_t dx = X[ib] - X[ia], dy = Y[ib] - Y[ia];
-            const int32_t tl = (dy > 0 || (dy == 0 && dx < 0)) ? 1 : 0;
-            const long long C = (long long)dy * (Px - X[ia]) - (long long)dx * (Py - Y[ia]) + (tl - 1);
-            flags |= (uint32_t)(1 - tl) << (4 + i);
-            A[i] = dy; B[i] = -dx;
-            Clo[i] = (int32_t)(uint32_t)(unsigned long long)C;
-            Chi[i] = (int32_t)(C >> 32);
-        }
-        fA2 = (float)((long long)(X[2] - X[0]) * (long long)(Y[1] - Y[0]) - (long long)(X[1] - X[0]) * (long long)(Y[2] - Y[0]));
-    }
-    const int32_t px0 = max(((xmin + 127) >> 8) - binx0, 0), px1 = min(((xmax - 128) >> 8) - binx0, min(MTR_BIN, vw) - 1);
-    const int32_t py0 = max(((ymin + 127) >> 8) - biny0, 0), py1 = min(((ymax - 128) >> 8) - biny0, min(MTR_BIN, vh) - 1);
+    TriSetup g;
+    tri_setup(X, Y, a.z0, a.z1, a.z2, binx0, biny0, g);
+    const int32_t px0 = max(g.px0, 0), px1 = min(g.px1, min(MTR_BIN, vw) - 1);
+    const int32_t py0 = max(g.py0, 0), py1 = min(g.py1, min(MTR_BIN, vh) - 1);
     const int32_t bw = px1 - px0 + 1, bh = py1 - py0 + 1;
     s.npx = (bw > 0 && bh > 0) ? bw * bh : 0;  // pixels of the bbox in this bin; the caller turns it into work items (walk_items)
     s.bhm1 = (uint32_t)max(bh - 1, 0);
-    s.t.A0 = A[0]; s.t.B0 = B[0]; s.t.C0 = Clo[0];
-    s.t.A1 = A[1]; s.t.B1 = B[1]; s.t.C1 = Clo[1];
-    s.t.A2 = A[2]; s.t.B2 = B[2]; s.t.C2 = Clo[2];
-    s.t.flags = flags;
-    s.t.z0 = a.z0; s.t.dz1 = a.z1 - a.z0; s.t.dz2 = a.z2 - a.z0;
-    s.t.rcpA = 1.0f / fA2;
+    s.t.A0 = g.A[0]; s.t.B0 = g.B[0]; s.t.C0 = g.Clo[0];
+    s.t.A1 = g.A[1]; s.t.B1 = g.B[1]; s.t.C1 = g.Clo[1];
+    s.t.A2 = g.A[2]; s.t.B2 = g.B[2]; s.t.C2 = g.Clo[2];
+    s.t.flags = g.flags;
+    s.t.z0 = g.z0; s.t.dz1 = g.dz1; s.t.dz2 = g.dz2; s.t.rcpA = g.rcpA;
     s.t.ordk = ord + 1u;
     s.t.box = (uint32_t)(px0 & 15) | ((uint32_t)(py0 & 15) << 4) | ((uint32_t)((bw - 1) & 15) << 8);  // + magic << 12 (walk_items)
-    s.chi = make_int4(Chi[0], Chi[1], Chi[2], 0);
+    s.chi = make_int4(g.Chi[0], g.Chi[1], g.Chi[2], 0);
+}
+
+// a triangle of the flattened walks in s_flat: its record with the edge functions rebased to the bbox origin (an item
+// evaluates E(col, row) with no bin coordinates), `pre` in place of flags, whose bits 5 / 6 (1 - tl) go to box bits 29 / 30
+__device__ __forceinline__ void stage_flat(uint4* dst, const VisTri& t, uint32_t pre) {
+    const int32_t ox = (int32_t)(t.box & 15u), oy = (int32_t)((t.box >> 4) & 15u);
+    const int32_t c0 = tri_edge(t.C0, t.A0, t.B0, ox, oy), c1 = tri_edge(t.C1, t.A1, t.B1, ox, oy), c2 = tri_edge(t.C2, t.A2, t.B2, ox, oy);
+    dst[0] = make_uint4((uint32_t)t.A0, (uint32_t)t.B0, (uint32_t)c0, (uint32_t)t.A1);
+    dst[1] = make_uint4((uint32_t)t.B1, (uint32_t)c1, (uint32_t)t.A2, (uint32_t)t.B2);
+    dst[2] = make_uint4((uint32_t)c2, pre, __float_as_uint(t.z0), __float_as_uint(t.dz1));
+    dst[3] = make_uint4(__float_as_uint(t.dz2), __float_as_uint(t.rcpA), t.ordk, t.box | ((t.flags & 0x60u) << 24));
 }
 
 #define STAIR_K 8u  // submission orders kept per pixel (STAIR)
@@ -137,47 +116,16 @@ __device__ __forceinline__ unsigned long long make_key(float z, uint32_t ordk) {
 // deferred textured shading of the winner at pixel (px,py): SPEC.md section 7, same operations as the
 // per-fragment path (the quad neighbours are evaluated from the same triangle's plane equations)
 __device__ __forceinline__ void sample_textured(const RecA& a, const RecB& b, const DMat& mat, int32_t px, int32_t py, float (&src)[4]) {
-    const long long A2 = (long long)(a.X2 - a.X0) * (long long)(a.Y1 - a.Y0) - (long long)(a.X1 - a.X0) * (long long)(a.Y2 - a.Y0);
-    const float rcpA = 1.0f / (float)A2;
-    const float diw1 = b.iw1 - b.iw0, diw2 = b.iw2 - b.iw0, dup1 = b.up1 - b.up0, dup2 = b.up2 - b.up0,
-                dvp1 = b.vp1 - b.vp0, dvp2 = b.vp2 - b.vp0;
-    auto uv_at = [&](int32_t qx, int32_t qy, float& u, float& v) {
-        const long long Px = (long long)qx * 256 + 128, Py = (long long)qy * 256 + 128;
-        const long long E1 = (long long)(a.Y0 - a.Y2) * (Px - a.X2) - (long long)(a.X0 - a.X2) * (Py - a.Y2);
-        const long long E2 = (long long)(a.Y1 - a.Y0) * (Px - a.X0) - (long long)(a.X1 - a.X0) * (Py - a.Y0);
-        const float b1 = (float)E1 * rcpA, b2 = (float)E2 * rcpA;
-        const float iw = fmaf(b2, diw2, fmaf(b1, diw1, b.iw0));
-        const float up = fmaf(b2, dup2, fmaf(b1, dup1, b.up0));
-        const float vp = fmaf(b2, dvp2, fmaf(b1, dvp1, b.vp0));
-        u = up / iw;
-        v = vp / iw;
-    };
-    // fine quad differences: (odd position) - (even position) along each axis; this pixel is one end of both, so two
-    // more evaluations give all four derivatives
-    float u, v, uh, vh, uw, vw;
-    uv_at(px, py, u, v);
-    uv_at(px ^ 1, py, uh, vh);
-    uv_at(px, py ^ 1, uw, vw);
-    const float dudx = (px & 1) ? u - uh : uh - u, dvdx = (px & 1) ? v - vh : vh - v;
-    const float dudy = (py & 1) ? u - uw : uw - u, dvdy = (py & 1) ? v - vw : vw - v;
+    const QuadUV q = quad_uv(uv_planes(b), px, py, [&](int32_t qx, int32_t qy, float& b1, float& b2) { tri_abs_bary(a.X0, a.Y0, a.X1, a.Y1, a.X2, a.Y2, qx, qy, b1, b2); });
     const TexRef tr = {mat.tex, mat.tw, mat.th, mat.tlevels};
-    sample_texture(tr, u, v, filter_select(dudx, dvdx, dudy, dvdy, mat.tw, mat.th, mat.tlevels), src);
-}
-__device__ __forceinline__ uint32_t shade_textured(const RecA& a, const RecB& b, const DMat& mat, int32_t px, int32_t py) {
-    float src[4];
-    sample_textured(a, b, mat, px, py, src);
-    return blend_store(0u, src, 0u);  // order-free: blending is off, or the texture is opaque (a == 1 exactly) and the blend a replace
+    sample_texture(tr, q.u, q.v, filter_select(q.dudx, q.dvdx, q.dudy, q.dvdy, mat.tw, mat.th, mat.tlevels), src);
 }
 // z of the record's triangle at the centre of pixel (px, py): the edge values are the exact integers the rasteriser
 // compares, so this is the float the flattened walk computed from its bin-relative form (SPEC.md section 6)
 __device__ __forceinline__ float z_at(const RecA& a, int32_t px, int32_t py) {
-    const long long A2 = (long long)(a.X2 - a.X0) * (long long)(a.Y1 - a.Y0) - (long long)(a.X1 - a.X0) * (long long)(a.Y2 - a.Y0);
-    const float rcpA = 1.0f / (float)A2;
-    const long long Px = (long long)px * 256 + 128, Py = (long long)py * 256 + 128;
-    const long long E1 = (long long)(a.Y0 - a.Y2) * (Px - a.X2) - (long long)(a.X0 - a.X2) * (Py - a.Y2);
-    const long long E2 = (long long)(a.Y1 - a.Y0) * (Px - a.X0) - (long long)(a.X1 - a.X0) * (Py - a.Y0);
-    const float b1 = (float)E1 * rcpA, b2 = (float)E2 * rcpA;
-    return fmaf(b2, a.z2 - a.z0, fmaf(b1, a.z1 - a.z0, a.z0));
+    float b1, b2;
+    tri_abs_bary(a.X0, a.Y0, a.X1, a.Y1, a.X2, a.Y2, px, py, b1, b2);
+    return tri_depth(b1, b2, a.z0, a.z1 - a.z0, a.z2 - a.z0);
 }
 
 // waves per bin: the passes (64 triangles each) of a bin are dealt round-robin to the waves of its workgroup;
@@ -290,8 +238,7 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
         for (uint64_t mb = __ballot(npx != 0 && large); mb; mb &= mb - 1) {
             const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)__ffsll((long long)mb) - 1);
 #define RL(x) __builtin_amdgcn_readlane((int)(x), t)
-            const int32_t A0 = RL(s.t.A0), B0 = RL(s.t.B0), C0 = RL(s.t.C0), A1 = RL(s.t.A1), B1 = RL(s.t.B1), C1 = RL(s.t.C1);
-            const int32_t A2 = RL(s.t.A2), B2 = RL(s.t.B2), C2 = RL(s.t.C2);
+            const TriEdges E = {RL(s.t.A0), RL(s.t.B0), RL(s.t.C0), RL(s.t.A1), RL(s.t.B1), RL(s.t.C1), RL(s.t.A2), RL(s.t.B2), RL(s.t.C2)};
             const uint32_t flags = (uint32_t)RL(s.t.flags), box = (uint32_t)RL(s.t.box), tord = (uint32_t)RL(s.t.ordk), tn = (uint32_t)RL(npx);
             const float z0 = __int_as_float(RL(__float_as_int(s.t.z0))), dz1 = __int_as_float(RL(__float_as_int(s.t.dz1)));
             const float dz2 = __int_as_float(RL(__float_as_int(s.t.dz2))), rcpA = __int_as_float(RL(__float_as_int(s.t.rcpA)));
@@ -301,18 +248,9 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
             for (uint32_t k = lane; k < tn; k += 64) {
                 const uint32_t row = (k * magic) >> 16;
                 const int32_t lx = (int32_t)((box & 15u) + (k - row * bw)), ly = (int32_t)(((box >> 4) & 15u) + row);
-                const long long Xp = (long long)lx * 256, Yp = (long long)ly * 256;
-                const long long c0 = ((long long)H0 << 32) | (unsigned long long)(uint32_t)C0;
-                const long long c1 = ((long long)H1 << 32) | (unsigned long long)(uint32_t)C1;
-                const long long c2 = ((long long)H2 << 32) | (unsigned long long)(uint32_t)C2;
-                const long long eb0 = c0 + (long long)A0 * Xp + (long long)B0 * Yp;
-                const long long eb1 = c1 + (long long)A1 * Xp + (long long)B1 * Yp;
-                const long long eb2 = c2 + (long long)A2 * Xp + (long long)B2 * Yp;
-                const bool inside = (eb0 | eb1 | eb2) >= 0;
-                const float e1f = (float)(eb1 + (long long)((flags >> 5) & 1u));
-                const float e2f = (float)(eb2 + (long long)((flags >> 6) & 1u));
-                const float b1 = e1f * rcpA, b2 = e2f * rcpA;
-                const float z = fmaf(b2, dz2, fmaf(b1, dz1, z0));
+                float b1, b2;
+                const bool inside = tri_inside_large(E, H0, H1, H2, flags, rcpA, lx, ly, b1, b2);
+                const float z = tri_depth(b1, b2, z0, dz1, dz2);
                 if (inside && z >= 0.0f && z <= 1.0f && z <= cd) put_fragment<STAIR>(s_key, s_cnt, s_list, (uint32_t)(ly * MTR_BIN + lx), make_key(z, tord));
             }
         }
@@ -329,58 +267,33 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
         const bool spans = zlim_ok && ncand != 0u && (uint32_t)__popcll(__ballot(!large && npx > 4)) * 2u >= ncand;
         if (spans) {
             const bool cand = npx != 0 && !large;
-            const uint64_t cm = __ballot(cand);
+            const uint32_t cidx = lane_rank(__ballot(cand));
             const uint32_t rows = cand ? s.bhm1 + 1u : 0u;
             const uint32_t inc = wave_incl_scan_u32(rows);
             const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);  // <= 64 x 16
-            const uint32_t pre = inc - rows;
-            s_start[wv][lane] = 0ull;
+            flat_stage_starts(s_start[wv], 64, lane, rows, inc - rows);
+            if (cand) stage_flat(&s_flat[wv][cidx * 4], s.t, inc - rows);  // the triangle's first row item in place of its first pair
             wave_lds_sync();
-            if (cand) {
-                // the pair walk's record, with the triangle's first row item in place of its first pair
-                uint4* dst = &s_flat[wv][__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u)) * 4];
-                const int32_t ox = (int32_t)(s.t.box & 15u), oy = (int32_t)((s.t.box >> 4) & 15u);
-                const int32_t c0 = s.t.C0 + __mul24(s.t.A0, ox) + __mul24(s.t.B0, oy);
-                const int32_t c1 = s.t.C1 + __mul24(s.t.A1, ox) + __mul24(s.t.B1, oy);
-                const int32_t c2 = s.t.C2 + __mul24(s.t.A2, ox) + __mul24(s.t.B2, oy);
-                dst[0] = make_uint4((uint32_t)s.t.A0, (uint32_t)s.t.B0, (uint32_t)c0, (uint32_t)s.t.A1);
-                dst[1] = make_uint4((uint32_t)s.t.B1, (uint32_t)c1, (uint32_t)s.t.A2, (uint32_t)s.t.B2);
-                dst[2] = make_uint4((uint32_t)c2, pre, __float_as_uint(s.t.z0), __float_as_uint(s.t.dz1));
-                dst[3] = make_uint4(__float_as_uint(s.t.dz2), __float_as_uint(s.t.rcpA), s.t.ordk, s.t.box | ((s.t.flags & 0x60u) << 24));
-                atomicOr(&s_start[wv][pre >> 6], 1ull << (pre & 63u));
-            }
-            wave_lds_sync();
-            const unsigned long long my_start = s_start[wv][lane];
-            const uint32_t nb = (total + 63u) >> 6;
-            uint32_t base = 0;
-            for (uint32_t b = 0; b < nb; b++) {
-                const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_start, b);
-                const uint32_t mhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(my_start >> 32), b);
-                const uint64_t m = ((uint64_t)mhi << 32) | mlo;
-                const uint32_t tri = base + __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u)) + (uint32_t)((m >> lane) & 1ull) - 1u;
-                base += (uint32_t)__popcll(m);
-                const uint32_t p = b * 64u + lane;
-                if (p < total) {
-                    const uint4* src = &s_flat[wv][tri * 4];
-                    const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-                    const uint32_t box = q3.w;
-                    const int32_t row = (int32_t)(p - q2.y);
-                    const int32_t A1 = (int32_t)q0.w, A2 = (int32_t)q1.z;
-                    int32_t e1 = (int32_t)q1.y + __mul24((int32_t)q1.x, row), e2 = (int32_t)q2.x + __mul24((int32_t)q1.w, row);
-                    int32_t lo, hi;
-                    span_of_row((int32_t)q0.z + __mul24((int32_t)q0.y, row), e1, e2, (int32_t)q0.x, A1, A2, (int32_t)((box >> 8) & 15u), lo, hi);
-                    // eb1 / eb2 of the run's first pixel, + (1 - tl): the pair walk's integers, stepped along the row
-                    e1 += __mul24(A1, lo) + (int32_t)((box >> 29) & 1u);
-                    e2 += __mul24(A2, lo) + (int32_t)((box >> 30) & 1u);
-                    const float rcp = __uint_as_float(q3.y), dz1 = __uint_as_float(q2.w), dz2 = __uint_as_float(q3.x), z0 = __uint_as_float(q2.z);
-                    uint32_t pix = (box & 0xffu) + (uint32_t)(row * MTR_BIN + lo);
-                    for (int32_t c = lo; c <= hi; c++, pix++, e1 += A1, e2 += A2) {
-                        const float b1 = (float)e1 * rcp, b2 = (float)e2 * rcp;
-                        const float z = fmaf(b2, dz2, fmaf(b1, dz1, z0));
-                        if (__float_as_uint(z) <= zlim) put_fragment<STAIR>(s_key, s_cnt, s_list, pix, make_key(z, q3.z));
-                    }
+            flat_for_each(s_start[wv], 64, lane, total, [&](uint32_t p, uint32_t tri) {
+                const uint4* src = &s_flat[wv][tri * 4];
+                const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+                const uint32_t box = q3.w;
+                const int32_t row = (int32_t)(p - q2.y);
+                const int32_t A1 = (int32_t)q0.w, A2 = (int32_t)q1.z;
+                int32_t e1 = (int32_t)q1.y + __mul24((int32_t)q1.x, row), e2 = (int32_t)q2.x + __mul24((int32_t)q1.w, row);
+                int32_t lo, hi;
+                span_of_row((int32_t)q0.z + __mul24((int32_t)q0.y, row), e1, e2, (int32_t)q0.x, A1, A2, (int32_t)((box >> 8) & 15u), lo, hi);
+                // eb1 / eb2 of the run's first pixel, + (1 - tl): the pair walk's integers, stepped along the row
+                e1 += __mul24(A1, lo) + (int32_t)((box >> 29) & 1u);
+                e2 += __mul24(A2, lo) + (int32_t)((box >> 30) & 1u);
+                const float rcp = __uint_as_float(q3.y), dz1 = __uint_as_float(q2.w), dz2 = __uint_as_float(q3.x), z0 = __uint_as_float(q2.z);
+                uint32_t pix = (box & 0xffu) + (uint32_t)(row * MTR_BIN + lo);
+                for (int32_t c = lo; c <= hi; c++, pix++, e1 += A1, e2 += A2) {
+                    const float b1 = (float)e1 * rcp, b2 = (float)e2 * rcp;
+                    const float z = tri_depth(b1, b2, z0, dz1, dz2);
+                    if (__float_as_uint(z) <= zlim) put_fragment<STAIR>(s_key, s_cnt, s_list, pix, make_key(z, q3.z));
                 }
-            }
+            });
         }
         // ---- lane = (triangle, pixel) pair, 64 pairs per step, for every i32-class triangle.  A round stages a
         //      prefix of the remaining triangles holding <= 4096 pairs (64 start masks, one per lane); one round
@@ -393,54 +306,27 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
             const uint64_t tm = __ballot(take);
             todo &= ~tm;
             const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63 - __builtin_clzll(tm));
-            const uint32_t cidx = __builtin_amdgcn_mbcnt_hi((uint32_t)(tm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tm, 0u));
-            const uint32_t pre = inc - mine;
-            s_start[wv][lane] = 0ull;
+            const uint32_t cidx = lane_rank(tm);
+            flat_stage_starts(s_start[wv], 64, lane, take ? mine : 0u, inc - mine);
+            if (take) stage_flat(&s_flat[wv][cidx * 4], s.t, inc - mine);
             wave_lds_sync();
-            if (take) {
-                uint4* dst = &s_flat[wv][cidx * 4];
-                // edge functions rebased to the bbox origin: a pair evaluates E(col, row) with no bin coordinates
-                const int32_t ox = (int32_t)(s.t.box & 15u), oy = (int32_t)((s.t.box >> 4) & 15u);
-                const int32_t c0 = s.t.C0 + __mul24(s.t.A0, ox) + __mul24(s.t.B0, oy);
-                const int32_t c1 = s.t.C1 + __mul24(s.t.A1, ox) + __mul24(s.t.B1, oy);
-                const int32_t c2 = s.t.C2 + __mul24(s.t.A2, ox) + __mul24(s.t.B2, oy);
-                dst[0] = make_uint4((uint32_t)s.t.A0, (uint32_t)s.t.B0, (uint32_t)c0, (uint32_t)s.t.A1);
-                dst[1] = make_uint4((uint32_t)s.t.B1, (uint32_t)c1, (uint32_t)s.t.A2, (uint32_t)s.t.B2);
-                dst[2] = make_uint4((uint32_t)c2, pre, __float_as_uint(s.t.z0), __float_as_uint(s.t.dz1));
-                // box bits 29 / 30: 1 - tl of edges 1 / 2 (flags bits 5 / 6)
-                dst[3] = make_uint4(__float_as_uint(s.t.dz2), __float_as_uint(s.t.rcpA), s.t.ordk, s.t.box | ((s.t.flags & 0x60u) << 24));
-                atomicOr(&s_start[wv][pre >> 6], 1ull << (pre & 63u));
-            }
-            wave_lds_sync();
-            const unsigned long long my_start = s_start[wv][lane];
-            const uint32_t nb = (total + 63u) >> 6;
-            uint32_t base = 0;
-            for (uint32_t b = 0; b < nb; b++) {
-                const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_start, b);
-                const uint32_t mhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(my_start >> 32), b);
-                const uint64_t m = ((uint64_t)mhi << 32) | mlo;
-                // triangles started before this batch + starts at or below this lane - 1
-                const uint32_t tri = base + __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u)) + (uint32_t)((m >> lane) & 1ull) - 1u;
-                base += (uint32_t)__popcll(m);
-                const uint32_t p = b * 64u + lane;
-                if (p < total) {
-                    const uint4* src = &s_flat[wv][tri * 4];
-                    const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-                    const uint32_t box = q3.w, k = p - q2.y;
-                    const int32_t row = (int32_t)((k * ((box >> 12) & 0x1ffffu)) >> 16);
-                    const int32_t col = (int32_t)k - __mul24(row, (int32_t)((box >> 8) & 15u) + 1);
-                    const int32_t eb0 = (int32_t)q0.z + __mul24((int32_t)q0.x, col) + __mul24((int32_t)q0.y, row);
-                    const int32_t eb1 = (int32_t)q1.y + __mul24((int32_t)q0.w, col) + __mul24((int32_t)q1.x, row);
-                    const int32_t eb2 = (int32_t)q2.x + __mul24((int32_t)q1.z, col) + __mul24((int32_t)q1.w, row);
-                    const float b1 = (float)(eb1 + (int32_t)((box >> 29) & 1u)) * __uint_as_float(q3.y);
-                    const float b2 = (float)(eb2 + (int32_t)((box >> 30) & 1u)) * __uint_as_float(q3.y);
-                    const float z = fmaf(b2, __uint_as_float(q3.x), fmaf(b1, __uint_as_float(q2.w), __uint_as_float(q2.z)));
-                    // 0 <= z <= min(1, clear depth) as ONE unsigned compare of the bit patterns (z is never -0, SPEC.md;
-                    // negative and NaN patterns are above every non-negative bound)
-                    if ((eb0 | eb1 | eb2) >= 0 && __float_as_uint(z) <= zlim)
-                        put_fragment<STAIR>(s_key, s_cnt, s_list, (box & 0xffu) + (uint32_t)(row * MTR_BIN + col), make_key(z, q3.z));
-                }
-            }
+            flat_for_each(s_start[wv], 64, lane, total, [&](uint32_t p, uint32_t tri) {
+                const uint4* src = &s_flat[wv][tri * 4];
+                const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+                const TriEdges E = {(int32_t)q0.x, (int32_t)q0.y, (int32_t)q0.z, (int32_t)q0.w, (int32_t)q1.x, (int32_t)q1.y, (int32_t)q1.z, (int32_t)q1.w, (int32_t)q2.x};
+                const uint32_t box = q3.w, k = p - q2.y;
+                const int32_t row = (int32_t)((k * ((box >> 12) & 0x1ffffu)) >> 16);
+                const int32_t col = (int32_t)k - __mul24(row, (int32_t)((box >> 8) & 15u) + 1);
+                int32_t e1, e2;
+                const bool inside = tri_inside(E, col, row, e1, e2);
+                const float rcpA = __uint_as_float(q3.y);
+                const float z = tri_depth(tri_bary(e1, (box >> 29) & 1u, rcpA), tri_bary(e2, (box >> 30) & 1u, rcpA), __uint_as_float(q2.z), __uint_as_float(q2.w),
+                                          __uint_as_float(q3.x));
+                // 0 <= z <= min(1, clear depth) as ONE unsigned compare of the bit patterns (z is never -0, SPEC.md;
+                // negative and NaN patterns are above every non-negative bound)
+                if (inside && __float_as_uint(z) <= zlim)
+                    put_fragment<STAIR>(s_key, s_cnt, s_list, (box & 0xffu) + (uint32_t)(row * MTR_BIN + col), make_key(z, q3.z));
+            });
         }
         a_cur = a_nxt;
         ord_cur = ord_nxt;
@@ -524,7 +410,9 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
                 if (TEX && mat.shader == MTR_SH_TEXTURED) {
                     const RecA a = load_rec(P.fb, r);
                     const RecB b = P.fb.rec_b[r];
-                    col = shade_textured(a, b, mat, (int32_t)x, (int32_t)y);
+                    float src[4];
+                    sample_textured(a, b, mat, (int32_t)x, (int32_t)y, src);
+                    col = blend_store(0u, src, 0u);  // order-free: blending is off, or the texture is opaque (a == 1 exactly) and the blend a replace
                 } else {
                     col = mat.rgba8;
                 }

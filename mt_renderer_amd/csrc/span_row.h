@@ -1,5 +1,5 @@
 // span_row.h -- the exact run of covered pixel centres in one bbox row of an i32-class triangle (k_tile_vis.hip's span
-// walk).  Plain C++ besides the two macros, so that tests/test_span_exact.py compiles it for the host and checks it
+// walk).  Plain C++ besides the macros, so that tests/test_span_exact.py compiles it for the host and checks it
 // against the per-pixel inside test.
 //
 // The row's edge functions are E_i(col) = e_i + A_i * col (e_i: the value at the bbox's first column, top-left bias
@@ -13,6 +13,8 @@
 #pragma once
 #include <cstdint>
 #include <cmath>
+
+#include "tri_setup.h"  // MTR_MUL24
 
 #if defined(__HIPCC__)
 #define MTR_SPAN_HD __host__ __device__ __forceinline__
@@ -28,12 +30,6 @@
 #endif
 #endif
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MTR_SPAN_MUL24(a, b) __mul24((a), (b))
-#else
-#define MTR_SPAN_MUL24(a, b) ((a) * (b))
-#endif
-
 namespace mtr {
 
 // narrows [lo, hi] to the columns where e + A * col >= 0
@@ -42,7 +38,7 @@ MTR_SPAN_HD void span_edge(int32_t e, int32_t A, int32_t& lo, int32_t& hi) {
     const float s = A > 0 ? -1.0f : 1.0f;                   // ceil(x) = -floor(-x): s * floor(s * q + 1/8)
     const float qc = fminf(fmaxf(q, -2.0f), 17.0f);
     int32_t c = (int32_t)(s * floorf(fmaf(s, qc, 0.125f)));
-    if (e + MTR_SPAN_MUL24(A, c) < 0) c += A > 0 ? 1 : -1;  // the estimate was one column outside: step in
+    if (e + MTR_MUL24(A, c) < 0) c += A > 0 ? 1 : -1;  // the estimate was one column outside: step in
     // selects, not branches: lo starts at 0 and hi at <= 15, so 0 and 16 bound nothing; A == 0 (an edge along the row): the
     // whole row is on one side of it
     const int32_t l = A > 0 ? c : 0, h = A < 0 ? c : (A == 0 && e < 0 ? -1 : 16);

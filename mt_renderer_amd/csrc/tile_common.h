@@ -164,6 +164,66 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---- the flattened walk: work items (pairs, rows) of up to 64 triangles spread over the wave 64 at a time.  The item ->
+//      triangle map needs no search: triangle t sets bit (prefix_t mod 64) of a 64-bit start mask per batch of 64 items
+//      (one ds_or_b64), and item p's triangle is  #starts before its batch + popcount(mask bits <= p) - 1  (v_mbcnt), an
+//      index into the triangles that have items, in lane order. ----
+// a lane with `mine` items after `pre` items of lower lanes marks its start in s_start[nmask].  The caller stages its
+// triangle records next and then calls wave_lds_sync()
+__device__ __forceinline__ void flat_stage_starts(unsigned long long* s_start, uint32_t nmask, uint32_t lane, uint32_t mine, uint32_t pre) {
+    if (lane < nmask) s_start[lane] = 0ull;
+    wave_lds_sync();
+    if (mine) atomicOr(&s_start[pre >> 6], 1ull << (pre & 63u));
+}
+// body(item, compacted triangle index) for every item below total, lane = item of the batch
+template <typename F>
+__device__ __forceinline__ void flat_for_each(const unsigned long long* s_start, uint32_t nmask, uint32_t lane, uint32_t total, F&& body) {
+    const unsigned long long my_start = lane < nmask ? s_start[lane] : 0ull;
+    const uint32_t nb = (total + 63u) >> 6;
+    uint32_t base = 0;
+    for (uint32_t b = 0; b < nb; b++) {
+        const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_start, b);
+        const uint32_t mhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(my_start >> 32), b);
+        const uint64_t m = ((uint64_t)mhi << 32) | mlo;
+        // triangles started before this batch + starts at or below this lane - 1
+        const uint32_t tri = base + __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u)) + (uint32_t)((m >> lane) & 1ull) - 1u;
+        base += (uint32_t)__popcll(m);
+        const uint32_t p = b * 64u + lane;
+        if (p < total) body(p, tri);
+    }
+}
+// this lane's rank among the lanes of a ballot: its compacted triangle index
+__device__ __forceinline__ uint32_t lane_rank(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
+
+// ---- perspective-correct texcoords from barycentrics, and their quad derivatives from the plane equations ----
+struct UVPlanes { float iw0, diw1, diw2, up0, dup1, dup2, vp0, dvp1, dvp2; };
+__device__ __forceinline__ UVPlanes uv_planes(const RecB& b) {
+    return {b.iw0, b.iw1 - b.iw0, b.iw2 - b.iw0, b.up0, b.up1 - b.up0, b.up2 - b.up0, b.vp0, b.vp1 - b.vp0, b.vp2 - b.vp0};
+}
+__device__ __forceinline__ void uv_at_bary(const UVPlanes& p, float b1, float b2, float& u, float& v) {
+    const float iw = fmaf(b2, p.diw2, fmaf(b1, p.diw1, p.iw0));
+    const float up = fmaf(b2, p.dup2, fmaf(b1, p.dup1, p.up0));
+    const float vp = fmaf(b2, p.dvp2, fmaf(b1, p.dvp1, p.vp0));
+    u = up / iw;
+    v = vp / iw;
+}
+struct QuadUV { float u, v, dudx, dvdx, dudy, dvdy; };
+// fine quad differences at pixel (x, y): (odd position) - (even position) along each axis; the pixel is one end of both,
+// so two more evaluations give all four derivatives.  bary(x, y, b1, b2): the triangle's barycentrics at a pixel
+template <typename B>
+__device__ __forceinline__ QuadUV quad_uv(const UVPlanes& p, int32_t x, int32_t y, B&& bary) {
+    auto uv_at = [&](int32_t qx, int32_t qy, float& u, float& v) {
+        float b1, b2;
+        bary(qx, qy, b1, b2);
+        uv_at_bary(p, b1, b2, u, v);
+    };
+    float u, v, uh, vh, uw, vw;
+    uv_at(x, y, u, v);
+    uv_at(x ^ 1, y, uh, vh);
+    uv_at(x, y ^ 1, uw, vw);
+    return {u, v, (x & 1) ? u - uh : uh - u, (x & 1) ? v - vh : vh - v, (y & 1) ? u - uw : uw - u, (y & 1) ? v - vw : vw - v};
+}
+
 // XCD-aware bin order: blocks b, b+8, ... share an XCD's L2: give each XCD a contiguous run of this rank's bins
 // (own_list is row-major for interleaved / band ownership and super-tile-major for super-tiles).
 // Returns false when this block has no bin.

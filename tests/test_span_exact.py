@@ -1,5 +1,5 @@
 """CPU: csrc/span_row.h -- the exact run of covered columns that k_tile_vis.hip's span walk computes for one bbox row --
-against the per-pixel inside test (every column of every row of >= 10^6 i32-class triangles set up as setup_tri does:
+against the per-pixel inside test (every column of every row of >= 10^6 i32-class triangles set up by csrc/tri_setup.h:
 vertices anywhere, on pixel centres and on bin corners, horizontal and vertical edges, long slivers, boxes clipped by the
 bin and by the viewport, edge values near the class limit).  The row bounds come from an f32 estimate settled by one
 integer evaluation, so the check is repeated with the reciprocal 1 ulp off either way (v_rcp_f32's error bound), and a
