@@ -145,11 +145,12 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
 
     const uint32_t ovf = tile_prologue(P);
     const uint32_t lane = threadIdx.x;
-    const uint32_t nbx = P.fb.nbx;
     uint32_t bin;
-    if (!block_to_bin(P.fb, bin, P.xcd_run)) return;
+    if (!block_to_bin(P, bin)) return;
     if (P.mixed && !P.bin_flag[bin]) return;  // mixed frame: k_tile_vis has rendered this bin (only opaque triangles in it)
-    const int32_t binx0 = (int32_t)(bin % nbx) * MTR_BIN, biny0 = (int32_t)(bin / nbx) * MTR_BIN;
+    uint32_t bin_x, bin_y;
+    bin_xy(P, bin, bin_x, bin_y);
+    const int32_t binx0 = (int32_t)bin_x * MTR_BIN, biny0 = (int32_t)bin_y * MTR_BIN;
 
     float dep[4];
     uint32_t col[4];
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
                         flat_stage_starts(s_start, 32, lane, mine, pre);
                         if (mine) {
                             s_tmap[cidx] = (uint8_t)lane;
-                            s_pm[lane] = pre | (((65536u + bw - 1u) / bw) << 12);  // exact k / bw for k < 256, bw <= 16
+                            s_pm[lane] = pre | (row_magic(bw) << 12);  // exact k / bw for k < 256, bw <= 16
                         }
                         wave_lds_sync();
                         flat_for_each(s_start, 32, lane, total, [&](uint32_t pidx, uint32_t ci) {
@@ -403,7 +404,9 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
 
 }  // namespace mtr
 
-void mtr_launch_tile(const TileParams& p, bool textured, hipStream_t s) {
+void mtr_launch_tile(const TileParams& p_in, bool textured, hipStream_t s) {
+    TileParams p = p_in;
+    tile_set_divisors(p);
     const uint32_t mine = p.fb.own.own_count;
     if (mine == 0) return;
     uint32_t grid = (mine + 7) / 8 * 8;

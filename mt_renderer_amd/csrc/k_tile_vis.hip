@@ -47,7 +47,7 @@ struct VisTri {
     float z0, dz1;
     float dz2, rcpA;
     uint32_t ordk;           // submission order + 1
-    uint32_t box;            // px0 | py0 << 4 | (bw-1) << 8 | magic(iw) << 12   (k / iw = k * magic >> 16; iw: items per bbox row)
+    uint32_t box;            // px0 | py0 << 4 | (bw-1) << 8 [| row_magic(iw) << 12 where the walk reads it; iw: items per bbox row]
 };
 static_assert(sizeof(VisTri) == 64, "VisTri is 64 B");
 
@@ -155,9 +155,10 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t ovf = tile_prologue(P);
     uint32_t bin;
-    if (!block_to_bin(P.fb, bin, P.xcd_run)) return;  // uniform over the workgroup, before any barrier
-    const uint32_t nbx = P.fb.nbx;
-    const int32_t binx0 = (int32_t)(bin % nbx) * MTR_BIN, biny0 = (int32_t)(bin / nbx) * MTR_BIN;
+    if (!block_to_bin(P, bin)) return;  // uniform over the workgroup, before any barrier
+    uint32_t bin_x, bin_y;
+    bin_xy(P, bin, bin_x, bin_y);
+    const int32_t binx0 = (int32_t)bin_x * MTR_BIN, biny0 = (int32_t)bin_y * MTR_BIN;
     const float cd = P.clear_depth;
     // fragments pass 0 <= z <= 1 and z <= clear depth (nothing else is in the depth buffer before the resolve)
     const bool zlim_ok = cd >= 0.0f;
@@ -231,15 +232,19 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
         const bool large = (s.t.flags & 1u) != 0;
         const uint32_t iw = ((s.t.box >> 8) & 15u) + 1u;  // bbox width
         const uint32_t npx = (uint32_t)s.npx;
-        // k / iw = k * magic >> 16, exact for k < 256 and iw <= 16: magic = ceil(65536 / iw)
-        s.t.box |= ((65536u + iw - 1u) / iw) << 12;
+        // k / iw = k * magic >> 16 (row_magic, tile_common.h) is read by the whole-wave walk of large triangles and by the
+        // pair walk only, so it is computed in their branches: the span walk, which takes nearly every pass of a frame of
+        // small triangles, never pays for the division.  (A span pass can still hold a large triangle.)
         // ---- lane = pixel of the bbox: triangles that need 64-bit edge functions (more than 64 px across: rare),
         //      broadcast one at a time with v_readlane ----
-        for (uint64_t mb = __ballot(npx != 0 && large); mb; mb &= mb - 1) {
+        const uint64_t mlarge = __ballot(npx != 0 && large);
+        uint32_t lbox = s.t.box;
+        if (mlarge) lbox |= row_magic(iw) << 12;  // uniform branch
+        for (uint64_t mb = mlarge; mb; mb &= mb - 1) {
             const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)__ffsll((long long)mb) - 1);
 #define RL(x) __builtin_amdgcn_readlane((int)(x), t)
             const TriEdges E = {RL(s.t.A0), RL(s.t.B0), RL(s.t.C0), RL(s.t.A1), RL(s.t.B1), RL(s.t.C1), RL(s.t.A2), RL(s.t.B2), RL(s.t.C2)};
-            const uint32_t flags = (uint32_t)RL(s.t.flags), box = (uint32_t)RL(s.t.box), tord = (uint32_t)RL(s.t.ordk), tn = (uint32_t)RL(npx);
+            const uint32_t flags = (uint32_t)RL(s.t.flags), box = (uint32_t)RL(lbox), tord = (uint32_t)RL(s.t.ordk), tn = (uint32_t)RL(npx);
             const float z0 = __int_as_float(RL(__float_as_int(s.t.z0))), dz1 = __int_as_float(RL(__float_as_int(s.t.dz1)));
             const float dz2 = __int_as_float(RL(__float_as_int(s.t.dz2))), rcpA = __int_as_float(RL(__float_as_int(s.t.rcpA)));
             const int32_t H0 = RL(s.chi.x), H1 = RL(s.chi.y), H2 = RL(s.chi.z);
@@ -280,12 +285,12 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
                 const uint32_t box = q3.w;
                 const int32_t row = (int32_t)(p - q2.y);
                 const int32_t A1 = (int32_t)q0.w, A2 = (int32_t)q1.z;
-                int32_t e1 = (int32_t)q1.y + __mul24((int32_t)q1.x, row), e2 = (int32_t)q2.x + __mul24((int32_t)q1.w, row);
+                int32_t e1 = (int32_t)q1.y + MTR_MUL24((int32_t)q1.x, row), e2 = (int32_t)q2.x + MTR_MUL24((int32_t)q1.w, row);
                 int32_t lo, hi;
-                span_of_row((int32_t)q0.z + __mul24((int32_t)q0.y, row), e1, e2, (int32_t)q0.x, A1, A2, (int32_t)((box >> 8) & 15u), lo, hi);
+                span_of_row((int32_t)q0.z + MTR_MUL24((int32_t)q0.y, row), e1, e2, (int32_t)q0.x, A1, A2, (int32_t)((box >> 8) & 15u), lo, hi);
                 // eb1 / eb2 of the run's first pixel, + (1 - tl): the pair walk's integers, stepped along the row
-                e1 += __mul24(A1, lo) + (int32_t)((box >> 29) & 1u);
-                e2 += __mul24(A2, lo) + (int32_t)((box >> 30) & 1u);
+                e1 = MTR_MAD24(A1, lo, e1 + (int32_t)((box >> 29) & 1u));  // lo in [0, 15], A = 256 * dy, |dy| <= 2^14
+                e2 = MTR_MAD24(A2, lo, e2 + (int32_t)((box >> 30) & 1u));
                 const float rcp = __uint_as_float(q3.y), dz1 = __uint_as_float(q2.w), dz2 = __uint_as_float(q3.x), z0 = __uint_as_float(q2.z);
                 uint32_t pix = (box & 0xffu) + (uint32_t)(row * MTR_BIN + lo);
                 for (int32_t c = lo; c <= hi; c++, pix++, e1 += A1, e2 += A2) {
@@ -308,7 +313,10 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
             const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63 - __builtin_clzll(tm));
             const uint32_t cidx = lane_rank(tm);
             flat_stage_starts(s_start[wv], 64, lane, take ? mine : 0u, inc - mine);
-            if (take) stage_flat(&s_flat[wv][cidx * 4], s.t, inc - mine);
+            if (take) {
+                s.t.box |= row_magic(iw) << 12;  // a triangle is taken by one round only
+                stage_flat(&s_flat[wv][cidx * 4], s.t, inc - mine);
+            }
             wave_lds_sync();
             flat_for_each(s_start[wv], 64, lane, total, [&](uint32_t p, uint32_t tri) {
                 const uint4* src = &s_flat[wv][tri * 4];
@@ -428,7 +436,9 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
 
 }  // namespace mtr
 
-void mtr_launch_tile_vis(const TileParams& p, bool textured, hipStream_t s) {
+void mtr_launch_tile_vis(const TileParams& p_in, bool textured, hipStream_t s) {
+    TileParams p = p_in;
+    tile_set_divisors(p);
     const uint32_t mine = p.fb.own.own_count;
     if (mine == 0) return;
     uint32_t grid = (mine + 7) / 8 * 8;

@@ -337,6 +337,9 @@ struct TileParams {
     uint32_t* hint_out;
     uint32_t nhint;
     uint16_t hint_word[4], hint_slot[4];
+    // n / nbx and n / xcd_run as multiply-highs (tile_common.h: udiv_apply); filled in by the launchers, whatever the
+    // caller left here
+    uint32_t nbx_mul, nbx_shift, run_mul, run_shift;
 };
 
 // launchers (defined in the .hip files, called from mtr_api.cpp)

@@ -1,6 +1,51 @@
 // tile_common.h -- fragment-stage helpers shared by the ordered (k_tile.hip) and visibility
 // (k_tile_vis.hip) tile kernels.  Every formula is SPEC.md section 7, bit for bit.
 #pragma once
+#include <cstdint>
+
+// ---- divisions by multiply-high: plain C++, so that tests/cpp/bin_magic_exact.cpp compiles this part for the host and
+//      holds it to `/` and `%` over every value the kernels can meet (tests/test_bin_magic_exact.py) ----
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MTR_UMULHI(a, b) __umulhi((a), (b))
+#else
+#define MTR_UMULHI(a, b) ((uint32_t)(((uint64_t)(uint32_t)(a) * (uint64_t)(uint32_t)(b)) >> 32))
+#endif
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define MTR_DIV_HD __host__ __device__ __forceinline__
+#else
+#define MTR_DIV_HD inline
+#endif
+
+namespace mtr {
+
+// n / d for a divisor fixed per launch (the scalar unit has no divide; on a uniform n this is s_lshl + s_mul_hi_u32 +
+// s_lshr).  With s = floor(log2 d) and mul = ceil(2^(31 + s) / d) <= 2^31:  2n * mul / 2^(32 + s) = n / d + n * e / (d *
+// 2^(31 + s)), e = mul * d - 2^(31 + s) < d, and the excess stays below 1 / d -- the floor is exact -- while n * e <
+// 2^(31 + s), which n < 2^30 guarantees (e < d < 2^(s + 1)).  EXACT FOR EVERY d >= 1 AND EVERY n < 2^30: a bin index is
+// below 2^20 (frames are at most 16384 x 16384: nbx, nby <= 1024) and blockIdx.x >> 3 below 2^18 (at most 2^17 bins per
+// XCD, rounded up to whole runs of at most 65536).  d == 0 (no runs: the divisor is not used) gives {0, 0}.
+struct UDiv {
+    uint32_t mul, shift;
+};
+MTR_DIV_HD UDiv udiv_make(uint32_t d) {
+    UDiv r = {0u, 0u};
+    if (d == 0u) return r;
+    while ((d >> r.shift) > 1u) r.shift++;
+    r.mul = (uint32_t)((((uint64_t)1 << (31u + r.shift)) + d - 1u) / d);
+    return r;
+}
+MTR_DIV_HD uint32_t udiv_apply(uint32_t n, uint32_t mul, uint32_t shift) { return MTR_UMULHI(n << 1, mul) >> shift; }
+
+// the pair walks' item -> bbox row:  k / iw = k * row_magic(iw) >> 16, exact for k < 256 and iw = 1 .. 16 (items per bbox
+// row), with magic = ceil(65536 / iw):  k * magic / 65536 = k / iw + k * e / (iw * 65536), e = magic * iw - 65536 < iw, and
+// the excess stays below 1 / iw because k * e < 256 * 16 < 65536.  A lane-varying u32 division (28 VALU, three of them
+// quarter-rate), so the kernels compute it only for the triangles whose walk reads it
+MTR_DIV_HD uint32_t row_magic(uint32_t iw) { return (65536u + iw - 1u) / iw; }
+
+}  // namespace mtr
+
+#if defined(__HIPCC__)  // everything below is device code
 #include "bc_sample.h"
 #include "mtr_internal.h"
 #include "span_row.h"
@@ -226,16 +271,37 @@ __device__ __forceinline__ QuadUV quad_uv(const UVPlanes& p, int32_t x, int32_t 
 
 // XCD-aware bin order: blocks b, b+8, ... share an XCD's L2: give each XCD a contiguous run of this rank's bins
 // (own_list is row-major for interleaved / band ownership and super-tile-major for super-tiles).
-// Returns false when this block has no bin.
-__device__ __forceinline__ bool block_to_bin(const FrameBuffers& fb, uint32_t& bin, uint32_t run = 0) {
+// Returns false when this block has no bin.  The divisions by the run length and (bin_xy) by the bins per row are
+// multiply-highs by the launcher's multipliers (tile_set_divisors): every value here is uniform over the workgroup, and
+// a scalar division is a float-reciprocal sequence of some 25 instructions that every wave of every bin would pay.
+__device__ __forceinline__ bool block_to_bin(const TileParams& P, uint32_t& bin) {
+    const FrameBuffers& fb = P.fb;
+    const uint32_t run = P.xcd_run;
     const uint32_t per = (gridDim.x + 7) / 8;
     const uint32_t x = blockIdx.x & 7, i = blockIdx.x >> 3;
     // run == 0: XCD x takes one contiguous eighth of the bins; run > 0: runs of `run` consecutive bins are dealt to the
     // XCDs in turn (the launch covers whole runs), so every XCD sees every region of the frame
-    const uint32_t slot = run ? ((i / run) * 8 + x) * run + (i % run) : x * per + i;
+    uint32_t slot = x * per + i;
+    if (run) {
+        const uint32_t q = udiv_apply(i, P.run_mul, P.run_shift);  // i / run
+        slot = (q * 8 + x) * run + (i - q * run);
+    }
     if (slot >= fb.own.own_count) return false;
     bin = fb.own.own_list ? fb.own.own_list[slot] : slot;
     return bin < fb.nbx * fb.nby;
 }
+// bin -> its column and row in the grid of bins
+__device__ __forceinline__ void bin_xy(const TileParams& P, uint32_t bin, uint32_t& bx, uint32_t& by) {
+    by = udiv_apply(bin, P.nbx_mul, P.nbx_shift);  // bin / nbx
+    bx = bin - by * P.fb.nbx;
+}
 
 }  // namespace mtr
+
+// what both launchers do to their copy of the parameters: the multipliers of the two launch-invariant divisors
+inline void tile_set_divisors(TileParams& p) {
+    const mtr::UDiv n = mtr::udiv_make(p.fb.nbx), r = mtr::udiv_make(p.xcd_run);
+    p.nbx_mul = n.mul; p.nbx_shift = n.shift;
+    p.run_mul = r.mul; p.run_shift = r.shift;
+}
+#endif  // __HIPCC__

@@ -24,6 +24,13 @@
 #else
 #define MTR_MUL24(a, b) mtr::mul24_model((a), (b))
 #endif
+// c + MTR_MUL24(a, b), as the instruction itself (v_mad_i32_i24) on the device: where the compiler cannot see that an operand
+// fits 24 bits it lowers __mul24 to a sign extension and a full 32-bit multiply, which issues at a quarter of the rate
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MTR_MAD24(a, b, c) mtr::mad24_inst((a), (b), (c))
+#else
+#define MTR_MAD24(a, b, c) ((int32_t)((uint32_t)mtr::mul24_model((a), (b)) + (uint32_t)(c)))
+#endif
 
 #ifndef MTR_TRI_CLASS_LIMIT  // the test's mutant build raises it until 256 * dy leaves the 24 bits
 #define MTR_TRI_CLASS_LIMIT 16384
@@ -35,6 +42,13 @@ MTR_TRI_HD int32_t mul24_model(int32_t a, int32_t b) {
     const uint32_t sa = (((uint32_t)a & 0xFFFFFFu) ^ 0x800000u) - 0x800000u, sb = (((uint32_t)b & 0xFFFFFFu) ^ 0x800000u) - 0x800000u;
     return (int32_t)(sa * sb);
 }
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ int32_t mad24_inst(int32_t a, int32_t b, int32_t c) {
+    int32_t r;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+#endif
 MTR_TRI_HD int32_t tri_min3(int32_t a, int32_t b, int32_t c) { const int32_t m = a < b ? a : b; return m < c ? m : c; }
 MTR_TRI_HD int32_t tri_max3(int32_t a, int32_t b, int32_t c) { const int32_t m = a > b ? a : b; return m > c ? m : c; }
 
