@@ -196,7 +196,9 @@ __device__ __forceinline__ VOut shade_vertex(const uint8_t* vbuf, const DPrim& p
 // ---------------------------------------------------------------------------------------------
 // The same vertex shader on the matrix cores: v_mfma_f32_4x4x1_16b_f32 = 16 independent
 // (4x1)*(1x4) outer products per wave; block = 4 consecutive lanes, D[lane][v] = A[block*4+v] * B[lane]
-// + C, and a k-step chain is bitwise an fmaf chain (tools/mfma_probe.hip, run on gfx950).  One lane =
+// + C, and a k-step chain is bitwise an fmaf chain (tools/mfma_probe.hip on benign values; tests/test_gpu_vertex_edges.py
+// under cancellation, with subnormal operands, products and sums, signed zeros, overflow and NaN, in coherent, incoherent
+// and partial blocks: 0 of 2 188 vertices differ from the oracle at five palette sizes).  One lane =
 // one vertex supplies B (its own w_k*p_c, or q_c) and row (lane & 3) of the 4x4 matrix as A:
 //   * clip = M * (q,1): A is the wave-uniform M -> 4 MFMAs for 64 vertices;
 //   * skinning: A is the bone matrix P[j_k], so a block must share its four joint indices (rows of a
