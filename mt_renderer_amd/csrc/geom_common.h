@@ -113,7 +113,7 @@ __device__ __forceinline__ void decode_regs(uint32_t fmt, uint32_t cnt, uint32_t
     default: break;
     }
 }
-// bytes of an element the decode reads (host: elem_bytes in mtr_api.cpp); 0 for formats the table does not hold
+// bytes of an element the decode reads (host: elem_bytes in host_model.cpp); 0 for formats the table does not hold
 __device__ __forceinline__ uint32_t elem_nbytes(uint32_t fmt, uint32_t cnt) {
     switch (fmt) {
     case 10: return cnt == 1 ? 2u : 4u;

@@ -1,0 +1,458 @@
+// host_batch.cpp -- instance batches and their versions, pose and animation staging, animation clip sets.
+#include "host.h"
+
+// k_pose.hip.  Weak: the host-only builds of this file (tests/cpp, over the HIP stub runtime) link no kernels and never
+// form a pose; libmtr.so links k_pose.o.
+void mtr_launch_pose(const PoseParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+// k_anim.hip, weak for the same reason
+void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+
+namespace mtr_host {
+
+// host local matrices -> the device's staging buffer, on s_copy (the render thread only)
+int32_t stage_pose(mtr_device* d, const float* local_mats, size_t count) {
+    if (count > d->pose_stage_cap) {
+        HIPCHK(d, hipStreamSynchronize(d->s_copy));  // a queued pose kernel may still read the old buffer
+        if (d->pose_stage) (void)hipFree(d->pose_stage);
+        d->pose_stage = nullptr; d->pose_stage_cap = 0;
+        int32_t rc = dev_alloc(d, &d->pose_stage, count);
+        if (rc) return rc;
+        d->pose_stage_cap = count;
+    }
+    HIPCHK(d, hipMemcpyAsync(d->pose_stage, local_mats, count * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
+    return MTR_OK;
+}
+
+PoseParams pose_params(const mtr_model::Skeleton& sk, const float* locals, float* out) {
+    PoseParams pp{};
+    pp.locals = locals; pp.out = out; pp.imats = sk.d;
+    pp.paths = reinterpret_cast<const uint32_t*>(sk.d + (size_t)sk.njoints * 16);
+    pp.path_words = reinterpret_cast<const uint32_t*>(sk.d + (size_t)sk.njoints * 17);
+    pp.njoints = sk.njoints; pp.path_bytes = sk.path_bytes;
+    return pp;
+}
+
+namespace {
+
+AnimParams anim_params(const mtr_anim* a, const mtr_model::Skeleton& sk, const void* states_dev, float* out) {
+    AnimParams ap{};
+    ap.pose = pose_params(sk, nullptr, out);
+    ap.clips = a->d;
+    ap.keys = reinterpret_cast<const float*>(a->d + (size_t)a->nclips * 4);
+    ap.states = static_cast<const uint32_t*>(states_dev);
+    ap.nclips = a->nclips;
+    return ap;
+}
+
+// around a kernel on `s` that reads the clip set: see mtr_anim::last
+int32_t anim_before(mtr_anim* a, hipStream_t s) {
+    if (a->recorded && a->last_stream != s) HIPCHK(a->dev, hipStreamWaitEvent(s, a->last, 0));
+    return MTR_OK;
+}
+int32_t anim_after(mtr_anim* a, hipStream_t s) {
+    HIPCHK(a->dev, hipEventRecord(a->last, s));
+    a->last_stream = s; a->recorded = true;
+    return MTR_OK;
+}
+
+// frame `f` has left the GPU (or certainly will have before anything queued after this call runs)
+bool frame_done(mtr_device* d, uint64_t f) {
+    if (d->frames_submitted >= f + 1 + d->max_inflight) return true;  // frame f + max_inflight waited for it
+    hipEvent_t e = d->inflight[f % d->max_inflight];
+    const bool done = !e || hipEventQuery(e) == hipSuccess;
+    (void)hipGetLastError();  // hipEventQuery reports "not ready" as an error code
+    return done;
+}
+
+}  // namespace
+
+void release_now(FreeList& fl) {
+    for (void* p : fl.bufs) (void)hipFree(p);
+    for (hipEvent_t e : fl.events) (void)hipEventDestroy(e);
+    fl.bufs.clear();
+    fl.events.clear();
+}
+
+namespace {
+
+// Retires the buffer of a version nobody will draw again: into `now` (released after the lock) when no frame in flight
+// reads it and its last write has completed, otherwise -- or when now is nullptr -- parked in d->garbage with the event of
+// that write, collected by a later submit.  submit_mu held.
+void retire_version(mtr_device* d, mtr_batch::Ver& v, FreeList* now) {
+    if (v.d) {
+        const bool read_in_flight = v.used && !frame_done(d, v.last_frame);
+        bool written = true;
+        if (v.ready) { written = hipEventQuery(v.ready) == hipSuccess; (void)hipGetLastError(); }
+        if (read_in_flight || !written || !now) {
+            d->garbage.push_back({v.d, v.used ? v.last_frame : 0, v.ready});
+            v.ready = nullptr;
+        } else {
+            now->bufs.push_back(v.d);
+        }
+    }
+    if (v.ready) {
+        if (now) now->events.push_back(v.ready);
+        else d->garbage.push_back({nullptr, 0, v.ready});
+    }
+    v = mtr_batch::Ver{};
+}
+
+}  // namespace
+
+// drops one reference of the batch; the last one retires every version and frees the handle.  submit_mu held.
+void batch_unref(mtr_batch* b, FreeList& fl) {
+    if (--b->refs) return;
+    mtr_device* d = b->dev;
+    if (b->hint_slot >= 0) { d->hint_used[b->hint_slot] = false; d->hint_host[2 * b->hint_slot] = d->hint_host[2 * b->hint_slot + 1] = 0u; }
+    for (auto& v : b->vers) retire_version(d, v, &fl);
+    delete b;
+}
+
+namespace {
+
+// A version the next update may write: not the current one, held by no frame that may still (re-)run, and preferably read
+// by no frame still on the GPU.  Once the ring has max_inflight + 1 versions the one read longest ago is taken and
+// *frame_ev is the completion event of the frame that read it: the writing stream must wait on it.  A version too small
+// for npal palettes per instance is emptied (its buffer parked in d->garbage) for the caller to allocate.  No allocation,
+// free or host wait here.  submit_mu held.
+int32_t batch_next_version(mtr_batch* b, uint32_t npal, int* out, hipEvent_t* frame_ev) {
+    mtr_device* d = b->dev;
+    int pick = -1, oldest = -1;
+    *frame_ev = nullptr;
+    for (size_t i = 0; i < b->vers.size() && pick < 0; i++) {
+        const mtr_batch::Ver& v = b->vers[i];
+        if ((int)i == b->cur || v.pinned) continue;
+        if (!v.used || frame_done(d, v.last_frame)) pick = (int)i;
+        else if (oldest < 0 || v.last_frame < b->vers[(size_t)oldest].last_frame) oldest = (int)i;
+    }
+    if (pick < 0 && (oldest < 0 || b->vers.size() < (size_t)d->max_inflight + 1)) {
+        if (b->vers.size() >= 4096) return fail(d, MTR_E_NOMEM, "more than 4096 live frames hold a version of this batch");
+        b->vers.emplace_back();
+        pick = (int)b->vers.size() - 1;
+    }
+    if (pick < 0) {
+        // not done, so its frame is one of the last max_inflight: the ring event still holds that frame's record
+        pick = oldest;
+        *frame_ev = d->inflight[b->vers[(size_t)pick].last_frame % d->max_inflight];
+    }
+    mtr_batch::Ver& v = b->vers[(size_t)pick];
+    if (v.cap < (size_t)b->n * 16 * (1 + (size_t)npal)) retire_version(d, v, nullptr);
+    v.used = false; v.last_frame = 0;
+    *out = pick;
+    return MTR_OK;
+}
+
+// Where the palettes of a pose come from: local matrices (k_pose), or animation states over a clip set (k_anim); device memory
+struct PoseSrc {
+    const float* locals = nullptr;
+    mtr_anim* anim = nullptr;
+    const void* states = nullptr;
+    explicit operator bool() const { return locals || anim; }
+};
+
+// What an update writes into a fresh version.  mats / pals: host arrays, or nullptr = keep the current version's (device
+// copy); a pose source replaces the palettes with the pose's.  Enqueued on `s`, the version made current.
+int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, uint32_t npal_new, const PoseSrc& src, hipStream_t s) {
+    mtr_device* d = b->dev;
+    const size_t n = b->n;
+    int vi = -1;
+    mtr_batch::Ver cur{}, v{};
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        cur = b->vers[(size_t)b->cur];
+        const uint32_t npal = (pals || src) ? npal_new : cur.npal;
+        hipEvent_t frame_ev = nullptr;
+        int32_t rc = batch_next_version(b, npal, &vi, &frame_ev);
+        if (rc) return rc;
+        mtr_batch::Ver& nv = b->vers[(size_t)vi];
+        nv.npal = npal;
+        nv.pinned++;  // nobody else takes it while it is being written
+        v = nv;
+        // a frame still on the GPU reads it: the write waits for that frame on the device (the enqueue happens under the
+        // lock, before any later frame can record the same ring event)
+        if (frame_ev) {
+            const hipError_t e = hipStreamWaitEvent(s, frame_ev, 0);
+            if (e != hipSuccess) { nv.pinned--; return fail(d, MTR_E_HIP, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e)); }
+        }
+    }
+    // only this thread touches the version's buffer and event while it is pinned
+    int32_t rc = MTR_OK;
+    const size_t need = n * 16 * (1 + (size_t)v.npal);
+    if (!v.d) {
+        if (!(rc = dev_alloc(d, &v.d, need))) v.cap = need;
+    }
+    if (!rc && !v.ready && hipEventCreateWithFlags(&v.ready, hipEventDisableTiming) != hipSuccess) rc = fail(d, MTR_E_HIP, "hipEventCreate failed");
+    auto enqueue = [&]() -> int32_t {
+        HIPCHK(d, hipStreamWaitEvent(s, v.ready, 0));    // its previous write (a version may be rewritten before any draw)
+        if (cur.ready) HIPCHK(d, hipStreamWaitEvent(s, cur.ready, 0));
+        if (mats) HIPCHK(d, hipMemcpyAsync(v.d, mats, n * 64, hipMemcpyHostToDevice, s));
+        else HIPCHK(d, hipMemcpyAsync(v.d, cur.d, n * 64, hipMemcpyDeviceToDevice, s));
+        float* vp = v.d + n * 16;
+        if (src.anim) {
+            int32_t arc = anim_before(src.anim, s);
+            if (arc) return arc;
+            mtr_launch_anim(anim_params(src.anim, b->model->skel, src.states, vp), (uint32_t)n, s);
+            HIPCHK(d, hipGetLastError());
+            if ((arc = anim_after(src.anim, s))) return arc;
+        } else if (src.locals) {
+            mtr_launch_pose(pose_params(b->model->skel, src.locals, vp), (uint32_t)n, s);
+            HIPCHK(d, hipGetLastError());
+        } else if (pals) {
+            HIPCHK(d, hipMemcpyAsync(vp, pals, n * v.npal * 64, hipMemcpyHostToDevice, s));
+        } else if (v.npal) {
+            HIPCHK(d, hipMemcpyAsync(vp, cur.d + n * 16, n * v.npal * 64, hipMemcpyDeviceToDevice, s));
+        }
+        HIPCHK(d, hipEventRecord(v.ready, s));
+        return MTR_OK;
+    };
+    if (!rc) rc = enqueue();
+    std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+    mtr_batch::Ver& nv = b->vers[(size_t)vi];
+    nv.d = v.d; nv.cap = v.cap; nv.ready = v.ready;
+    nv.pinned--;
+    if (!rc) b->cur = vi;
+    return rc;
+}
+
+int32_t check_batch_pose(mtr_batch* b, size_t njoints) {
+    mtr_device* d = b->dev;
+    if (!b->model->skel.d) return fail(d, MTR_E_INVALID, "pose: the batch's model has no skeleton");
+    if (njoints != b->model->skel.njoints) return fail(d, MTR_E_INVALID, "pose: one local matrix per joint of the skeleton");
+    if (!mtr_launch_pose) return fail(d, MTR_E_UNSUPPORTED, "pose: built without k_pose");
+    return set_device(d);
+}
+
+int32_t check_anim(mtr_device* d, const mtr_model* m, const mtr_anim* a) {
+    if (!a) return fail(d, MTR_E_INVALID, "animate: no animation set");
+    if (a->dev != d) return fail(d, MTR_E_INVALID, "animate: the animation set belongs to another device");
+    if (!m->skel.d) return fail(d, MTR_E_INVALID, "animate: the model has no skeleton");
+    if (a->njoints != m->skel.njoints) return fail(d, MTR_E_INVALID, "animate: the animation set's joint count is not the skeleton's");
+    if (!mtr_launch_anim) return fail(d, MTR_E_UNSUPPORTED, "animate: built without k_anim");
+    return set_device(d);
+}
+
+}  // namespace
+
+}  // namespace mtr_host
+
+using namespace mtr_host;
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------------------
+// instance batches
+// ---------------------------------------------------------------------------------------------
+int32_t mtr_batch_create(mtr_device* d, mtr_model* model, size_t n, const float* model_mats, const float* palettes,
+                         size_t npal, const int32_t* texture_override, mtr_batch** out) {
+    if (!d || !out) return MTR_E_INVALID;
+    *out = nullptr;
+    if (!model || model->dev != d || !model_mats || n == 0 || n > 0xFFFFu)
+        return fail(d, MTR_E_INVALID, "bad batch arguments");
+    if (npal > 256 || (npal && !palettes)) return fail(d, MTR_E_INVALID, "palette: at most 256 matrices");
+    auto b = std::unique_ptr<mtr_batch, BatchDeleter>(new mtr_batch());
+    b->dev = d; b->model = model; b->n = (uint32_t)n;
+    b->vers.emplace_back();
+    mtr_batch::Ver& v = b->vers[0];
+    v.npal = palettes ? (uint32_t)npal : 0;
+    if (texture_override) {
+        b->tex_override.assign(texture_override, texture_override + n);
+        for (int32_t t : b->tex_override)
+            if (t >= (int32_t)model->textures.size()) return fail(d, MTR_E_INVALID, "texture_override out of range");
+    }
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    v.cap = n * 16 * (1 + (size_t)v.npal);
+    if ((rc = dev_alloc(d, &v.d, v.cap))) return rc;
+    // uploads go through the copy stream and an event: creating a batch does not wait for frames in flight
+    HIPCHK(d, hipMemcpyAsync(v.d, model_mats, n * 64, hipMemcpyHostToDevice, d->s_copy));
+    if (v.npal) HIPCHK(d, hipMemcpyAsync(v.d + n * 16, palettes, n * npal * 64, hipMemcpyHostToDevice, d->s_copy));
+    HIPCHK(d, hipEventCreateWithFlags(&v.ready, hipEventDisableTiming));
+    HIPCHK(d, hipEventRecord(v.ready, d->s_copy));
+    *out = b.release();
+    return MTR_OK;
+}
+
+void mtr_batch_destroy(mtr_batch* b) {
+    if (!b) return;
+    mtr_device* d = b->dev;
+    (void)hipSetDevice(d->hip_dev);
+    // a frame that drew the batch may still be in flight, or be re-run: the versions its draws recorded stay until those
+    // frames are destroyed (their references), then they are parked until that frame has left the GPU (collected at a
+    // later submit), as is a version a pose kernel or copy may still be writing.  No stream is drained either way.  The
+    // exchange thread destroys the batches its frames own while the render thread submits: submit_mu guards the list.
+    FreeList fl;
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        batch_unref(b, fl);
+    }
+    release_now(fl);
+}
+
+int32_t mtr_batch_update(mtr_batch* b, const float* model_mats, const float* palettes, size_t npal) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (palettes && (npal == 0 || npal > 256)) return fail(d, MTR_E_INVALID, "batch update: 1 to 256 palette matrices per instance");
+    if (!model_mats && !palettes) return MTR_OK;
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    return batch_write_version(b, model_mats, palettes, (uint32_t)npal, PoseSrc{}, d->s_copy);
+}
+
+int32_t mtr_batch_set_poses(mtr_batch* b, const float* local_mats, size_t njoints) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!local_mats) return fail(d, MTR_E_INVALID, "pose: no local matrices");
+    int32_t rc = check_batch_pose(b, njoints);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, local_mats, (size_t)b->n * njoints * 16))) return rc;
+    PoseSrc src;
+    src.locals = d->pose_stage;
+    return batch_write_version(b, nullptr, nullptr, (uint32_t)njoints, src, d->s_copy);
+}
+
+int32_t mtr_batch_set_poses_device(mtr_batch* b, const float* local_mats_dev, size_t njoints, void* hip_stream) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!local_mats_dev || ((uintptr_t)local_mats_dev & 15u)) return fail(d, MTR_E_INVALID, "pose: device matrices must be 16-byte aligned");
+    int32_t rc = check_batch_pose(b, njoints);
+    if (rc) return rc;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    PoseSrc src;
+    src.locals = local_mats_dev;
+    return batch_write_version(b, nullptr, nullptr, (uint32_t)njoints, src, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// animation clips (SPEC.md section 14)
+// ---------------------------------------------------------------------------------------------
+int32_t mtr_anim_create(mtr_device* d, size_t njoints, size_t nclips, const uint32_t* nkeys, const uint32_t* flags,
+                        const mtr_anim_key* keys, mtr_anim** out) {
+    if (!d || !out) return MTR_E_INVALID;
+    *out = nullptr;
+    if (njoints == 0 || njoints > MTR_POSE_MAX_JOINTS) return fail(d, MTR_E_INVALID, "anim: 1 to 256 joints");
+    if (nclips == 0 || nclips > 0xFFFFFFu || !nkeys || !keys) return fail(d, MTR_E_INVALID, "anim: at least one clip, its key counts and keys");
+    std::vector<uint32_t> table(nclips * 4);
+    uint64_t total = 0;
+    for (size_t c = 0; c < nclips; c++) {
+        // key counts are exact in binary32 (the position arithmetic of section 14)
+        if (nkeys[c] == 0 || nkeys[c] > (1u << 24)) return fail(d, MTR_E_INVALID, "anim: a clip has 1 to 16 777 216 keys");
+        table[c * 4 + 0] = (uint32_t)total;
+        table[c * 4 + 1] = nkeys[c];
+        table[c * 4 + 2] = flags ? flags[c] : 0u;
+        table[c * 4 + 3] = 0u;
+        total += nkeys[c];
+        if (total * njoints > 0x3FFFFFFu) return fail(d, MTR_E_INVALID, "anim: more than 2^26 joint keys");
+    }
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    auto a = std::make_unique<mtr_anim>();
+    a->dev = d; a->njoints = (uint32_t)njoints; a->nclips = (uint32_t)nclips;
+    const size_t key_words = (size_t)total * njoints * 12;
+    if ((rc = dev_alloc(d, &a->d, table.size() + key_words))) return rc;
+    hipError_t e = hipMemcpy(a->d, table.data(), table.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(a->d + table.size(), keys, key_words * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&a->last, hipEventDisableTiming);
+    if (e != hipSuccess) { (void)hipFree(a->d); return fail(d, MTR_E_HIP, std::string("anim upload: ") + hipGetErrorString(e)); }
+    *out = a.release();
+    return MTR_OK;
+}
+
+void mtr_anim_destroy(mtr_anim* a) {
+    if (!a) return;
+    mtr_device* d = a->dev;
+    {
+        // a kernel may still read the clip set: parked behind the event of the last one, collected by a later submit
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        d->garbage.push_back({a->d, 0, a->last});
+    }
+    delete a;
+}
+
+int32_t mtr_model_animate(mtr_model* m, mtr_anim* a, const mtr_anim_state* state) {
+    if (!m) return MTR_E_INVALID;
+    mtr_device* d = m->dev;
+    if (!state) return fail(d, MTR_E_INVALID, "animate: no state");
+    int32_t rc = check_anim(d, m, a);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, reinterpret_cast<const float*>(state), sizeof(mtr_anim_state) / sizeof(float)))) return rc;
+    std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+    mtr_model::PalBuf* pb = nullptr;
+    if ((rc = next_palette_buffer(m, a->njoints, &pb))) return rc;
+    if ((rc = anim_before(a, d->s_copy))) return rc;
+    mtr_launch_anim(anim_params(a, m->skel, d->pose_stage, pb->d), 1, d->s_copy);
+    HIPCHK(d, hipGetLastError());
+    if ((rc = anim_after(a, d->s_copy))) return rc;
+    HIPCHK(d, hipEventRecord(pb->ready, d->s_copy));
+    return MTR_OK;
+}
+
+int32_t mtr_batch_animate(mtr_batch* b, mtr_anim* a, const mtr_anim_state* states) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!states) return fail(d, MTR_E_INVALID, "animate: no states");
+    int32_t rc = check_anim(d, b->model, a);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, reinterpret_cast<const float*>(states), (size_t)b->n * (sizeof(mtr_anim_state) / sizeof(float))))) return rc;
+    PoseSrc src;
+    src.anim = a; src.states = d->pose_stage;
+    return batch_write_version(b, nullptr, nullptr, a->njoints, src, d->s_copy);
+}
+
+int32_t mtr_batch_animate_device(mtr_batch* b, mtr_anim* a, const mtr_anim_state* states_dev, void* hip_stream) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!states_dev || ((uintptr_t)states_dev & 7u)) return fail(d, MTR_E_INVALID, "animate: device states must be 8-byte aligned");
+    int32_t rc = check_anim(d, b->model, a);
+    if (rc) return rc;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    PoseSrc src;
+    src.anim = a; src.states = states_dev;
+    return batch_write_version(b, nullptr, nullptr, a->njoints, src, s);
+}
+
+int32_t mtr_anim_sample(mtr_anim* a, const mtr_anim_state* states, size_t n, float* out_locals, size_t count) {
+    if (!a) return MTR_E_INVALID;
+    mtr_device* d = a->dev;
+    const size_t need = n * a->njoints * 16;
+    if (n > 0xFFFFFFu || (n && (!states || !out_locals)) || count < need) return fail(d, MTR_E_INVALID, "anim sample: n states and room for n * njoints * 16 floats");
+    if (!mtr_launch_anim_sample) return fail(d, MTR_E_UNSUPPORTED, "anim sample: built without k_anim");
+    int32_t rc = set_device(d);
+    if (rc || !n) return rc;
+    float* tmp = nullptr;  // the local matrices, then the states
+    if ((rc = dev_alloc(d, &tmp, need + n * 6))) return rc;
+    auto run = [&]() -> int32_t {
+        HIPCHK(d, hipMemcpyAsync(tmp + need, states, n * sizeof(mtr_anim_state), hipMemcpyHostToDevice, d->s_copy));
+        AnimParams ap = anim_params(a, mtr_model::Skeleton{}, tmp + need, tmp);
+        ap.pose.njoints = a->njoints;
+        mtr_launch_anim_sample(ap, (uint32_t)n, d->s_copy);
+        HIPCHK(d, hipGetLastError());
+        HIPCHK(d, hipMemcpyAsync(out_locals, tmp, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
+        return MTR_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(d->s_copy);  // also when a step failed: the buffer is freed next
+    (void)hipFree(tmp);
+    if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
+}
+
+int32_t mtr_batch_read_palettes(mtr_batch* b, float* out, size_t count) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    mtr_batch::Ver v{};
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        v = b->vers[(size_t)b->cur];
+    }
+    const size_t need = (size_t)b->n * v.npal * 16;
+    if ((!out && need) || count < need) return fail(d, MTR_E_INVALID, "read_palettes: room for n * npal * 16 floats needed");
+    int32_t rc = set_device(d);
+    if (rc || !need) return rc;
+    HIPCHK(d, hipStreamWaitEvent(d->s_copy, v.ready, 0));
+    HIPCHK(d, hipMemcpyAsync(out, v.d + (size_t)b->n * 16, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
+    HIPCHK(d, hipStreamSynchronize(d->s_copy));
+    return MTR_OK;
+}
+
+}  // extern "C"

@@ -19,7 +19,7 @@
 //     defines them -- per pixel, then the only framebuffer write of the frame.
 // Same arithmetic per fragment as k_tile.hip, bit for bit: the set-up, the edge evaluation and the absolute-coordinate
 // barycentrics are tri_setup.h's functions in both kernels, the flattened walk tile_common.h's; the host picks this kernel only when the
-// frame is eligible (mtr_api.cpp); tests run both kernels on the same scenes.
+// frame is eligible (host_submit.cpp); tests run both kernels on the same scenes.
 // VIS_WAVES waves per 16x16 bin (passes dealt round-robin, two workgroup barriers in total), no segment
 // sort (the submission order rides in the entry).
 //

@@ -796,7 +796,7 @@ int32_t mtr_rscheduler_apply(const mtr_rscheduler* s, uint32_t frame, const mtr_
     return MTR_OK;
 }
 
-// mtr_api.cpp.  Weak: the parser fuzz build (tests/cpp/files_fuzz.cpp) compiles this file alone, with stand-ins for the few
+// host_model.cpp.  Weak: the parser fuzz build (tests/cpp/files_fuzz.cpp) compiles this file alone, with stand-ins for the few
 // entry points of mtr.h it calls; libmtr.so always has it.
 extern "C" int32_t mtr_model_set_skeleton(mtr_model* model, const uint8_t* parents, const float* imats, size_t njoints) __attribute__((weak));
 

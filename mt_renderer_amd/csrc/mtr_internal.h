@@ -342,7 +342,7 @@ struct TileParams {
     uint32_t nbx_mul, nbx_shift, run_mul, run_shift;
 };
 
-// launchers (defined in the .hip files, called from mtr_api.cpp)
+// launchers (defined in the .hip files, called from host_*.cpp)
 void mtr_launch_geom(const GeomParams& p, hipStream_t s);
 void mtr_launch_scan(const FrameBuffers& fb, hipStream_t s);
 void mtr_launch_fill(const FrameBuffers& fb, uint32_t total_chunks, hipStream_t s);

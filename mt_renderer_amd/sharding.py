@@ -3,7 +3,7 @@
 Bins are MTR_BIN x MTR_BIN pixels, numbered row-major.  Which rank owns a bin is the host's choice per frame
 (include/mtr.h: MTR_OWN_*): interleaved (``b % world``), bands of bin rows, or super-tiles dealt round-robin.  Each rank
 packs its bins, in its list order, into ``shard_bins * BIN*BIN`` RGBA8 pixels (the all-gather send buffer, padded to the
-largest share); ``unpack_shards`` rebuilds the linear framebuffer from the gathered blocks.  csrc/mtr_api.cpp
+largest share); ``unpack_shards`` rebuilds the linear framebuffer from the gathered blocks.  csrc/host_shard.cpp
 (build_own_lists) and csrc/k_shard.hip implement exactly these functions for the device."""
 from __future__ import annotations
 

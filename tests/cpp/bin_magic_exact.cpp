@@ -19,7 +19,7 @@
 #include "../../mt_renderer_amd/csrc/tile_common.h"
 
 static const uint32_t MAX_NB = 16384 / 16;            // bins per row / column
-static const uint32_t MAX_RUN = 65536;                // mtr_api.cpp: MTR_TILE_RUN
+static const uint32_t MAX_RUN = 65536;                // host_device.cpp: MTR_TILE_RUN
 static const uint32_t MAX_PER_XCD = MAX_NB * MAX_NB / 8;  // (own_count + 7) / 8
 
 // every n below `count` against the quotient and remainder kept by counting (no division in the loop)

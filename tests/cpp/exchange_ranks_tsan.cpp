@@ -7,7 +7,8 @@
 //   * frames whose bin queues "overflow" (the stub tile launch publishes flag 4 now and then) are re-run by the exchange
 //     thread while the render thread flips parts_disp and the palette of the same model: ThreadSanitizer sees no race.
 // usage: exchange_ranks_tsan <frames>
-#include "../../mt_renderer_amd/csrc/mtr_api.cpp"
+#include "host_all.h"
+using namespace mtr_host;
 
 #include <atomic>
 #include <chrono>

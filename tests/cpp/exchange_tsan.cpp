@@ -1,9 +1,10 @@
-// ThreadSanitizer run of the device's exchange thread (csrc/mtr_api.cpp: mtr_device_exchange_start and friends) over the
+// ThreadSanitizer run of the device's exchange thread (csrc/host_shard.cpp: mtr_device_exchange_start and friends) over the
 // stand-in HIP runtime of tests/cpp/hip_stub: the render thread begins, draws and hands over thousands of sharded frames
 // while the exchange thread packs, "gathers", unpacks and destroys them; frames that never reach the exchange thread are
 // begun and destroyed in between, so the framebuffer pool is touched from both sides.  Any unsynchronised access to
 // shared host state is reported by TSan (exit code 66).          usage: exchange_tsan <frames>
-#include "../../mt_renderer_amd/csrc/mtr_api.cpp"
+#include "host_all.h"
+using namespace mtr_host;
 
 #include <atomic>
 

@@ -1,4 +1,4 @@
-// The launch sequence of a frame, pinned on the CPU: the host side of the library (csrc/mtr_api.cpp) over the stand-in HIP
+// The launch sequence of a frame, pinned on the CPU: the host side of the library (csrc/host_*.cpp) over the stand-in HIP
 // runtime of tests/cpp/hip_stub, with kernel launchers that append one line per launch to a log and a trace hook that adds
 // the memsets, uploads, stream waits, event records and stream syncs in between.  A line holds the kernel's name and the
 // scalar fields that encode a host decision (DESIGN.md "frames in flight", "binning", "tile kernels", "multi-GPU v2");
@@ -6,7 +6,8 @@
 // requires every buffer of the FrameBuffers it is handed to be non-null.  The expected logs are written out below.
 // usage: frame_launch_log            every scenario but the allocation failures
 //        frame_launch_log nomem      hipMalloc failing at each allocation of a frame in turn
-#include "../../mt_renderer_amd/csrc/mtr_api.cpp"
+#include "host_all.h"
+using namespace mtr_host;
 
 #include <cstdarg>
 

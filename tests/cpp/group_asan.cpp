@@ -4,7 +4,8 @@
 // byte it finds at src_of_bin[b] over bin b, so the gathered image is right exactly when every rank packed its own bins,
 // the group copied each shard to its rank's offset, and the tables agree -- and every copy is bounds-checked by ASan.
 // usage: group_asan <rounds>
-#include "../../mt_renderer_amd/csrc/mtr_api.cpp"
+#include "host_all.h"
+using namespace mtr_host;
 #include "../../mt_renderer_amd/csrc/mtr_group.cpp"
 
 void mtr_launch_geom(const GeomParams&, hipStream_t) {}

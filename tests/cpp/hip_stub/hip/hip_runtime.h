@@ -1,6 +1,6 @@
 // Stand-in for <hip/hip_runtime.h> used ONLY by the host-side tests of tests/cpp (host_fuzz.cpp, exchange_tsan.cpp,
 // exchange_ranks_tsan.cpp, group_asan.cpp, anim_host_asan.cpp, frame_launch_log.cpp): lets the host side of the library
-// (csrc/mtr_api.cpp, csrc/mtr_files.cpp, csrc/mtr_group.cpp) be compiled by g++ with AddressSanitizer / UBSan / TSan.
+// (csrc/host_*.cpp, csrc/mtr_files.cpp, csrc/mtr_group.cpp) be compiled by g++ with AddressSanitizer / UBSan / TSan.
 // "Device memory" is the host heap, so every hipMemcpy the host code issues is bounds-checked by ASan; streams and events
 // are inert tokens.
 #pragma once

@@ -1,8 +1,9 @@
-// AddressSanitizer / UBSan run of the HOST side of the library (csrc/mtr_api.cpp + csrc/mtr_files.cpp) over a stand-in
+// AddressSanitizer / UBSan run of the HOST side of the library (csrc/host_*.cpp + csrc/mtr_files.cpp) over a stand-in
 // HIP runtime (tests/cpp/hip_stub): model / texture / batch creation with random, mostly malformed arguments, frames
 // drawn, submitted, waited and read back.  The kernels are no-ops here; what is exercised is everything the host does
 // with caller-provided sizes, offsets and indices before a kernel may trust them.   usage: host_fuzz <iterations>
-#include "../../mt_renderer_amd/csrc/mtr_api.cpp"
+#include "host_all.h"
+using namespace mtr_host;
 #include "../../mt_renderer_amd/csrc/mtr_files.cpp"
 
 // kernel launchers: inert, except the ones whose output the host reads back

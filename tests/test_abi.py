@@ -4,6 +4,7 @@ without a GPU), the header compiles as plain C, and the FFI structs have the siz
 import ctypes
 import os
 import re
+import shutil
 import subprocess
 import tempfile
 
@@ -13,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "mtr.h")
 
 
-def _declared():
-    src = open(HDR).read()
+def _declared(hdr=HDR):
+    src = open(hdr).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(mtr_[a-z0-9_]+)\s*\(", src)))
 
@@ -28,6 +29,23 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), f"libmtr.so does not export {n}"
     assert sorted(api.EXPORTED_SYMBOLS) == names
     assert api.lib.mtr_abi_version() == 2
+
+
+def test_library_exports_nothing_but_the_declared_abi():
+    """What libmtr.so defines for the dynamic linker: its unmangled functions are exactly the ones include/mtr.h and
+    include/mtr_files.h declare, and nothing of the host's internal namespace (mtr_host: members of the internal types, std::
+    instantiations over them) is visible.  The library is loaded into hosts that have helpers and structs of their own; an
+    exported `frame_done` or `Draw::~Draw()` would be interposed by, or collide with, theirs."""
+    from mt_renderer_amd import api
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.check_output([nm, "-D", "--defined-only", api.LIB_PATH], text=True)
+    syms = [ln.split()[-2:] for ln in out.splitlines() if len(ln.split()) >= 2]
+    declared = set(_declared()) | set(_declared(os.path.join(ROOT, "include", "mtr_files.h")))
+    plain = {name for kind, name in syms if kind == "T" and not name.startswith("_Z")}
+    assert len(plain) >= 121, "the symbol table was not parsed"
+    assert plain == declared, (sorted(plain - declared), sorted(declared - plain))
+    internal = [name for kind, name in syms if "8mtr_host" in name]
+    assert not internal, internal
 
 
 def test_header_is_plain_c_and_struct_sizes():

@@ -1,4 +1,4 @@
-"""CPU: the launch sequence of a frame.  The host side of libmtr.so (csrc/mtr_api.cpp) compiled by g++ with AddressSanitizer
+"""CPU: the launch sequence of a frame.  The host side of libmtr.so (csrc/host_*.cpp) compiled by g++ with AddressSanitizer
 and UBSan over the stand-in HIP runtime (tests/cpp/hip_stub), with kernel launchers that log what they are asked to launch
 and a trace hook that logs the memsets, uploads, waits, event records and stream syncs in between; the expected logs --
 which kernels run in which order for direct / two-pass binning, visibility / mixed / ordered tile kernels, sharded draws,

@@ -299,7 +299,7 @@ def test_unsharded_frames_can_cull_what_is_off_the_target(gpu_device):
 
 def test_launch_sizes_from_reported_counts_survive_a_moving_camera_and_a_recycled_slot():
     """A sharded batch draw sizes its launches by the instance counts its last frames reported (pinned host words written by
-    the tile kernel; mtr_api.cpp: hint_host).  The count is a hint: frames whose rank keeps MANY more instances than the hint
+    the tile kernel; host_submit.cpp: pick_launch_hints).  The count is a hint: frames whose rank keeps MANY more instances than the hint
     says -- the camera jumps from a view where a few instances reach the band to one where most of them do -- must come out
     exactly as without it (the remainder launch takes what the hint misses), and a hint slot that changes hands when a batch
     is destroyed must not leak a frame's worth of wrong geometry into the next batch."""

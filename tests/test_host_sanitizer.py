@@ -1,4 +1,4 @@
-"""CPU: the HOST side of libmtr.so (csrc/mtr_api.cpp + csrc/mtr_files.cpp) compiled by g++ with AddressSanitizer and
+"""CPU: the HOST side of libmtr.so (csrc/host_*.cpp + csrc/mtr_files.cpp) compiled by g++ with AddressSanitizer and
 UBSan over a stand-in HIP runtime (tests/cpp/hip_stub: device memory = host heap, so every copy is bounds-checked), then
 driven with thousands of models, textures, batches and frames built from mostly malformed arguments.  GPU sanitizers
 are not available on the GPU pool; this covers what the host must validate before a kernel may trust it."""

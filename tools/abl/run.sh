@@ -1,10 +1,12 @@
 set -e
 cd $GRAFT_REPO_ROOT/mt_renderer_amd/csrc
+FL="$(make -s --no-print-directory print-flags)"
+OBJS="$(make -s --no-print-directory print-objs)"  # csrc/Makefile owns the flags and the object list
 mkdir -p ../../bench_out
 cp ../../tools/abl/k_tile_vis_abl.hip ./k_tile_vis_abl.hip
 for v in "VIS_LANE_MAX=32" "VIS_LANE_MAX=32 -DABL_NO_P2" "VIS_LANE_MAX=64" "VIS_LANE_MAX=256" "VIS_LANE_MAX=256 -DABL_NO_P2"; do
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -D$v -c k_tile_vis_abl.hip -o k_tile_vis.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libmtr.so k_geom.o k_bin.o k_tile.o k_tile_vis.o k_texture.o k_shard.o mtr_api.o
+  /opt/rocm/bin/hipcc $FL -D$v -c k_tile_vis_abl.hip -o k_tile_vis.o
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libmtr.so $OBJS -lz
   cd ../..
   echo "variant=$v" >> bench_out/abl.log
   timeout -k 10 200 python tools/tile_floor.py 2>/dev/null | grep "C2 mesh50k {" >> bench_out/abl.log

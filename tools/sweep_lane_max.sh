@@ -1,9 +1,11 @@
 set -e
 cd $GRAFT_REPO_ROOT/mt_renderer_amd/csrc
+FL="$(make -s --no-print-directory print-flags)"
+OBJS="$(make -s --no-print-directory print-objs)"  # csrc/Makefile owns the flags and the object list
 mkdir -p ../../bench_out
 for v in 8 16 32 64 128; do
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -DVIS_LANE_MAX=$v -c k_tile_vis.hip -o k_tile_vis.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libmtr.so k_geom.o k_bin.o k_tile.o k_tile_vis.o k_texture.o k_shard.o mtr_api.o
+  /opt/rocm/bin/hipcc $FL -DVIS_LANE_MAX=$v -c k_tile_vis.hip -o k_tile_vis.o
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libmtr.so $OBJS -lz
   cd ../..
   echo "VIS_LANE_MAX=$v" >> bench_out/sweep3.log
   timeout -k 10 200 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['roofline']['stage_ms'])" >> bench_out/sweep3.log

@@ -2,9 +2,10 @@
 set -e
 cd $GRAFT_REPO_ROOT/mt_renderer_amd/csrc
 mkdir -p ../../bench_out
-FL="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -Wno-missing-braces"
+FL="$(make -s --no-print-directory print-flags)"
+OBJS="$(make -s --no-print-directory print-objs)"  # csrc/Makefile owns the flags and the object list
 run() {
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libmtr.so k_geom.o k_bin.o k_tile.o k_tile_vis.o k_texture.o k_shard.o mtr_api.o mtr_files.o mtr_group.o -lz
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libmtr.so $OBJS -lz
   (cd ../.. && python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', d['ms_per_step'], d['roofline']['stage_ms_serial'])") >> ../../bench_out/sweep_overlap.log
 }
 for v in 3 4 5 6; do /opt/rocm/bin/hipcc $FL -DGEOM_OCC=$v -c k_geom.hip -o k_geom.o; run "GEOM_OCC=$v"; done

@@ -3,9 +3,10 @@
 cd "$(dirname "$0")/.."
 if [ "$1" = build ]; then
   cd mt_renderer_amd/csrc
-  FL="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -Wno-unused-function -Wno-missing-braces -Wno-pass-failed"
+  FL="$(make -s --no-print-directory print-flags) -Wno-pass-failed"
+  OBJS="$(make -s --no-print-directory print-objs)"  # csrc/Makefile owns the flags and the object list
   for n in 4 5 6 7 8; do /opt/rocm/bin/hipcc $FL -DVIS_OCC=$n -c k_tile_vis.hip -o /tmp/k_tv_occ$n.o & done; wait
-  for n in 4 5 6 7 8; do /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libmtr_vocc$n.so k_geom.o k_bin.o k_tile.o /tmp/k_tv_occ$n.o k_texture.o k_shard.o mtr_api.o mtr_files.o mtr_group.o -lz; done
+  for n in 4 5 6 7 8; do /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libmtr_vocc$n.so ${OBJS/k_tile_vis.o/\/tmp\/k_tv_occ$n.o} -lz; done
   ls ../libmtr_vocc*.so
 else
   for rep in 1 2; do for n in 4 5 6 7 8; do
