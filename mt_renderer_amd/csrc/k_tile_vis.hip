@@ -302,7 +302,8 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
         }
         // ---- lane = (triangle, pixel) pair, 64 pairs per step, for every i32-class triangle.  A round stages a
         //      prefix of the remaining triangles holding <= 4096 pairs (64 start masks, one per lane); one round
-        //      is the rule, a pass of 64 bin-filling triangles takes four. ----
+        //      is the rule.  Fewer than half of this walk's boxes are over four pixels, so a pass holds at most
+        //      31 x 256 + 33 x 4 pairs and needs three rounds at the most (64 bin-filling triangles take the span walk). ----
         for (uint64_t todo = (zlim_ok && !spans) ? __ballot(npx != 0 && !large) : 0ull; todo;) {
             const bool cand = (todo >> lane) & 1ull;
             const uint32_t mine = cand ? npx : 0u;
@@ -443,10 +444,7 @@ void mtr_launch_tile_vis(const TileParams& p_in, bool textured, hipStream_t s) {
     if (mine == 0) return;
     uint32_t grid = (mine + 7) / 8 * 8;
     if (p.xcd_run) grid = (grid / 8 + p.xcd_run - 1) / p.xcd_run * p.xcd_run * 8;  // whole runs
-    int waves = 2;
-    if (p.vis_waves) waves = (int)p.vis_waves;
-    else if (mine <= 1536) waves = 8;   // 256 CUs: every bin is resident at once, the heaviest bin bounds the frame
-    else if (mine <= 4096) waves = 4;
+    const int waves = (int)mtr_vis_waves_for(p.vis_waves, mine);
 #define MTR_LAUNCH_VIS(T, W, S) hipLaunchKernelGGL((mtr::k_tile_vis<T, W, S, false>), dim3(grid), dim3(64 * W), 0, s, p)
 #define MTR_LAUNCH_VIS_W(T, S) do { if (waves >= 8) MTR_LAUNCH_VIS(T, 8, S); else if (waves >= 4) MTR_LAUNCH_VIS(T, 4, S); else MTR_LAUNCH_VIS(T, 2, S); } while (0)
     // frames with translucent materials keep per-pixel order lists (STAIR); all-opaque frames need only the key

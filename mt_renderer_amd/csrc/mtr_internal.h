@@ -342,6 +342,15 @@ struct TileParams {
     uint32_t nbx_mul, nbx_shift, run_mul, run_shift;
 };
 
+// waves per bin of k_tile_vis for a rank that owns own_count bins: `forced` (TileParams::vis_waves) when set, else by how
+// many bins there are.  Up to 1536 bins (256 CUs) every bin is resident at once and the heaviest bin bounds the frame: 8
+// waves; up to 4096: 4; more: 2 (k_tile_vis.hip has the measurements).  Plain C++, so the CPU harness checks it too
+// (tests/cpp/frame_launch_log.cpp)
+static inline uint32_t mtr_vis_waves_for(uint32_t forced, uint32_t own_count) {
+    if (forced) return forced;
+    return own_count <= 1536 ? 8u : own_count <= 4096 ? 4u : 2u;
+}
+
 // launchers (defined in the .hip files, called from host_*.cpp)
 void mtr_launch_geom(const GeomParams& p, hipStream_t s);
 void mtr_launch_scan(const FrameBuffers& fb, hipStream_t s);

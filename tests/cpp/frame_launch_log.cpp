@@ -19,6 +19,7 @@ static std::string g_null;               // nomem: the first null buffer a launc
 static uint32_t g_flag_once = 0;         // overflow flags the next tile launch publishes (once)
 static uint32_t g_measured[2] = {0, 0};  // what that launch leaves in CTR_ENTRIES / CTR_SEGS (flag 2: "what the scan measured")
 static std::vector<FrameBuffers> g_geom_fb;  // FrameBuffers of every geometry launch since the last clear
+static uint32_t g_vis_waves = ~0u;       // TileParams::vis_waves of the last tile launch (remembered, not logged)
 
 static std::string S(const char* fmt, ...) {
     char buf[512];
@@ -56,6 +57,7 @@ static void tile_stub(const char* name, const TileParams& p, bool textured) {
     need_fb(p.fb, name); need(p.mats, name, "mats"); need(p.bin_flag, name, "bin_flag"); need(p.color, name, "color"); need(p.depth, name, "depth");
     need(p.host_status, name, "host_status");
     if (p.fb.own.own_count == 0) return;  // the real launchers return here: a rank without a bin launches no workgroup
+    g_vis_waves = p.vis_waves;
     g_log.push_back(S("%s mixed=%u nhint=%u zero_words=%d zero_nwords=%u hint_out=%d zero_next=%d xcd_run=%u textured=%d", name, p.mixed, p.nhint,
                       p.zero_words != nullptr, p.zero_nwords, p.hint_out != nullptr, p.zero_next != nullptr, p.xcd_run, (int)textured));
     // what tile_prologue does on the device: publish the overflow flags of the frame
@@ -482,6 +484,35 @@ static void scenario_11_profiling() {
     }
 }
 
+// 12: MTR_VIS_WAVES, read when the device is created, reaches the visibility kernel's launcher as TileParams::vis_waves -- 2, 4
+// and 8 as they are, anything else as 0 (the launcher's choice) -- and the launcher's rule (mtr_internal.h) picks the build
+static void scenario_12_vis_waves() {
+    const struct { const char* env; uint32_t want; } cases[] = {{nullptr, 0}, {"2", 2}, {"4", 4}, {"8", 8}, {"3", 0}, {"16", 0}};
+    for (const auto& c : cases) {
+        if (c.env) setenv("MTR_VIS_WAVES", c.env, 1);
+        else unsetenv("MTR_VIS_WAVES");
+        {
+            Scene s;
+            mtr_frame* f = s.frame();
+            MUST(mtr_frame_draw_model(f, s.model(1), kI));
+            g_vis_waves = ~0u;
+            const Log l = submit(f);
+            CHECK(has(l, "tile_vis "));
+            if (g_vis_waves != c.want) {
+                fprintf(stderr, "12: MTR_VIS_WAVES=%s reached the launcher as %u, expected %u\n", c.env ? c.env : "(unset)", g_vis_waves, c.want);
+                g_failed++;
+            }
+            MUST(mtr_frame_wait(f));
+        }
+        unsetenv("MTR_VIS_WAVES");
+    }
+    CHECK(mtr_vis_waves_for(0, 1) == 8 && mtr_vis_waves_for(0, 1536) == 8);
+    CHECK(mtr_vis_waves_for(0, 1537) == 4 && mtr_vis_waves_for(0, 4096) == 4);
+    CHECK(mtr_vis_waves_for(0, 4097) == 2 && mtr_vis_waves_for(0, 129600) == 2);
+    for (uint32_t w : {2u, 4u, 8u})
+        for (uint32_t n : {1u, 1536u, 1537u, 4096u, 4097u, 129600u}) CHECK(mtr_vis_waves_for(w, n) == w);
+}
+
 // ---- 10: hipMalloc fails at the k-th allocation of a submit, for every k the submit reaches ----
 // `grown`: the slot has already served a smaller frame, so its capacities are not zero when the allocation fails.  After
 // the failure a frame that fits what the slot held before (grown) or a fresh frame of the same size (first frame) is
@@ -547,6 +578,7 @@ int main(int argc, char** argv) {
     scenario_8_overflow_reruns();
     scenario_9_empty_band();
     scenario_11_profiling();
+    scenario_12_vis_waves();
     printf("failed=%d\n", g_failed);
     return g_failed ? 1 : 0;
 }

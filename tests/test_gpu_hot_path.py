@@ -12,7 +12,6 @@ band-sharded frame (an own_list).
 
 Every frame is compared with the oracle bit for bit, in colour and depth, through both tile kernels."""
 import os
-from fractions import Fraction as F
 
 import numpy as np
 import pytest
@@ -20,42 +19,12 @@ import pytest
 from mt_renderer_amd import scene, sharding
 from tests.helpers import assert_same, render_gpu, render_oracle
 from tests.pixel_scenes import pixel_model, pixel_to_ndc_matrix
-from tests.tile_path_scenes import BIN, Tri
+from tests.tile_path_scenes import BIN
+from tests.vis_wave_scenes import BX, PAIR_PASS, SPAN_PASS, TH, TW, _pass  # the triangles and passes of this file's scenes live there
 
 pytestmark = pytest.mark.gpu
 
-W, H = 128, 16  # 8 x 1 bins
-BX = 2          # the bin under test
-
-
-def _big(i):
-    """a triangle of bin BX whose box holds nine pixels or more"""
-    x, y = BX * BIN + 1 + (i * 5) % 10, 1 + (i * 3) % 11
-    s = 3 + F(i % 3, 2)
-    return Tri([(x + F(1, 4), y + F(1, 4)), (x + F(1, 2), y + F(1, 4) + s), (x + F(1, 4) + s, y + F(1, 2))], F(20 + (i * 7) % 23, 64))
-
-
-def _one(i):
-    """a triangle of bin BX whose box is the one pixel it covers"""
-    x, y = BX * BIN + (i * 7) % 16, (i * 5) % 16
-    return Tri([(x + F(5, 16), y + F(5, 16)), (x + F(7, 16), y + F(13, 16)), (x + F(13, 16), y + F(7, 16))], F(10 + (i * 11) % 40, 64))
-
-
-def _large(k):
-    """more than 64 px across: 64-bit edge functions; covers most of bin BX"""
-    return Tri([(F(5, 2) + k, F(3, 2)), (F(40) - 3 * k, F(31, 2)), (F(251, 2) - k, F(5, 2) + k)], F(33 - 6 * k, 64))
-
-
-def _pass(nbig, k):
-    """64 entries of bin BX: nbig boxes over four pixels, one-pixel boxes, and one large triangle in the middle"""
-    small = [_big(i) for i in range(nbig)] + [_one(i) for i in range(63 - nbig)]
-    order = np.random.default_rng(nbig).permutation(63)
-    tris = [small[j] for j in order]
-    tris.insert(31, _large(k))
-    return tris
-
-
-SPAN_PASS, PAIR_PASS = 40, 20  # boxes over four pixels among the 63 small triangles: 80 >= 63 > 40
+W, H = TW, TH  # 8 x 1 bins; BX: the bin under test
 
 
 def _check_premise(tris, walks):

@@ -4,7 +4,7 @@ k_tile_vis.hip's order lists and one-at-a-time walk beside them -- on scenes bui
 (tests/tile_path_scenes.py).  Before a scene is rendered its premise is computed from its integers and asserted
 (tests/test_tile_path_premises.py holds the same premises without a device).  Every scene goes through
 tests.helpers.render_gpu -- ordered two-pass, ordered single-pass and auto must agree -- and is compared with the oracle bit
-for bit."""
+for bit.  These scenes all run 8 waves per bin; tests/test_gpu_vis_waves.py holds k_tile_vis.hip at 2, 4 and 8."""
 import pytest
 
 from tests import tile_path_scenes as tp
