@@ -157,7 +157,7 @@ struct mtr_device {
     bool cull_unsharded = false;  // MTR_GEOM_CULL_ALL_FRAMES: unsharded frames cull against the target too (frustum culling)
     uint32_t vis_waves = 0;     // MTR_VIS_WAVES: waves per bin of the visibility kernel, 0 = by the number of bins
     // timing-ablation hooks, read ONCE at device creation (never in the submit path): MTR_CULL_DEBUG in {0, 1, 3, 4, 5}
-    // replaces the culling mode of maps that cull (k_geom.hip: k_cull_instances), MTR_GEOM_SLOTS bounds the instance
+    // replaces the culling mode of maps that cull (k_cull.hip: k_cull_instances), MTR_GEOM_SLOTS bounds the instance
     // slots the full-rate sharded geometry launch covers (tests force k_geom_rest with it); 0xFFFFFFFF / 0: not set
     uint32_t cull_debug = 0xFFFFFFFFu;
     uint32_t geom_slots = 0;

@@ -30,7 +30,7 @@ uint32_t elem_bytes(uint8_t fmt, uint8_t cnt) {
     }
 }
 
-// ---- host mirror of the position decode (csrc/geom_common.h: decode_elem), for the culling bounds ----
+// ---- host mirror of the position decode (csrc/geom_vertex.h: decode_regs, decode_elem), for the culling bounds ----
 float h_half(uint16_t h) {
     const uint32_t sign = (uint32_t)(h >> 15) << 31, ex = (h >> 10) & 0x1f, man = h & 0x3ff;
     uint32_t bits;

@@ -257,7 +257,7 @@ int32_t prepare_stream(mtr_device* d, mtr_frame* f, Slot& sl, FrameRun& r) {
     return MTR_OK;
 }
 
-// Launch sizes of a culled batch draw from what a recent frame of this batch kept under the same ownership (k_geom.hip); a
+// Launch sizes of a culled batch draw from what a recent frame of this batch kept under the same ownership (k_geom.hip, k_cull.hip); a
 // camera that moves changes the count gradually: the margin and the second geometry launch take what the hint misses.
 // Gives the batch a hint slot at its first culled draw (d->hint_used, b->hint_slot / hint_key), and books the draw's
 // counters for this frame's tile kernel to report (r.nhint, hint_word, hint_slot).

@@ -3,7 +3,7 @@
 // the run of records one geometry wave contributed to that bin, written in submission order and
 // tagged with the wave's global chunk id, so the tile kernel restores full submission order by
 // sorting a few segment descriptors instead of every triangle reference.
-#include "geom_common.h"
+#include "geom_bins.h"
 
 namespace mtr {
 

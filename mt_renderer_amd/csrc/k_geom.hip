@@ -10,9 +10,11 @@
 // (triangle -> 16x16 bin) counts are accumulated with one 64-bit atomic per (wave, bin) group.
 //
 // Replaces everything between `rpass.draw_indexed` (src/model.rs:357-361) and the rasteriser.
-#include "geom_common.h"
+#include "geom_bins.h"
+#include "geom_vertex.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace mtr {
 
@@ -140,18 +142,6 @@ __device__ __forceinline__ bool sample_cull(Rec& r, uint32_t W, uint32_t H) {
     return true;
 }
 
-__device__ __forceinline__ VOut clip_lerp(const VOut& in, const VOut& out) {  // in.z >= 0 > out.z
-    float t = in.z / (in.z - out.z);
-    VOut r;
-    r.x = fmaf(t, out.x - in.x, in.x);
-    r.y = fmaf(t, out.y - in.y, in.y);
-    r.z = 0.0f;
-    r.w = fmaf(t, out.w - in.w, in.w);
-    r.u = fmaf(t, out.u - in.u, in.u);
-    r.v = fmaf(t, out.v - in.v, in.v);
-    return r;
-}
-
 // guard-band planes (SPEC.md 5.3): 0: x <= 64 w, 1: x >= -64 w, 2: y <= 64 w, 3: y >= -64 w; inside: distance >= 0
 #define MTR_MAX_POLY 8
 __device__ __forceinline__ float guard_dist(const VOut& v, int plane) {
@@ -168,21 +158,20 @@ __device__ __forceinline__ VOut plane_lerp(const VOut& in, const VOut& out, floa
     r.v = fmaf(t, out.v - in.v, in.v);
     return r;
 }
+__device__ __forceinline__ VOut clip_lerp(const VOut& in, const VOut& out) {  // near plane: in.z >= 0 > out.z; lands on z = 0 exactly
+    VOut r = plane_lerp(in, out, in.z, out.z);
+    r.z = 0.0f;
+    return r;
+}
 
-// + the instance's clip matrix M = view_proj * model, ONCE per workgroup: sixteen threads compute one element each (a k-ordered
-// fma chain from 0, like every contraction of the numeric contract) into s_M.  Every wave used to compose its own copy -- 32 packed fmas + 30 moves per
+// + the instance's clip matrix M = view_proj * model, ONCE per workgroup: sixteen threads compute one element each
+// (vp_model_elem) into s_M.  Every wave used to compose its own copy -- 32 packed fmas + 30 moves per
 // wave, 11 % of k_geom's VALU instructions on the instanced configs (PMC ablation, round 3) -- and then hold it in 16
 // VGPRs for the whole kernel; the vertex stage now reads the row it needs straight from LDS.
 __device__ __forceinline__ void stage_palette(const GeomParams& P, uint32_t inst, float* s_pal, float* s_M) {
     if (threadIdx.x < 16) {
-        const uint32_t c = threadIdx.x >> 2, i = threadIdx.x & 3u;
         float a = P.vp[threadIdx.x];
-        if (P.model_mats) {
-            const float* B = P.model_mats + (size_t)inst * 16;
-            a = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) a = fmaf(P.vp[k * 4 + i], B[c * 4 + k], a);
-        }
+        if (P.model_mats) a = vp_model_elem(P.vp, P.model_mats, inst, threadIdx.x);
         s_M[threadIdx.x] = a;
     }
     if (P.palettes && P.npal) {
@@ -217,7 +206,7 @@ __device__ __forceinline__ void geom_chunk(const GeomParams& P, uint32_t inst, u
     const bool want_b = pr.has_uv && dmat.shader == MTR_SH_TEXTURED;
 
     // ---- vertex stage, in RAIL order.  The matrix-core skinning needs the four lanes of a block to share their joint
-    //      indices (geom_common.h: shade_vertex_mfma).  In strip order neighbouring lanes alternate between the two rails of
+    //      indices (geom_vertex.h: shade_vertex_mfma).  In strip order neighbouring lanes alternate between the two rails of
     //      the strip -- two rows of the mesh, which as often as not hang on different joints -- and every wave then also ran
     //      the whole VALU fallback for its incoherent blocks: 128 of ~600 VALU instructions per chunk (PMC, C5).  So the
     //      vertex stage runs permuted: shading lane s takes strip position pi(s) = the even positions first, then the odd
@@ -509,16 +498,6 @@ __device__ __forceinline__ void geom_chunk(const GeomParams& P, uint32_t inst, u
     }
 }
 
-// Length of the instance list: a SCALAR load of a uniform address.  Written as `count ? *count : ninst` the compiler selects
-// between the two ADDRESSES (the kernel argument's and the counter's) and loads through a flat VECTOR instruction -- the first
-// thing every wave of a sharded launch waits for, the ones of dead instance slots included (ISA of round 3: flat_load_dword
-// + v_cmp + s_and_saveexec).  Hiding the argument's value from that transformation leaves a branch and an s_load_dword.
-__device__ __forceinline__ uint32_t live_instances(const uint32_t* count, uint32_t ninst) {
-    asm("" : "+s"(ninst));
-    if (count) ninst = *count;
-    return ninst;
-}
-
 #ifndef GEOM_OCC
 #define GEOM_OCC 8  // waves per SIMD the register allocator must leave room for: 64 VGPRs.  Rounds 1-2 ran at 6 (80 VGPRs,
                     // the vertex stage's live ranges spilled below that); with the vertex stage feeding LDS the kernel fits 64
@@ -631,145 +610,6 @@ __global__ __launch_bounds__(256) void k_geom_rest(GeomParams P) {
         }
     }
 }
-
-__device__ __forceinline__ void compose_vp_model(const float (&vp)[16], const float* model_mats, uint32_t inst, float (&M)[16]) {
-    if (model_mats) {
-        const float* B = model_mats + (size_t)inst * 16;  // M = VP * Model, the fma chain of stage_palette
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                float a = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 4; k++) a = fmaf(vp[k * 4 + i], B[c * 4 + k], a);
-                M[c * 4 + i] = a;
-            }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; i++) M[i] = vp[i];
-    }
-}
-
-// Instance culling of a sharded batch draw, one wave per instance, lane = per-joint box of the whole model: the
-// instances that may reach a bin of this rank are appended to `list` (in no particular order: k_geom takes the instance
-// number from the work list, so submission-order keys do not change).
-__global__ __launch_bounds__(64) void k_cull_instances(CullParams P) {
-    const uint32_t inst = blockIdx.x, lane = threadIdx.x;
-    if (inst >= P.ninst) return;
-    float M[16];
-    compose_vp_model(P.vp, P.model_mats, inst, M);
-    const bool have_pal = P.palettes && P.npal;
-    const float* pal = have_pal ? P.palettes + (size_t)inst * P.pal_stride : nullptr;
-    ClipBox cb;
-#pragma unroll
-    for (int t = 0; t < 3; t++) { cb.lo[t] = __builtin_inff(); cb.hi[t] = -__builtin_inff(); }
-    bool bad = false;
-    for (uint32_t i = lane; i < P.nboxes; i += 64) {
-        const BoneBox bx = P.boxes[i];
-        const float* Pm = nullptr;
-        if (bx.joint != MTR_BOX_UNSKINNED && have_pal) Pm = pal + (size_t)min(bx.joint, P.npal - 1u) * 16;
-        const ClipBox one = box_clip_interval(bx, Pm, M);
-        bad = bad || !clipbox_finite(one);
-#pragma unroll
-        for (int t = 0; t < 3; t++) { cb.lo[t] = fminf(cb.lo[t], one.lo[t]); cb.hi[t] = fmaxf(cb.hi[t], one.hi[t]); }
-    }
-    bool keep = true, inside = false;
-    if (!__ballot(bad) && P.nboxes) {
-        ClipBox u;
-#pragma unroll
-        for (int t = 0; t < 3; t++) { u.lo[t] = wave_min_f32(cb.lo[t]); u.hi[t] = wave_max_f32(cb.hi[t]); }
-        FrameBuffers fb = {};
-        fb.W = P.W; fb.H = P.H; fb.nbx = P.nbx; fb.nby = P.nby; fb.own = P.own;
-        keep = clipbox_may_touch_rank(u, fb) || P.own.cull == 3u || P.own.cull == 4u;  // 3, 4: timing ablations (MTR_CULL_DEBUG), keep everything
-        inside = (keep && (clipbox_all_in_rank(u, fb) || P.own.cull == 5u)) || P.own.cull == 4u;  // 5: no chunk tests for kept instances
-    }
-    if (!keep) {
-        if (lane == 0) atomicAdd(&P.counters[MTR_CTR(CTR_CULL, inst)], P.nchunks);  // statistics only
-        return;
-    }
-    uint32_t slot = 0;
-    if (lane == 0) {
-        slot = atomicAdd(P.count, 1u);
-        P.list[slot] = inst;
-        if (!inside) P.strad[atomicAdd(P.count + 1, 1u)] = slot;
-    }
-    if (inside) {  // every chunk of it is this rank's: no chunk tests (k_cull_chunks skips the slot)
-        slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot);
-        const uint32_t nx = (P.nchunks + 15u) / 16u, tail = P.nchunks & 15u;
-        for (uint32_t x = lane; x < nx; x += 64) P.work_mask[(size_t)slot * nx + x] = (uint16_t)((x == nx - 1u && tail) ? (1u << tail) - 1u : 0xFFFFu);
-    }
-    if (P.comp && !inside) {  // what the chunk tests of this instance read (k_cull_chunks tests the straddlers only)
-        CompMat* out = P.comp + (size_t)inst * P.ncomp;
-        for (uint32_t j = lane; j < P.ncomp; j += 64) out[j] = make_comp((have_pal && j + 1 < P.ncomp) ? pal + (size_t)j * 16 : nullptr, M);
-    }
-}
-
-// Chunk culling of a sharded draw.  256 threads = 16 rows of 16 lanes: row = one chunk, lane = one of its boxes; the
-// per-joint composites of the instance are built once per workgroup in LDS.  Which of the workgroup's 16 chunks may
-// reach a bin of the rank is stored as one 16-bit mask per (instance slot, group of 16 chunks): no list to append to,
-// no atomic; k_geom<.., true> launches four workgroups per mask, each taking four of its set bits (one palette in LDS,
-// four waves).  A light kernel (no records, no binning state) at full occupancy: the test's chain of dependent loads
-// is not paid inside k_geom's 80-register workgroups.
-template <bool LDS_COMP>  // true: the workgroup builds its instance's composites in LDS (a single model); false: they come from k_cull_instances
-__global__ __launch_bounds__(256, LDS_COMP ? 4 : 8) void k_cull_chunks(ChunkCullParams P) {
-    extern __shared__ __align__(16) unsigned char s_raw[];
-    CompMat* s_comp = reinterpret_cast<CompMat*>(s_raw);
-    __shared__ uint32_t s_wmask[4];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = lane >> 4, sub = lane & 15u;
-    const uint32_t c = blockIdx.x * 16u + wave * 4u + row;
-    const bool has = c < P.nchunks;
-    DChunk ch = {};
-    if (has) ch = P.chunks[c];
-    const bool have_pal = P.palettes && P.npal;
-    const uint32_t ncomp = have_pal ? P.npal + 1u : 1u;
-    const bool skinned = (ch.b_flags & 2u) && have_pal;
-    // chunks that cannot be bounded are kept
-    const bool unbounded = has && (ch.b_count == 0 || (skinned && (ch.b_flags & 1u)) || (skinned && ch.b_count < 2) || ch.b_count > MTR_CHUNK_MAX_BOXES + 1u);
-    const uint32_t first = skinned ? ch.b_first + 1u : ch.b_first, n = has ? (skinned ? ch.b_count - 1u : 1u) : 0u;
-    BoneBox bx = {};
-    const bool tests = has && !unbounded && sub < n;
-    if (tests) bx = P.boxes[first + sub];
-    const uint32_t nlive = P.strad ? P.inst_count[1] : live_instances(P.inst_count, P.ninst);
-    for (uint32_t si = blockIdx.y; si < nlive; si += gridDim.y) {
-        const uint32_t ii = P.strad ? P.strad[si] : si;  // the instance's slot: where its masks go
-        const uint32_t inst = P.inst_list ? P.inst_list[ii] : ii;
-        __syncthreads();  // the composites and masks of the previous instance are no longer read
-        if (LDS_COMP) {
-            float M[16];
-            compose_vp_model(P.vp, P.model_mats, inst, M);
-            const float* pal = have_pal ? P.palettes + (size_t)inst * P.pal_stride : nullptr;
-            for (uint32_t j = threadIdx.x; j < ncomp; j += 256) s_comp[j] = make_comp((have_pal && j + 1 < ncomp) ? pal + (size_t)j * 16 : nullptr, M);
-        }
-        __syncthreads();
-        ClipBox cb;
-#pragma unroll
-        for (int t = 0; t < 3; t++) { cb.lo[t] = __builtin_inff(); cb.hi[t] = -__builtin_inff(); }
-        bool bad = false;
-        if (tests) {
-            const uint32_t j = skinned ? min(bx.joint, P.npal - 1u) : ncomp - 1u;  // the last composite is M itself
-            cb = box_comp_interval(bx, LDS_COMP ? s_comp[j] : P.comp[(size_t)inst * ncomp + j]);
-            bad = !clipbox_finite(cb);
-        }
-        const uint64_t badm = __ballot(bad);
-        const bool row_bad = ((badm >> (row * 16u)) & 0xFFFFull) != 0;
-        ClipBox u;
-#pragma unroll
-        for (int t = 0; t < 3; t++) { u.lo[t] = row_min_f32(cb.lo[t]); u.hi[t] = row_max_f32(cb.hi[t]); }
-        const bool keep = has && (unbounded || row_bad || P.keep_all || clipbox_may_touch_rank(u, P.fb));
-        const uint64_t km = __ballot(keep);
-        if (lane == 0)
-            s_wmask[wave] = (uint32_t)(km & 1ull) | (uint32_t)((km >> 15) & 2ull) | (uint32_t)((km >> 30) & 4ull) | (uint32_t)((km >> 45) & 8ull);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t m16 = s_wmask[0] | (s_wmask[1] << 4) | (s_wmask[2] << 8) | (s_wmask[3] << 12);
-            P.work_mask[(size_t)ii * gridDim.x + blockIdx.x] = (uint16_t)m16;
-            const uint32_t k = (uint32_t)__popc(m16);
-            const uint32_t nhave = blockIdx.x * 16u < P.nchunks ? min(16u, P.nchunks - blockIdx.x * 16u) : 0u;
-            if (nhave > k) atomicAdd(&P.fb.counters[MTR_CTR(CTR_CULL, blockIdx.x + inst)], nhave - k);  // statistics only
-        }
-    }
-}
-
 // vertex stage alone (unit-parity hook: mtr_model_vertex_stage)
 __global__ __launch_bounds__(256) void k_vertex_stage(GeomParams P, uint32_t prim, float* out_clip, float* out_uv) {
     extern __shared__ __align__(16) float s_pal[];
@@ -788,14 +628,22 @@ __global__ __launch_bounds__(256) void k_vertex_stage(GeomParams P, uint32_t pri
 
 }  // namespace mtr
 
-// MODE by the frame's queue builder, the register budget by the size of the draw
-#define MTR_LAUNCH_GEOM_O(C, O)                                                                                         \
-    do {                                                                                                                \
-        if (p.fb.direct && p.fb.unordered) hipLaunchKernelGGL((mtr::k_geom<2, C, O>), grid, dim3(256), lds, s, p);      \
-        else if (p.fb.direct) hipLaunchKernelGGL((mtr::k_geom<1, C, O>), grid, dim3(256), lds, s, p);                   \
-        else hipLaunchKernelGGL((mtr::k_geom<0, C, O>), grid, dim3(256), lds, s, p);                                    \
-    } while (0)
-#define MTR_LAUNCH_GEOM(C) do { if (p.small_draw) MTR_LAUNCH_GEOM_O(C, GEOM_OCC_SMALL); else MTR_LAUNCH_GEOM_O(C, GEOM_OCC); } while (0)
+// MODE by the frame's queue builder: launch(integral_constant<int, MODE>)
+template <class F>
+static void with_geom_mode(const FrameBuffers& fb, F launch) {
+    if (fb.direct && fb.unordered) launch(std::integral_constant<int, 2>());
+    else if (fb.direct) launch(std::integral_constant<int, 1>());
+    else launch(std::integral_constant<int, 0>());
+}
+// ... and the register budget by the size of the draw
+template <bool CULL>
+static void launch_geom(const GeomParams& p, dim3 grid, size_t lds, hipStream_t s) {
+    with_geom_mode(p.fb, [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        if (p.small_draw) hipLaunchKernelGGL((mtr::k_geom<MODE, CULL, GEOM_OCC_SMALL>), grid, dim3(256), lds, s, p);
+        else hipLaunchKernelGGL((mtr::k_geom<MODE, CULL, GEOM_OCC>), grid, dim3(256), lds, s, p);
+    });
+}
 void mtr_launch_geom(const GeomParams& p, hipStream_t s) {
     if (p.nchunks == 0 || p.ninst == 0) return;
     size_t lds = (size_t)p.npal * 64;
@@ -822,41 +670,21 @@ void mtr_launch_geom(const GeomParams& p, hipStream_t s) {
         if ((uint64_t)(p.ninst - slots) * p.work_nx * 4u <= 20000u) slots = p.ninst;
         if (p.slots_override) slots = std::min<uint32_t>(p.ninst, p.slots_override);  // MTR_GEOM_SLOTS at device creation: tests force the second launch
         dim3 grid(p.work_nx * 4u * slots);  // the host checked work_nx * 4 * ninst against the launch limit (2^32 threads)
-        MTR_LAUNCH_GEOM(true);
+        launch_geom<true>(p, grid, lds, s);
         if (slots < p.ninst) {
             GeomParams r = p;
             r.work_slot_base = slots;
             // sized by a recent frame's count the slots beyond are empty but for what a camera move added: a quarter of the workgroups
             r.rest_split = (p.inst_count && (p.slots_hint & 0x80000000u) && !p.slots_override) ? MTR_GEOM_REST_SPLIT / 4u : MTR_GEOM_REST_SPLIT;
             dim3 rest((p.ninst - slots) * std::min<uint32_t>(p.work_nx, r.rest_split));
-            if (p.fb.direct && p.fb.unordered) hipLaunchKernelGGL((mtr::k_geom_rest<2>), rest, dim3(256), lds, s, r);
-            else if (p.fb.direct) hipLaunchKernelGGL((mtr::k_geom_rest<1>), rest, dim3(256), lds, s, r);
-            else hipLaunchKernelGGL((mtr::k_geom_rest<0>), rest, dim3(256), lds, s, r);
+            with_geom_mode(p.fb, [&](auto mode) { hipLaunchKernelGGL((mtr::k_geom_rest<decltype(mode)::value>), rest, dim3(256), lds, s, r); });
         }
         return;
     }
     uint32_t nblk = (p.nchunks + 3) / 4;
     nblk = (nblk + 7) / 8 * 8;  // whole multiple of 8 for the XCD remap
     dim3 grid(nblk, p.ninst);
-    MTR_LAUNCH_GEOM(false);
-}
-
-void mtr_launch_cull_instances(const CullParams& p, hipStream_t s) {
-    if (p.ninst == 0) return;
-    hipLaunchKernelGGL(mtr::k_cull_instances, dim3(p.ninst), dim3(64), 0, s, p);
-}
-
-void mtr_launch_cull_chunks(const ChunkCullParams& p, hipStream_t s) {
-    if (p.nchunks == 0 || p.ninst == 0) return;
-    // instance slots: the kernel strides over the (possibly compacted) instance list; twice the rank's fair share
-    uint32_t ny = p.ninst;
-    if (p.inst_count && p.fb.own.world > 1) ny = std::max<uint32_t>(1u, std::min<uint32_t>(p.ninst, (2u * p.ninst + p.fb.own.world - 1) / p.fb.own.world));
-    // the straddlers a recent frame of the batch reported (the kernel strides over the list: any ny is correct)
-    if (p.strad && (p.strad_hint & 0x80000000u)) ny = std::max<uint32_t>(1u, std::min<uint32_t>(p.ninst, (p.strad_hint & 0x7FFFFFFFu) + (p.strad_hint & 0x7FFFFFFFu) / 8u + 2u));
-    ny = std::min<uint32_t>(ny, 65535u);
-    const uint32_t ncomp = (p.palettes && p.npal) ? p.npal + 1u : 1u;
-    if (p.comp) hipLaunchKernelGGL(mtr::k_cull_chunks<false>, dim3((p.nchunks + 15) / 16, ny), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(mtr::k_cull_chunks<true>, dim3((p.nchunks + 15) / 16, ny), dim3(256), (size_t)ncomp * sizeof(CompMat), s, p);
+    launch_geom<false>(p, grid, lds, s);
 }
 
 void mtr_launch_vertex_stage(const GeomParams& p, uint32_t prim, float* out_clip, float* out_uv, hipStream_t s) {

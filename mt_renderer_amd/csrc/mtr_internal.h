@@ -213,6 +213,55 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
     const uint32_t row = (threadIdx.x & 63u) >> 4;
     return v + (row == 0 ? 0u : row == 1 ? t0 : row == 2 ? t0 + t1 : t0 + t1 + t2);
 }
+
+// a 32-bit value of any type through one DPP move (lanes without a source read 0)
+template <int CTRL, class T>
+__device__ __forceinline__ T dpp_mov(T v) {
+    return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+// Reduction by an idempotent `op` (min, max; u32, packed u16 pairs, f32) inside each row of 16 lanes: rotate and combine
+// with DPP row_ror 8 / 4 / 2 / 1 -- idempotence is what lets rotations give EVERY lane of a row the row's result.
+template <class T, class Op>
+__device__ __forceinline__ T row_reduce(T v, Op op) {
+    v = op(v, dpp_mov<0x128>(v));  // row_ror:8
+    v = op(v, dpp_mov<0x124>(v));  // row_ror:4
+    v = op(v, dpp_mov<0x122>(v));  // row_ror:2
+    v = op(v, dpp_mov<0x121>(v));  // row_ror:1
+    return v;
+}
+// ... and across the wave: the four rows' results through v_readlane, combined on the scalar unit; every lane gets the
+// result.  Six ds_bpermute shuffles did this before and were the long pole of the binning loop (~700 cycles per group).
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+    v = row_reduce(v, op);
+    const int i = __builtin_bit_cast(int, v);
+    const T r0 = __builtin_bit_cast(T, __builtin_amdgcn_readlane(i, 0)), r1 = __builtin_bit_cast(T, __builtin_amdgcn_readlane(i, 16));
+    const T r2 = __builtin_bit_cast(T, __builtin_amdgcn_readlane(i, 32)), r3 = __builtin_bit_cast(T, __builtin_amdgcn_readlane(i, 48));
+    return op(op(r0, r1), op(r2, r3));
+}
+
+// element e = c * 4 + i (column c, row i; column-major like both factors) of VP * Model for instance `inst` of the draw:
+// a k-ordered fma chain from 0, like every contraction of the numeric contract.  The vertex stage and the culling bounds
+// must see the same matrix.
+__device__ __forceinline__ float vp_model_elem(const float (&vp)[16], const float* model_mats, uint32_t inst, uint32_t e) {
+    __builtin_assume(e < 16);  // a 4 x 4 matrix
+    const uint32_t i = e & 3u, c = e >> 2;
+    const float* B = model_mats + (size_t)inst * 16;
+    float a = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) a = fmaf(vp[k * 4 + i], B[c * 4 + k], a);
+    return a;
+}
+
+// Length of the instance list: a SCALAR load of a uniform address.  Written as `count ? *count : ninst` the compiler selects
+// between the two ADDRESSES (the kernel argument's and the counter's) and loads through a flat VECTOR instruction -- the first
+// thing every wave of a sharded launch waits for, the ones of dead instance slots included (ISA of round 3: flat_load_dword
+// + v_cmp + s_and_saveexec).  Hiding the argument's value from that transformation leaves a branch and an s_load_dword.
+__device__ __forceinline__ uint32_t live_instances(const uint32_t* count, uint32_t ninst) {
+    asm("" : "+s"(ninst));
+    if (count) ninst = *count;
+    return ninst;
+}
 #endif
 
 // counters[]: [1] entries, [2] segments (two-pass scan), [3] overflow flags, then CTR_NSHARDS statistics shards of one

@@ -1,7 +1,7 @@
 """CPU: the three-instruction division by 255 the tile kernels use for UNORM8 texel / framebuffer decoding
 (csrc/tile_common.h unorm8f) equals the IEEE binary32 division SPEC.md spells, for EVERY byte; the same holds for the
 SNORM8 / SNORM16 divisors, checked here too: the geometry kernel decodes positions and weights with the same sequence
-(csrc/geom_common.h div_small, its default since round 3; -DMTR_DIV_IEEE restores the plain division).  The fused
+(csrc/geom_vertex.h div_small, its default since round 3; -DMTR_DIV_IEEE restores the plain division).  The fused
 multiply-adds are evaluated exactly with rationals and rounded once, to nearest even, like v_fma_f32.  This is the
 arithmetic on paper; what the compiler makes of it on gfx950 is compared code by code in tests/test_gpu_vertex_decode.py."""
 from fractions import Fraction

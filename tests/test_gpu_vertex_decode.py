@@ -7,7 +7,7 @@ pins the tables to the IEEE division, the oracle to the tables, and the models t
   four placements in memory, every code in every component, words equal; a NaN input of a decode that computes must give
   a NaN (SPEC section 2), F32 texcoords are bits and compared as bits;
 * every weight byte in every slot, on the MFMA blocks and on the VALU redo, at palette sizes 1 and 64;
-* the clipper's re-shade (shade_vertex + decode_elem, reached by nothing else): frames whose triangles straddle the near
+* the clipper's re-shade (geom_vertex.h: shade_vertex + decode_elem, reached by nothing else): frames whose triangles straddle the near
   plane or leave the guard band, every pair aligned and unaligned, both tile kernels, bit-exact against the oracle;
 * the host mirror (decode_pos_host) behind the culling boxes: the same models, unsharded with culling of all frames and as
   rank 1 of 3, must come out the same with and without culling.

@@ -1,6 +1,6 @@
 """-m gpu: the skinned vertex stage at its numeric edges, HIP against the oracle, bit for bit.
 
-"A k-step v_mfma_f32_4x4x1 chain is bitwise an fmaf chain" (geom_common.h) carries the parity of all
+"A k-step v_mfma_f32_4x4x1 chain is bitwise an fmaf chain" (geom_vertex.h) carries the parity of all
 skinned geometry: coherent blocks are skinned on the matrix cores, the others by the VALU chain, and clipped triangles
 re-shade through the VALU chain vertices that their unclipped neighbours took from the MFMA.  tests/vertex_edge_cases.py
 holds the inputs (cancellation, subnormal operands / products / sums, signed zeros, overflow, every weight and joint

@@ -1,8 +1,8 @@
 """Every code of every vertex format: reference decode tables and the models that carry the codes.
 
 Plain Python and numpy, no GPU and no oracle.  The geometry stage decodes an element in three places that are meant to be
-one function -- decode_regs (registers, after load_elem: k_vertex_stage and the main path of k_geom), decode_elem (memory,
-the clipper's re-shade only) and decode_pos_host (the host mirror behind the culling boxes).  Four parts:
+one function -- decode_regs (geom_vertex.h; registers, after load_elem: k_vertex_stage and the main path of k_geom), decode_elem
+(geom_vertex.h; memory, the clipper's re-shade only) and decode_pos_host (the host mirror behind the culling boxes).  Four parts:
 
 * reference tables, built in integer arithmetic with ``div32`` of tests/vertex_edge_cases.py (U8N, S8N, S16N, the 10-bit
   fields of SCMP3N) and by integer construction (F16 -> binary32, all 65 536 patterns);
