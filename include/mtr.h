@@ -246,6 +246,28 @@ int32_t mtr_batch_animate_device(mtr_batch *batch, mtr_anim *anim, const mtr_ani
 /* test / debug hook: the local matrices of section 14 for n states, n * njoints * 16 floats to host memory */
 int32_t mtr_anim_sample(mtr_anim *anim, const mtr_anim_state *states, size_t n, float *out_locals, size_t count);
 
+/* ---- animation tracks (build extension, SPEC.md section 15): an animation set whose channel values come from tracks ----
+ * A track set is an mtr_anim: mtr_model_animate, mtr_batch_animate, mtr_batch_animate_device, mtr_anim_sample and
+ * mtr_anim_destroy take it with the same errors, frame semantics and parked destroy.  A clip has a length in TICKS
+ * (1..65536) instead of a key count, and positions mean what they mean for a uniform clip of as many keys.  For every
+ * clip, joint and channel (0 translation, 1 rotation, 2 scale) there is one track, described by tracks[(clip * njoints +
+ * joint) * 3 + channel]: its keys are first .. first + count - 1 of times[] (u16 ticks) and values[] (four 16-bit words per
+ * key).  Tracks may share keys.  Translation and scale keys are three u16 words, component = lo + word * step (the fourth
+ * word is not read); rotation keys are four s16 words (x, y, z, w), component = max(word / 32767, -1) (lo and step are
+ * not read).  Between two keys the channel is interpolated as section 14 interpolates between keys; past a track's last
+ * key a LOOP clip interpolates towards the track's first key at tick nticks, any other clip holds the last key.  The
+ * library copies every array.
+ * Errors: MTR_E_INVALID, nothing is created and *out is NULL, for a NULL argument (flags may be NULL = 0), njoints outside
+ * 1..256, nclips == 0, nkeys_total == 0 or above 2^31 - 1, a clip length outside 1..65536, and a track with count == 0,
+ * first + count > nkeys_total, times[first] != 0, times that do not strictly increase, or a last time above nticks - 1;
+ * mtr_last_error names the clip, joint and channel.  lo and step are not validated (any float, as section 14's keys).
+ * MTR_E_UNSUPPORTED from the animate calls when the library was built without the track kernels. */
+typedef struct mtr_anim_track { uint32_t first, count; float lo[3], step[3]; } mtr_anim_track;   /* 32 bytes */
+int32_t mtr_anim_create_tracks(mtr_device *dev, size_t njoints, size_t nclips, const uint32_t *nticks,
+                               const uint32_t *flags /* NULL = 0 */, const mtr_anim_track *tracks /* nclips*njoints*3 */,
+                               const uint16_t *times, const uint16_t *values /* 4 per key */, size_t nkeys_total,
+                               mtr_anim **out);
+
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],
                         float clear_depth, mtr_frame **out);

@@ -92,6 +92,14 @@ class Anim {
         if (!flags.empty() && flags.size() != nkeys.size()) throw Error(MTR_E_INVALID, "one flag word per clip");
         dev.check(mtr_anim_create(dev.handle(), njoints, nkeys.size(), nkeys.data(), flags.empty() ? nullptr : flags.data(), keys, &h_));
     }
+    // a track set (SPEC.md section 15): tracks holds nticks.size() * njoints * 3 descriptors, times / values nkeys_total keys
+    Anim(const Device& dev, size_t njoints, const std::vector<uint32_t>& nticks, const std::vector<uint32_t>& flags, const mtr_anim_track* tracks,
+         const uint16_t* times, const uint16_t* values, size_t nkeys_total)
+        : dev_(dev), njoints_(njoints) {
+        if (!flags.empty() && flags.size() != nticks.size()) throw Error(MTR_E_INVALID, "one flag word per clip");
+        dev.check(mtr_anim_create_tracks(dev.handle(), njoints, nticks.size(), nticks.data(), flags.empty() ? nullptr : flags.data(), tracks, times,
+                                         values, nkeys_total, &h_));
+    }
     Anim(Anim&& o) noexcept : dev_(o.dev_), njoints_(o.njoints_), h_(std::exchange(o.h_, nullptr)) {}
     Anim(const Anim&) = delete;
     ~Anim() { mtr_anim_destroy(h_); }

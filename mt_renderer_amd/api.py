@@ -45,12 +45,15 @@ EXPORTED_SYMBOLS = [
     "mtr_model_set_skeleton", "mtr_model_set_pose", "mtr_batch_update", "mtr_batch_set_poses", "mtr_batch_set_poses_device",
     "mtr_batch_read_palettes",
     "mtr_anim_create", "mtr_anim_destroy", "mtr_model_animate", "mtr_batch_animate", "mtr_batch_animate_device", "mtr_anim_sample",
+    "mtr_anim_create_tracks",
 ]
 
 CLIP_LOOP = 1
 # mtr_anim_key / mtr_anim_state (include/mtr.h; SPEC.md section 14)
 ANIM_KEY = np.dtype([("t", "<f4", 3), ("pad0", "<f4"), ("q", "<f4", 4), ("s", "<f4", 3), ("pad1", "<f4")])
 ANIM_STATE = np.dtype([("clip_a", "<u4"), ("clip_b", "<u4"), ("x_a", "<f4"), ("x_b", "<f4"), ("w", "<f4"), ("pad", "<u4")])
+# mtr_anim_track (SPEC.md section 15)
+ANIM_TRACK = np.dtype([("first", "<u4"), ("count", "<u4"), ("lo", "<f4", 3), ("step", "<f4", 3)])
 
 
 class MtrError(RuntimeError):
@@ -178,6 +181,7 @@ def _load() -> C.CDLL:
         "mtr_batch_animate": (i32, [vp, vp, vp]),
         "mtr_batch_animate_device": (i32, [vp, vp, vp, vp]),
         "mtr_anim_sample": (i32, [vp, vp, sz, vp, sz]),
+        "mtr_anim_create_tracks": (i32, [vp, sz, sz, vp, vp, vp, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -455,7 +459,10 @@ class Anim:
     in HBM.  clips: a list of (keys, flags); keys is [nkeys, njoints, 12] float32 (t.xyz 0 | q.xyzw | s.xyz 0) or an
     ANIM_KEY array [nkeys, njoints]; flags 0 or CLIP_LOOP."""
 
-    def __init__(self, dev: Device, njoints: int, clips):
+    def __init__(self, dev: Device, njoints: int, clips, _handle=None):
+        if _handle is not None:  # AnimTracks: created already
+            self.dev, self._h, self.njoints, self.nclips = dev, _handle, njoints, len(clips)
+            return
         if not 1 <= njoints <= 256:
             raise MtrError(MTR_E_INVALID, "anim: 1 to 256 joints")
         blocks, nkeys, flags = [], [], []
@@ -486,6 +493,40 @@ class Anim:
         if self._h:
             lib.mtr_anim_destroy(self._h)
             self._h = None
+
+
+def anim_track_arrays(njoints: int, clips):
+    """The arrays of mtr_anim_create_tracks from a list of track clips (nticks, flags, tracks, times, values): tracks an
+    ANIM_TRACK array [njoints, 3] whose ``first`` counts inside the clip's own times (u16 [nkeys]) and values (u16
+    [nkeys, 4]).  The clips are concatenated and ``first`` rebased.  Returns nticks, flags, tracks, times, values."""
+    nticks, flags, tracks, times, values, base = [], [], [], [], [], 0
+    for nt, fl, tr, tm, va in clips:
+        tr = np.array(tr, dtype=ANIM_TRACK).reshape(-1)
+        tm = np.ascontiguousarray(tm, dtype=np.uint16).reshape(-1)
+        va = np.ascontiguousarray(va, dtype=np.uint16).reshape(-1, 4)
+        if tr.size != njoints * 3 or va.shape[0] != tm.size:
+            raise MtrError(MTR_E_INVALID, "anim tracks: [njoints, 3] descriptors per clip, four value words per key time")
+        tr["first"] = np.minimum(tr["first"].astype(np.uint64) + np.uint64(base), np.uint64(0xFFFFFFFF))  # no wrap: an invalid first stays invalid
+        base += tm.size
+        nticks.append(int(nt))
+        flags.append(int(fl))
+        tracks.append(tr)
+        times.append(tm)
+        values.append(va)
+    if not clips:
+        raise MtrError(MTR_E_INVALID, "anim tracks: at least one clip")
+    return (np.asarray(nticks, dtype=np.uint32), np.asarray(flags, dtype=np.uint32), np.ascontiguousarray(np.concatenate(tracks)),
+            np.ascontiguousarray(np.concatenate(times)), np.ascontiguousarray(np.concatenate(values)))
+
+
+def AnimTracks(dev: Device, njoints: int, clips) -> Anim:
+    """A track set (include/mtr.h, SPEC.md section 15) as an Anim: per clip, joint and channel a track with its own key
+    times and 16-bit keys.  clips: a list of (nticks, flags, tracks, times, values) as anim_track_arrays describes
+    (mt_renderer_amd.anim_tracks.compress makes one from uniformly spaced keys).  The library validates every track."""
+    nt, fl, tr, tm, va = anim_track_arrays(njoints, clips)
+    h = C.c_void_p()
+    dev.check(lib.mtr_anim_create_tracks(dev._h, njoints, nt.size, _p(nt), _p(fl), _p(tr), _p(tm), _p(va), tm.size, C.byref(h)))
+    return Anim(dev, njoints, clips, _handle=h)
 
 
 _POSE_STREAMS = {}

@@ -316,9 +316,13 @@ struct mtr_batch {
 // An animation set (SPEC.md section 14): immutable once uploaded.  d: the clip table (nclips x 4 words: first key, key count,
 // flags, 0), then the keys.  `last` is recorded behind every kernel that reads d; a kernel queued on another stream than
 // the one before first waits for it, so the one event always covers every reader and mtr_anim_destroy can park d behind it.
+// A track set (section 15) is the same object with tracks set.  Then d holds: the clip table (0, length in ticks, flags, 0),
+// nclips * njoints * 3 descriptors of 32 bytes, nkeys key values of 8 bytes, nkeys u16 key times.
 struct mtr_anim {
     mtr_device* dev;
     uint32_t njoints = 0, nclips = 0;
+    bool tracks = false;
+    uint32_t nkeys = 0;          // a track set's key total
     uint32_t* d = nullptr;
     hipEvent_t last = nullptr;
     hipStream_t last_stream = nullptr;

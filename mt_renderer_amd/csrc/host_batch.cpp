@@ -7,6 +7,8 @@ void mtr_launch_pose(const PoseParams& p, uint32_t ninst, hipStream_t s) __attri
 // k_anim.hip, weak for the same reason
 void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 
 namespace mtr_host {
 
@@ -39,10 +41,22 @@ AnimParams anim_params(const mtr_anim* a, const mtr_model::Skeleton& sk, const v
     AnimParams ap{};
     ap.pose = pose_params(sk, nullptr, out);
     ap.clips = a->d;
-    ap.keys = reinterpret_cast<const float*>(a->d + (size_t)a->nclips * 4);
     ap.states = static_cast<const uint32_t*>(states_dev);
     ap.nclips = a->nclips;
+    if (a->tracks) {
+        ap.tracks = a->d + (size_t)a->nclips * 4;
+        ap.values = ap.tracks + (size_t)a->nclips * a->njoints * 3 * 8;
+        ap.times = reinterpret_cast<const uint16_t*>(ap.values + (size_t)a->nkeys * 2);
+    } else {
+        ap.keys = reinterpret_cast<const float*>(a->d + (size_t)a->nclips * 4);
+    }
     return ap;
+}
+
+// k_anim on the set's kind of source (check_anim has seen the launcher)
+void launch_anim(const mtr_anim* a, const AnimParams& ap, uint32_t ninst, hipStream_t s) {
+    if (a->tracks) mtr_launch_anim_tracks(ap, ninst, s);
+    else mtr_launch_anim(ap, ninst, s);
 }
 
 // around a kernel on `s` that reads the clip set: see mtr_anim::last
@@ -192,7 +206,7 @@ int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, 
         if (src.anim) {
             int32_t arc = anim_before(src.anim, s);
             if (arc) return arc;
-            mtr_launch_anim(anim_params(src.anim, b->model->skel, src.states, vp), (uint32_t)n, s);
+            launch_anim(src.anim, anim_params(src.anim, b->model->skel, src.states, vp), (uint32_t)n, s);
             HIPCHK(d, hipGetLastError());
             if ((arc = anim_after(src.anim, s))) return arc;
         } else if (src.locals) {
@@ -228,7 +242,7 @@ int32_t check_anim(mtr_device* d, const mtr_model* m, const mtr_anim* a) {
     if (a->dev != d) return fail(d, MTR_E_INVALID, "animate: the animation set belongs to another device");
     if (!m->skel.d) return fail(d, MTR_E_INVALID, "animate: the model has no skeleton");
     if (a->njoints != m->skel.njoints) return fail(d, MTR_E_INVALID, "animate: the animation set's joint count is not the skeleton's");
-    if (!mtr_launch_anim) return fail(d, MTR_E_UNSUPPORTED, "animate: built without k_anim");
+    if (!(a->tracks ? mtr_launch_anim_tracks : mtr_launch_anim)) return fail(d, MTR_E_UNSUPPORTED, "animate: built without k_anim");
     return set_device(d);
 }
 
@@ -358,6 +372,69 @@ int32_t mtr_anim_create(mtr_device* d, size_t njoints, size_t nclips, const uint
     return MTR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// animation tracks (SPEC.md section 15): the same mtr_anim, its channel values from tracks
+// ---------------------------------------------------------------------------------------------
+int32_t mtr_anim_create_tracks(mtr_device* d, size_t njoints, size_t nclips, const uint32_t* nticks, const uint32_t* flags,
+                               const mtr_anim_track* tracks, const uint16_t* times, const uint16_t* values, size_t nkeys_total,
+                               mtr_anim** out) {
+    if (!d || !out) return MTR_E_INVALID;
+    *out = nullptr;
+    if (njoints == 0 || njoints > MTR_POSE_MAX_JOINTS) return fail(d, MTR_E_INVALID, "anim tracks: 1 to 256 joints");
+    if (nclips == 0 || nclips > 0xFFFFFFu || !nticks || !tracks || !times || !values)
+        return fail(d, MTR_E_INVALID, "anim tracks: at least one clip, its lengths, track descriptors, key times and key values");
+    // first + count of a valid track is at most the key total: 32-bit arithmetic on the device cannot wrap
+    if (nkeys_total == 0 || nkeys_total > 0x7FFFFFFFu) return fail(d, MTR_E_INVALID, "anim tracks: 1 to 2^31 - 1 keys");
+    static const char* const channel[3] = {"translation", "rotation", "scale"};
+    for (size_t c = 0; c < nclips; c++) {
+        if (nticks[c] == 0 || nticks[c] > 65536u)
+            return fail(d, MTR_E_INVALID, "anim tracks: clip " + std::to_string(c) + " has 1 to 65536 ticks");
+        for (size_t j = 0; j < njoints; j++)
+            for (size_t ch = 0; ch < 3; ch++) {
+                const mtr_anim_track& t = tracks[(c * njoints + j) * 3 + ch];
+                const char* what = nullptr;
+                if (t.count == 0) what = "has no key";
+                else if (t.count > nkeys_total || t.first > nkeys_total - t.count) what = "reaches past the key arrays";
+                else if (times[t.first] != 0) what = "does not start at tick 0";
+                else if (times[(size_t)t.first + t.count - 1] > nticks[c] - 1u) what = "has a key past the clip's last tick";
+                else
+                    for (size_t k = (size_t)t.first + 1; k < (size_t)t.first + t.count && !what; k++)
+                        if (times[k] <= times[k - 1]) what = "has key times that do not increase";
+                if (what)
+                    return fail(d, MTR_E_INVALID, "anim tracks: clip " + std::to_string(c) + ", joint " + std::to_string(j) + ", channel " +
+                                                      std::to_string(ch) + " (" + channel[ch] + ") " + what);
+            }
+    }
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    // device layout: the clip table (0, ticks, flags, 0), the descriptors (32 bytes, a joint's three together), the
+    // values (8 bytes each), the times (dense u16)
+    const size_t ntracks = nclips * njoints * 3;
+    std::vector<uint32_t> table(nclips * 4, 0u);
+    for (size_t c = 0; c < nclips; c++) {
+        table[c * 4 + 1] = nticks[c];
+        table[c * 4 + 2] = flags ? flags[c] : 0u;
+    }
+    static_assert(sizeof(mtr_anim_track) == 32, "mtr_anim_track");
+    auto a = std::make_unique<mtr_anim>();
+    a->dev = d; a->njoints = (uint32_t)njoints; a->nclips = (uint32_t)nclips;
+    a->tracks = true; a->nkeys = (uint32_t)nkeys_total;
+    const size_t time_words = (nkeys_total + 1) / 2;
+    if ((rc = dev_alloc(d, &a->d, table.size() + ntracks * 8 + nkeys_total * 2 + time_words))) return rc;
+    uint32_t* p = a->d;
+    hipError_t e = hipMemcpy(p, table.data(), table.size() * 4, hipMemcpyHostToDevice);
+    p += table.size();
+    if (e == hipSuccess) e = hipMemcpy(p, tracks, ntracks * 32, hipMemcpyHostToDevice);
+    p += ntracks * 8;
+    if (e == hipSuccess) e = hipMemcpy(p, values, nkeys_total * 8, hipMemcpyHostToDevice);
+    p += nkeys_total * 2;
+    if (e == hipSuccess) e = hipMemcpy(p, times, nkeys_total * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&a->last, hipEventDisableTiming);
+    if (e != hipSuccess) { (void)hipFree(a->d); return fail(d, MTR_E_HIP, std::string("anim upload: ") + hipGetErrorString(e)); }
+    *out = a.release();
+    return MTR_OK;
+}
+
 void mtr_anim_destroy(mtr_anim* a) {
     if (!a) return;
     mtr_device* d = a->dev;
@@ -380,7 +457,7 @@ int32_t mtr_model_animate(mtr_model* m, mtr_anim* a, const mtr_anim_state* state
     mtr_model::PalBuf* pb = nullptr;
     if ((rc = next_palette_buffer(m, a->njoints, &pb))) return rc;
     if ((rc = anim_before(a, d->s_copy))) return rc;
-    mtr_launch_anim(anim_params(a, m->skel, d->pose_stage, pb->d), 1, d->s_copy);
+    launch_anim(a, anim_params(a, m->skel, d->pose_stage, pb->d), 1, d->s_copy);
     HIPCHK(d, hipGetLastError());
     if ((rc = anim_after(a, d->s_copy))) return rc;
     HIPCHK(d, hipEventRecord(pb->ready, d->s_copy));
@@ -416,7 +493,7 @@ int32_t mtr_anim_sample(mtr_anim* a, const mtr_anim_state* states, size_t n, flo
     mtr_device* d = a->dev;
     const size_t need = n * a->njoints * 16;
     if (n > 0xFFFFFFu || (n && (!states || !out_locals)) || count < need) return fail(d, MTR_E_INVALID, "anim sample: n states and room for n * njoints * 16 floats");
-    if (!mtr_launch_anim_sample) return fail(d, MTR_E_UNSUPPORTED, "anim sample: built without k_anim");
+    if (!(a->tracks ? mtr_launch_anim_tracks_sample : mtr_launch_anim_sample)) return fail(d, MTR_E_UNSUPPORTED, "anim sample: built without k_anim");
     int32_t rc = set_device(d);
     if (rc || !n) return rc;
     float* tmp = nullptr;  // the local matrices, then the states
@@ -425,7 +502,8 @@ int32_t mtr_anim_sample(mtr_anim* a, const mtr_anim_state* states, size_t n, flo
         HIPCHK(d, hipMemcpyAsync(tmp + need, states, n * sizeof(mtr_anim_state), hipMemcpyHostToDevice, d->s_copy));
         AnimParams ap = anim_params(a, mtr_model::Skeleton{}, tmp + need, tmp);
         ap.pose.njoints = a->njoints;
-        mtr_launch_anim_sample(ap, (uint32_t)n, d->s_copy);
+        if (a->tracks) mtr_launch_anim_tracks_sample(ap, (uint32_t)n, d->s_copy);
+        else mtr_launch_anim_sample(ap, (uint32_t)n, d->s_copy);
         HIPCHK(d, hipGetLastError());
         HIPCHK(d, hipMemcpyAsync(out_locals, tmp, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
         return MTR_OK;

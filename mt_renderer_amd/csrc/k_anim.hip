@@ -6,6 +6,10 @@
 // workgroup; thread j reads its joint's keys (3 x 16 bytes each: 2 keys, or 4 with a cross-fade) with every load issued
 // before the first use.  Section 14 has no fused multiply-add: every operator below is one rounded operation (the file
 // is compiled with -ffp-contract=off), so a plain binary32 model reproduces the local matrices bit for bit.
+//
+// Two sources of channel values: clips of uniformly spaced 48-byte keys (section 14), and track sets (section 15: per joint
+// and channel a track with its own key times and 16-bit keys).  Everything after "one clip's (T, Q, S)" is one copy.
+#include "anim_tracks.h"
 #include "pose_common.h"
 
 namespace mtr {
@@ -72,7 +76,91 @@ __device__ __forceinline__ AnimKey anim_mix(const AnimKey& k0, const AnimKey& k1
     return r;
 }
 
-// The local matrix of joint j of instance inst (column-major)
+// ---- the track source (section 15) ----
+// What one thread holds of one clip's three tracks of its joint while they are searched
+struct TrackClip {
+    float r;
+    uint32_t nticks, flags;
+    uint32_t first[3], count[3];
+    float lo[2][3], step[2][3];  // [0] translation, [1] scale; the rotation's are never read
+    TrackSearch s[3];
+};
+
+// Memory safety by construction.  Every index below is formed from a descriptor of the set, which mtr_anim_create_tracks
+// validated on the host before the upload (count >= 1, first + count <= the key total, times[first] == 0, strictly
+// increasing times, the last one <= N - 1) and which nothing writes afterwards.  The device-side state only chooses
+// (a) the clip, and the index is clamped to nclips - 1, and (b) the position x, and track_position() returns -0 or a
+// value of [0, N) for every x (NaN, +-inf, huge, -0).  The search keeps base + n <= first + count and probes inside that
+// range whatever r is; k is its base, k1 is k + 1 < first + count, first or k.  So no state can move a read of times[] or
+// values[] outside [first, first + count) of a validated track, and the descriptor index (clip * J + j) * 3 + ch lies
+// inside the nclips * J * 3 descriptors because j < J.
+__device__ __forceinline__ void track_clip_begin(const AnimParams& p, uint32_t clip, float x, uint32_t j, TrackClip& c) {
+    const uint32_t ci = clip < p.nclips ? clip : p.nclips - 1u;
+    const uint4 ct = reinterpret_cast<const uint4*>(p.clips)[ci];
+    c.nticks = ct.y; c.flags = ct.z;
+    c.r = track_position(x, ct.y, ct.z);
+    const uint4* d = reinterpret_cast<const uint4*>(p.tracks) + ((size_t)ci * p.pose.njoints + j) * 6;  // 3 x 32 bytes
+    const uint4 t0 = d[0], t1 = d[1], s0 = d[4], s1 = d[5];
+    const uint2 q0 = *reinterpret_cast<const uint2*>(d + 2);
+    c.first[0] = t0.x; c.count[0] = t0.y;
+    c.first[1] = q0.x; c.count[1] = q0.y;
+    c.first[2] = s0.x; c.count[2] = s0.y;
+    c.lo[0][0] = __uint_as_float(t0.z); c.lo[0][1] = __uint_as_float(t0.w); c.lo[0][2] = __uint_as_float(t1.x);
+    c.step[0][0] = __uint_as_float(t1.y); c.step[0][1] = __uint_as_float(t1.z); c.step[0][2] = __uint_as_float(t1.w);
+    c.lo[1][0] = __uint_as_float(s0.z); c.lo[1][1] = __uint_as_float(s0.w); c.lo[1][2] = __uint_as_float(s1.x);
+    c.step[1][0] = __uint_as_float(s1.y); c.step[1][1] = __uint_as_float(s1.z); c.step[1][2] = __uint_as_float(s1.w);
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) c.s[ch] = track_search_begin(c.first[ch], c.count[ch]);
+}
+
+// the (T, Q, S) of NC clips at once: the 3 * NC searches advance in one loop, a step's loads in flight together; then
+// every time and value load is issued before the first use
+template <int NC>
+__device__ __forceinline__ void track_sample(const AnimParams& p, TrackClip (&c)[NC], AnimKey (&out)[NC]) {
+    const uint16_t* times = p.times;
+    const uint2* values = reinterpret_cast<const uint2*>(p.values);
+    uint32_t left = 0u;
+#pragma unroll
+    for (int i = 0; i < NC; i++) left |= c[i].count[0] | c[i].count[1] | c[i].count[2];
+    for (; left > 1u; left = track_search_left(left)) {  // as many steps as the longest of this thread's tracks takes
+#pragma unroll
+        for (int i = 0; i < NC; i++)
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) track_search_step(times, c[i].r, c[i].s[ch]);
+    }
+    uint32_t k1[NC][3], tk1[NC][3];
+    uint2 v0[NC][3], v1[NC][3];
+#pragma unroll
+    for (int i = 0; i < NC; i++)
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            const uint32_t k = c[i].s[ch].base;
+            k1[i][ch] = track_next_key(c[i].first[ch], c[i].count[ch], k, c[i].flags);
+            tk1[i][ch] = times[k1[i][ch]];
+            v0[i][ch] = values[k];
+            v1[i][ch] = values[k1[i][ch]];
+        }
+#pragma unroll
+    for (int i = 0; i < NC; i++) {
+        float a[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++)
+            a[ch] = track_fraction(c[i].r, c[i].first[ch], c[i].count[ch], c[i].s[ch].base, k1[i][ch], c[i].s[ch].tk, tk1[i][ch], c[i].nticks);
+        float t0[3], t1[3], q0[4], q1[4], s0[3], s1[3];
+        track_decode_lin(v0[i][0].x, v0[i][0].y, c[i].lo[0], c[i].step[0], t0);
+        track_decode_lin(v1[i][0].x, v1[i][0].y, c[i].lo[0], c[i].step[0], t1);
+        track_decode_rot(v0[i][1].x, v0[i][1].y, q0);
+        track_decode_rot(v1[i][1].x, v1[i][1].y, q1);
+        track_decode_lin(v0[i][2].x, v0[i][2].y, c[i].lo[1], c[i].step[1], s0);
+        track_decode_lin(v1[i][2].x, v1[i][2].y, c[i].lo[1], c[i].step[1], s1);
+        out[i].t = make_float4(anim_lerp(t0[0], t1[0], a[0]), anim_lerp(t0[1], t1[1], a[0]), anim_lerp(t0[2], t1[2], a[0]), 0.0f);
+        out[i].q = anim_nlerp(make_float4(q0[0], q0[1], q0[2], q0[3]), make_float4(q1[0], q1[1], q1[2], q1[3]), a[1]);
+        out[i].s = make_float4(anim_lerp(s0[0], s1[0], a[2]), anim_lerp(s0[1], s1[1], a[2]), anim_lerp(s0[2], s1[2], a[2]), 0.0f);
+    }
+}
+
+// The local matrix of joint j of instance inst (column-major); TRACKS: the set is a track set
+template <bool TRACKS>
 __device__ __forceinline__ void anim_local(const AnimParams& p, uint32_t inst, uint32_t j, float4 (&M)[4]) {
     const uint32_t J = p.pose.njoints;
     const uint2* st = reinterpret_cast<const uint2*>(p.states + (size_t)inst * 6);
@@ -80,20 +168,37 @@ __device__ __forceinline__ void anim_local(const AnimParams& p, uint32_t inst, u
     float w = __uint_as_float(sw.x);
     w = w > 0.0f ? w : 0.0f;  // NaN -> 0
     w = w > 1.0f ? 1.0f : w;
-    const uint4* clips = reinterpret_cast<const uint4*>(p.clips);
-    const float4* keys = reinterpret_cast<const float4*>(p.keys);
-    const uint4 ca = clips[sc.x < p.nclips ? sc.x : p.nclips - 1u];
-    const AnimPos pa = anim_position(__uint_as_float(sx.x), ca.y, ca.z);
     AnimKey r;
-    if (w == 0.0f) {  // clip B is not read
-        const AnimKey a0 = anim_load_key(keys, ca.x + pa.i0, J, j), a1 = anim_load_key(keys, ca.x + pa.i1, J, j);
-        r = anim_mix(a0, a1, pa.a);
+    if constexpr (TRACKS) {
+        if (w == 0.0f) {  // clip B is not read
+            TrackClip c[1];
+            AnimKey v[1];
+            track_clip_begin(p, sc.x, __uint_as_float(sx.x), j, c[0]);
+            track_sample<1>(p, c, v);
+            r = v[0];
+        } else {
+            TrackClip c[2];
+            AnimKey v[2];
+            track_clip_begin(p, sc.x, __uint_as_float(sx.x), j, c[0]);
+            track_clip_begin(p, sc.y, __uint_as_float(sx.y), j, c[1]);
+            track_sample<2>(p, c, v);
+            r = anim_mix(v[0], v[1], w);
+        }
     } else {
-        const uint4 cb = clips[sc.y < p.nclips ? sc.y : p.nclips - 1u];
-        const AnimPos pb = anim_position(__uint_as_float(sx.y), cb.y, cb.z);
-        const AnimKey a0 = anim_load_key(keys, ca.x + pa.i0, J, j), a1 = anim_load_key(keys, ca.x + pa.i1, J, j);
-        const AnimKey b0 = anim_load_key(keys, cb.x + pb.i0, J, j), b1 = anim_load_key(keys, cb.x + pb.i1, J, j);
-        r = anim_mix(anim_mix(a0, a1, pa.a), anim_mix(b0, b1, pb.a), w);
+        const uint4* clips = reinterpret_cast<const uint4*>(p.clips);
+        const float4* keys = reinterpret_cast<const float4*>(p.keys);
+        const uint4 ca = clips[sc.x < p.nclips ? sc.x : p.nclips - 1u];
+        const AnimPos pa = anim_position(__uint_as_float(sx.x), ca.y, ca.z);
+        if (w == 0.0f) {  // clip B is not read
+            const AnimKey a0 = anim_load_key(keys, ca.x + pa.i0, J, j), a1 = anim_load_key(keys, ca.x + pa.i1, J, j);
+            r = anim_mix(a0, a1, pa.a);
+        } else {
+            const uint4 cb = clips[sc.y < p.nclips ? sc.y : p.nclips - 1u];
+            const AnimPos pb = anim_position(__uint_as_float(sx.y), cb.y, cb.z);
+            const AnimKey a0 = anim_load_key(keys, ca.x + pa.i0, J, j), a1 = anim_load_key(keys, ca.x + pa.i1, J, j);
+            const AnimKey b0 = anim_load_key(keys, cb.x + pb.i0, J, j), b1 = anim_load_key(keys, cb.x + pb.i1, J, j);
+            r = anim_mix(anim_mix(a0, a1, pa.a), anim_mix(b0, b1, pb.a), w);
+        }
     }
     const float x = r.q.x, y = r.q.y, z = r.q.z, qw = r.q.w;
     const float x2 = x + x, y2 = y + y, z2 = z + z;
@@ -105,13 +210,14 @@ __device__ __forceinline__ void anim_local(const AnimParams& p, uint32_t inst, u
     M[3] = make_float4(r.t.x, r.t.y, r.t.z, 1.0f);
 }
 
-__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim(AnimParams p) {
+template <bool TRACKS>
+__device__ __forceinline__ void anim_palettes(const AnimParams& p) {
     __shared__ float4 loc[MTR_POSE_MAX_JOINTS * 4];
     extern __shared__ uint32_t path_lds[];  // p.pose.path_bytes / 4 words
     const uint32_t inst = blockIdx.x, t = threadIdx.x, J = p.pose.njoints;
     if (t < J) {
         float4 M[4];
-        anim_local(p, inst, t, M);
+        anim_local<TRACKS>(p, inst, t, M);
 #pragma unroll
         for (int c = 0; c < 4; c++) loc[t * 4 + c] = M[c];
     }
@@ -122,15 +228,21 @@ __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim(AnimParams p) {
 }
 
 // the local matrices themselves (mtr_anim_sample): the same sampling function, stored instead of folded
-__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_sample(AnimParams p) {
+template <bool TRACKS>
+__device__ __forceinline__ void anim_locals(const AnimParams& p) {
     const uint32_t inst = blockIdx.x, t = threadIdx.x, J = p.pose.njoints;
     if (t >= J) return;
     float4 M[4];
-    anim_local(p, inst, t, M);
+    anim_local<TRACKS>(p, inst, t, M);
     float4* out = reinterpret_cast<float4*>(p.pose.out + ((size_t)inst * J + t) * 16);
 #pragma unroll
     for (int c = 0; c < 4; c++) out[c] = M[c];
 }
+
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim(AnimParams p) { anim_palettes<false>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_sample(AnimParams p) { anim_locals<false>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_tracks(AnimParams p) { anim_palettes<true>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_tracks_sample(AnimParams p) { anim_locals<true>(p); }
 
 }  // namespace mtr
 
@@ -148,4 +260,16 @@ void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) 
     if (!anim_launchable(p, ninst)) return;
     const uint32_t threads = (p.pose.njoints + 63u) & ~63u;
     hipLaunchKernelGGL(mtr::k_anim_sample, dim3(ninst), dim3(threads), 0, s, p);
+}
+
+void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_launchable(p, ninst) || p.pose.path_bytes > MTR_POSE_MAX_PATH_BYTES || !p.tracks) return;
+    const uint32_t threads = (p.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_tracks, dim3(ninst), dim3(threads), p.pose.path_bytes, s, p);
+}
+
+void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_launchable(p, ninst) || !p.tracks) return;
+    const uint32_t threads = (p.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_tracks_sample, dim3(ninst), dim3(threads), 0, s, p);
 }

@@ -480,6 +480,13 @@ struct AnimParams {
     const float* keys;          // (total keys) x njoints x 12 f32, key-major, joint fastest; 16-byte aligned
     const uint32_t* states;     // ninst x 6 words: clip_a, clip_b, x_a, x_b, w (f32 bits), pad; 8-byte aligned
     uint32_t nclips;            // >= 1
+    // a track set (SPEC.md section 15; the *_tracks launchers only, nullptr otherwise).  clips then holds per clip: 0, its
+    // length in ticks (1..65536), flags, 0; keys is nullptr
+    const uint32_t* tracks;     // nclips x njoints x 3 descriptors of 8 words (mtr_anim_track: first, count, lo[3], step[3]); 16-byte aligned
+    const uint32_t* values;     // (total keys) x 2 words: four 16-bit words per key; 8-byte aligned
+    const uint16_t* times;      // (total keys) u16 ticks
 };
 void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t s);

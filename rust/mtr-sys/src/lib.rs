@@ -83,6 +83,16 @@ pub struct mtr_anim_key {
     pub s: [f32; 3],
     pub pad1: f32,
 }
+/// animation tracks (mtr.h, SPEC.md section 15): one track's keys and quantisation, 32 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_anim_track {
+    pub first: u32,
+    pub count: u32,
+    pub lo: [f32; 3],
+    pub step: [f32; 3],
+}
+
 /// what one instance plays: clip A at x_a cross-faded by w with clip B at x_b, positions in keys; 24 bytes
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -181,5 +191,9 @@ extern "C" {
     pub fn mtr_batch_animate_device(batch: *mut mtr_batch, anim: *mut mtr_anim, states_dev: *const mtr_anim_state,
                                     hip_stream: *mut c_void) -> i32;
     pub fn mtr_anim_sample(anim: *mut mtr_anim, states: *const mtr_anim_state, n: usize, out_locals: *mut f32, count: usize) -> i32;
+    // animation tracks (SPEC.md section 15): declaration only; a descriptor is 32 bytes (u32 first, count; f32 lo[3], step[3])
+    pub fn mtr_anim_create_tracks(dev: *mut mtr_device, njoints: usize, nclips: usize, nticks: *const u32, flags: *const u32,
+                                  tracks: *const mtr_anim_track, times: *const u16, values: *const u16, nkeys_total: usize,
+                                  out: *mut *mut mtr_anim) -> i32;
 }
 pub mod files;

@@ -5,14 +5,16 @@ Frames are submitted without waiting, through api.FrameLoop; a timed region is `
 synchronise, repeated `--reps` times per mode with the modes alternating, and the median is reported.
 Extra modes: device_side_stream (device poses from a non-default torch stream), poses_only (device poses, no frames);
 anim (host animation states before every frame: Batch.animate(numpy), 24 bytes per instance + k_anim on the copy stream),
-anim_device (states in a torch tensor: k_anim on torch's current stream), anim_only (device states, no frames).  The clip
+anim_device (states in a torch tensor: k_anim on torch's current stream), anim_only (device states, no frames); tracks,
+tracks_device, tracks_only: the same three from a track set (SPEC.md section 15) that mt_renderer_amd.anim_tracks.compress
+made of the same clips (--tol: its three tolerances; the encoded and the uniform size are printed and recorded).  The clip
 set (four clips of 120 / 60 / 31 / 2 keys, small bends about z) and the states are generated from --seed.
     python tools/probe/animated_batch.py [--only c3|c5] [--frames N] [--reps R] [--modes static,host,anim] [--seed S] [--json OUT]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 import torch
-from mt_renderer_amd import api, scene
+from mt_renderer_amd import anim_tracks, api, scene
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--only", default="")
@@ -21,6 +23,7 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--modes", default="static,host,device,device_side_stream,poses_only")
 ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--json", default=None)
+ap.add_argument("--tol", type=float, default=1e-4)
 args = ap.parse_args()
 modes = args.modes.split(",")
 CHAIN = [255] + list(range(63))  # mesh50k's 64 bones run along the capsule: a chain
@@ -72,7 +75,15 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
     rng = np.random.default_rng(args.seed)
     host = poses(rng, n, 8)
     devp = [torch.tensor(p, device="cuda:0") for p in host]
-    anim = api.Anim(dev, 64, clips(rng))
+    uniform_clips = clips(rng)
+    anim = api.Anim(dev, 64, uniform_clips)
+    sizes = None
+    if any(m.startswith("tracks") for m in modes):
+        track_clips = [anim_tracks.compress(k, fl, args.tol, args.tol, args.tol) for k, fl in uniform_clips]
+        tracks = api.AnimTracks(dev, 64, track_clips)
+        sizes = dict(uniform_bytes=sum(anim_tracks.uniform_bytes(k.shape[0], 64) for k, _ in uniform_clips),
+                     track_bytes=sum(anim_tracks.encoded_bytes(c) for c in track_clips), track_keys=int(sum(c[3].size for c in track_clips)), tol=args.tol)
+        print(json.dumps(dict(config=name, clip_set=sizes)), flush=True)
     host_st = states(rng, n, 8)
     dev_st = [torch.from_numpy(s.view(np.uint8).reshape(n, 24).copy()).to("cuda:0") for s in host_st]
     loop = api.FrameLoop(dev, W, H, batch=batch, view_proj=scene.to_f32_colmajor(scene.reference_view_proj(W, H)))
@@ -95,6 +106,13 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
             elif mode == "anim_only":  # device states and no frames: k_anim alone on the GPU
                 batch.animate(anim, dev_st[k % 8])
                 continue
+            elif mode == "tracks":
+                batch.animate(tracks, host_st[k % 8])
+            elif mode == "tracks_device":
+                batch.animate(tracks, dev_st[k % 8])
+            elif mode == "tracks_only":  # device states and no frames: k_anim_tracks alone on the GPU
+                batch.animate(tracks, dev_st[k % 8])
+                continue
             elif mode == "poses_only":  # device poses and no frames: k_pose alone on the GPU
                 batch.set_poses(devp[k % 8])
                 continue
@@ -116,10 +134,14 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
     for mode in modes:
         r = dict(config=name, instances=n, joints=64, width=W, height=H, mode=mode, frames=args.frames,
                  ms_per_frame=round(float(np.median(ms[mode])), 4), ms_all=[round(v, 4) for v in ms[mode]])
+        if sizes and mode.startswith("tracks"):
+            r["clip_set"] = sizes
         results.append(r)
         print(json.dumps(r), flush=True)
     batch.close()
     anim.close()
+    if sizes:
+        tracks.close()
     model.close()
 dev.close()
 if args.json:
