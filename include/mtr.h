@@ -268,6 +268,46 @@ int32_t mtr_anim_create_tracks(mtr_device *dev, size_t njoints, size_t nclips, c
                                const uint16_t *times, const uint16_t *values /* 4 per key */, size_t nkeys_total,
                                mtr_anim **out);
 
+/* ---- animation layers (build extension, SPEC.md section 16): a stack of up to 8 layers per instance over one set ----
+ * A layer names a clip of the animation set (of either kind), a position x in it (section 14 / 15), a weight w, a per-joint
+ * mask and a mode.  Layer 0 is the base: the pose of its clip at x; its w, mask and mode are not read.  Every further layer
+ * is blended over the result so far, joint by joint, by e = clamp(w) * mask[joint]: MTR_LAYER_OVERRIDE cross-fades towards
+ * the layer's pose as section 14 cross-fades clip A towards clip B; MTR_LAYER_ADDITIVE takes the layer's clip as deltas
+ * from a reference pose (translation added, rotation multiplied on the right, scale multiplied; mt_renderer_amd/
+ * anim_layers.py makes such clips) and applies e of them.  Where e == 0 the joint is left as it is, bit for bit, and the
+ * layer's clip is not read.  Two layers with mask 0 and OVERRIDE are section 14's cross-fade, bit for bit.
+ * A mask set belongs to a joint count and holds nmasks >= 1 masks of njoints weights in [0, 1] (mask after mask; the
+ * library copies); a layer's mask index 0 is the built-in mask "every joint 1.0", 1..nmasks are the set's.  Clip and mask
+ * indices are clamped (to nclips - 1, to nmasks, to 0 without a mask set), never rejected; only bit 0 of mode is read.
+ * Every instance of a call has the same number of layers, contiguous per instance: layers[inst * nlayers + l].
+ * Errors: MTR_E_INVALID, and nothing changes, for a NULL handle or pointer (masks may be NULL: every mask index is 0),
+ * nlayers outside 1..MTR_ANIM_MAX_LAYERS, njoints outside 1..256, nmasks == 0 or above 65535, a weight that is NaN or
+ * outside [0, 1] (mtr_last_error names the mask and the joint), a mask set whose njoints is not the skeleton's or that
+ * belongs to another device, everything the animate calls of section 14 reject, a misaligned device pointer;
+ * MTR_E_UNSUPPORTED when the library was built without the layer kernels. */
+#define MTR_ANIM_MAX_LAYERS 8
+#define MTR_LAYER_OVERRIDE 0u
+#define MTR_LAYER_ADDITIVE 1u
+typedef struct mtr_anim_masks mtr_anim_masks;
+typedef struct mtr_anim_layer { uint32_t clip; float x, w; uint16_t mask, mode; } mtr_anim_layer;   /* 16 bytes */
+int32_t mtr_anim_masks_create(mtr_device *dev, size_t njoints, size_t nmasks, const float *weights /* nmasks*njoints */,
+                              mtr_anim_masks **out);
+/* may follow an animate call directly: parked like mtr_anim_destroy */
+void mtr_anim_masks_destroy(mtr_anim_masks *masks);
+/* the model's palette from one layer stack (host memory, free on return); frame semantics of mtr_model_animate */
+int32_t mtr_model_animate_layers(mtr_model *model, mtr_anim *anim, mtr_anim_masks *masks /* or NULL */,
+                                 const mtr_anim_layer *layers /* nlayers, host */, size_t nlayers);
+/* one layer stack per instance (host memory, free on return); frame semantics of mtr_batch_animate */
+int32_t mtr_batch_animate_layers(mtr_batch *batch, mtr_anim *anim, mtr_anim_masks *masks /* or NULL */,
+                                 const mtr_anim_layer *layers /* n*nlayers, host */, size_t nlayers);
+/* the same from device memory, read in stream order on hip_stream with the rules of mtr_batch_animate_device */
+int32_t mtr_batch_animate_layers_device(mtr_batch *batch, mtr_anim *anim, mtr_anim_masks *masks /* or NULL */,
+                                        const mtr_anim_layer *layers_dev /* 16-byte aligned */, size_t nlayers,
+                                        void *hip_stream /* as mtr_batch_set_poses_device */);
+/* test / debug hook: the local matrices of section 16 for n layer stacks, n * njoints * 16 floats to host memory */
+int32_t mtr_anim_sample_layers(mtr_anim *anim, mtr_anim_masks *masks /* or NULL */, const mtr_anim_layer *layers,
+                               size_t nlayers, size_t n, float *out_locals, size_t count);
+
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],
                         float clear_depth, mtr_frame **out);

@@ -110,12 +110,34 @@ class Anim {
         dev_.check(mtr_anim_sample(h_, states, n, out.data(), out.size()));
         return out;
     }
+    // the local matrices of n layer stacks of nlayers layers each (SPEC.md section 16); masks may be nullptr
+    std::vector<float> sample_layers(mtr_anim_masks* masks, const mtr_anim_layer* layers, size_t nlayers, size_t n) const {
+        std::vector<float> out(n * njoints_ * 16);
+        dev_.check(mtr_anim_sample_layers(h_, masks, layers, nlayers, n, out.data(), out.size()));
+        return out;
+    }
     mtr_anim* handle() const { return h_; }
 
   private:
     const Device& dev_;
     size_t njoints_;
     mtr_anim* h_ = nullptr;
+};
+
+// A mask set for animation layers (include/mtr.h, SPEC.md section 16): nmasks masks of njoints weights in [0, 1]
+class AnimMasks {
+  public:
+    AnimMasks(const Device& dev, size_t njoints, size_t nmasks, const float* weights) : dev_(dev) {
+        dev.check(mtr_anim_masks_create(dev.handle(), njoints, nmasks, weights, &h_));
+    }
+    AnimMasks(AnimMasks&& o) noexcept : dev_(o.dev_), h_(std::exchange(o.h_, nullptr)) {}
+    AnimMasks(const AnimMasks&) = delete;
+    ~AnimMasks() { mtr_anim_masks_destroy(h_); }
+    mtr_anim_masks* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    mtr_anim_masks* h_ = nullptr;
 };
 
 class Model {
@@ -145,6 +167,10 @@ class Model {
     void set_pose(const float* local_mats, size_t njoints) { dev_.check(mtr_model_set_pose(h_, local_mats, njoints)); }
     // the palette from one animation state through the skeleton (SPEC.md section 14)
     void animate(const Anim& anim, const mtr_anim_state& state) { dev_.check(mtr_model_animate(h_, anim.handle(), &state)); }
+    // the palette from one layer stack (SPEC.md section 16); masks may be nullptr
+    void animate_layers(const Anim& anim, const AnimMasks* masks, const mtr_anim_layer* layers, size_t nlayers) {
+        dev_.check(mtr_model_animate_layers(h_, anim.handle(), masks ? masks->handle() : nullptr, layers, nlayers));
+    }
     // the state objects a material names (src/rmaterial.rs:211-230), applied per primitive; default = src/model.rs:240-262
     void set_prim_states(const std::vector<mtr_prim_state>& states) { dev_.check(mtr_model_set_prim_states(h_, states.data(), states.size())); }
     // joint positions for the per-joint debug cubes of Model::render (src/model.rs:309-315)
@@ -183,6 +209,15 @@ class Batch {
     void animate(const Anim& anim, const mtr_anim_state* states) { dev_.check(mtr_batch_animate(h_, anim.handle(), states)); npal_ = anim.njoints(); }
     void animate_device(const Anim& anim, const mtr_anim_state* states_dev, void* hip_stream = nullptr) {
         dev_.check(mtr_batch_animate_device(h_, anim.handle(), states_dev, hip_stream));
+        npal_ = anim.njoints();
+    }
+    // nlayers layers per instance (SPEC.md section 16): host memory, or device memory read in stream order; masks may be nullptr
+    void animate_layers(const Anim& anim, const AnimMasks* masks, const mtr_anim_layer* layers, size_t nlayers) {
+        dev_.check(mtr_batch_animate_layers(h_, anim.handle(), masks ? masks->handle() : nullptr, layers, nlayers));
+        npal_ = anim.njoints();
+    }
+    void animate_layers_device(const Anim& anim, const AnimMasks* masks, const mtr_anim_layer* layers_dev, size_t nlayers, void* hip_stream = nullptr) {
+        dev_.check(mtr_batch_animate_layers_device(h_, anim.handle(), masks ? masks->handle() : nullptr, layers_dev, nlayers, hip_stream));
         npal_ = anim.njoints();
     }
     std::vector<float> read_palettes() const {

@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = [
     "mtr_batch_read_palettes",
     "mtr_anim_create", "mtr_anim_destroy", "mtr_model_animate", "mtr_batch_animate", "mtr_batch_animate_device", "mtr_anim_sample",
     "mtr_anim_create_tracks",
+    "mtr_anim_masks_create", "mtr_anim_masks_destroy", "mtr_model_animate_layers", "mtr_batch_animate_layers",
+    "mtr_batch_animate_layers_device", "mtr_anim_sample_layers",
 ]
 
 CLIP_LOOP = 1
@@ -54,6 +56,11 @@ ANIM_KEY = np.dtype([("t", "<f4", 3), ("pad0", "<f4"), ("q", "<f4", 4), ("s", "<
 ANIM_STATE = np.dtype([("clip_a", "<u4"), ("clip_b", "<u4"), ("x_a", "<f4"), ("x_b", "<f4"), ("w", "<f4"), ("pad", "<u4")])
 # mtr_anim_track (SPEC.md section 15)
 ANIM_TRACK = np.dtype([("first", "<u4"), ("count", "<u4"), ("lo", "<f4", 3), ("step", "<f4", 3)])
+# mtr_anim_layer (SPEC.md section 16)
+ANIM_LAYER = np.dtype([("clip", "<u4"), ("x", "<f4"), ("w", "<f4"), ("mask", "<u2"), ("mode", "<u2")])
+ANIM_MAX_LAYERS = 8
+LAYER_OVERRIDE = 0
+LAYER_ADDITIVE = 1
 
 
 class MtrError(RuntimeError):
@@ -182,6 +189,12 @@ def _load() -> C.CDLL:
         "mtr_batch_animate_device": (i32, [vp, vp, vp, vp]),
         "mtr_anim_sample": (i32, [vp, vp, sz, vp, sz]),
         "mtr_anim_create_tracks": (i32, [vp, sz, sz, vp, vp, vp, vp, vp, sz, vp]),
+        "mtr_anim_masks_create": (i32, [vp, sz, sz, vp, vp]),
+        "mtr_anim_masks_destroy": (None, [vp]),
+        "mtr_model_animate_layers": (i32, [vp, vp, vp, vp, sz]),
+        "mtr_batch_animate_layers": (i32, [vp, vp, vp, vp, sz]),
+        "mtr_batch_animate_layers_device": (i32, [vp, vp, vp, vp, sz, vp]),
+        "mtr_anim_sample_layers": (i32, [vp, vp, vp, sz, sz, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -401,6 +414,11 @@ class Model:
         st = anim_states(state, 1)
         self.dev.check(lib.mtr_model_animate(self._h, anim._h, _p(st)))
 
+    def animate_layers(self, anim: "Anim", layers, masks: Optional["AnimMasks"] = None):
+        """palette formed on the GPU (k_anim_layers) from one layer stack: an ANIM_LAYER array [L] or a dict of its fields"""
+        ly = anim_layers(layers, 1)
+        self.dev.check(lib.mtr_model_animate_layers(self._h, anim._h, masks._h if masks is not None else None, _p(ly), ly.shape[1]))
+
     def render(self, frame: "Frame", view_proj: np.ndarray, joints: bool = False):
         """Model::render(rpass, queue, transform_bind_group, debug_overlay) -- src/model.rs:299-305; the
         transform uniform (src/bin/modelviewer.rs:217-221) is passed directly.  joints: also the per-joint debug cubes the
@@ -454,6 +472,61 @@ def anim_states(states, n: Optional[int] = None) -> np.ndarray:
     return st
 
 
+def anim_layers(layers, n: Optional[int] = None, L: Optional[int] = None) -> np.ndarray:
+    """layer stacks as a contiguous ANIM_LAYER array [n, L] (SPEC.md section 16): from a structured array of that dtype
+    ([n, L], or flat with n or L given), or from a dict of clip and x, optionally w, mask and mode (arrays [n, L], or
+    anything that broadcasts to it; a missing w is 1, a missing mask / mode 0)"""
+    if isinstance(layers, dict):
+        unknown = set(layers) - set(ANIM_LAYER.names)
+        if unknown or "clip" not in layers or "x" not in layers:
+            raise MtrError(MTR_E_INVALID, "animation layers: clip and x, optionally w, mask and mode")
+        cols = {k: np.asarray(v) for k, v in layers.items()}
+        shape = np.broadcast_shapes(*[c.shape for c in cols.values()])
+        if len(shape) > 2:
+            raise MtrError(MTR_E_INVALID, "animation layers: fields of shape [n, L]")
+        shape = (1,) * (2 - len(shape)) + tuple(shape)
+        shape = (n if n is not None and shape[0] == 1 else shape[0], L if L is not None and shape[1] == 1 else shape[1])
+        ly = np.zeros(shape, dtype=ANIM_LAYER)
+        ly["w"] = 1.0
+        for k, v in cols.items():
+            ly[k] = v
+    else:
+        a = np.asarray(layers)
+        if a.dtype != ANIM_LAYER:
+            raise MtrError(MTR_E_INVALID, "animation layers: an array of dtype ANIM_LAYER or a dict of its fields")
+        a = np.ascontiguousarray(a)
+        if a.ndim == 2:
+            ly = a
+        elif n is not None and n and a.size % n == 0:
+            ly = a.reshape(n, a.size // n)
+        elif L is not None and L and a.size % L == 0:
+            ly = a.reshape(a.size // L, L)
+        else:
+            raise MtrError(MTR_E_INVALID, "animation layers: an [n, L] array")
+    if (n is not None and ly.shape[0] != n) or (L is not None and ly.shape[1] != L):
+        raise MtrError(MTR_E_INVALID, f"animation layers: [{n}, {L}] expected, {list(ly.shape)} given")
+    return ly
+
+
+class AnimMasks:
+    """A mask set for animation layers (include/mtr.h, SPEC.md section 16): weights [nmasks, njoints] in [0, 1], resident
+    in HBM.  A layer's mask index 0 is the built-in mask of ones, index k >= 1 is weights[k - 1]."""
+
+    def __init__(self, dev: Device, njoints: int, weights):
+        w = _f32(weights)
+        if njoints < 1 or w.size == 0 or w.size % njoints:
+            raise MtrError(MTR_E_INVALID, "anim masks: weights are [nmasks, njoints] float32, at least one mask")
+        w = np.ascontiguousarray(w).reshape(-1, njoints)
+        h = C.c_void_p()
+        dev.check(lib.mtr_anim_masks_create(dev._h, njoints, w.shape[0], _p(w), C.byref(h)))
+        self.dev, self._h, self.njoints, self.nmasks = dev, h, njoints, w.shape[0]
+
+    def close(self):
+        if self._h:
+            lib.mtr_anim_masks_destroy(self._h)
+            self._h = None
+
+
 class Anim:
     """An animation set (include/mtr.h, SPEC.md section 14): clips of uniformly spaced keys for ``njoints`` joints, resident
     in HBM.  clips: a list of (keys, flags); keys is [nkeys, njoints, 12] float32 (t.xyz 0 | q.xyzw | s.xyz 0) or an
@@ -487,6 +560,13 @@ class Anim:
         st = anim_states(states)
         out = np.zeros((st.size, self.njoints, 16), dtype=np.float32)
         self.dev.check(lib.mtr_anim_sample(self._h, _p(st), st.size, _p(out), out.size))
+        return out
+
+    def sample_layers(self, layers, masks: Optional[AnimMasks] = None) -> np.ndarray:
+        """the local matrices [n, njoints, 16] of the given layer stacks ([n, L], SPEC.md section 16), formed on the GPU"""
+        ly = anim_layers(layers)
+        out = np.zeros((ly.shape[0], self.njoints, 16), dtype=np.float32)
+        self.dev.check(lib.mtr_anim_sample_layers(self._h, masks._h if masks is not None else None, _p(ly), ly.shape[1], ly.shape[0], _p(out), out.size))
         return out
 
     def close(self):
@@ -626,6 +706,40 @@ class Batch:
             side = _pose_stream(t.device)
             side.wait_stream(cur)
             self.dev.check(lib.mtr_batch_animate_device(self._h, anim._h, C.c_void_p(t.data_ptr()), C.c_void_p(side.cuda_stream)))
+            t.record_stream(side)
+            cur.wait_stream(side)
+        self.npal = anim.njoints
+
+    def animate_layers(self, anim: Anim, layers, masks: Optional[AnimMasks] = None, L: Optional[int] = None):
+        """one layer stack per instance through ``anim``, ``masks`` (or None) and the model's skeleton (k_anim_layers, SPEC.md
+        section 16).  A structured numpy array (ANIM_LAYER, [n, L]) or a dict of its fields is copied in; a torch uint8
+        [n, L * 16] / int32 [n, L * 4] tensor on the batch's device holding ANIM_LAYER records is read in stream order on
+        torch.cuda.current_stream()."""
+        mh = masks._h if masks is not None else None
+        if isinstance(layers, (np.ndarray, dict)):
+            ly = anim_layers(layers, self.n, L)
+            self.dev.check(lib.mtr_batch_animate_layers(self._h, anim._h, mh, _p(ly), ly.shape[1]))
+            self.npal = anim.njoints
+            return
+        import torch
+        t = layers
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32):
+            raise MtrError(MTR_E_INVALID, "animate_layers: a numpy ANIM_LAYER array, a dict, or a uint8 / int32 tensor on the GPU")
+        if t.get_device() != self.dev.hip_device:
+            raise MtrError(MTR_E_INVALID, f"animate_layers: the tensor is on cuda:{t.get_device()}, the batch on cuda:{self.dev.hip_device}")
+        nbytes = t.numel() * t.element_size()
+        if nbytes == 0 or nbytes % (self.n * ANIM_LAYER.itemsize) or (L is not None and nbytes != self.n * L * ANIM_LAYER.itemsize):
+            raise MtrError(MTR_E_INVALID, "animate_layers: n x L layers of 16 bytes")
+        nl = nbytes // (self.n * ANIM_LAYER.itemsize)
+        cur = torch.cuda.current_stream(t.device)
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            t = t.contiguous().clone()
+        if cur.cuda_stream != 0:
+            self.dev.check(lib.mtr_batch_animate_layers_device(self._h, anim._h, mh, C.c_void_p(t.data_ptr()), nl, C.c_void_p(cur.cuda_stream)))
+        else:  # torch's legacy default stream: as set_poses
+            side = _pose_stream(t.device)
+            side.wait_stream(cur)
+            self.dev.check(lib.mtr_batch_animate_layers_device(self._h, anim._h, mh, C.c_void_p(t.data_ptr()), nl, C.c_void_p(side.cuda_stream)))
             t.record_stream(side)
             cur.wait_stream(side)
         self.npal = anim.njoints

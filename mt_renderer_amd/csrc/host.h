@@ -329,6 +329,17 @@ struct mtr_anim {
     bool recorded = false;
 };
 
+// A mask set (SPEC.md section 16): immutable once uploaded.  d: nmasks x njoints weights (the user's masks 1..nmasks).  `last`
+// as mtr_anim's: recorded behind every kernel that reads d, so that mtr_anim_masks_destroy can park d behind it.
+struct mtr_anim_masks {
+    mtr_device* dev;
+    uint32_t njoints = 0, nmasks = 0;
+    float* d = nullptr;
+    hipEvent_t last = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool recorded = false;
+};
+
 namespace mtr_host {
 
 struct BatchDeleter {

@@ -1,4 +1,4 @@
-// host_batch.cpp -- instance batches and their versions, pose and animation staging, animation clip sets.
+// host_batch.cpp -- instance batches and their versions, pose and animation staging, animation clip sets, mask sets and layers.
 #include "host.h"
 
 // k_pose.hip.  Weak: the host-only builds of this file (tests/cpp, over the HIP stub runtime) link no kernels and never
@@ -9,6 +9,10 @@ void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s) __attri
 void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 
 namespace mtr_host {
 
@@ -59,12 +63,30 @@ void launch_anim(const mtr_anim* a, const AnimParams& ap, uint32_t ninst, hipStr
     else mtr_launch_anim(ap, ninst, s);
 }
 
-// around a kernel on `s` that reads the clip set: see mtr_anim::last
-int32_t anim_before(mtr_anim* a, hipStream_t s) {
+// a layer stack over the set (section 16): layers_dev holds ninst * nlayers records; masks may be nullptr
+AnimLayerParams anim_layer_params(const mtr_anim* a, const mtr_anim_masks* mk, const mtr_model::Skeleton& sk, const void* layers_dev,
+                                  uint32_t nlayers, float* out) {
+    AnimLayerParams lp{};
+    lp.anim = anim_params(a, sk, nullptr, out);
+    lp.layers = static_cast<const uint32_t*>(layers_dev);
+    lp.nlayers = nlayers;
+    if (mk) { lp.masks = mk->d; lp.nmasks = mk->nmasks; }
+    return lp;
+}
+
+void launch_anim_layers(const mtr_anim* a, const AnimLayerParams& lp, uint32_t ninst, hipStream_t s) {
+    if (a->tracks) mtr_launch_anim_layers_tracks(lp, ninst, s);
+    else mtr_launch_anim_layers(lp, ninst, s);
+}
+
+// around a kernel on `s` that reads the clip set or the mask set: see mtr_anim::last
+template <class Set>
+int32_t anim_before(Set* a, hipStream_t s) {
     if (a->recorded && a->last_stream != s) HIPCHK(a->dev, hipStreamWaitEvent(s, a->last, 0));
     return MTR_OK;
 }
-int32_t anim_after(mtr_anim* a, hipStream_t s) {
+template <class Set>
+int32_t anim_after(Set* a, hipStream_t s) {
     HIPCHK(a->dev, hipEventRecord(a->last, s));
     a->last_stream = s; a->recorded = true;
     return MTR_OK;
@@ -157,11 +179,14 @@ int32_t batch_next_version(mtr_batch* b, uint32_t npal, int* out, hipEvent_t* fr
     return MTR_OK;
 }
 
-// Where the palettes of a pose come from: local matrices (k_pose), or animation states over a clip set (k_anim); device memory
+// Where the palettes of a pose come from: local matrices (k_pose), animation states over a clip set (k_anim), or layer
+// stacks over a clip set and an optional mask set (k_anim_layers: nlayers != 0, states holds the layers); device memory
 struct PoseSrc {
     const float* locals = nullptr;
     mtr_anim* anim = nullptr;
     const void* states = nullptr;
+    mtr_anim_masks* masks = nullptr;
+    uint32_t nlayers = 0;
     explicit operator bool() const { return locals || anim; }
 };
 
@@ -206,9 +231,12 @@ int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, 
         if (src.anim) {
             int32_t arc = anim_before(src.anim, s);
             if (arc) return arc;
-            launch_anim(src.anim, anim_params(src.anim, b->model->skel, src.states, vp), (uint32_t)n, s);
+            if (src.masks && (arc = anim_before(src.masks, s))) return arc;
+            if (src.nlayers) launch_anim_layers(src.anim, anim_layer_params(src.anim, src.masks, b->model->skel, src.states, src.nlayers, vp), (uint32_t)n, s);
+            else launch_anim(src.anim, anim_params(src.anim, b->model->skel, src.states, vp), (uint32_t)n, s);
             HIPCHK(d, hipGetLastError());
             if ((arc = anim_after(src.anim, s))) return arc;
+            if (src.masks && (arc = anim_after(src.masks, s))) return arc;
         } else if (src.locals) {
             mtr_launch_pose(pose_params(b->model->skel, src.locals, vp), (uint32_t)n, s);
             HIPCHK(d, hipGetLastError());
@@ -244,6 +272,17 @@ int32_t check_anim(mtr_device* d, const mtr_model* m, const mtr_anim* a) {
     if (a->njoints != m->skel.njoints) return fail(d, MTR_E_INVALID, "animate: the animation set's joint count is not the skeleton's");
     if (!(a->tracks ? mtr_launch_anim_tracks : mtr_launch_anim)) return fail(d, MTR_E_UNSUPPORTED, "animate: built without k_anim");
     return set_device(d);
+}
+
+// what every layered animate call checks besides check_anim
+int32_t check_anim_layers(mtr_device* d, const mtr_model* m, const mtr_anim* a, const mtr_anim_masks* mk, size_t nlayers) {
+    if (nlayers < 1 || nlayers > MTR_ANIM_MAX_LAYERS) return fail(d, MTR_E_INVALID, "animate layers: 1 to 8 layers per instance");
+    if (mk && mk->dev != d) return fail(d, MTR_E_INVALID, "animate layers: the mask set belongs to another device");
+    if (mk && mk->njoints != m->skel.njoints) return fail(d, MTR_E_INVALID, "animate layers: the mask set's joint count is not the skeleton's");
+    int32_t rc = check_anim(d, m, a);
+    if (rc) return rc;
+    if (!(a->tracks ? mtr_launch_anim_layers_tracks : mtr_launch_anim_layers)) return fail(d, MTR_E_UNSUPPORTED, "animate layers: built without k_anim_layers");
+    return MTR_OK;
 }
 
 }  // namespace
@@ -504,6 +543,119 @@ int32_t mtr_anim_sample(mtr_anim* a, const mtr_anim_state* states, size_t n, flo
         ap.pose.njoints = a->njoints;
         if (a->tracks) mtr_launch_anim_tracks_sample(ap, (uint32_t)n, d->s_copy);
         else mtr_launch_anim_sample(ap, (uint32_t)n, d->s_copy);
+        HIPCHK(d, hipGetLastError());
+        HIPCHK(d, hipMemcpyAsync(out_locals, tmp, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
+        return MTR_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(d->s_copy);  // also when a step failed: the buffer is freed next
+    (void)hipFree(tmp);
+    if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// animation layers (SPEC.md section 16)
+// ---------------------------------------------------------------------------------------------
+static_assert(sizeof(mtr_anim_layer) == 16, "mtr_anim_layer");
+
+int32_t mtr_anim_masks_create(mtr_device* d, size_t njoints, size_t nmasks, const float* weights, mtr_anim_masks** out) {
+    if (!d || !out) return MTR_E_INVALID;
+    *out = nullptr;
+    if (njoints == 0 || njoints > MTR_POSE_MAX_JOINTS) return fail(d, MTR_E_INVALID, "anim masks: 1 to 256 joints");
+    if (nmasks == 0 || nmasks > 0xFFFFu || !weights) return fail(d, MTR_E_INVALID, "anim masks: 1 to 65535 masks and their weights");
+    for (size_t m = 0; m < nmasks; m++)
+        for (size_t j = 0; j < njoints; j++) {
+            const float w = weights[m * njoints + j];
+            if (!(w >= 0.0f && w <= 1.0f))  // NaN fails both
+                return fail(d, MTR_E_INVALID, "anim masks: mask " + std::to_string(m + 1) + ", joint " + std::to_string(j) + " has a weight outside [0, 1]");
+        }
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    auto mk = std::make_unique<mtr_anim_masks>();
+    mk->dev = d; mk->njoints = (uint32_t)njoints; mk->nmasks = (uint32_t)nmasks;
+    if ((rc = dev_alloc(d, &mk->d, nmasks * njoints))) return rc;
+    hipError_t e = hipMemcpy(mk->d, weights, nmasks * njoints * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&mk->last, hipEventDisableTiming);
+    if (e != hipSuccess) { (void)hipFree(mk->d); return fail(d, MTR_E_HIP, std::string("anim masks upload: ") + hipGetErrorString(e)); }
+    *out = mk.release();
+    return MTR_OK;
+}
+
+void mtr_anim_masks_destroy(mtr_anim_masks* mk) {
+    if (!mk) return;
+    mtr_device* d = mk->dev;
+    {
+        // a kernel may still read the weights: parked behind the event of the last one, collected by a later submit
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        d->garbage.push_back({mk->d, 0, mk->last});
+    }
+    delete mk;
+}
+
+int32_t mtr_model_animate_layers(mtr_model* m, mtr_anim* a, mtr_anim_masks* mk, const mtr_anim_layer* layers, size_t nlayers) {
+    if (!m) return MTR_E_INVALID;
+    mtr_device* d = m->dev;
+    if (!layers) return fail(d, MTR_E_INVALID, "animate layers: no layers");
+    int32_t rc = check_anim_layers(d, m, a, mk, nlayers);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, reinterpret_cast<const float*>(layers), nlayers * (sizeof(mtr_anim_layer) / sizeof(float))))) return rc;
+    std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+    mtr_model::PalBuf* pb = nullptr;
+    if ((rc = next_palette_buffer(m, a->njoints, &pb))) return rc;
+    if ((rc = anim_before(a, d->s_copy))) return rc;
+    if (mk && (rc = anim_before(mk, d->s_copy))) return rc;
+    launch_anim_layers(a, anim_layer_params(a, mk, m->skel, d->pose_stage, (uint32_t)nlayers, pb->d), 1, d->s_copy);
+    HIPCHK(d, hipGetLastError());
+    if ((rc = anim_after(a, d->s_copy))) return rc;
+    if (mk && (rc = anim_after(mk, d->s_copy))) return rc;
+    HIPCHK(d, hipEventRecord(pb->ready, d->s_copy));
+    return MTR_OK;
+}
+
+int32_t mtr_batch_animate_layers(mtr_batch* b, mtr_anim* a, mtr_anim_masks* mk, const mtr_anim_layer* layers, size_t nlayers) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!layers) return fail(d, MTR_E_INVALID, "animate layers: no layers");
+    int32_t rc = check_anim_layers(d, b->model, a, mk, nlayers);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, reinterpret_cast<const float*>(layers), (size_t)b->n * nlayers * (sizeof(mtr_anim_layer) / sizeof(float))))) return rc;
+    PoseSrc src;
+    src.anim = a; src.states = d->pose_stage; src.masks = mk; src.nlayers = (uint32_t)nlayers;
+    return batch_write_version(b, nullptr, nullptr, a->njoints, src, d->s_copy);
+}
+
+int32_t mtr_batch_animate_layers_device(mtr_batch* b, mtr_anim* a, mtr_anim_masks* mk, const mtr_anim_layer* layers_dev, size_t nlayers, void* hip_stream) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!layers_dev || ((uintptr_t)layers_dev & 15u)) return fail(d, MTR_E_INVALID, "animate layers: device layers must be 16-byte aligned");
+    int32_t rc = check_anim_layers(d, b->model, a, mk, nlayers);
+    if (rc) return rc;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    PoseSrc src;
+    src.anim = a; src.states = layers_dev; src.masks = mk; src.nlayers = (uint32_t)nlayers;
+    return batch_write_version(b, nullptr, nullptr, a->njoints, src, s);
+}
+
+int32_t mtr_anim_sample_layers(mtr_anim* a, mtr_anim_masks* mk, const mtr_anim_layer* layers, size_t nlayers, size_t n, float* out_locals, size_t count) {
+    if (!a) return MTR_E_INVALID;
+    mtr_device* d = a->dev;
+    if (nlayers < 1 || nlayers > MTR_ANIM_MAX_LAYERS) return fail(d, MTR_E_INVALID, "anim sample layers: 1 to 8 layers per instance");
+    if (mk && (mk->dev != d || mk->njoints != a->njoints)) return fail(d, MTR_E_INVALID, "anim sample layers: the mask set is of another device or joint count");
+    const size_t need = n * a->njoints * 16;
+    if (n > 0xFFFFFFu || (n && (!layers || !out_locals)) || count < need)
+        return fail(d, MTR_E_INVALID, "anim sample layers: n * nlayers layers and room for n * njoints * 16 floats");
+    if (!(a->tracks ? mtr_launch_anim_layers_tracks_sample : mtr_launch_anim_layers_sample)) return fail(d, MTR_E_UNSUPPORTED, "anim sample layers: built without k_anim_layers");
+    int32_t rc = set_device(d);
+    if (rc || !n) return rc;
+    float* tmp = nullptr;  // the local matrices, then the layers (need is a multiple of 16 floats: 16-byte aligned)
+    if ((rc = dev_alloc(d, &tmp, need + n * nlayers * 4))) return rc;
+    auto run = [&]() -> int32_t {
+        HIPCHK(d, hipMemcpyAsync(tmp + need, layers, n * nlayers * sizeof(mtr_anim_layer), hipMemcpyHostToDevice, d->s_copy));
+        AnimLayerParams lp = anim_layer_params(a, mk, mtr_model::Skeleton{}, tmp + need, (uint32_t)nlayers, tmp);
+        lp.anim.pose.njoints = a->njoints;
+        if (a->tracks) mtr_launch_anim_layers_tracks_sample(lp, (uint32_t)n, d->s_copy);
+        else mtr_launch_anim_layers_sample(lp, (uint32_t)n, d->s_copy);
         HIPCHK(d, hipGetLastError());
         HIPCHK(d, hipMemcpyAsync(out_locals, tmp, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
         return MTR_OK;

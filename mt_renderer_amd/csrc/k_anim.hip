@@ -9,6 +9,11 @@
 //
 // Two sources of channel values: clips of uniformly spaced 48-byte keys (section 14), and track sets (section 15: per joint
 // and channel a track with its own key times and 16-bit keys).  Everything after "one clip's (T, Q, S)" is one copy.
+//
+// Layers (section 16): the k_anim_layers kernels evaluate a stack of up to 8 layers per instance on either source -- a
+// base clip, then per layer a clip blended over it per joint (override or additive) by its weight times a mask weight.
+// The scalar blend rules of both sections live in anim_blend.h.
+#include "anim_blend.h"
 #include "anim_tracks.h"
 #include "pose_common.h"
 
@@ -40,39 +45,10 @@ __device__ __forceinline__ AnimPos anim_position(float x, uint32_t nkeys, uint32
     return r;
 }
 
-__device__ __forceinline__ float anim_lerp(float v0, float v1, float a) { return v0 + a * (v1 - v0); }
-
-__device__ __forceinline__ float4 anim_lerp4(const float4& v0, const float4& v1, float a) {
-    return make_float4(anim_lerp(v0.x, v1.x, a), anim_lerp(v0.y, v1.y, a), anim_lerp(v0.z, v1.z, a), anim_lerp(v0.w, v1.w, a));
-}
-
-__device__ __forceinline__ float anim_dot(const float4& p, const float4& q) { return ((p.x * q.x + p.y * q.y) + p.z * q.z) + p.w * q.w; }
-
-__device__ __forceinline__ float4 anim_nlerp(const float4& q0, float4 q1, float a) {
-    if (anim_dot(q0, q1) < 0.0f) q1 = make_float4(-q1.x, -q1.y, -q1.z, -q1.w);  // the shortest path; NaN compares false
-    const float4 q = anim_lerp4(q0, q1, a);
-    const float n2 = anim_dot(q, q);
-    const float rn = 1.0f / sqrtf(n2);
-    if (n2 == 0.0f || !(fabsf(rn) <= 3.402823466e38f)) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-    return make_float4(q.x * rn, q.y * rn, q.z * rn, q.w * rn);
-}
-
-struct AnimKey {
-    float4 t, q, s;
-};
-
 __device__ __forceinline__ AnimKey anim_load_key(const float4* keys, uint32_t key, uint32_t J, uint32_t j) {
     const float4* k = keys + ((size_t)key * J + j) * 3;
     AnimKey r;
     r.t = k[0]; r.q = k[1]; r.s = k[2];
-    return r;
-}
-
-__device__ __forceinline__ AnimKey anim_mix(const AnimKey& k0, const AnimKey& k1, float a) {
-    AnimKey r;
-    r.t = anim_lerp4(k0.t, k1.t, a);
-    r.q = anim_nlerp(k0.q, k1.q, a);
-    r.s = anim_lerp4(k0.s, k1.s, a);
     return r;
 }
 
@@ -159,15 +135,25 @@ __device__ __forceinline__ void track_sample(const AnimParams& p, TrackClip (&c)
     }
 }
 
+// (T, Q, S) -> the local matrix (column-major)
+__device__ __forceinline__ void anim_matrix(const AnimKey& r, float4 (&M)[4]) {
+    const float x = r.q.x, y = r.q.y, z = r.q.z, qw = r.q.w;
+    const float x2 = x + x, y2 = y + y, z2 = z + z;
+    const float xx = x * x2, yy = y * y2, zz = z * z2, xy = x * y2, xz = x * z2, yz = y * z2;
+    const float wx = qw * x2, wy = qw * y2, wz = qw * z2;
+    M[0] = make_float4((1.0f - (yy + zz)) * r.s.x, (xy + wz) * r.s.x, (xz - wy) * r.s.x, 0.0f);
+    M[1] = make_float4((xy - wz) * r.s.y, (1.0f - (xx + zz)) * r.s.y, (yz + wx) * r.s.y, 0.0f);
+    M[2] = make_float4((xz + wy) * r.s.z, (yz - wx) * r.s.z, (1.0f - (xx + yy)) * r.s.z, 0.0f);
+    M[3] = make_float4(r.t.x, r.t.y, r.t.z, 1.0f);
+}
+
 // The local matrix of joint j of instance inst (column-major); TRACKS: the set is a track set
 template <bool TRACKS>
 __device__ __forceinline__ void anim_local(const AnimParams& p, uint32_t inst, uint32_t j, float4 (&M)[4]) {
     const uint32_t J = p.pose.njoints;
     const uint2* st = reinterpret_cast<const uint2*>(p.states + (size_t)inst * 6);
     const uint2 sc = st[0], sx = st[1], sw = st[2];
-    float w = __uint_as_float(sw.x);
-    w = w > 0.0f ? w : 0.0f;  // NaN -> 0
-    w = w > 1.0f ? 1.0f : w;
+    const float w = anim_weight(__uint_as_float(sw.x));
     AnimKey r;
     if constexpr (TRACKS) {
         if (w == 0.0f) {  // clip B is not read
@@ -200,41 +186,127 @@ __device__ __forceinline__ void anim_local(const AnimParams& p, uint32_t inst, u
             r = anim_mix(anim_mix(a0, a1, pa.a), anim_mix(b0, b1, pb.a), w);
         }
     }
-    const float x = r.q.x, y = r.q.y, z = r.q.z, qw = r.q.w;
-    const float x2 = x + x, y2 = y + y, z2 = z + z;
-    const float xx = x * x2, yy = y * y2, zz = z * z2, xy = x * y2, xz = x * z2, yz = y * z2;
-    const float wx = qw * x2, wy = qw * y2, wz = qw * z2;
-    M[0] = make_float4((1.0f - (yy + zz)) * r.s.x, (xy + wz) * r.s.x, (xz - wy) * r.s.x, 0.0f);
-    M[1] = make_float4((xy - wz) * r.s.y, (1.0f - (xx + zz)) * r.s.y, (yz + wx) * r.s.y, 0.0f);
-    M[2] = make_float4((xz + wy) * r.s.z, (yz - wx) * r.s.z, (1.0f - (xx + yy)) * r.s.z, 0.0f);
-    M[3] = make_float4(r.t.x, r.t.y, r.t.z, 1.0f);
+    anim_matrix(r, M);
+}
+
+// ---- layers (section 16) ----
+// What one thread holds of one layer between the issue of its loads and its blend: the layer's weight and mode, the
+// joint's mask weight and the source's values -- both keys of the joint and their fraction (uniform keys), or the sampled
+// (T, Q, S) in k0 (tracks).  Two of these are live at a time, in named registers: the layer being blended and the next
+// one, whose loads are in flight.
+struct LayerFetch {
+    float w, m;  // the weight as stored and the mask weight: e = anim_layer_weight(w, m), formed when the layer is blended
+    uint32_t mode;
+    AnimKey k0, k1;
+    float a;
+};
+
+// Issues the loads of layer l of instance inst for joint j.  The 16-byte record, the clip table entry and the position
+// are the same for the whole workgroup (scalar loads and arithmetic); the mask weight and the keys are per lane.  A
+// layer whose clamped weight is 0 returns before any further load for the whole workgroup (m = 0 stands for e = 0).
+// The base (l == 0) reads its clip and x only.
+//
+// Memory safety, extending the argument at track_clip_begin: nlayers is a host value validated to 1..8 and the layer
+// array holds ninst * nlayers records, so inst * nlayers + l lies inside it.  From a record come (a) the clip index,
+// clamped to nclips - 1, (b) the position x, which anim_position / track_position turn into key indices inside the
+// clip for every x, (c) the mask index, clamped to nmasks -- 0 without a mask set, and index 0 reads nothing -- so that
+// (mask - 1) * J + j lies inside the nmasks * J weights because j < J, and (d) the weight and the mode, which reach no
+// address.  No device-side value forms an address unclamped.
+template <bool TRACKS>
+__device__ __forceinline__ LayerFetch anim_layer_fetch(const AnimLayerParams& p, uint32_t inst, uint32_t l, uint32_t j) {
+    const AnimParams& ap = p.anim;
+    const uint32_t J = ap.pose.njoints;
+    const uint4 rec = reinterpret_cast<const uint4*>(p.layers)[(size_t)inst * p.nlayers + l];  // clip, x, w, mask | mode << 16
+    LayerFetch f;  // the keys stay unset where no load is issued: they are read only where e != 0 (a zero fill would be merged
+                   // with the loaded registers by copies that wait for the loads, ahead of the previous layer's arithmetic)
+    f.mode = rec.w >> 16;
+    f.w = __uint_as_float(rec.z);
+    f.m = 0.0f;
+    if (l != 0u) {
+        if (anim_weight(f.w) == 0.0f) return f;
+        uint32_t mask = rec.w & 0xFFFFu;
+        mask = mask < p.nmasks ? mask : p.nmasks;
+        f.m = mask ? p.masks[(size_t)(mask - 1u) * J + j] : 1.0f;
+        // Tracks: a lane whose e is 0 takes no part in the searches.  Uniform keys: every lane issues the key loads at once
+        // with the mask weight's, without waiting for it (one memory latency less per layer on a chain of dependent
+        // layers); a lane whose e turns out 0 leaves what it loaded unused.
+        if constexpr (TRACKS) {
+            if (anim_layer_weight(f.w, f.m) == 0.0f) return f;
+        }
+    }
+    if constexpr (TRACKS) {
+        TrackClip c[1];
+        AnimKey v[1];
+        track_clip_begin(ap, rec.x, __uint_as_float(rec.y), j, c[0]);
+        track_sample<1>(ap, c, v);
+        f.k0 = v[0];
+    } else {
+        const float4* keys = reinterpret_cast<const float4*>(ap.keys);
+        const uint4 ct = reinterpret_cast<const uint4*>(ap.clips)[rec.x < ap.nclips ? rec.x : ap.nclips - 1u];
+        const AnimPos pos = anim_position(__uint_as_float(rec.y), ct.y, ct.z);
+        f.k0 = anim_load_key(keys, ct.x + pos.i0, J, j);
+        f.k1 = anim_load_key(keys, ct.x + pos.i1, J, j);
+        f.a = pos.a;
+    }
+    return f;
 }
 
 template <bool TRACKS>
-__device__ __forceinline__ void anim_palettes(const AnimParams& p) {
+__device__ __forceinline__ AnimKey anim_layer_value(const LayerFetch& f) {
+    if constexpr (TRACKS) return f.k0;
+    else return anim_mix(f.k0, f.k1, f.a);
+}
+
+// The local matrix of joint j of instance inst from its layer stack: layer l + 1's loads are issued before layer l's
+// blend arithmetic
+template <bool TRACKS>
+__device__ __forceinline__ void anim_local(const AnimLayerParams& p, uint32_t inst, uint32_t j, float4 (&M)[4]) {
+    const uint32_t L = p.nlayers;
+    LayerFetch cu, nx = anim_layer_fetch<TRACKS>(p, inst, 0u, j);
+    AnimKey r = {};
+    for (uint32_t l = 0u; l < L; l++) {
+        cu = nx;
+        if (l + 1u < L) nx = anim_layer_fetch<TRACKS>(p, inst, l + 1u, j);
+        if (l == 0u) {
+            r = anim_layer_value<TRACKS>(cu);
+        } else {
+            const float e = anim_layer_weight(cu.w, cu.m);
+            if (e != 0.0f) r = anim_layer_step(r, anim_layer_value<TRACKS>(cu), e, cu.mode);  // e == 0: untouched, bit for bit
+        }
+    }
+    anim_matrix(r, M);
+}
+
+__device__ __forceinline__ const PoseParams& anim_pose(const AnimParams& p) { return p.pose; }
+__device__ __forceinline__ const PoseParams& anim_pose(const AnimLayerParams& p) { return p.anim.pose; }
+
+template <bool TRACKS, class P>
+__device__ __forceinline__ void anim_palettes(const P& p) {
+    const PoseParams& pose = anim_pose(p);
     __shared__ float4 loc[MTR_POSE_MAX_JOINTS * 4];
     extern __shared__ uint32_t path_lds[];  // p.pose.path_bytes / 4 words
-    const uint32_t inst = blockIdx.x, t = threadIdx.x, J = p.pose.njoints;
+    const uint32_t inst = blockIdx.x, t = threadIdx.x, J = pose.njoints;
     if (t < J) {
         float4 M[4];
         anim_local<TRACKS>(p, inst, t, M);
 #pragma unroll
         for (int c = 0; c < 4; c++) loc[t * 4 + c] = M[c];
     }
-    for (uint32_t i = t; i < p.pose.path_bytes / 4; i += blockDim.x) path_lds[i] = p.pose.path_words[i];
+    for (uint32_t i = t; i < pose.path_bytes / 4; i += blockDim.x) path_lds[i] = pose.path_words[i];
     __syncthreads();
     if (t >= J) return;
-    pose_fold_store(p.pose, loc, path_lds, inst, t);
+    pose_fold_store(pose, loc, path_lds, inst, t);
 }
 
 // the local matrices themselves (mtr_anim_sample): the same sampling function, stored instead of folded
-template <bool TRACKS>
-__device__ __forceinline__ void anim_locals(const AnimParams& p) {
-    const uint32_t inst = blockIdx.x, t = threadIdx.x, J = p.pose.njoints;
+template <bool TRACKS, class P>
+__device__ __forceinline__ void anim_locals(const P& p) {
+    const PoseParams& pose = anim_pose(p);
+    const uint32_t inst = blockIdx.x, t = threadIdx.x, J = pose.njoints;
     if (t >= J) return;
     float4 M[4];
     anim_local<TRACKS>(p, inst, t, M);
-    float4* out = reinterpret_cast<float4*>(p.pose.out + ((size_t)inst * J + t) * 16);
+    float4* out = reinterpret_cast<float4*>(pose.out + ((size_t)inst * J + t) * 16);
 #pragma unroll
     for (int c = 0; c < 4; c++) out[c] = M[c];
 }
@@ -243,6 +315,10 @@ __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim(AnimParams p) { an
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_sample(AnimParams p) { anim_locals<false>(p); }
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_tracks(AnimParams p) { anim_palettes<true>(p); }
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_tracks_sample(AnimParams p) { anim_locals<true>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_layers(AnimLayerParams p) { anim_palettes<false>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_layers_sample(AnimLayerParams p) { anim_locals<false>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_layers_tracks(AnimLayerParams p) { anim_palettes<true>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_layers_tracks_sample(AnimLayerParams p) { anim_locals<true>(p); }
 
 }  // namespace mtr
 
@@ -272,4 +348,33 @@ void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStrea
     if (!anim_launchable(p, ninst) || !p.tracks) return;
     const uint32_t threads = (p.pose.njoints + 63u) & ~63u;
     hipLaunchKernelGGL(mtr::k_anim_tracks_sample, dim3(ninst), dim3(threads), 0, s, p);
+}
+
+static bool anim_layers_launchable(const AnimLayerParams& p, uint32_t ninst, bool tracks) {
+    return anim_launchable(p.anim, ninst) && p.layers && p.nlayers >= 1u && p.nlayers <= MTR_ANIM_MAX_LAYERS && (p.nmasks == 0u || p.masks) &&
+           (tracks ? p.anim.tracks != nullptr : p.anim.keys != nullptr);
+}
+
+void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_layers_launchable(p, ninst, false) || p.anim.pose.path_bytes > MTR_POSE_MAX_PATH_BYTES) return;
+    const uint32_t threads = (p.anim.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_layers, dim3(ninst), dim3(threads), p.anim.pose.path_bytes, s, p);
+}
+
+void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_layers_launchable(p, ninst, false)) return;
+    const uint32_t threads = (p.anim.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_layers_sample, dim3(ninst), dim3(threads), 0, s, p);
+}
+
+void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_layers_launchable(p, ninst, true) || p.anim.pose.path_bytes > MTR_POSE_MAX_PATH_BYTES) return;
+    const uint32_t threads = (p.anim.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_layers_tracks, dim3(ninst), dim3(threads), p.anim.pose.path_bytes, s, p);
+}
+
+void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_layers_launchable(p, ninst, true)) return;
+    const uint32_t threads = (p.anim.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_layers_tracks_sample, dim3(ninst), dim3(threads), 0, s, p);
 }

@@ -490,3 +490,16 @@ void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t s);
+// animation layers (k_anim.hip, SPEC.md section 16): per instance nlayers records over the same set; AnimParams::states unused
+#define MTR_ANIM_MAX_LAYERS 8
+struct AnimLayerParams {
+    AnimParams anim;
+    const uint32_t* layers;     // ninst x nlayers x 4 words: clip, x, w (f32 bits), mask | mode << 16; 16-byte aligned
+    const float* masks;         // nmasks x njoints weights of the user's masks 1..nmasks (index 0 is built in: no memory), or nullptr
+    uint32_t nlayers;           // 1..MTR_ANIM_MAX_LAYERS, a validated host value
+    uint32_t nmasks;            // 0 without a mask set
+};
+void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);

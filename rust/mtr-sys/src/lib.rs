@@ -70,7 +70,7 @@ pub const MTR_OWN_SUPERTILES: u32 = 2;
 pub const MTR_TEXRES_DECODED: u32 = 0;
 pub const MTR_TEXRES_BLOCKS: u32 = 1;
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim);
+opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks);
 
 /// animation clips (mtr.h, SPEC.md section 14): one key of one joint, 48 bytes
 pub const MTR_CLIP_LOOP: u32 = 1;
@@ -93,6 +93,19 @@ pub struct mtr_anim_track {
     pub step: [f32; 3],
 }
 
+/// animation layers (mtr.h, SPEC.md section 16): one layer of one instance, 16 bytes
+pub const MTR_ANIM_MAX_LAYERS: usize = 8;
+pub const MTR_LAYER_OVERRIDE: u16 = 0;
+pub const MTR_LAYER_ADDITIVE: u16 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_anim_layer {
+    pub clip: u32,
+    pub x: f32,
+    pub w: f32,
+    pub mask: u16,
+    pub mode: u16,
+}
 /// what one instance plays: clip A at x_a cross-faded by w with clip B at x_b, positions in keys; 24 bytes
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -195,5 +208,16 @@ extern "C" {
     pub fn mtr_anim_create_tracks(dev: *mut mtr_device, njoints: usize, nclips: usize, nticks: *const u32, flags: *const u32,
                                   tracks: *const mtr_anim_track, times: *const u16, values: *const u16, nkeys_total: usize,
                                   out: *mut *mut mtr_anim) -> i32;
+    // animation layers (SPEC.md section 16): declarations only
+    pub fn mtr_anim_masks_create(dev: *mut mtr_device, njoints: usize, nmasks: usize, weights: *const f32, out: *mut *mut mtr_anim_masks) -> i32;
+    pub fn mtr_anim_masks_destroy(masks: *mut mtr_anim_masks);
+    pub fn mtr_model_animate_layers(model: *mut mtr_model, anim: *mut mtr_anim, masks: *mut mtr_anim_masks, layers: *const mtr_anim_layer,
+                                    nlayers: usize) -> i32;
+    pub fn mtr_batch_animate_layers(batch: *mut mtr_batch, anim: *mut mtr_anim, masks: *mut mtr_anim_masks, layers: *const mtr_anim_layer,
+                                    nlayers: usize) -> i32;
+    pub fn mtr_batch_animate_layers_device(batch: *mut mtr_batch, anim: *mut mtr_anim, masks: *mut mtr_anim_masks,
+                                           layers_dev: *const mtr_anim_layer, nlayers: usize, hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_sample_layers(anim: *mut mtr_anim, masks: *mut mtr_anim_masks, layers: *const mtr_anim_layer, nlayers: usize, n: usize,
+                                  out_locals: *mut f32, count: usize) -> i32;
 }
 pub mod files;

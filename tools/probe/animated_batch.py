@@ -7,14 +7,18 @@ Extra modes: device_side_stream (device poses from a non-default torch stream), 
 anim (host animation states before every frame: Batch.animate(numpy), 24 bytes per instance + k_anim on the copy stream),
 anim_device (states in a torch tensor: k_anim on torch's current stream), anim_only (device states, no frames); tracks,
 tracks_device, tracks_only: the same three from a track set (SPEC.md section 15) that mt_renderer_amd.anim_tracks.compress
-made of the same clips (--tol: its three tolerances; the encoded and the uniform size are printed and recorded).  The clip
+made of the same clips (--tol: its three tolerances; the encoded and the uniform size are printed and recorded).
+Layers (SPEC.md section 16): layers2 (Batch.animate_layers(numpy) with two OVERRIDE layers on mask 0 that say what anim's
+states say: the same two clips, positions and weight), layers2_tracks (the same over the track set), layers2_device (the
+layers in a torch tensor), layers4 (two more layers on top: a masked OVERRIDE and an ADDITIVE layer of a delta clip that
+anim_layers.delta_clip made), layers2_only / layers4_only (device layers, no frames: k_anim_layers alone).  The clip
 set (four clips of 120 / 60 / 31 / 2 keys, small bends about z) and the states are generated from --seed.
     python tools/probe/animated_batch.py [--only c3|c5] [--frames N] [--reps R] [--modes static,host,anim] [--seed S] [--json OUT]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 import torch
-from mt_renderer_amd import anim_tracks, api, scene
+from mt_renderer_amd import anim_layers, anim_tracks, api, scene
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--only", default="")
@@ -61,6 +65,20 @@ def states(rng, n, k):
     return st
 
 
+def layers(st, L, rng):
+    """layer stacks [k, n, L] that say what the states say with their first two layers (OVERRIDE, mask 0); for L = 4 a masked
+    OVERRIDE of another clip and an ADDITIVE layer of the delta clip (clip 4) on top"""
+    ly = np.zeros(st.shape + (L,), dtype=api.ANIM_LAYER)
+    ly["clip"][..., 0], ly["x"][..., 0] = st["clip_a"], st["x_a"]
+    ly["clip"][..., 1], ly["x"][..., 1], ly["w"][..., 1] = st["clip_b"], st["x_b"], st["w"]
+    if L == 4:
+        ly["clip"][..., 2], ly["x"][..., 2] = rng.integers(0, 4, st.shape), rng.uniform(0, 240, st.shape)
+        ly["w"][..., 2], ly["mask"][..., 2] = rng.uniform(0.2, 1, st.shape), 1
+        ly["clip"][..., 3], ly["x"][..., 3] = 4, rng.uniform(0, 30, st.shape)
+        ly["w"][..., 3], ly["mask"][..., 3], ly["mode"][..., 3] = rng.uniform(0.2, 1, st.shape), 2, api.LAYER_ADDITIVE
+    return ly
+
+
 dev = api.Device(0)
 results = []
 for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)):
@@ -77,8 +95,9 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
     devp = [torch.tensor(p, device="cuda:0") for p in host]
     uniform_clips = clips(rng)
     anim = api.Anim(dev, 64, uniform_clips)
+    with_layers = any(m.startswith("layers") for m in modes)
     sizes = None
-    if any(m.startswith("tracks") for m in modes):
+    if any(m.startswith("tracks") or m == "layers2_tracks" for m in modes):
         track_clips = [anim_tracks.compress(k, fl, args.tol, args.tol, args.tol) for k, fl in uniform_clips]
         tracks = api.AnimTracks(dev, 64, track_clips)
         sizes = dict(uniform_bytes=sum(anim_tracks.uniform_bytes(k.shape[0], 64) for k, _ in uniform_clips),
@@ -86,6 +105,14 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
         print(json.dumps(dict(config=name, clip_set=sizes)), flush=True)
     host_st = states(rng, n, 8)
     dev_st = [torch.from_numpy(s.view(np.uint8).reshape(n, 24).copy()).to("cuda:0") for s in host_st]
+    if with_layers:  # after everything the other modes draw from rng: their inputs stay what they were
+        layer_clips = uniform_clips + [(anim_layers.delta_clip(uniform_clips[2][0], uniform_clips[0][0][0]), 0)]
+        lanim = api.Anim(dev, 64, layer_clips)
+        mw = np.zeros((2, 64), dtype=np.float32)
+        mw[0, 32:], mw[1] = np.linspace(0.0, 1.0, 32), rng.uniform(0.0, 1.0, 64)
+        lmasks = api.AnimMasks(dev, 64, mw)
+        host_ly = {L: layers(host_st, L, rng) for L in (2, 4)}
+        dev_ly = {L: [torch.from_numpy(x.view(np.uint8).reshape(n, L * 16).copy()).to("cuda:0") for x in host_ly[L]] for L in (2, 4)}
     loop = api.FrameLoop(dev, W, H, batch=batch, view_proj=scene.to_f32_colmajor(scene.reference_view_proj(W, H)))
 
     side = torch.cuda.Stream()
@@ -112,6 +139,15 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
                 batch.animate(tracks, dev_st[k % 8])
             elif mode == "tracks_only":  # device states and no frames: k_anim_tracks alone on the GPU
                 batch.animate(tracks, dev_st[k % 8])
+                continue
+            elif mode in ("layers2", "layers4"):
+                batch.animate_layers(lanim, host_ly[int(mode[6])][k % 8], lmasks)
+            elif mode == "layers2_tracks":
+                batch.animate_layers(tracks, host_ly[2][k % 8], lmasks)
+            elif mode == "layers2_device":
+                batch.animate_layers(lanim, dev_ly[2][k % 8], lmasks)
+            elif mode in ("layers2_only", "layers4_only"):  # device layers and no frames: k_anim_layers alone on the GPU
+                batch.animate_layers(lanim, dev_ly[int(mode[6])][k % 8], lmasks)
                 continue
             elif mode == "poses_only":  # device poses and no frames: k_pose alone on the GPU
                 batch.set_poses(devp[k % 8])
@@ -140,6 +176,9 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
         print(json.dumps(r), flush=True)
     batch.close()
     anim.close()
+    if with_layers:
+        lmasks.close()
+        lanim.close()
     if sizes:
         tracks.close()
     model.close()
