@@ -20,6 +20,17 @@ static uint32_t g_flag_once = 0;         // overflow flags the next tile launch 
 static uint32_t g_measured[2] = {0, 0};  // what that launch leaves in CTR_ENTRIES / CTR_SEGS (flag 2: "what the scan measured")
 static std::vector<FrameBuffers> g_geom_fb;  // FrameBuffers of every geometry launch since the last clear
 static uint32_t g_vis_waves = ~0u;       // TileParams::vis_waves of the last tile launch (remembered, not logged)
+// A draw's share of the slot's four culling buffers, as element offsets from the slot's buffer (remembered, not logged): one
+// entry per k_cull_chunks launch = per draw of a culled frame, checked against the k_cull_instances launch in front of it and
+// the geometry launch behind it.  -1: the launch was handed a null pointer.
+struct DrawRanges { uint32_t nx, ninst; long work, list, strad, comp, count; };
+static std::vector<DrawRanges> g_ranges;
+static const CullParams* g_cull_inst = nullptr;  // the k_cull_instances launch the next k_cull_chunks launch belongs to
+static CullParams g_cull_inst_copy;
+static int g_range_mismatch = 0;                 // launches of one draw that were handed different ranges
+static bool g_remember = false;                  // inside logged(): g_frame is the frame being submitted
+template <class T>
+static long off_in(const T* p, const T* base) { return p ? (long)(p - base) : -1; }
 
 static std::string S(const char* fmt, ...) {
     char buf[512];
@@ -46,6 +57,11 @@ static void need_fb(const FrameBuffers& fb, const char* who) {
 void mtr_launch_geom(const GeomParams& p, hipStream_t) {
     need_fb(p.fb, "geom"); need(p.mats, "geom", "mats");
     g_geom_fb.push_back(p.fb);
+    if (p.work_mask && g_remember) {  // the masks, the list and the counters k_cull_chunks wrote for this draw
+        const Slot& sl = g_frame->dev->slots[g_frame->slot];
+        if (g_ranges.empty() || g_ranges.back().work != off_in(p.work_mask, sl.work_mask) || g_ranges.back().list != off_in(p.inst_list, sl.inst_list) ||
+            g_ranges.back().count != off_in(p.inst_count, sl.inst_count) || g_ranges.back().nx != p.work_nx) g_range_mismatch++;
+    }
     g_log.push_back(S("geom nchunks=%u ninst=%u chunk_base=%u mat_base=%u small_draw=%u work_mask=%d inst_list=%d direct=%u unordered=%u "
                       "own={map=%u rank=%u world=%u cull=%u own_count=%u}", p.nchunks, p.ninst, p.chunk_base, p.mat_base, p.small_draw,
                       p.work_mask != nullptr, p.inst_list != nullptr, p.fb.direct, p.fb.unordered, p.fb.own.map, p.fb.own.rank, p.fb.own.world,
@@ -77,11 +93,22 @@ void mtr_launch_cull_instances(const CullParams& p, hipStream_t) {
     need(p.boxes, "cull_instances", "boxes"); need(p.list, "cull_instances", "list"); need(p.count, "cull_instances", "count");
     need(p.comp, "cull_instances", "comp"); need(p.work_mask, "cull_instances", "work_mask"); need(p.strad, "cull_instances", "strad");
     need(p.counters, "cull_instances", "counters");
+    g_cull_inst_copy = p; g_cull_inst = &g_cull_inst_copy;
     g_log.push_back(S("cull_instances ninst=%u", p.ninst));
 }
 void mtr_launch_cull_chunks(const ChunkCullParams& p, hipStream_t) {
     need_fb(p.fb, "cull_chunks"); need(p.work_mask, "cull_chunks", "work_mask");
     g_log.push_back(S("cull_chunks keep_all=%u inst_count=%d comp=%d", p.keep_all, p.inst_count != nullptr, p.comp != nullptr));
+    if (!g_remember) return;
+    const Slot& sl = g_frame->dev->slots[g_frame->slot];
+    g_ranges.push_back(DrawRanges{(p.nchunks + 15u) / 16u, p.ninst, off_in(p.work_mask, sl.work_mask), off_in(p.inst_list, sl.inst_list),
+                                  off_in(p.strad, sl.inst_list), off_in(p.comp, sl.comp), off_in(p.inst_count, sl.inst_count)});
+    if (p.inst_count) {  // k_cull_instances wrote what this launch reads
+        const CullParams* ci = g_cull_inst;
+        if (!ci || ci->work_mask != p.work_mask || ci->list != p.inst_list || ci->strad != p.strad || ci->comp != p.comp || ci->count != p.inst_count ||
+            ci->ninst != p.ninst || ci->nchunks != p.nchunks) g_range_mismatch++;
+    } else if (g_cull_inst) g_range_mismatch++;
+    g_cull_inst = nullptr;
 }
 
 // ---- the trace hook: streams, events and buffers by name ----
@@ -173,10 +200,10 @@ struct Scene {  // one device with a single slot (every frame then runs on slot0
 
 template <class F>
 static Log logged(mtr_frame* f, int32_t* rc, F call) {
-    g_frame = f; g_log.clear(); g_geom_fb.clear();
-    hipStubTrace() = trace;
+    g_frame = f; g_log.clear(); g_geom_fb.clear(); g_ranges.clear(); g_cull_inst = nullptr; g_range_mismatch = 0;
+    hipStubTrace() = trace; g_remember = true;
     *rc = call(f);
-    hipStubTrace() = nullptr;
+    hipStubTrace() = nullptr; g_remember = false;
     return g_log;
 }
 static Log submit(mtr_frame* f, int32_t want = MTR_OK) {
@@ -570,6 +597,171 @@ static int scenario_10_nomem() {
     return (first.empty() && grown.empty() && !g_failed) ? 0 : 1;
 }
 
+// ---- 13 - 17: frames of several draws (one slot, 64 x 64, rank 0 of 2 under bands) ----
+// A draw of these scenarios: a model of `prims` one-triangle primitives (one chunk each), drawn alone (ninst 0) or as a
+// persistent batch of three instances.  What the host must hand each launch follows from the draw list alone: chunk_base and
+// mat_base are running sums, every batch draw gets an instance list, the first four of them report a launch hint.
+struct DrawSpec { uint32_t prims, ninst; };
+static Log draw_kernels(const std::vector<DrawSpec>& draws, const char* own, uint32_t unordered) {
+    Log l;
+    uint32_t chunk_base = 0, mat_base = 0;
+    for (const DrawSpec& d : draws) {
+        const uint32_t n = d.ninst ? d.ninst : 1u;
+        if (d.ninst) { l.push_back("hipStreamWaitEvent pal_ready slot0"); l.push_back(S("cull_instances ninst=%u", n)); }
+        l.push_back(S("cull_chunks keep_all=0 inst_count=%d comp=%d", d.ninst != 0, d.ninst != 0));
+        l.push_back(S("geom nchunks=%u ninst=%u chunk_base=%u mat_base=%u small_draw=1 work_mask=1 inst_list=%d direct=1 unordered=%u %s", d.prims, n,
+                      chunk_base, mat_base, d.ninst != 0, unordered, own));
+        chunk_base += d.prims * n; mat_base += d.prims;
+    }
+    return l;
+}
+static std::string tile_line(const char* name, uint32_t mixed, uint32_t nhint, size_t ndraws) {
+    return S("%s mixed=%u nhint=%u zero_words=1 zero_nwords=%zu hint_out=1 zero_next=1 xcd_run=0 textured=0", name, mixed, nhint, ndraws * MTR_CULL_CTR_WORDS);
+}
+static std::string zero_cull_counters(size_t draw_cap) { return S("hipMemsetAsync cull_counters %zu slot0", draw_cap * MTR_CULL_CTR_WORDS * sizeof(uint32_t)); }
+
+// the ranges the launches of the frame just submitted were handed (g_ranges): no two draws share an element
+static void check_ranges(const char* what, const std::vector<DrawSpec>& draws) {
+    bool ok = g_ranges.size() == draws.size() && g_range_mismatch == 0;
+    uint64_t ninst_total = 0;
+    for (const DrawSpec& d : draws) ninst_total += d.ninst;
+    for (size_t i = 0; ok && i < draws.size(); i++) {
+        const DrawRanges& a = g_ranges[i];
+        const uint32_t n = draws[i].ninst ? draws[i].ninst : 1u;
+        ok = ok && a.ninst == n && a.nx == (draws[i].prims + 15u) / 16u;
+        ok = ok && a.work >= 0 && a.work % 2 == 0;  // k_geom reads a 16-bit mask through the aligned dword that holds it
+        if (!draws[i].ninst) { ok = ok && a.list == -1 && a.strad == -1 && a.comp == -1 && a.count == -1; continue; }
+        ok = ok && a.list >= 0 && a.strad >= 0 && a.comp >= 0 && a.count == (long)(i * MTR_CULL_CTR_WORDS);
+        ok = ok && (uint64_t)a.list + n <= ninst_total && (uint64_t)a.strad >= ninst_total;  // lists in front, straddler lists behind all of them
+    }
+    auto disjoint = [](long a, long an, long b, long bn) { return a + an <= b || b + bn <= a; };
+    for (size_t i = 0; ok && i < draws.size(); i++)
+        for (size_t j = i + 1; ok && j < draws.size(); j++) {
+            const DrawRanges &a = g_ranges[i], &b = g_ranges[j];
+            ok = ok && disjoint(a.work, (long)a.nx * a.ninst, b.work, (long)b.nx * b.ninst);
+            if (a.list < 0 || b.list < 0) continue;
+            ok = ok && disjoint(a.list, a.ninst, b.list, b.ninst) && disjoint(a.strad, a.ninst, b.strad, b.ninst);
+            ok = ok && disjoint(a.list, a.ninst, b.strad, b.ninst) && disjoint(a.strad, a.ninst, b.list, b.ninst);
+            ok = ok && disjoint(a.comp, a.ninst, b.comp, b.ninst);  // unskinned: one composite per instance
+        }
+    if (ok) return;
+    g_failed++;
+    fprintf(stderr, "---- %s: the draws' shares of the culling buffers (%d launches of one draw disagree) ----\n", what, g_range_mismatch);
+    for (const DrawRanges& a : g_ranges)
+        fprintf(stderr, "  nx=%u ninst=%u work_mask=%ld inst_list=%ld strad=%ld comp=%ld inst_count=%ld\n", a.nx, a.ninst, a.work, a.list, a.strad, a.comp, a.count);
+}
+
+struct ManyDraws : Scene {  // the models and batches of scenarios 13 - 17
+    mtr_model *m1, *m2;
+    mtr_batch *a, *b;
+    ManyDraws() { m1 = model(1); m2 = model(2); a = batch3(m1); b = batch3(m2); }
+    // model m1, batch a, model m2, batch b, batch a again, model m1: chunks 1 + 3 + 2 + 6 + 3 + 1, materials 1 + 1 + 2 + 2 + 1 + 1
+    std::vector<DrawSpec> six() const { return {{1, 0}, {1, 3}, {2, 0}, {2, 3}, {1, 3}, {1, 0}}; }
+    std::vector<DrawSpec> two() const { return {{1, 0}, {1, 3}}; }
+    mtr_frame* sharded(const std::vector<DrawSpec>& draws, const uint32_t* bands = nullptr) {
+        mtr_frame* f = frame();
+        MUST(mtr_frame_set_shard_map(f, 0, 2, MTR_OWN_BANDS, 0, bands));
+        for (const DrawSpec& d : draws) {
+            if (!d.ninst) MUST(mtr_frame_draw_model(f, d.prims == 1 ? m1 : m2, kI));
+            else MUST(mtr_frame_draw_batch(f, d.prims == 1 ? a : b, kI));
+        }
+        return f;
+    }
+};
+
+static void scenario_13_six_draws() {
+    // single models and batches in turn: the counter buffer grows past its four lines and is cleared at that size; chunk_base
+    // and mat_base run over the draws; the tile kernel clears six lines and reports the three batch draws
+    ManyDraws s;
+    const std::vector<DrawSpec> six = s.six();
+    mtr_frame* f = s.sharded(six);
+    expect("13: six draws", submit(f), kGrowSlot + Log{upload_mats(8), kZeroCounters, kZeroBinFill} + kGrowCull + Log{zero_cull_counters(6)} +
+           draw_kernels(six, OWN_BAND0, 1) + Log{tile_line("tile_vis", 0, 3, 6)} + kFinish);
+    check_ranges("13: six draws", six);
+    MUST(mtr_frame_wait(f));
+}
+
+static void scenario_14_five_batches() {
+    // a frame reports at most four launch hints: the fifth batch draw sizes its launches from what its slot last held
+    Scene s;
+    mtr_model* m = s.model(1);
+    mtr_frame* f = s.frame();
+    MUST(mtr_frame_set_shard_map(f, 0, 2, MTR_OWN_BANDS, 0, nullptr));
+    std::vector<DrawSpec> five(5, DrawSpec{1, 3});
+    for (int i = 0; i < 5; i++) MUST(mtr_frame_draw_batch(f, s.batch3(m), kI));
+    expect("14: five batch draws", submit(f), kGrowSlot + Log{upload_mats(5), kZeroCounters, kZeroBinFill} + kGrowCull + Log{zero_cull_counters(5)} +
+           draw_kernels(five, OWN_BAND0, 1) + Log{tile_line("tile_vis", 0, 4, 5)} + kFinish);
+    check_ranges("14: five batch draws", five);  // 3 masks each: every second draw starts behind a padding mask
+    MUST(mtr_frame_wait(f));
+}
+
+static void scenario_15_six_two_six() {
+    // the tile kernel of a frame clears the culling counters of ITS draws for the slot's next frame: the frame of two draws
+    // finds them clean, the frame of six after it finds four lines nobody cleared and zeroes the buffer with a fill
+    ManyDraws s;
+    const std::vector<DrawSpec> six = s.six(), two = s.two();
+    mtr_frame* f = s.sharded(six);
+    submit(f);
+    check_ranges("15: six draws", six);
+    MUST(mtr_frame_wait(f));
+    s.drop(f);
+    f = s.sharded(two);
+    const Log second = submit(f);
+    expect("15: two draws after six", second, Log{upload_mats(2), "hipStreamWaitEvent fb.done slot0"} + draw_kernels(two, OWN_BAND0, 1) +
+           Log{tile_line("tile_vis", 0, 1, 2)} + kFinish);
+    CHECK(!has(second, "hipMemsetAsync cull_counters"));
+    check_ranges("15: two draws after six", two);
+    MUST(mtr_frame_wait(f));
+    s.drop(f);
+    f = s.sharded(six);
+    expect("15: six draws after two", submit(f), Log{upload_mats(8), "hipStreamWaitEvent fb.done slot0", zero_cull_counters(6)} +
+           draw_kernels(six, OWN_BAND0, 1) + Log{tile_line("tile_vis", 0, 3, 6)} + kFinish);
+    check_ranges("15: six draws after two", six);
+    MUST(mtr_frame_wait(f));
+}
+
+static void scenario_16_mixed_with_batches() {
+    // a mixed frame: the visibility kernel reports the hints and clears the counters, the ordered kernel behind it must not
+    // report again (it would report zeros)
+    Scene s;
+    mtr_model* m = s.model(2);
+    const mtr_prim_state states[2] = {{MTR_BLEND_OFF, 1, 1, MTR_CULL_BACK}, {MTR_BLEND_ADD, 1, 1, MTR_CULL_BACK}};
+    MUST(mtr_model_set_prim_states(m, states, 2));
+    mtr_frame* f = s.frame();
+    MUST(mtr_frame_set_shard_map(f, 0, 2, MTR_OWN_BANDS, 0, nullptr));
+    const std::vector<DrawSpec> draws(2, DrawSpec{2, 3});
+    for (int i = 0; i < 2; i++) MUST(mtr_frame_draw_batch(f, s.batch3(m), kI));
+    expect("16: mixed, two batch draws", submit(f), kGrowSlot + Log{upload_mats(4), kZeroCounters, kZeroBinFill} + kGrowCull + Log{kZeroCullCounters} +
+           draw_kernels(draws, OWN_BAND0, 0) + Log{tile_line("tile_vis", 1, 2, 2), tile_line("tile", 1, 0, 2)} + kFinish);
+    check_ranges("16: mixed, two batch draws", draws);
+    MUST(mtr_frame_wait(f));
+    mtr_frame_stats st;
+    MUST(mtr_frame_get_stats(f, &st));
+    CHECK(st.tile_kernel == MTR_TILE_MIXED);
+}
+
+static void scenario_17_empty_band_twice() {
+    // a rank without a bin launches no tile kernel: nothing clears the culling counters (or the frame's other counter block),
+    // so every frame zeroes them with a fill
+    ManyDraws s;
+    const uint32_t bands[3] = {0, 0, 4};
+    const std::vector<DrawSpec> two = s.two();
+    const char* own = "own={map=1 rank=0 world=2 cull=1 own_count=0}";
+    mtr_frame* f = s.sharded(two, bands);
+    const Log first = submit(f);
+    expect("17: empty band, first frame", first, kGrowSlot + Log{upload_mats(2), kZeroCounters, kZeroBinFill} + kGrowCull + Log{kZeroCullCounters} +
+           draw_kernels(two, own, 1) + kFinish);
+    check_ranges("17: empty band, first frame", two);
+    MUST(mtr_frame_wait(f));
+    s.drop(f);
+    f = s.sharded(two, bands);
+    const Log second = submit(f);
+    expect("17: empty band, second frame", second, Log{"hipStreamWaitEvent fb.done slot0", kZeroCounters, kZeroCullCounters} + draw_kernels(two, own, 1) + kFinish);
+    CHECK(!has(first, "tile") && !has(second, "tile"));
+    check_ranges("17: empty band, second frame", two);
+    MUST(mtr_frame_wait(f));
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && !strcmp(argv[1], "nomem")) return scenario_10_nomem();
     scenario_1_2_3_direct_two_pass_ordered();
@@ -579,6 +771,11 @@ int main(int argc, char** argv) {
     scenario_9_empty_band();
     scenario_11_profiling();
     scenario_12_vis_waves();
+    scenario_13_six_draws();
+    scenario_14_five_batches();
+    scenario_15_six_two_six();
+    scenario_16_mixed_with_batches();
+    scenario_17_empty_band_twice();
     printf("failed=%d\n", g_failed);
     return g_failed ? 1 : 0;
 }

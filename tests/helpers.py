@@ -58,7 +58,9 @@ def render_gpu(dev, w, h, draws, clear=(1.0, 1.0, 1.0, 1.0), clear_depth=1.0, sh
                 # "make_model": build the api.Model some other way (e.g. from resource files) for the same md
                 models[id(md)] = d["make_model"](dev) if "make_model" in d else api.Model.new(dev, md)
             m = models[id(md)]
-            if "model_mats" in d:
+            if "model_mats" in d and d.get("owned"):  # a batch the frame owns (no launch hints, freed with the frame)
+                fr.draw_instances(m, d["vp"], d["model_mats"], d.get("palettes"))
+            elif "model_mats" in d:
                 if "poses" in d:  # the palettes are formed on the GPU (k_pose) from one pose per instance
                     m.set_skeleton(*d["skeleton"])
                     b = api.Batch(dev, m, d["model_mats"], None, d.get("tex_override"))

@@ -2,7 +2,8 @@
 and UBSan over the stand-in HIP runtime (tests/cpp/hip_stub), with kernel launchers that log what they are asked to launch
 and a trace hook that logs the memsets, uploads, waits, event records and stream syncs in between; the expected logs --
 which kernels run in which order for direct / two-pass binning, visibility / mixed / ordered tile kernels, sharded draws,
-overflow re-runs, an empty band, profiling -- are written out in tests/cpp/frame_launch_log.cpp."""
+overflow re-runs, an empty band, profiling, frames of several draws on one slot (with every draw's share of the culling
+buffers checked) -- are written out in tests/cpp/frame_launch_log.cpp."""
 import os
 import shutil
 import subprocess

@@ -7,6 +7,7 @@ import pytest
 
 from mt_renderer_amd import scene, sharding
 from tests.helpers import assert_same, render_gpu, render_oracle
+from tests.many_draw_scenes import _random_model
 
 pytestmark = pytest.mark.gpu
 
@@ -128,44 +129,6 @@ def test_band_sharding_culls_most_of_the_geometry(gpu_device):
         part = render_gpu(gpu_device, w, h, draws, shard=(rank, 8, sharding.BANDS), tile_mode=api.TILE_AUTO)
         own = owner == rank
         assert (part[0][own] == full[0][own]).all() and (part[1].view(np.uint32)[own] == full[1].view(np.uint32)[own]).all(), rank
-
-
-def _random_model(rng, normalised, many_joints):
-    """strips of random quads with random joints / weights: nothing like the tidy capsule"""
-    nverts, nquads = 600, 260
-    pos = rng.uniform(-1, 1, size=(nverts, 3))
-    pos[:, 2] *= 0.2
-    stride = 24
-    vb = np.zeros((nverts, stride), dtype=np.uint8)
-    p16 = np.clip(np.round(pos * 32767), -32767, 32767).astype(np.int16)
-    vb[:, 0:6] = p16.view(np.uint8).reshape(nverts, 6)
-    vb[:, 12:16] = np.float16(rng.uniform(0, 1, size=(nverts, 2))).view(np.uint8).reshape(nverts, 4)
-    joints = rng.integers(0, 40 if many_joints else 6, size=(nverts, 4)).astype(np.uint8)
-    wts = rng.integers(0, 256, size=(nverts, 4)).astype(np.int64)
-    wts[rng.uniform(size=nverts) < 0.3, 2:] = 0  # some vertices use two joints only
-    if normalised:
-        wts = np.maximum(wts, 0)
-        tot = wts.sum(axis=1, keepdims=True)
-        tot[tot == 0] = 1
-        wts = wts * 255 // tot
-        wts[:, 0] += 255 - wts.sum(axis=1)
-    vb[:, 16:20] = joints
-    vb[:, 20:24] = np.clip(wts, 0, 255).astype(np.uint8)
-    idx = []
-    for q in range(nquads):  # short strips of nearby vertices so triangles stay small
-        a = int(rng.integers(0, nverts - 8))
-        idx += [a, a + 1, a + 2, a + 3, a + 4, 0xFFFF]
-    # make triangles local: sort vertices along x so neighbours in index are neighbours in space
-    order = np.argsort(pos[:, 0] + 0.05 * pos[:, 1])
-    vb = vb[order]
-    index_buf = np.array(idx, dtype=np.uint16)
-    prim = scene.pack_primitive(vertex_num=nverts, vertex_stride=stride, topology=scene.TOPO_STRIP, vertex_base=0, index_ofs=0,
-                                index_num=len(idx), index_base=0)
-    lay = [(scene.SEM_POSITION, scene.IEF_S16N, 3, 0), (scene.SEM_TEXCOORD, scene.IEF_F16, 2, 12), (scene.SEM_JOINT, scene.IEF_U8, 4, 16),
-           (scene.SEM_WEIGHT, scene.IEF_U8N, 4, 20)]
-    return scene.ModelData(vertex_buf=vb.reshape(-1), index_buf=index_buf, prims=np.stack([prim]), layouts=[lay],
-                           prim_to_texture=np.array([-1], dtype=np.int32), prim_debug_id=np.array([5], dtype=np.uint32),
-                           parts_disp=np.ones(1, dtype=np.uint8))
 
 
 @pytest.mark.parametrize("seed", range(6))
