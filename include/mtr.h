@@ -308,6 +308,56 @@ int32_t mtr_batch_animate_layers_device(mtr_batch *batch, mtr_anim *anim, mtr_an
 int32_t mtr_anim_sample_layers(mtr_anim *anim, mtr_anim_masks *masks /* or NULL */, const mtr_anim_layer *layers,
                                size_t nlayers, size_t n, float *out_locals, size_t count);
 
+/* ---- inverse kinematics (build extension, SPEC.md section 17): two-bone reach and aim after the layer stack ----
+ * An IK set belongs to a skeleton: it holds the skeleton's parents (the rules of mtr_model_set_skeleton) and 1..4 chains.
+ * After the layer stack of section 16 has given every joint its (translation, rotation, scale), the chains are evaluated
+ * in order on the GPU, each against one target per instance, before the skeleton is folded; a later chain sees what an
+ * earlier one changed.  MTR_IK_TWO_BONE: joint = (a, b, c), b the child of a and c the child of b; the rotations of a and
+ * b are changed so that c reaches pos (clamped to what the two bones can reach), bending in the plane the pose already
+ * has or, with MTR_IK_POLE, towards pole.  MTR_IK_AIM: the rotation of joint[0] is changed so that axis (in the joint's
+ * own space) points at pos; joint[1..2] and MTR_IK_POLE are not read.  Only rotations change.  pos and pole are in the
+ * instance's model space (the space of the world matrices of section 12, before the instance matrix).  w blends from the
+ * animated rotation (0) to the solved one (1), clamped as a cross-fade weight (NaN -> 0); at w == 0 the chain changes
+ * nothing, bit for bit, and reads no other field of its target.  A chain that cannot be solved (a bone or the distance
+ * of length 0, a NaN target, an infinite target of a TWO_BONE chain, a pole or a limb on the line to the target) changes
+ * nothing either; an infinite target of an AIM chain has no direction and gives a defined rotation without a meaning.
+ * The solve reads rotations above a and ignores their scales: it is exact under ancestors of uniform positive scale.
+ * Every instance of a call has nchains targets, contiguous per instance: targets[inst * nchains + k].
+ * Errors: MTR_E_INVALID, and nothing changes, for everything the layered calls reject, a NULL IK set or NULL targets, an
+ * IK set of another device or joint count or whose parents differ from the model's skeleton (mtr_last_error names the
+ * first joint), and misaligned device targets; at creation for njoints outside 1..256, invalid parents, nchains outside
+ * 1..MTR_ANIM_MAX_IK, a kind other than 0 or 1, unknown flag bits, a joint >= njoints, a TWO_BONE chain whose joints are
+ * not a, its child and that child's child, an AIM axis that is not finite or all zero (mtr_last_error names the chain).
+ * MTR_E_UNSUPPORTED when the library was built without the IK kernels. */
+#define MTR_ANIM_MAX_IK 4
+#define MTR_IK_TWO_BONE 0u
+#define MTR_IK_AIM 1u
+#define MTR_IK_POLE 1u
+typedef struct mtr_anim_ik mtr_anim_ik;
+typedef struct mtr_ik_chain  { uint32_t kind, joint[3]; float axis[3]; uint32_t flags; } mtr_ik_chain;   /* 32 bytes */
+typedef struct mtr_ik_target { float pos[3], w, pole[3]; uint32_t pad; } mtr_ik_target;                  /* 32 bytes */
+int32_t mtr_anim_ik_create(mtr_device *dev, size_t njoints, const uint8_t *parents, size_t nchains,
+                           const mtr_ik_chain *chains, mtr_anim_ik **out);
+/* may follow an animate call directly: parked like mtr_anim_destroy */
+void mtr_anim_ik_destroy(mtr_anim_ik *ik);
+/* the model's palette from one layer stack and nchains targets (host memory, free on return); frame semantics of
+ * mtr_model_animate_layers */
+int32_t mtr_model_animate_ik(mtr_model *model, mtr_anim *anim, mtr_anim_masks *masks /* or NULL */,
+                             const mtr_anim_layer *layers /* nlayers, host */, size_t nlayers, mtr_anim_ik *ik,
+                             const mtr_ik_target *targets /* nchains, host */);
+/* one layer stack and nchains targets per instance (host memory, free on return); frame semantics of mtr_batch_animate */
+int32_t mtr_batch_animate_ik(mtr_batch *batch, mtr_anim *anim, mtr_anim_masks *masks /* or NULL */,
+                             const mtr_anim_layer *layers /* n*nlayers, host */, size_t nlayers, mtr_anim_ik *ik,
+                             const mtr_ik_target *targets /* n*nchains, host */);
+/* the same from device memory, read in stream order on hip_stream with the rules of mtr_batch_animate_device */
+int32_t mtr_batch_animate_ik_device(mtr_batch *batch, mtr_anim *anim, mtr_anim_masks *masks /* or NULL */,
+                                    const mtr_anim_layer *layers_dev /* 16-byte aligned */, size_t nlayers, mtr_anim_ik *ik,
+                                    const mtr_ik_target *targets_dev /* 16-byte aligned */,
+                                    void *hip_stream /* as mtr_batch_set_poses_device */);
+/* test / debug hook: the local matrices of section 17 for n layer stacks and n * nchains targets, to host memory */
+int32_t mtr_anim_sample_ik(mtr_anim *anim, mtr_anim_masks *masks /* or NULL */, mtr_anim_ik *ik, const mtr_anim_layer *layers,
+                           size_t nlayers, const mtr_ik_target *targets, size_t n, float *out_locals, size_t count);
+
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],
                         float clear_depth, mtr_frame **out);

@@ -116,6 +116,13 @@ class Anim {
         dev_.check(mtr_anim_sample_layers(h_, masks, layers, nlayers, n, out.data(), out.size()));
         return out;
     }
+    // the same after the chains of an IK set, against n * nchains targets (SPEC.md section 17)
+    std::vector<float> sample_ik(mtr_anim_masks* masks, mtr_anim_ik* ik, const mtr_anim_layer* layers, size_t nlayers, const mtr_ik_target* targets,
+                                 size_t n) const {
+        std::vector<float> out(n * njoints_ * 16);
+        dev_.check(mtr_anim_sample_ik(h_, masks, ik, layers, nlayers, targets, n, out.data(), out.size()));
+        return out;
+    }
     mtr_anim* handle() const { return h_; }
 
   private:
@@ -138,6 +145,24 @@ class AnimMasks {
   private:
     const Device& dev_;
     mtr_anim_masks* h_ = nullptr;
+};
+
+// An IK set (include/mtr.h, SPEC.md section 17): the parents of a skeleton and 1..MTR_ANIM_MAX_IK chains over it
+class AnimIK {
+  public:
+    AnimIK(const Device& dev, size_t njoints, const uint8_t* parents, size_t nchains, const mtr_ik_chain* chains) : dev_(dev), nchains_(nchains) {
+        dev.check(mtr_anim_ik_create(dev.handle(), njoints, parents, nchains, chains, &h_));
+    }
+    AnimIK(AnimIK&& o) noexcept : dev_(o.dev_), nchains_(o.nchains_), h_(std::exchange(o.h_, nullptr)) {}
+    AnimIK(const AnimIK&) = delete;
+    ~AnimIK() { mtr_anim_ik_destroy(h_); }
+    size_t nchains() const { return nchains_; }
+    mtr_anim_ik* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    size_t nchains_;
+    mtr_anim_ik* h_ = nullptr;
 };
 
 class Model {
@@ -170,6 +195,10 @@ class Model {
     // the palette from one layer stack (SPEC.md section 16); masks may be nullptr
     void animate_layers(const Anim& anim, const AnimMasks* masks, const mtr_anim_layer* layers, size_t nlayers) {
         dev_.check(mtr_model_animate_layers(h_, anim.handle(), masks ? masks->handle() : nullptr, layers, nlayers));
+    }
+    // the palette from one layer stack and one target per chain of ik (SPEC.md section 17); masks may be nullptr
+    void animate_ik(const Anim& anim, const AnimMasks* masks, const mtr_anim_layer* layers, size_t nlayers, const AnimIK& ik, const mtr_ik_target* targets) {
+        dev_.check(mtr_model_animate_ik(h_, anim.handle(), masks ? masks->handle() : nullptr, layers, nlayers, ik.handle(), targets));
     }
     // the state objects a material names (src/rmaterial.rs:211-230), applied per primitive; default = src/model.rs:240-262
     void set_prim_states(const std::vector<mtr_prim_state>& states) { dev_.check(mtr_model_set_prim_states(h_, states.data(), states.size())); }
@@ -218,6 +247,16 @@ class Batch {
     }
     void animate_layers_device(const Anim& anim, const AnimMasks* masks, const mtr_anim_layer* layers_dev, size_t nlayers, void* hip_stream = nullptr) {
         dev_.check(mtr_batch_animate_layers_device(h_, anim.handle(), masks ? masks->handle() : nullptr, layers_dev, nlayers, hip_stream));
+        npal_ = anim.njoints();
+    }
+    // nlayers layers and ik.nchains() targets per instance (SPEC.md section 17): host memory, or device memory read in stream order
+    void animate_ik(const Anim& anim, const AnimMasks* masks, const mtr_anim_layer* layers, size_t nlayers, const AnimIK& ik, const mtr_ik_target* targets) {
+        dev_.check(mtr_batch_animate_ik(h_, anim.handle(), masks ? masks->handle() : nullptr, layers, nlayers, ik.handle(), targets));
+        npal_ = anim.njoints();
+    }
+    void animate_ik_device(const Anim& anim, const AnimMasks* masks, const mtr_anim_layer* layers_dev, size_t nlayers, const AnimIK& ik,
+                           const mtr_ik_target* targets_dev, void* hip_stream = nullptr) {
+        dev_.check(mtr_batch_animate_ik_device(h_, anim.handle(), masks ? masks->handle() : nullptr, layers_dev, nlayers, ik.handle(), targets_dev, hip_stream));
         npal_ = anim.njoints();
     }
     std::vector<float> read_palettes() const {

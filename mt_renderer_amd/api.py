@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = [
     "mtr_anim_create_tracks",
     "mtr_anim_masks_create", "mtr_anim_masks_destroy", "mtr_model_animate_layers", "mtr_batch_animate_layers",
     "mtr_batch_animate_layers_device", "mtr_anim_sample_layers",
+    "mtr_anim_ik_create", "mtr_anim_ik_destroy", "mtr_model_animate_ik", "mtr_batch_animate_ik", "mtr_batch_animate_ik_device",
+    "mtr_anim_sample_ik",
 ]
 
 CLIP_LOOP = 1
@@ -61,6 +63,13 @@ ANIM_LAYER = np.dtype([("clip", "<u4"), ("x", "<f4"), ("w", "<f4"), ("mask", "<u
 ANIM_MAX_LAYERS = 8
 LAYER_OVERRIDE = 0
 LAYER_ADDITIVE = 1
+# mtr_ik_chain / mtr_ik_target (SPEC.md section 17)
+ANIM_IK_CHAIN = np.dtype([("kind", "<u4"), ("joint", "<u4", 3), ("axis", "<f4", 3), ("flags", "<u4")])
+ANIM_IK_TARGET = np.dtype([("pos", "<f4", 3), ("w", "<f4"), ("pole", "<f4", 3), ("pad", "<u4")])
+ANIM_MAX_IK = 4
+IK_TWO_BONE = 0
+IK_AIM = 1
+IK_POLE = 1
 
 
 class MtrError(RuntimeError):
@@ -195,6 +204,12 @@ def _load() -> C.CDLL:
         "mtr_batch_animate_layers": (i32, [vp, vp, vp, vp, sz]),
         "mtr_batch_animate_layers_device": (i32, [vp, vp, vp, vp, sz, vp]),
         "mtr_anim_sample_layers": (i32, [vp, vp, vp, sz, sz, vp, sz]),
+        "mtr_anim_ik_create": (i32, [vp, sz, vp, sz, vp, vp]),
+        "mtr_anim_ik_destroy": (None, [vp]),
+        "mtr_model_animate_ik": (i32, [vp, vp, vp, vp, sz, vp, vp]),
+        "mtr_batch_animate_ik": (i32, [vp, vp, vp, vp, sz, vp, vp]),
+        "mtr_batch_animate_ik_device": (i32, [vp, vp, vp, vp, sz, vp, vp, vp]),
+        "mtr_anim_sample_ik": (i32, [vp, vp, vp, vp, sz, vp, sz, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -419,6 +434,13 @@ class Model:
         ly = anim_layers(layers, 1)
         self.dev.check(lib.mtr_model_animate_layers(self._h, anim._h, masks._h if masks is not None else None, _p(ly), ly.shape[1]))
 
+    def animate_ik(self, anim: "Anim", layers, ik: "AnimIK", targets, masks: Optional["AnimMasks"] = None):
+        """palette formed on the GPU (k_anim_ik) from one layer stack and one target per chain of ``ik`` (an ANIM_IK_TARGET
+        array [K] or a dict of its fields; SPEC.md section 17)"""
+        ly = anim_layers(layers, 1)
+        tg = ik_targets(targets, 1, ik.nchains)
+        self.dev.check(lib.mtr_model_animate_ik(self._h, anim._h, masks._h if masks is not None else None, _p(ly), ly.shape[1], ik._h, _p(tg)))
+
     def render(self, frame: "Frame", view_proj: np.ndarray, joints: bool = False):
         """Model::render(rpass, queue, transform_bind_group, debug_overlay) -- src/model.rs:299-305; the
         transform uniform (src/bin/modelviewer.rs:217-221) is passed directly.  joints: also the per-joint debug cubes the
@@ -508,6 +530,59 @@ def anim_layers(layers, n: Optional[int] = None, L: Optional[int] = None) -> np.
     return ly
 
 
+def ik_targets(targets, n: Optional[int], K: int) -> np.ndarray:
+    """IK targets as a contiguous ANIM_IK_TARGET array [n, K] (SPEC.md section 17): from a structured array of that dtype
+    ([n, K] or flat), or from a dict of pos ([n, K, 3]), optionally w ([n, K], missing = 1) and pole ([n, K, 3])"""
+    if isinstance(targets, dict):
+        unknown = set(targets) - {"pos", "w", "pole"}
+        if unknown or "pos" not in targets:
+            raise MtrError(MTR_E_INVALID, "ik targets: pos, optionally w and pole")
+        pos = _f32(targets["pos"]).reshape(-1, K, 3)
+        tg = np.zeros((pos.shape[0], K), dtype=ANIM_IK_TARGET)
+        tg["pos"], tg["w"] = pos, 1.0
+        if "w" in targets:
+            tg["w"] = np.asarray(targets["w"], dtype=np.float32).reshape(-1, K)
+        if "pole" in targets:
+            tg["pole"] = _f32(targets["pole"]).reshape(-1, K, 3)
+    else:
+        a = np.asarray(targets)
+        if a.dtype != ANIM_IK_TARGET or a.size == 0 or a.size % K:
+            raise MtrError(MTR_E_INVALID, "ik targets: an [n, nchains] array of dtype ANIM_IK_TARGET or a dict of its fields")
+        tg = np.ascontiguousarray(a).reshape(-1, K)
+    if n is not None and tg.shape[0] != n:
+        raise MtrError(MTR_E_INVALID, f"ik targets: [{n}, {K}] expected, {list(tg.shape)} given")
+    return tg
+
+
+class AnimIK:
+    """An IK set (include/mtr.h, SPEC.md section 17): the parents of a skeleton of ``njoints`` joints (a root: 255 or itself)
+    and 1 to 4 chains, an ANIM_IK_CHAIN array or a list of dicts of its fields (kind, joint, optionally axis and flags)."""
+
+    def __init__(self, dev: Device, parents, chains):
+        par = np.ascontiguousarray(np.asarray(parents, dtype=np.uint8).reshape(-1))
+        if isinstance(chains, np.ndarray):
+            if chains.dtype != ANIM_IK_CHAIN:
+                raise MtrError(MTR_E_INVALID, "anim ik: chains of dtype ANIM_IK_CHAIN or a list of dicts of its fields")
+            ch = np.ascontiguousarray(chains).reshape(-1)
+        else:
+            ch = np.zeros(len(chains), dtype=ANIM_IK_CHAIN)
+            for k, c in enumerate(chains):
+                if set(c) - set(ANIM_IK_CHAIN.names) or "kind" not in c or "joint" not in c:
+                    raise MtrError(MTR_E_INVALID, "anim ik: a chain has kind and joint, optionally axis and flags")
+                jt = np.atleast_1d(np.asarray(c["joint"], dtype=np.uint32))
+                ch["kind"][k], ch["flags"][k] = c["kind"], c.get("flags", 0)
+                ch["joint"][k, :jt.size] = jt[:3]
+                ch["axis"][k] = c.get("axis", (0.0, 0.0, 0.0))
+        h = C.c_void_p()
+        dev.check(lib.mtr_anim_ik_create(dev._h, par.size, _p(par), ch.size, _p(ch) if ch.size else None, C.byref(h)))
+        self.dev, self._h, self.njoints, self.nchains = dev, h, par.size, ch.size
+
+    def close(self):
+        if self._h:
+            lib.mtr_anim_ik_destroy(self._h)
+            self._h = None
+
+
 class AnimMasks:
     """A mask set for animation layers (include/mtr.h, SPEC.md section 16): weights [nmasks, njoints] in [0, 1], resident
     in HBM.  A layer's mask index 0 is the built-in mask of ones, index k >= 1 is weights[k - 1]."""
@@ -567,6 +642,16 @@ class Anim:
         ly = anim_layers(layers)
         out = np.zeros((ly.shape[0], self.njoints, 16), dtype=np.float32)
         self.dev.check(lib.mtr_anim_sample_layers(self._h, masks._h if masks is not None else None, _p(ly), ly.shape[1], ly.shape[0], _p(out), out.size))
+        return out
+
+    def sample_ik(self, layers, ik: "AnimIK", targets, masks: Optional[AnimMasks] = None) -> np.ndarray:
+        """the local matrices [n, njoints, 16] of the given layer stacks ([n, L]) after the chains of ``ik`` have been
+        evaluated against ``targets`` ([n, K], SPEC.md section 17), formed on the GPU"""
+        ly = anim_layers(layers)
+        tg = ik_targets(targets, ly.shape[0], ik.nchains)
+        out = np.zeros((ly.shape[0], self.njoints, 16), dtype=np.float32)
+        self.dev.check(lib.mtr_anim_sample_ik(self._h, masks._h if masks is not None else None, ik._h, _p(ly), ly.shape[1], _p(tg), ly.shape[0],
+                                              _p(out), out.size))
         return out
 
     def close(self):
@@ -741,6 +826,55 @@ class Batch:
             side.wait_stream(cur)
             self.dev.check(lib.mtr_batch_animate_layers_device(self._h, anim._h, mh, C.c_void_p(t.data_ptr()), nl, C.c_void_p(side.cuda_stream)))
             t.record_stream(side)
+            cur.wait_stream(side)
+        self.npal = anim.njoints
+
+    def animate_ik(self, anim: Anim, layers, ik: AnimIK, targets, masks: Optional[AnimMasks] = None, L: Optional[int] = None):
+        """one layer stack and one target per chain of ``ik`` per instance (k_anim_ik, SPEC.md section 17).  Numpy arrays
+        (ANIM_LAYER [n, L], ANIM_IK_TARGET [n, K]) or dicts of their fields are copied in.  Where either is a torch uint8 /
+        int32 / float32 tensor on the batch's device holding the records, both are read from device memory in stream order
+        on torch.cuda.current_stream() (a numpy one of the pair is uploaded on that stream first)."""
+        mh = masks._h if masks is not None else None
+        host = (np.ndarray, dict)
+        if isinstance(layers, host) and isinstance(targets, host):
+            ly = anim_layers(layers, self.n, L)
+            tg = ik_targets(targets, self.n, ik.nchains)
+            self.dev.check(lib.mtr_batch_animate_ik(self._h, anim._h, mh, _p(ly), ly.shape[1], ik._h, _p(tg)))
+            self.npal = anim.njoints
+            return
+        import torch
+        device = torch.device("cuda", self.dev.hip_device)
+
+        def on_device(t, what, make):
+            if isinstance(t, host):
+                raw = np.ascontiguousarray(make(t)).view(np.uint8).reshape(self.n, -1)
+                return torch.from_numpy(raw.copy()).to(device)
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32, torch.float32):
+                raise MtrError(MTR_E_INVALID, f"animate_ik: {what} as a numpy array, a dict, or a uint8 / int32 / float32 tensor on the GPU")
+            if t.get_device() != self.dev.hip_device:
+                raise MtrError(MTR_E_INVALID, f"animate_ik: the tensor is on cuda:{t.get_device()}, the batch on cuda:{self.dev.hip_device}")
+            if not t.is_contiguous() or t.data_ptr() % 16:
+                t = t.contiguous().clone()
+            return t
+        tl = on_device(layers, "layers", lambda a: anim_layers(a, self.n, L))
+        tt = on_device(targets, "targets", lambda a: ik_targets(a, self.n, ik.nchains))
+        nbytes = tl.numel() * tl.element_size()
+        if nbytes == 0 or nbytes % (self.n * ANIM_LAYER.itemsize) or (L is not None and nbytes != self.n * L * ANIM_LAYER.itemsize):
+            raise MtrError(MTR_E_INVALID, "animate_ik: n x L layers of 16 bytes")
+        if tt.numel() * tt.element_size() != self.n * ik.nchains * ANIM_IK_TARGET.itemsize:
+            raise MtrError(MTR_E_INVALID, "animate_ik: n x nchains targets of 32 bytes")
+        nl = nbytes // (self.n * ANIM_LAYER.itemsize)
+        cur = torch.cuda.current_stream(device)
+        if cur.cuda_stream != 0:
+            self.dev.check(lib.mtr_batch_animate_ik_device(self._h, anim._h, mh, C.c_void_p(tl.data_ptr()), nl, ik._h, C.c_void_p(tt.data_ptr()),
+                                                           C.c_void_p(cur.cuda_stream)))
+        else:  # torch's legacy default stream: as set_poses
+            side = _pose_stream(device)
+            side.wait_stream(cur)
+            self.dev.check(lib.mtr_batch_animate_ik_device(self._h, anim._h, mh, C.c_void_p(tl.data_ptr()), nl, ik._h, C.c_void_p(tt.data_ptr()),
+                                                           C.c_void_p(side.cuda_stream)))
+            tl.record_stream(side)
+            tt.record_stream(side)
             cur.wait_stream(side)
         self.npal = anim.njoints
 

@@ -1,5 +1,5 @@
 // anim_blend.h -- the scalar blend rules of SPEC.md sections 14 and 16 that k_anim.hip is made of: lerp, the dot product,
-// nlerp, the Hamilton product, the clamped weight and the two layer steps.  Plain C++ besides the macro, so that
+// nlerp, the local matrix, the Hamilton product, the clamped weight and the two layer steps.  Plain C++ besides the macro, so that
 // tests/test_anim_layers_exact.py compiles this very source for the host (-ffp-contract=off) and compares it bit for bit
 // with the numpy model of section 16.
 //
@@ -66,6 +66,18 @@ MTR_BLEND_HD AnimKey anim_mix(const AnimKey& k0, const AnimKey& k1, float a) {
     r.q = anim_nlerp(k0.q, k1.q, a);
     r.s = anim_lerp4(k0.s, k1.s, a);
     return r;
+}
+
+// (T, Q, S) -> section 14's local matrix (column-major)
+MTR_BLEND_HD void anim_matrix(const AnimKey& r, AnimVec (&M)[4]) {
+    const float x = r.q.x, y = r.q.y, z = r.q.z, qw = r.q.w;
+    const float x2 = x + x, y2 = y + y, z2 = z + z;
+    const float xx = x * x2, yy = y * y2, zz = z * z2, xy = x * y2, xz = x * z2, yz = y * z2;
+    const float wx = qw * x2, wy = qw * y2, wz = qw * z2;
+    M[0] = anim_vec((1.0f - (yy + zz)) * r.s.x, (xy + wz) * r.s.x, (xz - wy) * r.s.x, 0.0f);
+    M[1] = anim_vec((xy - wz) * r.s.y, (1.0f - (xx + zz)) * r.s.y, (yz + wx) * r.s.y, 0.0f);
+    M[2] = anim_vec((xz + wy) * r.s.z, (yz - wx) * r.s.z, (1.0f - (xx + yy)) * r.s.z, 0.0f);
+    M[3] = anim_vec(r.t.x, r.t.y, r.t.z, 1.0f);
 }
 
 // the Hamilton product p q, in section 16's operation order

@@ -253,7 +253,11 @@ struct mtr_model {
     std::shared_ptr<const mtr_host::ChunkTable> table;  // for the current parts_disp; rebuilt by the next draw when chunks_dirty (submit_mu)
     float* d_palette = nullptr;   // the current palette: one buffer of pal_ring
     // skeleton of mtr_model_set_skeleton (what k_pose needs): immutable once uploaded; replacing it waits for the device
-    struct Skeleton { uint32_t njoints = 0, path_bytes = 0; float* d = nullptr; /* imats (njoints * 16 f32), paths (njoints u32), path bytes */ };
+    struct Skeleton {
+        uint32_t njoints = 0, path_bytes = 0;
+        float* d = nullptr;            /* imats (njoints * 16 f32), paths (njoints u32), path bytes */
+        std::vector<uint8_t> parents;  /* as given, a root as 255: what an IK set's parents are compared with */
+    };
     Skeleton skel;
     uint32_t npal = 0;
     // mtr_model_set_palette does not wait for frames in flight: every call uploads into the next buffer of a ring
@@ -335,6 +339,19 @@ struct mtr_anim_masks {
     mtr_device* dev;
     uint32_t njoints = 0, nmasks = 0;
     float* d = nullptr;
+    hipEvent_t last = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool recorded = false;
+};
+
+// An IK set (SPEC.md section 17): immutable once uploaded.  d: nchains x 8 words of validated chains, the path table
+// (njoints u32) and the path bytes of the skeleton its parents describe (what mtr_anim_sample_ik walks; the animate calls
+// walk the model's own, after comparing the parents).  `last` as mtr_anim's.
+struct mtr_anim_ik {
+    mtr_device* dev;
+    uint32_t njoints = 0, nchains = 0, path_bytes = 0;
+    std::vector<uint8_t> parents;  // a root as 255
+    uint32_t* d = nullptr;
     hipEvent_t last = nullptr;
     hipStream_t last_stream = nullptr;
     bool recorded = false;
@@ -467,6 +484,7 @@ int32_t report_sticky(mtr_device* d);
 // ---- host_model.cpp ----
 int32_t current_table(mtr_model* m, std::shared_ptr<const ChunkTable>* out);
 int32_t next_palette_buffer(mtr_model* m, size_t n, mtr_model::PalBuf** out);
+bool pose_paths(const uint8_t* parents, size_t n, std::vector<uint32_t>& paths, std::vector<uint8_t>& bytes);
 
 // ---- host_batch.cpp ----
 int32_t stage_pose(mtr_device* d, const float* local_mats, size_t count);

@@ -1,4 +1,4 @@
-// host_batch.cpp -- instance batches and their versions, pose and animation staging, animation clip sets, mask sets and layers.
+// host_batch.cpp -- instance batches and their versions, pose and animation staging, animation clip sets, mask sets and layers, IK sets.
 #include "host.h"
 
 // k_pose.hip.  Weak: the host-only builds of this file (tests/cpp, over the HIP stub runtime) link no kernels and never
@@ -13,11 +13,17 @@ void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_
 void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 
 namespace mtr_host {
 
-// host local matrices -> the device's staging buffer, on s_copy (the render thread only)
-int32_t stage_pose(mtr_device* d, const float* local_mats, size_t count) {
+namespace {
+
+// room for count floats in the device's staging buffer (the render thread only)
+int32_t stage_reserve(mtr_device* d, size_t count) {
     if (count > d->pose_stage_cap) {
         HIPCHK(d, hipStreamSynchronize(d->s_copy));  // a queued pose kernel may still read the old buffer
         if (d->pose_stage) (void)hipFree(d->pose_stage);
@@ -26,6 +32,15 @@ int32_t stage_pose(mtr_device* d, const float* local_mats, size_t count) {
         if (rc) return rc;
         d->pose_stage_cap = count;
     }
+    return MTR_OK;
+}
+
+}  // namespace
+
+// host local matrices -> the device's staging buffer, on s_copy (the render thread only)
+int32_t stage_pose(mtr_device* d, const float* local_mats, size_t count) {
+    int32_t rc = stage_reserve(d, count);
+    if (rc) return rc;
     HIPCHK(d, hipMemcpyAsync(d->pose_stage, local_mats, count * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
     return MTR_OK;
 }
@@ -79,7 +94,41 @@ void launch_anim_layers(const mtr_anim* a, const AnimLayerParams& lp, uint32_t n
     else mtr_launch_anim_layers(lp, ninst, s);
 }
 
-// around a kernel on `s` that reads the clip set or the mask set: see mtr_anim::last
+// the layer stacks and the IK targets of one call behind each other in the staging buffer, on s_copy; the layers are a
+// multiple of 16 bytes, so the targets (*targets_dev) are 16-byte aligned
+int32_t stage_ik(mtr_device* d, const mtr_anim_layer* layers, size_t nl, const mtr_ik_target* targets, size_t nt, const void** targets_dev) {
+    const size_t lw = nl * (sizeof(mtr_anim_layer) / sizeof(float)), tw = nt * (sizeof(mtr_ik_target) / sizeof(float));
+    int32_t rc = stage_reserve(d, lw + tw);
+    if (rc) return rc;
+    HIPCHK(d, hipMemcpyAsync(d->pose_stage, layers, lw * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
+    HIPCHK(d, hipMemcpyAsync(d->pose_stage + lw, targets, tw * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
+    *targets_dev = d->pose_stage + lw;
+    return MTR_OK;
+}
+
+// the chains of an IK set after a layer stack (section 17): targets_dev holds ninst * nchains records.  sk: the model's
+// skeleton, whose path table the chain walks read as the fold does; without one (mtr_anim_sample_ik) the IK set's copy
+AnimIkParams anim_ik_params(const mtr_anim* a, const mtr_anim_masks* mk, const mtr_model::Skeleton& sk, const void* layers_dev, uint32_t nlayers,
+                            const mtr_anim_ik* ik, const void* targets_dev, float* out) {
+    AnimIkParams ip{};
+    ip.layers = anim_layer_params(a, mk, sk, layers_dev, nlayers, out);
+    ip.chains = ik->d;
+    ip.targets = static_cast<const uint32_t*>(targets_dev);
+    ip.nchains = ik->nchains;
+    if (sk.d) {
+        ip.paths = ip.layers.anim.pose.paths; ip.path_words = ip.layers.anim.pose.path_words; ip.path_bytes = sk.path_bytes;
+    } else {
+        ip.paths = ik->d + (size_t)ik->nchains * 8; ip.path_words = ip.paths + ik->njoints; ip.path_bytes = ik->path_bytes;
+    }
+    return ip;
+}
+
+void launch_anim_ik(const mtr_anim* a, const AnimIkParams& ip, uint32_t ninst, hipStream_t s) {
+    if (a->tracks) mtr_launch_anim_ik_tracks(ip, ninst, s);
+    else mtr_launch_anim_ik(ip, ninst, s);
+}
+
+// around a kernel on `s` that reads the clip set, the mask set or the IK set: see mtr_anim::last
 template <class Set>
 int32_t anim_before(Set* a, hipStream_t s) {
     if (a->recorded && a->last_stream != s) HIPCHK(a->dev, hipStreamWaitEvent(s, a->last, 0));
@@ -179,14 +228,17 @@ int32_t batch_next_version(mtr_batch* b, uint32_t npal, int* out, hipEvent_t* fr
     return MTR_OK;
 }
 
-// Where the palettes of a pose come from: local matrices (k_pose), animation states over a clip set (k_anim), or layer
-// stacks over a clip set and an optional mask set (k_anim_layers: nlayers != 0, states holds the layers); device memory
+// Where the palettes of a pose come from: local matrices (k_pose), animation states over a clip set (k_anim), layer
+// stacks over a clip set and an optional mask set (k_anim_layers: nlayers != 0, states holds the layers), or such stacks
+// followed by the chains of an IK set (k_anim_ik: ik != nullptr, targets holds the targets); device memory
 struct PoseSrc {
     const float* locals = nullptr;
     mtr_anim* anim = nullptr;
     const void* states = nullptr;
     mtr_anim_masks* masks = nullptr;
     uint32_t nlayers = 0;
+    mtr_anim_ik* ik = nullptr;
+    const void* targets = nullptr;
     explicit operator bool() const { return locals || anim; }
 };
 
@@ -232,11 +284,15 @@ int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, 
             int32_t arc = anim_before(src.anim, s);
             if (arc) return arc;
             if (src.masks && (arc = anim_before(src.masks, s))) return arc;
-            if (src.nlayers) launch_anim_layers(src.anim, anim_layer_params(src.anim, src.masks, b->model->skel, src.states, src.nlayers, vp), (uint32_t)n, s);
+            if (src.ik && (arc = anim_before(src.ik, s))) return arc;
+            if (src.ik)
+                launch_anim_ik(src.anim, anim_ik_params(src.anim, src.masks, b->model->skel, src.states, src.nlayers, src.ik, src.targets, vp), (uint32_t)n, s);
+            else if (src.nlayers) launch_anim_layers(src.anim, anim_layer_params(src.anim, src.masks, b->model->skel, src.states, src.nlayers, vp), (uint32_t)n, s);
             else launch_anim(src.anim, anim_params(src.anim, b->model->skel, src.states, vp), (uint32_t)n, s);
             HIPCHK(d, hipGetLastError());
             if ((arc = anim_after(src.anim, s))) return arc;
             if (src.masks && (arc = anim_after(src.masks, s))) return arc;
+            if (src.ik && (arc = anim_after(src.ik, s))) return arc;
         } else if (src.locals) {
             mtr_launch_pose(pose_params(b->model->skel, src.locals, vp), (uint32_t)n, s);
             HIPCHK(d, hipGetLastError());
@@ -282,6 +338,20 @@ int32_t check_anim_layers(mtr_device* d, const mtr_model* m, const mtr_anim* a, 
     int32_t rc = check_anim(d, m, a);
     if (rc) return rc;
     if (!(a->tracks ? mtr_launch_anim_layers_tracks : mtr_launch_anim_layers)) return fail(d, MTR_E_UNSUPPORTED, "animate layers: built without k_anim_layers");
+    return MTR_OK;
+}
+
+// what every IK animate call checks besides check_anim_layers
+int32_t check_anim_ik(mtr_device* d, const mtr_model* m, const mtr_anim* a, const mtr_anim_masks* mk, size_t nlayers, const mtr_anim_ik* ik) {
+    int32_t rc = check_anim_layers(d, m, a, mk, nlayers);
+    if (rc) return rc;
+    if (!ik) return fail(d, MTR_E_INVALID, "animate ik: no IK set");
+    if (ik->dev != d) return fail(d, MTR_E_INVALID, "animate ik: the IK set belongs to another device");
+    if (ik->njoints != m->skel.njoints) return fail(d, MTR_E_INVALID, "animate ik: the IK set's joint count is not the skeleton's");
+    for (uint32_t j = 0; j < ik->njoints; j++)
+        if (ik->parents[j] != m->skel.parents[j])
+            return fail(d, MTR_E_INVALID, "animate ik: the IK set's parent of joint " + std::to_string(j) + " is not the skeleton's");
+    if (!(a->tracks ? mtr_launch_anim_ik_tracks : mtr_launch_anim_ik)) return fail(d, MTR_E_UNSUPPORTED, "animate ik: built without k_anim_ik");
     return MTR_OK;
 }
 
@@ -656,6 +726,156 @@ int32_t mtr_anim_sample_layers(mtr_anim* a, mtr_anim_masks* mk, const mtr_anim_l
         lp.anim.pose.njoints = a->njoints;
         if (a->tracks) mtr_launch_anim_layers_tracks_sample(lp, (uint32_t)n, d->s_copy);
         else mtr_launch_anim_layers_sample(lp, (uint32_t)n, d->s_copy);
+        HIPCHK(d, hipGetLastError());
+        HIPCHK(d, hipMemcpyAsync(out_locals, tmp, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
+        return MTR_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(d->s_copy);  // also when a step failed: the buffer is freed next
+    (void)hipFree(tmp);
+    if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// inverse kinematics (SPEC.md section 17)
+// ---------------------------------------------------------------------------------------------
+static_assert(sizeof(mtr_ik_chain) == 32 && sizeof(mtr_ik_target) == 32, "mtr_ik_chain, mtr_ik_target");
+
+int32_t mtr_anim_ik_create(mtr_device* d, size_t njoints, const uint8_t* parents, size_t nchains, const mtr_ik_chain* chains, mtr_anim_ik** out) {
+    if (!d || !out) return MTR_E_INVALID;
+    *out = nullptr;
+    if (njoints == 0 || njoints > MTR_POSE_MAX_JOINTS || !parents) return fail(d, MTR_E_INVALID, "anim ik: 1 to 256 joints and their parents");
+    if (nchains < 1 || nchains > MTR_ANIM_MAX_IK || !chains) return fail(d, MTR_E_INVALID, "anim ik: 1 to 4 chains");
+    std::vector<uint32_t> paths;
+    std::vector<uint8_t> bytes;
+    if (!pose_paths(parents, njoints, paths, bytes)) return fail(d, MTR_E_INVALID, "anim ik: a parent out of range or a cycle");
+    auto root = [&](uint32_t j) { return parents[j] == 255 || parents[j] == j; };
+    for (size_t k = 0; k < nchains; k++) {
+        const mtr_ik_chain& c = chains[k];
+        const char* what = nullptr;
+        if (c.kind != MTR_IK_TWO_BONE && c.kind != MTR_IK_AIM) what = "has a kind other than MTR_IK_TWO_BONE and MTR_IK_AIM";
+        else if (c.flags & ~MTR_IK_POLE) what = "has unknown flag bits";
+        else if (c.joint[0] >= njoints) what = "names a joint past the skeleton's";
+        else if (c.kind == MTR_IK_TWO_BONE) {
+            const uint32_t a = c.joint[0], b = c.joint[1], cc = c.joint[2];
+            if (b >= njoints || cc >= njoints) what = "names a joint past the skeleton's";
+            else if (a == b || b == cc || a == cc) what = "names a joint twice";
+            else if (root(b) || root(cc)) what = "has a root for its middle or end joint";
+            else if (parents[b] != a || parents[cc] != b) what = "is not a joint, its child and that child's child";
+        } else {
+            const float* ax = c.axis;
+            if (!(std::isfinite(ax[0]) && std::isfinite(ax[1]) && std::isfinite(ax[2]))) what = "has an axis that is not finite";
+            else if (ax[0] == 0.0f && ax[1] == 0.0f && ax[2] == 0.0f) what = "has a zero axis";
+        }
+        if (what) return fail(d, MTR_E_INVALID, "anim ik: chain " + std::to_string(k) + " " + what);
+    }
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    auto ik = std::make_unique<mtr_anim_ik>();
+    ik->dev = d; ik->njoints = (uint32_t)njoints; ik->nchains = (uint32_t)nchains; ik->path_bytes = (uint32_t)bytes.size();
+    ik->parents.assign(parents, parents + njoints);
+    for (size_t j = 0; j < njoints; j++)
+        if (ik->parents[j] == j) ik->parents[j] = 255;  // a root either way
+    std::vector<uint32_t> img(nchains * 8 + njoints + bytes.size() / 4);  // the chains, the path table, the paths
+    memcpy(img.data(), chains, nchains * sizeof(mtr_ik_chain));
+    memcpy(img.data() + nchains * 8, paths.data(), njoints * 4);
+    memcpy(img.data() + nchains * 8 + njoints, bytes.data(), bytes.size());
+    if ((rc = dev_alloc(d, &ik->d, img.size()))) return rc;
+    hipError_t e = hipMemcpy(ik->d, img.data(), img.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ik->last, hipEventDisableTiming);
+    if (e != hipSuccess) { (void)hipFree(ik->d); return fail(d, MTR_E_HIP, std::string("anim ik upload: ") + hipGetErrorString(e)); }
+    *out = ik.release();
+    return MTR_OK;
+}
+
+void mtr_anim_ik_destroy(mtr_anim_ik* ik) {
+    if (!ik) return;
+    mtr_device* d = ik->dev;
+    {
+        // a kernel may still read the chains: parked behind the event of the last one, collected by a later submit
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        d->garbage.push_back({ik->d, 0, ik->last});
+    }
+    delete ik;
+}
+
+int32_t mtr_model_animate_ik(mtr_model* m, mtr_anim* a, mtr_anim_masks* mk, const mtr_anim_layer* layers, size_t nlayers, mtr_anim_ik* ik,
+                             const mtr_ik_target* targets) {
+    if (!m) return MTR_E_INVALID;
+    mtr_device* d = m->dev;
+    if (!layers) return fail(d, MTR_E_INVALID, "animate ik: no layers");
+    if (!targets) return fail(d, MTR_E_INVALID, "animate ik: no targets");
+    int32_t rc = check_anim_ik(d, m, a, mk, nlayers, ik);
+    if (rc) return rc;
+    const void* tg = nullptr;
+    if ((rc = stage_ik(d, layers, nlayers, targets, ik->nchains, &tg))) return rc;
+    std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+    mtr_model::PalBuf* pb = nullptr;
+    if ((rc = next_palette_buffer(m, a->njoints, &pb))) return rc;
+    if ((rc = anim_before(a, d->s_copy))) return rc;
+    if (mk && (rc = anim_before(mk, d->s_copy))) return rc;
+    if ((rc = anim_before(ik, d->s_copy))) return rc;
+    launch_anim_ik(a, anim_ik_params(a, mk, m->skel, d->pose_stage, (uint32_t)nlayers, ik, tg, pb->d), 1, d->s_copy);
+    HIPCHK(d, hipGetLastError());
+    if ((rc = anim_after(a, d->s_copy))) return rc;
+    if (mk && (rc = anim_after(mk, d->s_copy))) return rc;
+    if ((rc = anim_after(ik, d->s_copy))) return rc;
+    HIPCHK(d, hipEventRecord(pb->ready, d->s_copy));
+    return MTR_OK;
+}
+
+int32_t mtr_batch_animate_ik(mtr_batch* b, mtr_anim* a, mtr_anim_masks* mk, const mtr_anim_layer* layers, size_t nlayers, mtr_anim_ik* ik,
+                             const mtr_ik_target* targets) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!layers) return fail(d, MTR_E_INVALID, "animate ik: no layers");
+    if (!targets) return fail(d, MTR_E_INVALID, "animate ik: no targets");
+    int32_t rc = check_anim_ik(d, b->model, a, mk, nlayers, ik);
+    if (rc) return rc;
+    PoseSrc src;
+    if ((rc = stage_ik(d, layers, (size_t)b->n * nlayers, targets, (size_t)b->n * ik->nchains, &src.targets))) return rc;
+    src.anim = a; src.states = d->pose_stage; src.masks = mk; src.nlayers = (uint32_t)nlayers; src.ik = ik;
+    return batch_write_version(b, nullptr, nullptr, a->njoints, src, d->s_copy);
+}
+
+int32_t mtr_batch_animate_ik_device(mtr_batch* b, mtr_anim* a, mtr_anim_masks* mk, const mtr_anim_layer* layers_dev, size_t nlayers, mtr_anim_ik* ik,
+                                    const mtr_ik_target* targets_dev, void* hip_stream) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!layers_dev || ((uintptr_t)layers_dev & 15u)) return fail(d, MTR_E_INVALID, "animate ik: device layers must be 16-byte aligned");
+    if (!targets_dev || ((uintptr_t)targets_dev & 15u)) return fail(d, MTR_E_INVALID, "animate ik: device targets must be 16-byte aligned");
+    int32_t rc = check_anim_ik(d, b->model, a, mk, nlayers, ik);
+    if (rc) return rc;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    PoseSrc src;
+    src.anim = a; src.states = layers_dev; src.masks = mk; src.nlayers = (uint32_t)nlayers; src.ik = ik; src.targets = targets_dev;
+    return batch_write_version(b, nullptr, nullptr, a->njoints, src, s);
+}
+
+int32_t mtr_anim_sample_ik(mtr_anim* a, mtr_anim_masks* mk, mtr_anim_ik* ik, const mtr_anim_layer* layers, size_t nlayers, const mtr_ik_target* targets,
+                           size_t n, float* out_locals, size_t count) {
+    if (!a) return MTR_E_INVALID;
+    mtr_device* d = a->dev;
+    if (nlayers < 1 || nlayers > MTR_ANIM_MAX_LAYERS) return fail(d, MTR_E_INVALID, "anim sample ik: 1 to 8 layers per instance");
+    if (mk && (mk->dev != d || mk->njoints != a->njoints)) return fail(d, MTR_E_INVALID, "anim sample ik: the mask set is of another device or joint count");
+    if (!ik || ik->dev != d || ik->njoints != a->njoints) return fail(d, MTR_E_INVALID, "anim sample ik: an IK set of this device and joint count");
+    const size_t need = n * a->njoints * 16;
+    if (n > 0xFFFFFFu || (n && (!layers || !targets || !out_locals)) || count < need)
+        return fail(d, MTR_E_INVALID, "anim sample ik: n * nlayers layers, n * nchains targets and room for n * njoints * 16 floats");
+    if (!(a->tracks ? mtr_launch_anim_ik_tracks_sample : mtr_launch_anim_ik_sample)) return fail(d, MTR_E_UNSUPPORTED, "anim sample ik: built without k_anim_ik");
+    int32_t rc = set_device(d);
+    if (rc || !n) return rc;
+    float* tmp = nullptr;  // the local matrices, the layers, the targets (each a multiple of 16 bytes)
+    const size_t lw = n * nlayers * 4, tw = n * ik->nchains * 8;
+    if ((rc = dev_alloc(d, &tmp, need + lw + tw))) return rc;
+    auto run = [&]() -> int32_t {
+        HIPCHK(d, hipMemcpyAsync(tmp + need, layers, lw * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
+        HIPCHK(d, hipMemcpyAsync(tmp + need + lw, targets, tw * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
+        AnimIkParams ip = anim_ik_params(a, mk, mtr_model::Skeleton{}, tmp + need, (uint32_t)nlayers, ik, tmp + need + lw, tmp);
+        ip.layers.anim.pose.njoints = a->njoints;
+        if (a->tracks) mtr_launch_anim_ik_tracks_sample(ip, (uint32_t)n, d->s_copy);
+        else mtr_launch_anim_ik_sample(ip, (uint32_t)n, d->s_copy);
         HIPCHK(d, hipGetLastError());
         HIPCHK(d, hipMemcpyAsync(out_locals, tmp, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
         return MTR_OK;

@@ -211,6 +211,8 @@ void rebuild_chunks(const mtr_model* m, ChunkTable* t) {
     }
 }
 
+}  // namespace
+
 // The k_pose path table of a skeleton: paths[j] = offset | length << 16 of joint j's path in `bytes`, the joints from its
 // root down to j (a root's path is itself).  false: a parent out of range or a cycle.
 bool pose_paths(const uint8_t* parents, size_t n, std::vector<uint32_t>& paths, std::vector<uint8_t>& bytes) {
@@ -244,8 +246,6 @@ bool pose_paths(const uint8_t* parents, size_t n, std::vector<uint32_t>& paths, 
     bytes.resize((bytes.size() + 3) & ~size_t(3), 0);
     return true;
 }
-
-}  // namespace
 
 // The model's chunk table for its current parts_disp, built and uploaded on first use.  submit_mu held.
 int32_t current_table(mtr_model* m, std::shared_ptr<const ChunkTable>* out) {
@@ -510,6 +510,9 @@ int32_t mtr_model_set_skeleton(mtr_model* m, const uint8_t* parents, const float
         const hipError_t e = hipMemcpy(sk.d, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e != hipSuccess) { (void)hipFree(sk.d); return fail(d, MTR_E_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
         sk.njoints = (uint32_t)njoints;
+        sk.parents.assign(parents, parents + njoints);
+        for (size_t j = 0; j < njoints; j++)
+            if (sk.parents[j] == j) sk.parents[j] = 255;  // a root either way
     }
     mtr_model::Skeleton old;
     {

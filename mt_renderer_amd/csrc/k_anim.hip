@@ -13,7 +13,12 @@
 // Layers (section 16): the k_anim_layers kernels evaluate a stack of up to 8 layers per instance on either source -- a
 // base clip, then per layer a clip blended over it per joint (override or additive) by its weight times a mask weight.
 // The scalar blend rules of both sections live in anim_blend.h.
+//
+// Inverse kinematics (section 17): the k_anim_ik kernels evaluate the same stack through the same code, keep each joint's
+// (T, Q, S) in registers and, between the stack and the fold, solve up to 4 chains per instance (two-bone reach, aim) in
+// order over the local matrices and rotations in LDS.  The scalar solve lives in anim_ik.h.
 #include "anim_blend.h"
+#include "anim_ik.h"
 #include "anim_tracks.h"
 #include "pose_common.h"
 
@@ -135,18 +140,6 @@ __device__ __forceinline__ void track_sample(const AnimParams& p, TrackClip (&c)
     }
 }
 
-// (T, Q, S) -> the local matrix (column-major)
-__device__ __forceinline__ void anim_matrix(const AnimKey& r, float4 (&M)[4]) {
-    const float x = r.q.x, y = r.q.y, z = r.q.z, qw = r.q.w;
-    const float x2 = x + x, y2 = y + y, z2 = z + z;
-    const float xx = x * x2, yy = y * y2, zz = z * z2, xy = x * y2, xz = x * z2, yz = y * z2;
-    const float wx = qw * x2, wy = qw * y2, wz = qw * z2;
-    M[0] = make_float4((1.0f - (yy + zz)) * r.s.x, (xy + wz) * r.s.x, (xz - wy) * r.s.x, 0.0f);
-    M[1] = make_float4((xy - wz) * r.s.y, (1.0f - (xx + zz)) * r.s.y, (yz + wx) * r.s.y, 0.0f);
-    M[2] = make_float4((xz + wy) * r.s.z, (yz - wx) * r.s.z, (1.0f - (xx + yy)) * r.s.z, 0.0f);
-    M[3] = make_float4(r.t.x, r.t.y, r.t.z, 1.0f);
-}
-
 // The local matrix of joint j of instance inst (column-major); TRACKS: the set is a track set
 template <bool TRACKS>
 __device__ __forceinline__ void anim_local(const AnimParams& p, uint32_t inst, uint32_t j, float4 (&M)[4]) {
@@ -257,10 +250,10 @@ __device__ __forceinline__ AnimKey anim_layer_value(const LayerFetch& f) {
     else return anim_mix(f.k0, f.k1, f.a);
 }
 
-// The local matrix of joint j of instance inst from its layer stack: layer l + 1's loads are issued before layer l's
-// blend arithmetic
+// The (T, Q, S) of joint j of instance inst after its layer stack: layer l + 1's loads are issued before layer l's blend
+// arithmetic
 template <bool TRACKS>
-__device__ __forceinline__ void anim_local(const AnimLayerParams& p, uint32_t inst, uint32_t j, float4 (&M)[4]) {
+__device__ __forceinline__ AnimKey anim_layer_tqs(const AnimLayerParams& p, uint32_t inst, uint32_t j) {
     const uint32_t L = p.nlayers;
     LayerFetch cu, nx = anim_layer_fetch<TRACKS>(p, inst, 0u, j);
     AnimKey r = {};
@@ -274,7 +267,13 @@ __device__ __forceinline__ void anim_local(const AnimLayerParams& p, uint32_t in
             if (e != 0.0f) r = anim_layer_step(r, anim_layer_value<TRACKS>(cu), e, cu.mode);  // e == 0: untouched, bit for bit
         }
     }
-    anim_matrix(r, M);
+    return r;
+}
+
+// The local matrix of joint j of instance inst from its layer stack
+template <bool TRACKS>
+__device__ __forceinline__ void anim_local(const AnimLayerParams& p, uint32_t inst, uint32_t j, float4 (&M)[4]) {
+    anim_matrix(anim_layer_tqs<TRACKS>(p, inst, j), M);
 }
 
 __device__ __forceinline__ const PoseParams& anim_pose(const AnimParams& p) { return p.pose; }
@@ -310,6 +309,124 @@ __device__ __forceinline__ void anim_locals(const P& p) {
 #pragma unroll
     for (int c = 0; c < 4; c++) out[c] = M[c];
 }
+
+// ---- inverse kinematics (section 17) ----
+// The world matrix W of joint a and the world rotation P above it, from the local matrices and rotations in LDS: the
+// joint's path root first, as pose_fold_store walks it -- the same k-ordered fma chain, parent on the left, so W is bit for
+// bit what the fold will produce for a.  P is the product of the rotations of the path without a itself, the identity for
+// a root.  Every lane that calls it reads the same LDS addresses (broadcasts).
+__device__ __forceinline__ void ik_walk(const float4* loc, const float4* rot, const uint32_t* path_lds, uint32_t pw, float4 (&W)[4], AnimVec& P) {
+    const uint8_t* path = reinterpret_cast<const uint8_t*>(path_lds) + (pw & 0xFFFFu);
+    const uint32_t len = pw >> 16;  // >= 1: the root first, a itself last
+    uint32_t j = path[0];
+#pragma unroll
+    for (int c = 0; c < 4; c++) W[c] = loc[j * 4 + c];
+    P = len > 1 ? rot[j] : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    for (uint32_t s = 1; s < len; s++) {
+        j = path[s];
+        float4 L[4], R[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) L[c] = loc[j * 4 + c];
+        if (s + 1 < len) P = anim_qmul(P, rot[j]);
+        pose_mul(W, L, R);
+#pragma unroll
+        for (int c = 0; c < 4; c++) W[c] = R[c];
+    }
+}
+
+// One workgroup per instance, one thread per joint, as anim_palettes.  Thread j keeps the (T, Q, S) of its layer stack in
+// registers and puts its local matrix into loc[] and its rotation into rot[].  Then the chains are evaluated in order.  A
+// chain whose clamped weight is 0 is skipped by the whole workgroup before any other read.  Otherwise the wave that owns
+// joint a walks a's path (every lane of it the same walk: broadcast reads, no divergence, nothing to share afterwards),
+// solves, and lane a writes the new rotations of a and b into rot[]; after a barrier the owners of a and b take their
+// rotation from rot[] and rebuild their local matrix into loc[] from their registers; a second barrier ends the chain.
+// A chain whose guard fails writes nothing, and the owners rebuild the matrix they had.
+//
+// Memory safety, extending the argument at anim_layer_fetch: nchains is a host value validated to 1..4 and the target
+// array holds ninst * nchains records of 32 bytes, so inst * nchains + k lies inside it.  From a target come the weight,
+// the position and the pole, which reach no address.  The chain records come from the IK set, which mtr_anim_ik_create
+// validated on the host (kind 0 or 1, every joint that is read < njoints, b and c the child and grandchild of a) and
+// nothing writes afterwards; a, b and c index loc[], rot[] and paths[], all of njoints entries.  paths[] and the path bytes
+// were built on the host from validated parents: an offset plus a length stays inside path_bytes, and every path byte is
+// a joint < njoints.  No device-side value forms an address.
+template <bool TRACKS, bool FOLD>
+__device__ __forceinline__ void anim_ik(const AnimIkParams& p) {
+    const PoseParams& pose = p.layers.anim.pose;
+    __shared__ float4 loc[MTR_POSE_MAX_JOINTS * 4];
+    __shared__ float4 rot[MTR_POSE_MAX_JOINTS];
+    extern __shared__ uint32_t path_lds[];  // p.path_bytes / 4 words
+    const uint32_t inst = blockIdx.x, t = threadIdx.x, J = pose.njoints, K = p.nchains;
+    AnimKey r = {};
+    if (t < J) {
+        r = anim_layer_tqs<TRACKS>(p.layers, inst, t);
+        float4 M[4];
+        anim_matrix(r, M);
+#pragma unroll
+        for (int c = 0; c < 4; c++) loc[t * 4 + c] = M[c];
+        rot[t] = r.q;
+    }
+    for (uint32_t i = t; i < p.path_bytes / 4; i += blockDim.x) path_lds[i] = p.path_words[i];
+    __syncthreads();
+    const uint4* chains = reinterpret_cast<const uint4*>(p.chains);
+    const uint4* targets = reinterpret_cast<const uint4*>(p.targets) + (size_t)inst * K * 2;
+    for (uint32_t k = 0; k < K; k++) {  // uniform for the workgroup: every barrier below is met by every wave
+        const uint4 g0 = targets[k * 2];  // pos, w
+        const float e = anim_weight(__uint_as_float(g0.w));
+        if (e == 0.0f) continue;  // untouched, bit for bit; no other target field is read
+        const uint4 g1 = targets[k * 2 + 1];  // pole, pad
+        const uint4 c0 = chains[k * 2], c1 = chains[k * 2 + 1];  // kind, a, b, c | axis, flags
+        const bool two = c0.x == 0u;  // MTR_IK_TWO_BONE; otherwise MTR_IK_AIM, which reads neither b nor c
+        const uint32_t a = c0.y, b = c0.z;
+        if ((t >> 6) == (a >> 6)) {
+            float4 W[4];
+            AnimVec P, qa = rot[a];
+            ik_walk(loc, rot, path_lds, p.paths[a], W, P);
+            const IkVec3 pa = ik_vec3(W[3].x, W[3].y, W[3].z);
+            const IkVec3 g = ik_vec3(__uint_as_float(g0.x), __uint_as_float(g0.y), __uint_as_float(g0.z));
+            if (two) {
+                const uint32_t c = c0.w;
+                float4 L[4], Wb[4], Wc[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) L[i] = loc[b * 4 + i];
+                pose_mul(W, L, Wb);
+#pragma unroll
+                for (int i = 0; i < 4; i++) L[i] = loc[c * 4 + i];
+                pose_mul(Wb, L, Wc);
+                AnimVec qb = rot[b];
+                const IkVec3 pole = ik_vec3(__uint_as_float(g1.x), __uint_as_float(g1.y), __uint_as_float(g1.z));
+                const bool hit = ik_two_bone(pa, ik_vec3(Wb[3].x, Wb[3].y, Wb[3].z), ik_vec3(Wc[3].x, Wc[3].y, Wc[3].z), P, qa, qb, g, pole,
+                                             (c1.w & 1u) != 0u, e);
+                if (hit && t == a) { rot[a] = qa; rot[b] = qb; }
+            } else {
+                const IkVec3 axis = ik_vec3(__uint_as_float(c1.x), __uint_as_float(c1.y), __uint_as_float(c1.z));
+                const bool hit = ik_aim(pa, P, qa, axis, g, e);
+                if (hit && t == a) rot[a] = qa;
+            }
+        }
+        __syncthreads();
+        if (t == a || (two && t == b)) {
+            r.q = rot[t];
+            float4 M[4];
+            anim_matrix(r, M);
+#pragma unroll
+            for (int c = 0; c < 4; c++) loc[t * 4 + c] = M[c];
+        }
+        __syncthreads();
+    }
+    if (t >= J) return;
+    if constexpr (FOLD) {
+        pose_fold_store(pose, loc, path_lds, inst, t);
+    } else {
+        float4* out = reinterpret_cast<float4*>(pose.out + ((size_t)inst * J + t) * 16);
+#pragma unroll
+        for (int c = 0; c < 4; c++) out[c] = loc[t * 4 + c];
+    }
+}
+
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_ik(AnimIkParams p) { anim_ik<false, true>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_ik_sample(AnimIkParams p) { anim_ik<false, false>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_ik_tracks(AnimIkParams p) { anim_ik<true, true>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_ik_tracks_sample(AnimIkParams p) { anim_ik<true, false>(p); }
 
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim(AnimParams p) { anim_palettes<false>(p); }
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_sample(AnimParams p) { anim_locals<false>(p); }
@@ -377,4 +494,33 @@ void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t nin
     if (!anim_layers_launchable(p, ninst, true)) return;
     const uint32_t threads = (p.anim.pose.njoints + 63u) & ~63u;
     hipLaunchKernelGGL(mtr::k_anim_layers_tracks_sample, dim3(ninst), dim3(threads), 0, s, p);
+}
+
+static bool anim_ik_launchable(const AnimIkParams& p, uint32_t ninst, bool tracks) {
+    return anim_layers_launchable(p.layers, ninst, tracks) && p.chains && p.targets && p.paths && p.path_words && p.nchains >= 1u &&
+           p.nchains <= MTR_ANIM_MAX_IK && p.path_bytes != 0u && p.path_bytes <= MTR_POSE_MAX_PATH_BYTES;
+}
+
+void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_ik_launchable(p, ninst, false) || p.layers.anim.pose.path_bytes != p.path_bytes) return;
+    const uint32_t threads = (p.layers.anim.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_ik, dim3(ninst), dim3(threads), p.path_bytes, s, p);
+}
+
+void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_ik_launchable(p, ninst, false)) return;
+    const uint32_t threads = (p.layers.anim.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_ik_sample, dim3(ninst), dim3(threads), p.path_bytes, s, p);
+}
+
+void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_ik_launchable(p, ninst, true) || p.layers.anim.pose.path_bytes != p.path_bytes) return;
+    const uint32_t threads = (p.layers.anim.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_ik_tracks, dim3(ninst), dim3(threads), p.path_bytes, s, p);
+}
+
+void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
+    if (!anim_ik_launchable(p, ninst, true)) return;
+    const uint32_t threads = (p.layers.anim.pose.njoints + 63u) & ~63u;
+    hipLaunchKernelGGL(mtr::k_anim_ik_tracks_sample, dim3(ninst), dim3(threads), p.path_bytes, s, p);
 }

@@ -503,3 +503,20 @@ void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_
 void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);
+// inverse kinematics after the layer stack (k_anim.hip, SPEC.md section 17): per instance nchains targets over the chains
+// of an IK set.  paths / path_words: the skeleton's path table and path bytes that the chain walks read -- the model's own
+// (the same memory as layers.anim.pose's) where the palettes are folded, the IK set's copy where the locals are sampled
+#define MTR_ANIM_MAX_IK 4
+struct AnimIkParams {
+    AnimLayerParams layers;
+    const uint32_t* chains;     // nchains x 8 words (mtr_ik_chain: kind, joint[3], axis[3] (f32 bits), flags), validated on the host
+    const uint32_t* targets;    // ninst x nchains x 8 words (mtr_ik_target: pos[3], w, pole[3], pad); 16-byte aligned
+    const uint32_t* paths;      // njoints: offset of joint j's path in path_words (bytes) | its length << 16
+    const uint32_t* path_words; // path_bytes / 4 words
+    uint32_t nchains;           // 1..MTR_ANIM_MAX_IK, a validated host value
+    uint32_t path_bytes;
+};
+void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s);

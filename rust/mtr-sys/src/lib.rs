@@ -70,7 +70,7 @@ pub const MTR_OWN_SUPERTILES: u32 = 2;
 pub const MTR_TEXRES_DECODED: u32 = 0;
 pub const MTR_TEXRES_BLOCKS: u32 = 1;
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks);
+opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik);
 
 /// animation clips (mtr.h, SPEC.md section 14): one key of one joint, 48 bytes
 pub const MTR_CLIP_LOOP: u32 = 1;
@@ -105,6 +105,27 @@ pub struct mtr_anim_layer {
     pub w: f32,
     pub mask: u16,
     pub mode: u16,
+}
+/// inverse kinematics (mtr.h, SPEC.md section 17): a chain of an IK set and one instance's target for it, 32 bytes each
+pub const MTR_ANIM_MAX_IK: usize = 4;
+pub const MTR_IK_TWO_BONE: u32 = 0;
+pub const MTR_IK_AIM: u32 = 1;
+pub const MTR_IK_POLE: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_ik_chain {
+    pub kind: u32,
+    pub joint: [u32; 3],
+    pub axis: [f32; 3],
+    pub flags: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_ik_target {
+    pub pos: [f32; 3],
+    pub w: f32,
+    pub pole: [f32; 3],
+    pub pad: u32,
 }
 /// what one instance plays: clip A at x_a cross-faded by w with clip B at x_b, positions in keys; 24 bytes
 #[repr(C)]
@@ -219,5 +240,18 @@ extern "C" {
                                            layers_dev: *const mtr_anim_layer, nlayers: usize, hip_stream: *mut c_void) -> i32;
     pub fn mtr_anim_sample_layers(anim: *mut mtr_anim, masks: *mut mtr_anim_masks, layers: *const mtr_anim_layer, nlayers: usize, n: usize,
                                   out_locals: *mut f32, count: usize) -> i32;
+    // inverse kinematics (SPEC.md section 17): declarations only
+    pub fn mtr_anim_ik_create(dev: *mut mtr_device, njoints: usize, parents: *const u8, nchains: usize, chains: *const mtr_ik_chain,
+                              out: *mut *mut mtr_anim_ik) -> i32;
+    pub fn mtr_anim_ik_destroy(ik: *mut mtr_anim_ik);
+    pub fn mtr_model_animate_ik(model: *mut mtr_model, anim: *mut mtr_anim, masks: *mut mtr_anim_masks, layers: *const mtr_anim_layer,
+                                nlayers: usize, ik: *mut mtr_anim_ik, targets: *const mtr_ik_target) -> i32;
+    pub fn mtr_batch_animate_ik(batch: *mut mtr_batch, anim: *mut mtr_anim, masks: *mut mtr_anim_masks, layers: *const mtr_anim_layer,
+                                nlayers: usize, ik: *mut mtr_anim_ik, targets: *const mtr_ik_target) -> i32;
+    pub fn mtr_batch_animate_ik_device(batch: *mut mtr_batch, anim: *mut mtr_anim, masks: *mut mtr_anim_masks,
+                                       layers_dev: *const mtr_anim_layer, nlayers: usize, ik: *mut mtr_anim_ik,
+                                       targets_dev: *const mtr_ik_target, hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_sample_ik(anim: *mut mtr_anim, masks: *mut mtr_anim_masks, ik: *mut mtr_anim_ik, layers: *const mtr_anim_layer,
+                              nlayers: usize, targets: *const mtr_ik_target, n: usize, out_locals: *mut f32, count: usize) -> i32;
 }
 pub mod files;

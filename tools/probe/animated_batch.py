@@ -13,7 +13,14 @@ states say: the same two clips, positions and weight), layers2_tracks (the same 
 layers in a torch tensor), layers4 (two more layers on top: a masked OVERRIDE and an ADDITIVE layer of a delta clip that
 anim_layers.delta_clip made), layers2_only / layers4_only (device layers, no frames: k_anim_layers alone).  The clip
 set (four clips of 120 / 60 / 31 / 2 keys, small bends about z) and the states are generated from --seed.
-    python tools/probe/animated_batch.py [--only c3|c5] [--frames N] [--reps R] [--modes static,host,anim] [--seed S] [--json OUT]"""
+Inverse kinematics (SPEC.md section 17): anim_ik (Batch.animate_ik(numpy, numpy): three layers -- a base, an OVERRIDE and a
+masked OVERRIDE -- and two chains per instance, a TWO_BONE reach with a pole on joints (61, 62, 63) and an AIM at joint 63, at
+weight 1), anim_ik_device (layers and targets in torch tensors), ik_only (device records, no frames: k_anim_ik alone) and
+layers_only (the same three layers without the chains, no frames: k_anim_layers alone, the yardstick in the same run).
+--skeleton chain (the 64-joint chain: both chains walk a path of 62 / 64 joints) or shallow (four chains of 16 joints: paths
+of at most 16).
+    python tools/probe/animated_batch.py [--only c3|c5] [--frames N] [--reps R] [--modes static,host,anim] [--seed S] [--json OUT]
+                                         [--skeleton chain|shallow]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
@@ -28,9 +35,13 @@ ap.add_argument("--modes", default="static,host,device,device_side_stream,poses_
 ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--json", default=None)
 ap.add_argument("--tol", type=float, default=1e-4)
+ap.add_argument("--skeleton", default="chain", choices=("chain", "shallow"))
 args = ap.parse_args()
 modes = args.modes.split(",")
 CHAIN = [255] + list(range(63))  # mesh50k's 64 bones run along the capsule: a chain
+if args.skeleton == "shallow":   # four chains of 16: no path longer than 16 joints
+    CHAIN = [255 if j % 16 == 0 else j - 1 for j in range(64)]
+IK_MODES = ("anim_ik", "anim_ik_device", "ik_only", "layers_only")
 
 
 def poses(rng, n, k):
@@ -95,7 +106,8 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
     devp = [torch.tensor(p, device="cuda:0") for p in host]
     uniform_clips = clips(rng)
     anim = api.Anim(dev, 64, uniform_clips)
-    with_layers = any(m.startswith("layers") for m in modes)
+    with_ik = any(m in IK_MODES for m in modes)
+    with_layers = with_ik or any(m.startswith("layers") for m in modes)
     sizes = None
     if any(m.startswith("tracks") or m == "layers2_tracks" for m in modes):
         track_clips = [anim_tracks.compress(k, fl, args.tol, args.tol, args.tol) for k, fl in uniform_clips]
@@ -113,6 +125,16 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
         lmasks = api.AnimMasks(dev, 64, mw)
         host_ly = {L: layers(host_st, L, rng) for L in (2, 4)}
         dev_ly = {L: [torch.from_numpy(x.view(np.uint8).reshape(n, L * 16).copy()).to("cuda:0") for x in host_ly[L]] for L in (2, 4)}
+    if with_ik:
+        chains = np.zeros(2, dtype=api.ANIM_IK_CHAIN)
+        chains["kind"], chains["flags"] = [api.IK_TWO_BONE, api.IK_AIM], [api.IK_POLE, 0]
+        chains["joint"], chains["axis"][1] = [(61, 62, 63), (63, 0, 0)], (0.0, 1.0, 0.0)
+        iks = api.AnimIK(dev, CHAIN, chains)
+        host_ly3 = [np.ascontiguousarray(x[:, :3]) for x in host_ly[4]]
+        dev_ly3 = [torch.from_numpy(x.view(np.uint8).reshape(n, 48).copy()).to("cuda:0") for x in host_ly3]
+        host_tg = np.zeros((8, n, 2), dtype=api.ANIM_IK_TARGET)
+        host_tg["pos"], host_tg["pole"], host_tg["w"] = rng.uniform(-1, 1, (8, n, 2, 3)), rng.uniform(-2, 2, (8, n, 2, 3)), 1.0
+        dev_tg = [torch.from_numpy(x.view(np.uint8).reshape(n, 64).copy()).to("cuda:0") for x in host_tg]
     loop = api.FrameLoop(dev, W, H, batch=batch, view_proj=scene.to_f32_colmajor(scene.reference_view_proj(W, H)))
 
     side = torch.cuda.Stream()
@@ -149,6 +171,16 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
             elif mode in ("layers2_only", "layers4_only"):  # device layers and no frames: k_anim_layers alone on the GPU
                 batch.animate_layers(lanim, dev_ly[int(mode[6])][k % 8], lmasks)
                 continue
+            elif mode == "anim_ik":
+                batch.animate_ik(lanim, host_ly3[k % 8], iks, host_tg[k % 8], lmasks)
+            elif mode == "anim_ik_device":
+                batch.animate_ik(lanim, dev_ly3[k % 8], iks, dev_tg[k % 8], lmasks)
+            elif mode == "ik_only":  # device records and no frames: k_anim_ik alone on the GPU
+                batch.animate_ik(lanim, dev_ly3[k % 8], iks, dev_tg[k % 8], lmasks)
+                continue
+            elif mode == "layers_only":  # the same three layers without the chains: k_anim_layers alone on the GPU
+                batch.animate_layers(lanim, dev_ly3[k % 8], lmasks)
+                continue
             elif mode == "poses_only":  # device poses and no frames: k_pose alone on the GPU
                 batch.set_poses(devp[k % 8])
                 continue
@@ -168,7 +200,7 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
         for mode in modes:
             ms[mode].append(timed(mode))
     for mode in modes:
-        r = dict(config=name, instances=n, joints=64, width=W, height=H, mode=mode, frames=args.frames,
+        r = dict(config=name, instances=n, joints=64, width=W, height=H, mode=mode, frames=args.frames, skeleton=args.skeleton,
                  ms_per_frame=round(float(np.median(ms[mode])), 4), ms_all=[round(v, 4) for v in ms[mode]])
         if sizes and mode.startswith("tracks"):
             r["clip_set"] = sizes
@@ -176,6 +208,8 @@ for name, nx, ny, W, H in (("c3", 16, 8, 1920, 1080), ("c5", 32, 32, 3840, 2160)
         print(json.dumps(r), flush=True)
     batch.close()
     anim.close()
+    if with_ik:
+        iks.close()
     if with_layers:
         lmasks.close()
         lanim.close()
