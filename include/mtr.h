@@ -358,6 +358,46 @@ int32_t mtr_batch_animate_ik_device(mtr_batch *batch, mtr_anim *anim, mtr_anim_m
 int32_t mtr_anim_sample_ik(mtr_anim *anim, mtr_anim_masks *masks /* or NULL */, mtr_anim_ik *ik, const mtr_anim_layer *layers,
                            size_t nlayers, const mtr_ik_target *targets, size_t n, float *out_locals, size_t count);
 
+/* ---- attachments (build extension, SPEC.md section 18): instance matrices from another batch's joints (k_attach) ----
+ * An object rigidly attached to joint j of instance s of a source batch is a vertex skinned to j with weight 1, so its
+ * instance matrix is M_src[s] * palette[s][j] * offset, offset being where the object sits in the source model's BIND
+ * space (inverse(imat_j) * a placement relative to the joint; in Python, mt_renderer_amd/attach.py: bind_offsets).  One
+ * record per instance of the attached batch:
+ *   src_instance, joint : clamped to the source's instance and palette counts, never rejected; joint ==
+ *                         MTR_ATTACH_NO_JOINT (or a source without palettes) follows the source instance's matrix alone;
+ *   flags               : bit 0, MTR_ATTACH_POSITION_ONLY: the object follows the joint's position and keeps the orientation
+ *                         and scale of its offset (name tags, blob shadows); the other bits and pad are not read.
+ * The products are section 12's fma chain, (M_src * palette) * offset in that association, so a numpy model reproduces
+ * the matrices bit for bit.
+ * Every attach call is ONE SHOT, like every animate call: it reads the source's CURRENT version (waiting, on the device,
+ * for that version's pending write: an animate call just before it) and writes a fresh version of `batch` whose
+ * instance matrices are the kernel's; the batch's palettes and npal are kept.  Frames drawn afterwards wait for it; a
+ * draw uses what was current when it was recorded.  The source is not tied to the batch: animate the source again and
+ * attach again.  batch == src is allowed (instance 3 rides instance 0 of the same batch): the call reads the current
+ * version and writes a fresh one.  A chain of attachments is the host's call order: attach the rider to the mount, then
+ * the sword to the rider.  The source may be updated or destroyed directly after the call: the version the kernel reads
+ * is kept until the kernel has run (no host wait).  Sources are batches on the same device; a single character drawn
+ * with mtr_frame_draw_model is not one -- make it a batch of one.
+ * MTR_E_INVALID, nothing changed: a NULL handle or pointer, src on another device, a misaligned device pointer, n == 0 or
+ * n > 2^27 or count < n * 16 for the socket calls.  MTR_E_UNSUPPORTED: a library built without k_attach. */
+#define MTR_ATTACH_NO_JOINT      0xFFFFFFFFu
+#define MTR_ATTACH_POSITION_ONLY 1u
+typedef struct mtr_attach { uint32_t src_instance, joint, flags, pad; float offset[16]; } mtr_attach;   /* 80 bytes */
+/* one record per instance of batch (host memory, free on return) */
+int32_t mtr_batch_attach(mtr_batch *batch, mtr_batch *src, const mtr_attach *recs /* batch's n, host */);
+/* the same from device memory, read in stream order on hip_stream with the rules of mtr_batch_set_poses_device */
+int32_t mtr_batch_attach_device(mtr_batch *batch, mtr_batch *src, const mtr_attach *recs_dev /* 16-byte aligned */,
+                                void *hip_stream /* as mtr_batch_set_poses_device */);
+/* the matrices alone, for the host's own use (emitters, hit boxes): n records against src's current version, n x 16 floats
+ * out.  Host memory; waits for the result */
+int32_t mtr_batch_sockets(mtr_batch *src, const mtr_attach *recs, size_t n, float *out, size_t count /* >= n * 16 */);
+/* device memory (both 16-byte aligned), in stream order on hip_stream; no wait */
+int32_t mtr_batch_sockets_device(mtr_batch *src, const mtr_attach *recs_dev, size_t n, float *out_dev,
+                                 void *hip_stream /* as mtr_batch_set_poses_device */);
+/* test / debug hook next to mtr_batch_read_palettes: the batch's current instance matrices (n x 16 floats; count = room in
+ * floats), after its pending update has completed */
+int32_t mtr_batch_read_model_mats(mtr_batch *batch, float *out, size_t count);
+
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],
                         float clear_depth, mtr_frame **out);

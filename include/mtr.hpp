@@ -259,6 +259,26 @@ class Batch {
         dev_.check(mtr_batch_animate_ik_device(h_, anim.handle(), masks ? masks->handle() : nullptr, layers_dev, nlayers, ik.handle(), targets_dev, hip_stream));
         npal_ = anim.njoints();
     }
+    // instance matrices from the joints of src's current version (SPEC.md section 18): one record per instance, host memory
+    // or device memory read in stream order; one shot, the palettes are kept; src may be this batch
+    void attach(const Batch& src, const mtr_attach* recs) { dev_.check(mtr_batch_attach(h_, src.handle(), recs)); }
+    void attach_device(const Batch& src, const mtr_attach* recs_dev, void* hip_stream = nullptr) {
+        dev_.check(mtr_batch_attach_device(h_, src.handle(), recs_dev, hip_stream));
+    }
+    // the matrices alone, n x 16 floats, of n records against THIS batch: to host memory (waits), or in stream order
+    std::vector<float> sockets(const mtr_attach* recs, size_t n) const {
+        std::vector<float> out(n * 16);
+        dev_.check(mtr_batch_sockets(h_, recs, n, out.data(), out.size()));
+        return out;
+    }
+    void sockets_device(const mtr_attach* recs_dev, size_t n, float* out_dev, void* hip_stream = nullptr) const {
+        dev_.check(mtr_batch_sockets_device(h_, recs_dev, n, out_dev, hip_stream));
+    }
+    std::vector<float> read_model_mats() const {
+        std::vector<float> out(n_ * 16);
+        dev_.check(mtr_batch_read_model_mats(h_, out.data(), out.size()));
+        return out;
+    }
     std::vector<float> read_palettes() const {
         std::vector<float> out(n_ * npal_ * 16);
         dev_.check(mtr_batch_read_palettes(h_, out.data(), out.size()));

@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "mtr_batch_animate_layers_device", "mtr_anim_sample_layers",
     "mtr_anim_ik_create", "mtr_anim_ik_destroy", "mtr_model_animate_ik", "mtr_batch_animate_ik", "mtr_batch_animate_ik_device",
     "mtr_anim_sample_ik",
+    "mtr_batch_attach", "mtr_batch_attach_device", "mtr_batch_sockets", "mtr_batch_sockets_device", "mtr_batch_read_model_mats",
 ]
 
 CLIP_LOOP = 1
@@ -70,6 +71,10 @@ ANIM_MAX_IK = 4
 IK_TWO_BONE = 0
 IK_AIM = 1
 IK_POLE = 1
+# mtr_attach (SPEC.md section 18): one attached instance
+ATTACH = np.dtype([("src_instance", "<u4"), ("joint", "<u4"), ("flags", "<u4"), ("pad", "<u4"), ("offset", "<f4", 16)])
+ATTACH_NO_JOINT = 0xFFFFFFFF
+ATTACH_POSITION_ONLY = 1
 
 
 class MtrError(RuntimeError):
@@ -210,6 +215,11 @@ def _load() -> C.CDLL:
         "mtr_batch_animate_ik": (i32, [vp, vp, vp, vp, sz, vp, vp]),
         "mtr_batch_animate_ik_device": (i32, [vp, vp, vp, vp, sz, vp, vp, vp]),
         "mtr_anim_sample_ik": (i32, [vp, vp, vp, vp, sz, vp, sz, vp, sz]),
+        "mtr_batch_attach": (i32, [vp, vp, vp]),
+        "mtr_batch_attach_device": (i32, [vp, vp, vp, vp]),
+        "mtr_batch_sockets": (i32, [vp, vp, sz, vp, sz]),
+        "mtr_batch_sockets_device": (i32, [vp, vp, sz, vp, vp]),
+        "mtr_batch_read_model_mats": (i32, [vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -554,6 +564,34 @@ def ik_targets(targets, n: Optional[int], K: int) -> np.ndarray:
     return tg
 
 
+def attach_records(recs, n: Optional[int]) -> np.ndarray:
+    """attachment records as a contiguous flat ATTACH array (SPEC.md section 18): from a structured array of that dtype, or
+    from a dict of src_instance ([n]), optionally joint ([n], missing = ATTACH_NO_JOINT), flags ([n], missing = 0) and
+    offset ([n, 16], column-major, missing = the identity)"""
+    if isinstance(recs, dict):
+        unknown = set(recs) - {"src_instance", "joint", "flags", "offset"}
+        if unknown or "src_instance" not in recs:
+            raise MtrError(MTR_E_INVALID, "attach records: src_instance, optionally joint, flags and offset")
+        si = np.asarray(recs["src_instance"], dtype=np.uint32).reshape(-1)
+        rc = np.zeros(si.shape[0], dtype=ATTACH)
+        rc["src_instance"], rc["joint"] = si, ATTACH_NO_JOINT
+        rc["offset"] = np.eye(4, dtype=np.float32).reshape(16)
+        if "joint" in recs:
+            rc["joint"] = np.asarray(recs["joint"], dtype=np.uint32).reshape(-1)
+        if "flags" in recs:
+            rc["flags"] = np.asarray(recs["flags"], dtype=np.uint32).reshape(-1)
+        if "offset" in recs:
+            rc["offset"] = _f32(recs["offset"]).reshape(-1, 16)
+    else:
+        a = np.asarray(recs)
+        if a.dtype != ATTACH or a.size == 0:
+            raise MtrError(MTR_E_INVALID, "attach records: an array of dtype ATTACH or a dict of its fields")
+        rc = np.ascontiguousarray(a).reshape(-1)
+    if n is not None and rc.shape[0] != n:
+        raise MtrError(MTR_E_INVALID, f"attach records: {n} expected, {rc.shape[0]} given")
+    return rc
+
+
 class AnimIK:
     """An IK set (include/mtr.h, SPEC.md section 17): the parents of a skeleton of ``njoints`` joints (a root: 255 or itself)
     and 1 to 4 chains, an ANIM_IK_CHAIN array or a list of dicts of its fields (kind, joint, optionally axis and flags)."""
@@ -877,6 +915,52 @@ class Batch:
             tt.record_stream(side)
             cur.wait_stream(side)
         self.npal = anim.njoints
+
+    def attach(self, src: "Batch", recs, stream=None):
+        """instance matrices from the joints of ``src``'s current version (k_attach, SPEC.md section 18): one ATTACH record
+        per instance.  One shot: animate ``src`` again, attach again.  A structured numpy array (or a dict of ATTACH's
+        fields) is copied in; a torch uint8 [n, 80] / int32 / float32 [n, 20] tensor on the batch's device holding ATTACH
+        records is read in stream order on ``stream`` (a torch stream; None: torch.cuda.current_stream()).  The batch's
+        palettes and npal are kept; ``src`` may be the batch itself."""
+        if isinstance(recs, (np.ndarray, dict)):
+            rc = attach_records(recs, self.n)
+            self.dev.check(lib.mtr_batch_attach(self._h, src._h, _p(rc)))
+            return
+        import torch
+        t = recs
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32, torch.float32):
+            raise MtrError(MTR_E_INVALID, "attach: a numpy ATTACH array, a dict, or a uint8 / int32 / float32 tensor on the GPU")
+        if t.get_device() != self.dev.hip_device:
+            raise MtrError(MTR_E_INVALID, f"attach: the tensor is on cuda:{t.get_device()}, the batch on cuda:{self.dev.hip_device}")
+        if t.numel() * t.element_size() != self.n * ATTACH.itemsize:
+            raise MtrError(MTR_E_INVALID, "attach: n records of 80 bytes")
+        cur = stream if stream is not None else torch.cuda.current_stream(t.device)
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            with torch.cuda.stream(cur):
+                t = t.contiguous().clone()
+        if cur.cuda_stream != 0:
+            self.dev.check(lib.mtr_batch_attach_device(self._h, src._h, C.c_void_p(t.data_ptr()), C.c_void_p(cur.cuda_stream)))
+            t.record_stream(cur)
+        else:  # torch's legacy default stream: as set_poses
+            side = _pose_stream(t.device)
+            side.wait_stream(cur)
+            self.dev.check(lib.mtr_batch_attach_device(self._h, src._h, C.c_void_p(t.data_ptr()), C.c_void_p(side.cuda_stream)))
+            t.record_stream(side)
+            cur.wait_stream(side)
+
+    def sockets(self, recs) -> np.ndarray:
+        """the matrices alone, [len(recs), 16]: ATTACH records (a numpy array or a dict) against THIS batch's current
+        version, for the host's own use (emitters, hit boxes).  Waits for the result."""
+        rc = attach_records(recs, None)
+        out = np.zeros((rc.shape[0], 16), dtype=np.float32)
+        self.dev.check(lib.mtr_batch_sockets(self._h, _p(rc), rc.shape[0], _p(out), out.size))
+        return out
+
+    def read_model_mats(self) -> np.ndarray:
+        """the batch's current instance matrices [n, 16], after its pending update has completed"""
+        out = np.zeros((self.n, 16), dtype=np.float32)
+        self.dev.check(lib.mtr_batch_read_model_mats(self._h, _p(out), out.size))
+        return out
 
     def read_palettes(self) -> np.ndarray:
         """the batch's current palettes [n, npal, 16], after its pending update has completed"""

@@ -306,7 +306,14 @@ struct mtr_batch {
     // is held or in flight (up to max_inflight + 1 before it waits for a frame), so the steady state allocates nothing.
     // d: n model matrices, then n * npal palette matrices (cap floats); ready: the last write into d (copy stream, or the
     // caller's stream of mtr_batch_set_poses_device); frames that draw the version wait on it.
-    struct Ver { float* d = nullptr; size_t cap = 0; uint32_t npal = 0; hipEvent_t ready = nullptr; uint64_t last_frame = 0; bool used = false; uint32_t pinned = 0; };
+    // read: recorded behind the last outside reader of d, a k_attach launched for ANOTHER batch's update or for a socket call
+    // (SPEC.md section 18), on a stream this batch's updates need not share.  A reader queued on another stream than the one
+    // before first waits for it, so the one event covers every reader (as mtr_anim::last does).  read_pending: recorded since
+    // the version's last write; that write's successor waits for it, and a buffer retired meanwhile is parked behind it.
+    struct Ver {
+        float* d = nullptr; size_t cap = 0; uint32_t npal = 0; hipEvent_t ready = nullptr; uint64_t last_frame = 0; bool used = false; uint32_t pinned = 0;
+        hipEvent_t read = nullptr; hipStream_t read_stream = nullptr; bool read_pending = false;
+    };
     std::vector<Ver> vers;
     int cur = 0;
     uint32_t refs = 1;           // the handle + every recorded draw (submit_mu): the last one parks the versions

@@ -1,5 +1,7 @@
-// host_batch.cpp -- instance batches and their versions, pose and animation staging, animation clip sets, mask sets and layers, IK sets.
+// host_batch.cpp -- instance batches and their versions, pose and animation staging, animation clip sets, mask sets and layers, IK sets,
+// attachments.
 #include "host.h"
+#include "attach_math.h"
 
 // k_pose.hip.  Weak: the host-only builds of this file (tests/cpp, over the HIP stub runtime) link no kernels and never
 // form a pose; libmtr.so links k_pose.o.
@@ -17,6 +19,8 @@ void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __
 void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+// k_attach.hip, weak for the same reason
+void mtr_launch_attach(const AttachParams& p, hipStream_t s) __attribute__((weak));
 
 namespace mtr_host {
 
@@ -163,24 +167,75 @@ namespace {
 
 // Retires the buffer of a version nobody will draw again: into `now` (released after the lock) when no frame in flight
 // reads it and its last write has completed, otherwise -- or when now is nullptr -- parked in d->garbage with the event of
-// that write, collected by a later submit.  submit_mu held.
+// that write, collected by a later submit.  A version with an outside reader pending (Ver::read, a k_attach of another
+// batch's update) is always parked, behind that reader's event: the reader waited for the write, so its event covers both,
+// and nobody asks the host whether it has run.  submit_mu held.
 void retire_version(mtr_device* d, mtr_batch::Ver& v, FreeList* now) {
     if (v.d) {
         const bool read_in_flight = v.used && !frame_done(d, v.last_frame);
         bool written = true;
         if (v.ready) { written = hipEventQuery(v.ready) == hipSuccess; (void)hipGetLastError(); }
-        if (read_in_flight || !written || !now) {
+        if (v.read_pending) {
+            d->garbage.push_back({v.d, v.used ? v.last_frame : 0, v.read});
+            v.read = nullptr;
+            if (v.ready) d->garbage.push_back({nullptr, 0, v.ready});
+            v.ready = nullptr;
+        } else if (read_in_flight || !written || !now) {
             d->garbage.push_back({v.d, v.used ? v.last_frame : 0, v.ready});
             v.ready = nullptr;
         } else {
             now->bufs.push_back(v.d);
         }
     }
-    if (v.ready) {
-        if (now) now->events.push_back(v.ready);
-        else d->garbage.push_back({nullptr, 0, v.ready});
+    for (hipEvent_t e : {v.ready, v.read}) {
+        if (!e) continue;
+        if (now) now->events.push_back(e);
+        else d->garbage.push_back({nullptr, 0, e});
     }
     v = mtr_batch::Ver{};
+}
+
+// An outside reader of a batch's current version: a k_attach that forms matrices from its instance matrices and palettes
+// (SPEC.md section 18) on a stream the batch's own updates need not share.  pin (submit_mu held) takes the current version
+// and keeps batch_next_version off it; launch (no lock: only this thread touches a pinned version's events) makes `s` wait
+// for the version's write and, when the reader before ran on another stream, for that reader, runs the kernel and records
+// Ver::read behind it; unpin (submit_mu held) publishes the event.  The next write into the version waits for it
+// (batch_write_version), and a buffer retired meanwhile is parked behind it (retire_version).
+struct SrcRead {
+    mtr_batch* b = nullptr;
+    int vi = -1;
+    mtr_batch::Ver v{};
+    bool recorded = false;
+};
+
+void src_read_pin(mtr_batch* src, SrcRead& r) {
+    r.b = src; r.vi = src->cur;
+    r.v = src->vers[(size_t)r.vi];
+    src->vers[(size_t)r.vi].pinned++;
+}
+
+int32_t src_read_launch(SrcRead& r, const void* recs_dev, size_t n, float* out_dev, hipStream_t s) {
+    mtr_device* d = r.b->dev;
+    if (!r.v.read && hipEventCreateWithFlags(&r.v.read, hipEventDisableTiming) != hipSuccess) return fail(d, MTR_E_HIP, "hipEventCreate failed");
+    if (r.v.ready) HIPCHK(d, hipStreamWaitEvent(s, r.v.ready, 0));
+    if (r.v.read_pending && r.v.read_stream != s) HIPCHK(d, hipStreamWaitEvent(s, r.v.read, 0));
+    AttachParams ap{};
+    ap.recs = static_cast<const uint32_t*>(recs_dev);
+    ap.src_mats = r.v.d; ap.src_pals = r.v.d + (size_t)r.b->n * 16;
+    ap.out = out_dev;
+    ap.n = (uint32_t)n; ap.n_src = r.b->n; ap.npal = r.v.npal;
+    mtr_launch_attach(ap, s);
+    HIPCHK(d, hipGetLastError());
+    HIPCHK(d, hipEventRecord(r.v.read, s));
+    r.recorded = true;
+    return MTR_OK;
+}
+
+void src_read_unpin(SrcRead& r, hipStream_t s) {
+    mtr_batch::Ver& v = r.b->vers[(size_t)r.vi];
+    v.read = r.v.read;
+    if (r.recorded) { v.read_pending = true; v.read_stream = s; }
+    v.pinned--;
 }
 
 }  // namespace
@@ -242,13 +297,22 @@ struct PoseSrc {
     explicit operator bool() const { return locals || anim; }
 };
 
+// the matrices of an attach call: one record per instance (device memory) against the current version of `src`
+struct AttachSrc {
+    mtr_batch* src = nullptr;
+    const void* recs = nullptr;
+};
+
 // What an update writes into a fresh version.  mats / pals: host arrays, or nullptr = keep the current version's (device
-// copy); a pose source replaces the palettes with the pose's.  Enqueued on `s`, the version made current.
-int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, uint32_t npal_new, const PoseSrc& src, hipStream_t s) {
+// copy); a pose source replaces the palettes with the pose's; an attach source (at) replaces the matrices with k_attach's.
+// Enqueued on `s`, the version made current.
+int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, uint32_t npal_new, const PoseSrc& src, hipStream_t s,
+                            const AttachSrc* at = nullptr) {
     mtr_device* d = b->dev;
     const size_t n = b->n;
     int vi = -1;
     mtr_batch::Ver cur{}, v{};
+    SrcRead rd;
     {
         std::lock_guard<std::mutex> submit_lock(d->submit_mu);
         cur = b->vers[(size_t)b->cur];
@@ -260,11 +324,12 @@ int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, 
         nv.npal = npal;
         nv.pinned++;  // nobody else takes it while it is being written
         v = nv;
+        if (at) src_read_pin(at->src, rd);  // the source's current version (b's own when batch == src: never the one written)
         // a frame still on the GPU reads it: the write waits for that frame on the device (the enqueue happens under the
         // lock, before any later frame can record the same ring event)
         if (frame_ev) {
             const hipError_t e = hipStreamWaitEvent(s, frame_ev, 0);
-            if (e != hipSuccess) { nv.pinned--; return fail(d, MTR_E_HIP, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e)); }
+            if (e != hipSuccess) { nv.pinned--; if (at) src_read_unpin(rd, s); return fail(d, MTR_E_HIP, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e)); }
         }
     }
     // only this thread touches the version's buffer and event while it is pinned
@@ -276,8 +341,12 @@ int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, 
     if (!rc && !v.ready && hipEventCreateWithFlags(&v.ready, hipEventDisableTiming) != hipSuccess) rc = fail(d, MTR_E_HIP, "hipEventCreate failed");
     auto enqueue = [&]() -> int32_t {
         HIPCHK(d, hipStreamWaitEvent(s, v.ready, 0));    // its previous write (a version may be rewritten before any draw)
+        if (v.read_pending) HIPCHK(d, hipStreamWaitEvent(s, v.read, 0));  // and a k_attach of another update that still reads it
         if (cur.ready) HIPCHK(d, hipStreamWaitEvent(s, cur.ready, 0));
-        if (mats) HIPCHK(d, hipMemcpyAsync(v.d, mats, n * 64, hipMemcpyHostToDevice, s));
+        if (at) {
+            int32_t arc = src_read_launch(rd, at->recs, n, v.d, s);
+            if (arc) return arc;
+        } else if (mats) HIPCHK(d, hipMemcpyAsync(v.d, mats, n * 64, hipMemcpyHostToDevice, s));
         else HIPCHK(d, hipMemcpyAsync(v.d, cur.d, n * 64, hipMemcpyDeviceToDevice, s));
         float* vp = v.d + n * 16;
         if (src.anim) {
@@ -308,7 +377,9 @@ int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, 
     std::lock_guard<std::mutex> submit_lock(d->submit_mu);
     mtr_batch::Ver& nv = b->vers[(size_t)vi];
     nv.d = v.d; nv.cap = v.cap; nv.ready = v.ready;
+    if (!rc) nv.read_pending = false;  // the write waited for it
     nv.pinned--;
+    if (at) src_read_unpin(rd, s);
     if (!rc) b->cur = vi;
     return rc;
 }
@@ -885,6 +956,110 @@ int32_t mtr_anim_sample_ik(mtr_anim* a, mtr_anim_masks* mk, mtr_anim_ik* ik, con
     (void)hipFree(tmp);
     if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// attachments (SPEC.md section 18)
+// ---------------------------------------------------------------------------------------------
+static_assert(sizeof(mtr_attach) == 80 && sizeof(mtr_attach) == MTR_ATTACH_WORDS * 4, "mtr_attach");
+
+int32_t mtr_batch_attach(mtr_batch* b, mtr_batch* src, const mtr_attach* recs) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!src || !recs) return fail(d, MTR_E_INVALID, "attach: no source batch or no records");
+    if (src->dev != d) return fail(d, MTR_E_INVALID, "attach: the source batch belongs to another device");
+    if (!mtr_launch_attach) return fail(d, MTR_E_UNSUPPORTED, "attach: built without k_attach");
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, reinterpret_cast<const float*>(recs), (size_t)b->n * MTR_ATTACH_WORDS))) return rc;
+    const AttachSrc at{src, d->pose_stage};
+    return batch_write_version(b, nullptr, nullptr, 0, PoseSrc{}, d->s_copy, &at);
+}
+
+int32_t mtr_batch_attach_device(mtr_batch* b, mtr_batch* src, const mtr_attach* recs_dev, void* hip_stream) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!src) return fail(d, MTR_E_INVALID, "attach: no source batch");
+    if (!recs_dev || ((uintptr_t)recs_dev & 15u)) return fail(d, MTR_E_INVALID, "attach: device records must be 16-byte aligned");
+    if (src->dev != d) return fail(d, MTR_E_INVALID, "attach: the source batch belongs to another device");
+    if (!mtr_launch_attach) return fail(d, MTR_E_UNSUPPORTED, "attach: built without k_attach");
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    const AttachSrc at{src, recs_dev};
+    return batch_write_version(b, nullptr, nullptr, 0, PoseSrc{}, s, &at);
+}
+
+int32_t mtr_batch_sockets_device(mtr_batch* src, const mtr_attach* recs_dev, size_t n, float* out_dev, void* hip_stream) {
+    if (!src) return MTR_E_INVALID;
+    mtr_device* d = src->dev;
+    if (!recs_dev || ((uintptr_t)recs_dev & 15u) || !out_dev || ((uintptr_t)out_dev & 15u))
+        return fail(d, MTR_E_INVALID, "sockets: device records and matrices must be 16-byte aligned");
+    if (n == 0 || n > (1u << 27)) return fail(d, MTR_E_INVALID, "sockets: 1 to 2^27 records");
+    if (!mtr_launch_attach) return fail(d, MTR_E_UNSUPPORTED, "sockets: built without k_attach");
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    SrcRead rd;
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        src_read_pin(src, rd);
+    }
+    rc = src_read_launch(rd, recs_dev, n, out_dev, s);
+    std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+    src_read_unpin(rd, s);
+    return rc;
+}
+
+int32_t mtr_batch_sockets(mtr_batch* src, const mtr_attach* recs, size_t n, float* out, size_t count) {
+    if (!src) return MTR_E_INVALID;
+    mtr_device* d = src->dev;
+    if (!recs || !out) return fail(d, MTR_E_INVALID, "sockets: no records or no room for the matrices");
+    if (n == 0 || n > (1u << 27) || count < n * 16) return fail(d, MTR_E_INVALID, "sockets: 1 to 2^27 records and room for n * 16 floats");
+    if (!mtr_launch_attach) return fail(d, MTR_E_UNSUPPORTED, "sockets: built without k_attach");
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    float* tmp = nullptr;  // the matrices, then the records (n * 64 bytes in: 16-byte aligned)
+    if ((rc = dev_alloc(d, &tmp, n * 16 + n * MTR_ATTACH_WORDS))) return rc;
+    SrcRead rd;
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        src_read_pin(src, rd);
+    }
+    auto run = [&]() -> int32_t {
+        HIPCHK(d, hipMemcpyAsync(tmp + n * 16, recs, n * sizeof(mtr_attach), hipMemcpyHostToDevice, d->s_copy));
+        int32_t r2 = src_read_launch(rd, tmp + n * 16, n, tmp, d->s_copy);
+        if (r2) return r2;
+        HIPCHK(d, hipMemcpyAsync(out, tmp, n * 64, hipMemcpyDeviceToHost, d->s_copy));
+        return MTR_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(d->s_copy);  // also when a step failed: the buffer is freed next
+    (void)hipFree(tmp);
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        src_read_unpin(rd, d->s_copy);
+    }
+    if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
+}
+
+int32_t mtr_batch_read_model_mats(mtr_batch* b, float* out, size_t count) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    const size_t need = (size_t)b->n * 16;
+    if (!out || count < need) return fail(d, MTR_E_INVALID, "read_model_mats: room for n * 16 floats needed");
+    mtr_batch::Ver v{};
+    {
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        v = b->vers[(size_t)b->cur];
+    }
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    HIPCHK(d, hipStreamWaitEvent(d->s_copy, v.ready, 0));
+    HIPCHK(d, hipMemcpyAsync(out, v.d, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
+    HIPCHK(d, hipStreamSynchronize(d->s_copy));
+    return MTR_OK;
 }
 
 int32_t mtr_batch_read_palettes(mtr_batch* b, float* out, size_t count) {

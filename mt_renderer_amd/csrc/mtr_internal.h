@@ -520,3 +520,12 @@ void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
+// attachments (k_attach.hip, SPEC.md section 18): n instance matrices from the matrices and palettes of a source batch's version
+struct AttachParams {
+    const uint32_t* recs;       // n x 20 words (mtr_attach: src_instance, joint, flags, pad, offset[16]); 16-byte aligned
+    const float* src_mats;      // n_src x 16: the source's instance matrices
+    const float* src_pals;      // n_src x npal x 16: its palettes (not read when npal == 0)
+    float* out;                 // n x 16
+    uint32_t n, n_src, npal;    // n_src >= 1
+};
+void mtr_launch_attach(const AttachParams& p, hipStream_t s);

@@ -127,6 +127,18 @@ pub struct mtr_ik_target {
     pub pole: [f32; 3],
     pub pad: u32,
 }
+/// attachments (mtr.h, SPEC.md section 18): one attached instance, 80 bytes; offset is column-major, in the source model's bind space
+pub const MTR_ATTACH_NO_JOINT: u32 = 0xFFFF_FFFF;
+pub const MTR_ATTACH_POSITION_ONLY: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_attach {
+    pub src_instance: u32,
+    pub joint: u32,
+    pub flags: u32,
+    pub pad: u32,
+    pub offset: [f32; 16],
+}
 /// what one instance plays: clip A at x_a cross-faded by w with clip B at x_b, positions in keys; 24 bytes
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -253,5 +265,11 @@ extern "C" {
                                        targets_dev: *const mtr_ik_target, hip_stream: *mut c_void) -> i32;
     pub fn mtr_anim_sample_ik(anim: *mut mtr_anim, masks: *mut mtr_anim_masks, ik: *mut mtr_anim_ik, layers: *const mtr_anim_layer,
                               nlayers: usize, targets: *const mtr_ik_target, n: usize, out_locals: *mut f32, count: usize) -> i32;
+    // attachments (SPEC.md section 18): declarations only
+    pub fn mtr_batch_attach(batch: *mut mtr_batch, src: *mut mtr_batch, recs: *const mtr_attach) -> i32;
+    pub fn mtr_batch_attach_device(batch: *mut mtr_batch, src: *mut mtr_batch, recs_dev: *const mtr_attach, hip_stream: *mut c_void) -> i32;
+    pub fn mtr_batch_sockets(src: *mut mtr_batch, recs: *const mtr_attach, n: usize, out: *mut f32, count: usize) -> i32;
+    pub fn mtr_batch_sockets_device(src: *mut mtr_batch, recs_dev: *const mtr_attach, n: usize, out_dev: *mut f32, hip_stream: *mut c_void) -> i32;
+    pub fn mtr_batch_read_model_mats(batch: *mut mtr_batch, out: *mut f32, count: usize) -> i32;
 }
 pub mod files;
