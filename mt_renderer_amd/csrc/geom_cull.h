@@ -18,7 +18,14 @@ namespace mtr {
 // holds for the vertices it creates.  With w_lo > 0 the screen rectangle follows by interval division; a pixel of
 // slack and 2^-20 of the coordinate cover the divide, the viewport fma and the 1/256 snap.  Anything that cannot be
 // bounded (w_lo <= 0, NaN, weights that are not normalised) is kept.
+// m_i is a RELATIVE bound: a product or sum of the vertex shader that lands among the subnormals is rounded to a
+// multiple of 2^-149 whatever its size, which no multiple of the magnitudes covers.  A clip coordinate whose sum of
+// magnitudes lies below MTR_CULL_MIN_MAG = 2^-100 is therefore not bounded at all (infinite margin: the geometry is
+// kept; tests/test_cull_model_premises.py has the matrices with subnormal rows that stepped out of the interval by
+// thousands of margins).  Above it the shader's results are normal numbers unless the POSITIONS themselves are
+// subnormal and a matrix element of 2^100 or more blows their rounding up again, which no model format produces.
 // ---------------------------------------------------------------------------------------------
+#define MTR_CULL_MIN_MAG 7.888609052210118e-31f  // 2^-100
 struct ClipBox {
     float lo[3], hi[3];  // x, y, w
 };
@@ -56,7 +63,7 @@ __device__ __forceinline__ ClipBox box_clip_interval(const BoneBox& b, const flo
                 mag += A;
             }
         }
-        const float m = mag * 1.52587890625e-05f;  // 2^-16
+        const float m = mag >= MTR_CULL_MIN_MAG ? mag * 1.52587890625e-05f : __builtin_inff();  // 2^-16; NaN: not bounded either
         r.lo[t] = v - rad - m;
         r.hi[t] = v + rad + m;
     }
@@ -93,7 +100,7 @@ __device__ __forceinline__ ClipBox box_comp_interval(const BoneBox& b, const Com
             rad += fabsf(cm.C[c * 3 + t]) * ext[c];
             mag += cm.A[c * 3 + t] * (fabsf(cen[c]) + ext[c]);
         }
-        const float m = mag * 1.52587890625e-05f;  // 2^-16
+        const float m = mag >= MTR_CULL_MIN_MAG ? mag * 1.52587890625e-05f : __builtin_inff();  // 2^-16; NaN: not bounded either
         r.lo[t] = v - rad - m;
         r.hi[t] = v + rad + m;
     }
