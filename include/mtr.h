@@ -398,6 +398,46 @@ int32_t mtr_batch_sockets_device(mtr_batch *src, const mtr_attach *recs_dev, siz
  * floats), after its pending update has completed */
 int32_t mtr_batch_read_model_mats(mtr_batch *batch, float *out, size_t count);
 
+/* ---- root motion (build extension, SPEC.md section 19): clips move their instances (k_root) ----
+ * A trajectory is joint `joint` of an ordinary animation set of either kind (uniform keys or tracks; any joint count, 1 is
+ * usual; none of its clips may carry MTR_CLIP_LOOP; scale is not read).  A root set belongs to such a set's (njoints,
+ * nclips) and holds the joint and one flag word per clip: MTR_ROOT_CYCLIC makes key N - 1 the end of the cycle, where the
+ * next cycle's key 0 stands (period N - 1).  Per instance and call there are nsteps (1..MTR_ROOT_MAX_STEPS) steps:
+ *   clip  : clamped to the set's clip count, never rejected;
+ *   x, dx : the rigid delta of the trajectory joint between position x and x + dx (in keys / ticks), across one cycle seam
+ *           where needed; a step that would cross a second seam, a NaN or an infinite dx move nothing;
+ *   w     : steps 1 .. nsteps - 1 are blended over step 0 in order by their clamped weight, as section 16's OVERRIDE layers
+ *           (a cross-fade of walk into run); step 0's w is not read, and a step of weight 0 does not read its clip.
+ * The blended delta D is a local matrix of section 14 and M_new[i] = M_old[i] * D_i in section 12's fma chain, so a numpy
+ * model reproduces the matrices bit for bit.  The library defines no clock: the host advances x by dx itself.
+ * mtr_batch_root_motion* is ONE SHOT with the frame semantics of mtr_batch_attach with batch == src: it reads the batch's
+ * current version (after its pending write) and writes a fresh one; palettes and npal are kept; a draw uses what was current
+ * when it was recorded.  The batch's model needs no skeleton.  A mount moved this way and then mtr_batch_attach carries its
+ * rider.  The trajectory set and the root set may be destroyed directly after the call (no host wait).
+ * MTR_E_INVALID, nothing changed: a NULL handle or pointer, nsteps outside 1..8, joint >= njoints, unknown flag bits
+ * (mtr_last_error names the clip), a root set whose (njoints, nclips) or device is not the trajectory set's, a trajectory set
+ * with a LOOP clip, a misaligned device pointer, n == 0 or n > 2^27 or count < n * 16 for the delta calls.
+ * MTR_E_UNSUPPORTED: a library built without k_root. */
+#define MTR_ROOT_MAX_STEPS 8
+#define MTR_ROOT_CYCLIC 1u
+typedef struct mtr_anim_root mtr_anim_root;
+typedef struct mtr_root_step { uint32_t clip; float x, dx, w; } mtr_root_step;   /* 16 bytes */
+int32_t mtr_anim_root_create(mtr_device *dev, size_t njoints, size_t nclips, uint32_t joint,
+                             const uint32_t *flags /* nclips, NULL = 0 */, mtr_anim_root **out);
+void    mtr_anim_root_destroy(mtr_anim_root *root);      /* parked like mtr_anim_destroy */
+/* nsteps steps per instance of batch, steps[inst * nsteps + i] (host memory, free on return) */
+int32_t mtr_batch_root_motion(mtr_batch *batch, mtr_anim *traj, mtr_anim_root *root, const mtr_root_step *steps /* n*nsteps, host */,
+                              size_t nsteps);
+/* the same from device memory, read in stream order on hip_stream with the rules of mtr_batch_set_poses_device */
+int32_t mtr_batch_root_motion_device(mtr_batch *batch, mtr_anim *traj, mtr_anim_root *root,
+                                     const mtr_root_step *steps_dev /* 16-byte aligned */, size_t nsteps,
+                                     void *hip_stream /* as mtr_batch_set_poses_device */);
+/* the deltas alone (character controllers, collision): n x 16 floats; the host version waits, the device version does not */
+int32_t mtr_anim_root_deltas(mtr_anim *traj, mtr_anim_root *root, const mtr_root_step *steps, size_t nsteps, size_t n, float *out,
+                             size_t count /* >= n * 16 */);
+int32_t mtr_anim_root_deltas_device(mtr_anim *traj, mtr_anim_root *root, const mtr_root_step *steps_dev, size_t nsteps, size_t n,
+                                    float *out_dev /* 16-byte aligned */, void *hip_stream);
+
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],
                         float clear_depth, mtr_frame **out);

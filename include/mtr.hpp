@@ -165,6 +165,32 @@ class AnimIK {
     mtr_anim_ik* h_ = nullptr;
 };
 
+// A root set (include/mtr.h, SPEC.md section 19): the trajectory joint and one flag word per clip (MTR_ROOT_CYCLIC) for
+// trajectory sets of njoints joints and nclips clips
+class AnimRoot {
+  public:
+    AnimRoot(const Device& dev, size_t njoints, size_t nclips, uint32_t joint = 0, const uint32_t* flags = nullptr) : dev_(dev) {
+        dev.check(mtr_anim_root_create(dev.handle(), njoints, nclips, joint, flags, &h_));
+    }
+    AnimRoot(AnimRoot&& o) noexcept : dev_(o.dev_), h_(std::exchange(o.h_, nullptr)) {}
+    AnimRoot(const AnimRoot&) = delete;
+    ~AnimRoot() { mtr_anim_root_destroy(h_); }
+    // the delta matrices alone, n x 16 floats, of n * nsteps steps on traj: to host memory (waits), or in stream order
+    std::vector<float> deltas(const Anim& traj, const mtr_root_step* steps, size_t nsteps, size_t n) const {
+        std::vector<float> out(n * 16);
+        dev_.check(mtr_anim_root_deltas(traj.handle(), h_, steps, nsteps, n, out.data(), out.size()));
+        return out;
+    }
+    void deltas_device(const Anim& traj, const mtr_root_step* steps_dev, size_t nsteps, size_t n, float* out_dev, void* hip_stream = nullptr) const {
+        dev_.check(mtr_anim_root_deltas_device(traj.handle(), h_, steps_dev, nsteps, n, out_dev, hip_stream));
+    }
+    mtr_anim_root* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    mtr_anim_root* h_ = nullptr;
+};
+
 class Model {
   public:
     // Model::new(model_file, material_file, shader2, resource_manager, device, queue, ..) -- src/model.rs:36-45
@@ -264,6 +290,14 @@ class Batch {
     void attach(const Batch& src, const mtr_attach* recs) { dev_.check(mtr_batch_attach(h_, src.handle(), recs)); }
     void attach_device(const Batch& src, const mtr_attach* recs_dev, void* hip_stream = nullptr) {
         dev_.check(mtr_batch_attach_device(h_, src.handle(), recs_dev, hip_stream));
+    }
+    // M := M * D, D the blended delta of nsteps steps per instance on the trajectory set (SPEC.md section 19): host memory or
+    // device memory read in stream order; one shot, the palettes are kept
+    void root_motion(const Anim& traj, const AnimRoot& root, const mtr_root_step* steps, size_t nsteps) {
+        dev_.check(mtr_batch_root_motion(h_, traj.handle(), root.handle(), steps, nsteps));
+    }
+    void root_motion_device(const Anim& traj, const AnimRoot& root, const mtr_root_step* steps_dev, size_t nsteps, void* hip_stream = nullptr) {
+        dev_.check(mtr_batch_root_motion_device(h_, traj.handle(), root.handle(), steps_dev, nsteps, hip_stream));
     }
     // the matrices alone, n x 16 floats, of n records against THIS batch: to host memory (waits), or in stream order
     std::vector<float> sockets(const mtr_attach* recs, size_t n) const {

@@ -51,6 +51,8 @@ EXPORTED_SYMBOLS = [
     "mtr_anim_ik_create", "mtr_anim_ik_destroy", "mtr_model_animate_ik", "mtr_batch_animate_ik", "mtr_batch_animate_ik_device",
     "mtr_anim_sample_ik",
     "mtr_batch_attach", "mtr_batch_attach_device", "mtr_batch_sockets", "mtr_batch_sockets_device", "mtr_batch_read_model_mats",
+    "mtr_anim_root_create", "mtr_anim_root_destroy", "mtr_batch_root_motion", "mtr_batch_root_motion_device", "mtr_anim_root_deltas",
+    "mtr_anim_root_deltas_device",
 ]
 
 CLIP_LOOP = 1
@@ -75,6 +77,10 @@ IK_POLE = 1
 ATTACH = np.dtype([("src_instance", "<u4"), ("joint", "<u4"), ("flags", "<u4"), ("pad", "<u4"), ("offset", "<f4", 16)])
 ATTACH_NO_JOINT = 0xFFFFFFFF
 ATTACH_POSITION_ONLY = 1
+# mtr_root_step (SPEC.md section 19): one step of an instance's root motion
+ROOT_STEP = np.dtype([("clip", "<u4"), ("x", "<f4"), ("dx", "<f4"), ("w", "<f4")])
+ROOT_MAX_STEPS = 8
+ROOT_CYCLIC = 1
 
 
 class MtrError(RuntimeError):
@@ -220,6 +226,12 @@ def _load() -> C.CDLL:
         "mtr_batch_sockets": (i32, [vp, vp, sz, vp, sz]),
         "mtr_batch_sockets_device": (i32, [vp, vp, sz, vp, vp]),
         "mtr_batch_read_model_mats": (i32, [vp, vp, sz]),
+        "mtr_anim_root_create": (i32, [vp, sz, sz, C.c_uint32, vp, vp]),
+        "mtr_anim_root_destroy": (None, [vp]),
+        "mtr_batch_root_motion": (i32, [vp, vp, vp, vp, sz]),
+        "mtr_batch_root_motion_device": (i32, [vp, vp, vp, vp, sz, vp]),
+        "mtr_anim_root_deltas": (i32, [vp, vp, vp, sz, sz, vp, sz]),
+        "mtr_anim_root_deltas_device": (i32, [vp, vp, vp, sz, sz, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -592,6 +604,89 @@ def attach_records(recs, n: Optional[int]) -> np.ndarray:
     return rc
 
 
+def root_steps(steps, n: Optional[int]) -> np.ndarray:
+    """root-motion steps as a contiguous ROOT_STEP array [n, S] (SPEC.md section 19): from a structured array [n, S] or [n]
+    of that dtype, or from a dict of its fields (clip, x, dx, optionally w; each [n, S] or [n])"""
+    if isinstance(steps, dict):
+        if set(steps) - set(ROOT_STEP.names) or not {"clip", "x", "dx"} <= set(steps):
+            raise MtrError(MTR_E_INVALID, "root steps: clip, x and dx, optionally w")
+        x = np.asarray(steps["x"], dtype=np.float32)
+        st = np.zeros(x.shape if x.ndim == 2 else (x.size, 1), dtype=ROOT_STEP)
+        for k, v in steps.items():
+            st[k] = np.asarray(v).reshape(st.shape)
+    else:
+        st = np.asarray(steps)
+        if st.dtype != ROOT_STEP or st.ndim not in (1, 2):
+            raise MtrError(MTR_E_INVALID, "root steps: an array [n, S] of dtype ROOT_STEP or a dict of its fields")
+        st = st.reshape(st.shape[0], -1)
+    if n is not None and st.shape[0] != n:
+        raise MtrError(MTR_E_INVALID, f"root steps: {n} instances expected, {st.shape[0]} given")
+    return np.ascontiguousarray(st)
+
+
+class AnimRoot:
+    """A root set (include/mtr.h, SPEC.md section 19) for trajectory sets of ``njoints`` joints and ``nclips`` clips: the
+    trajectory joint and one flag word per clip (0 or ROOT_CYCLIC; None: all 0)."""
+
+    def __init__(self, dev: Device, njoints: int, nclips: int, joint: int = 0, flags=None):
+        fl = None if flags is None else np.ascontiguousarray(np.asarray(flags, dtype=np.uint32).reshape(-1))
+        if fl is not None and fl.size != nclips:
+            raise MtrError(MTR_E_INVALID, "anim root: one flag word per clip")
+        if not 0 <= joint <= 0xFFFFFFFF:
+            raise MtrError(MTR_E_INVALID, "anim root: the trajectory joint lies past the set's joints")
+        h = C.c_void_p()
+        dev.check(lib.mtr_anim_root_create(dev._h, njoints, nclips, joint, _p(fl), C.byref(h)))
+        self.dev, self._h, self.njoints, self.nclips, self.joint = dev, h, njoints, nclips, joint
+
+    def deltas(self, traj: "Anim", steps) -> np.ndarray:
+        """the delta matrices alone, [n, 16], of the given steps ([n, S]) on the trajectory set ``traj`` (character controllers,
+        collision).  A numpy ROOT_STEP array or a dict is copied in and the result waited for; a torch uint8 [n, S, 16] /
+        int32 / float32 [n, S, 4] tensor on the GPU is read in stream order on torch.cuda.current_stream() and a float32
+        tensor [n, 16] on the GPU is returned without a wait."""
+        if isinstance(steps, (np.ndarray, dict)):
+            st = root_steps(steps, None)
+            out = np.zeros((st.shape[0], 16), dtype=np.float32)
+            self.dev.check(lib.mtr_anim_root_deltas(traj._h, self._h, _p(st), st.shape[1], st.shape[0], _p(out), out.size))
+            return out
+        import torch
+        t = _root_tensor(steps, self.dev, "root deltas")
+        if t.dim() != 3:
+            raise MtrError(MTR_E_INVALID, "root deltas: a tensor [n, S, 16 bytes]")
+        cur = torch.cuda.current_stream(t.device)
+        with torch.cuda.stream(cur):
+            if not t.is_contiguous() or t.data_ptr() % 16:
+                t = t.contiguous().clone()
+            out = torch.empty((t.shape[0], 16), dtype=torch.float32, device=t.device)
+        args = (traj._h, self._h, C.c_void_p(t.data_ptr()), t.shape[1], t.shape[0], C.c_void_p(out.data_ptr()))
+        if cur.cuda_stream != 0:
+            self.dev.check(lib.mtr_anim_root_deltas_device(*args, C.c_void_p(cur.cuda_stream)))
+            t.record_stream(cur)
+        else:  # torch's legacy default stream: as set_poses
+            side = _pose_stream(t.device)
+            side.wait_stream(cur)
+            self.dev.check(lib.mtr_anim_root_deltas_device(*args, C.c_void_p(side.cuda_stream)))
+            t.record_stream(side)
+            out.record_stream(side)
+            cur.wait_stream(side)
+        return out
+
+    def close(self):
+        if self._h:
+            lib.mtr_anim_root_destroy(self._h)
+            self._h = None
+
+
+def _root_tensor(t, dev: "Device", what: str):
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32, torch.float32):
+        raise MtrError(MTR_E_INVALID, f"{what}: a numpy ROOT_STEP array, a dict, or a uint8 / int32 / float32 tensor on the GPU")
+    if t.get_device() != dev.hip_device:
+        raise MtrError(MTR_E_INVALID, f"{what}: the tensor is on cuda:{t.get_device()}, the device is cuda:{dev.hip_device}")
+    if t.dim() < 2 or (t.shape[-1] * t.element_size()) != ROOT_STEP.itemsize:
+        raise MtrError(MTR_E_INVALID, f"{what}: steps of 16 bytes, [n, S, 16] uint8 or [n, S, 4] int32 / float32")
+    return t
+
+
 class AnimIK:
     """An IK set (include/mtr.h, SPEC.md section 17): the parents of a skeleton of ``njoints`` joints (a root: 255 or itself)
     and 1 to 4 chains, an ANIM_IK_CHAIN array or a list of dicts of its fields (kind, joint, optionally axis and flags)."""
@@ -945,6 +1040,35 @@ class Batch:
             side = _pose_stream(t.device)
             side.wait_stream(cur)
             self.dev.check(lib.mtr_batch_attach_device(self._h, src._h, C.c_void_p(t.data_ptr()), C.c_void_p(side.cuda_stream)))
+            t.record_stream(side)
+            cur.wait_stream(side)
+
+    def root_motion(self, traj: "Anim", root: "AnimRoot", steps):
+        """moves every instance by the blended delta of its steps on the trajectory set ``traj`` (k_root, SPEC.md section 19):
+        M := M . D into a fresh version; palettes and npal are kept.  One shot; the host advances the positions itself.
+        steps: a ROOT_STEP array [n, S] (or [n]: one step each) or a dict of its fields, host memory."""
+        st = root_steps(steps, self.n)
+        self.dev.check(lib.mtr_batch_root_motion(self._h, traj._h, root._h, _p(st), st.shape[1]))
+
+    def root_motion_device(self, traj: "Anim", root: "AnimRoot", steps, stream=None):
+        """the same from a torch uint8 [n, S, 16] / int32 / float32 [n, S, 4] tensor on the batch's device holding ROOT_STEP
+        records, read in stream order on ``stream`` (a torch stream; None: torch.cuda.current_stream())."""
+        import torch
+        t = _root_tensor(steps, self.dev, "root motion")
+        if t.dim() != 3 or t.shape[0] != self.n:
+            raise MtrError(MTR_E_INVALID, "root motion: a tensor [n, S, 16 bytes]")
+        nsteps = t.shape[1]
+        cur = stream if stream is not None else torch.cuda.current_stream(t.device)
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            with torch.cuda.stream(cur):
+                t = t.contiguous().clone()
+        if cur.cuda_stream != 0:
+            self.dev.check(lib.mtr_batch_root_motion_device(self._h, traj._h, root._h, C.c_void_p(t.data_ptr()), nsteps, C.c_void_p(cur.cuda_stream)))
+            t.record_stream(cur)
+        else:  # torch's legacy default stream: as set_poses
+            side = _pose_stream(t.device)
+            side.wait_stream(cur)
+            self.dev.check(lib.mtr_batch_root_motion_device(self._h, traj._h, root._h, C.c_void_p(t.data_ptr()), nsteps, C.c_void_p(side.cuda_stream)))
             t.record_stream(side)
             cur.wait_stream(side)
 

@@ -59,6 +59,18 @@ MTR_TRK_HD void track_search_step(const uint16_t* times, float r, TrackSearch& s
     s.n -= half;
 }
 
+// The same step in two halves, for a caller that issues the probes of several searches before it uses any of them
+// (root_math.h): the key the step probes, and the step taken with the time t read there.
+MTR_TRK_HD uint32_t track_search_probe(const TrackSearch& s) { return s.base + (s.n >> 1); }
+
+MTR_TRK_HD void track_search_take(uint32_t t, float r, TrackSearch& s) {
+    const uint32_t half = s.n >> 1;
+    const bool le = (float)t <= r;
+    s.base = le ? s.base + half : s.base;
+    s.tk = le ? t : s.tk;
+    s.n -= half;
+}
+
 // an upper bound of n after a step, for any n up to `left`: the number of steps a loop over several searches runs
 MTR_TRK_HD uint32_t track_search_left(uint32_t left) { return left - (left >> 1); }
 

@@ -334,6 +334,7 @@ struct mtr_anim {
     uint32_t njoints = 0, nclips = 0;
     bool tracks = false;
     uint32_t nkeys = 0;          // a track set's key total
+    bool has_loop = false;       // a clip carries MTR_CLIP_LOOP: no trajectory for root motion (section 19)
     uint32_t* d = nullptr;
     hipEvent_t last = nullptr;
     hipStream_t last_stream = nullptr;
@@ -358,6 +359,16 @@ struct mtr_anim_ik {
     mtr_device* dev;
     uint32_t njoints = 0, nchains = 0, path_bytes = 0;
     std::vector<uint8_t> parents;  // a root as 255
+    uint32_t* d = nullptr;
+    hipEvent_t last = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool recorded = false;
+};
+
+// A root set (SPEC.md section 19): immutable once uploaded.  d: nclips flag words (MTR_ROOT_CYCLIC).  `last` as mtr_anim's.
+struct mtr_anim_root {
+    mtr_device* dev;
+    uint32_t njoints = 0, nclips = 0, joint = 0;
     uint32_t* d = nullptr;
     hipEvent_t last = nullptr;
     hipStream_t last_stream = nullptr;

@@ -1,5 +1,5 @@
 // host_batch.cpp -- instance batches and their versions, pose and animation staging, animation clip sets, mask sets and layers, IK sets,
-// attachments.
+// attachments, root motion.
 #include "host.h"
 #include "attach_math.h"
 
@@ -21,6 +21,9 @@ void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_
 void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 // k_attach.hip, weak for the same reason
 void mtr_launch_attach(const AttachParams& p, hipStream_t s) __attribute__((weak));
+// k_root.hip, weak for the same reason
+void mtr_launch_root(const RootParams& p, hipStream_t s) __attribute__((weak));
+void mtr_launch_root_deltas(const RootParams& p, hipStream_t s) __attribute__((weak));
 
 namespace mtr_host {
 
@@ -195,6 +198,32 @@ void retire_version(mtr_device* d, mtr_batch::Ver& v, FreeList* now) {
     v = mtr_batch::Ver{};
 }
 
+// what a root-motion call (section 19) runs in place of k_attach: M * D from the steps (the records) over a trajectory set
+struct RootSrc {
+    mtr_anim* traj = nullptr;
+    mtr_anim_root* root = nullptr;
+    uint32_t nsteps = 0;
+};
+
+RootParams root_params(const mtr_anim* traj, const mtr_anim_root* root, const void* steps_dev, uint32_t nsteps, size_t n, const float* mats_in, float* out) {
+    RootParams rp{};
+    rp.anim.clips = traj->d;
+    rp.anim.nclips = traj->nclips;
+    rp.anim.pose.njoints = traj->njoints;
+    if (traj->tracks) {
+        rp.anim.tracks = traj->d + (size_t)traj->nclips * 4;
+        rp.anim.values = rp.anim.tracks + (size_t)traj->nclips * traj->njoints * 3 * 8;
+        rp.anim.times = reinterpret_cast<const uint16_t*>(rp.anim.values + (size_t)traj->nkeys * 2);
+    } else {
+        rp.anim.keys = reinterpret_cast<const float*>(traj->d + (size_t)traj->nclips * 4);
+    }
+    rp.root_flags = root->d;
+    rp.steps = static_cast<const uint32_t*>(steps_dev);
+    rp.mats_in = mats_in; rp.out = out;
+    rp.joint = root->joint; rp.nsteps = nsteps; rp.n = (uint32_t)n;
+    return rp;
+}
+
 // An outside reader of a batch's current version: a k_attach that forms matrices from its instance matrices and palettes
 // (SPEC.md section 18) on a stream the batch's own updates need not share.  pin (submit_mu held) takes the current version
 // and keeps batch_next_version off it; launch (no lock: only this thread touches a pinned version's events) makes `s` wait
@@ -214,18 +243,26 @@ void src_read_pin(mtr_batch* src, SrcRead& r) {
     src->vers[(size_t)r.vi].pinned++;
 }
 
-int32_t src_read_launch(SrcRead& r, const void* recs_dev, size_t n, float* out_dev, hipStream_t s) {
+int32_t src_read_launch(SrcRead& r, const void* recs_dev, size_t n, float* out_dev, hipStream_t s, const RootSrc* rt = nullptr) {
     mtr_device* d = r.b->dev;
     if (!r.v.read && hipEventCreateWithFlags(&r.v.read, hipEventDisableTiming) != hipSuccess) return fail(d, MTR_E_HIP, "hipEventCreate failed");
     if (r.v.ready) HIPCHK(d, hipStreamWaitEvent(s, r.v.ready, 0));
     if (r.v.read_pending && r.v.read_stream != s) HIPCHK(d, hipStreamWaitEvent(s, r.v.read, 0));
-    AttachParams ap{};
-    ap.recs = static_cast<const uint32_t*>(recs_dev);
-    ap.src_mats = r.v.d; ap.src_pals = r.v.d + (size_t)r.b->n * 16;
-    ap.out = out_dev;
-    ap.n = (uint32_t)n; ap.n_src = r.b->n; ap.npal = r.v.npal;
-    mtr_launch_attach(ap, s);
-    HIPCHK(d, hipGetLastError());
+    if (rt) {  // the version's own matrices times the deltas; the trajectory set and the root set are read like a clip set
+        int32_t rc = anim_before(rt->traj, s);
+        if (rc || (rc = anim_before(rt->root, s))) return rc;
+        mtr_launch_root(root_params(rt->traj, rt->root, recs_dev, rt->nsteps, n, r.v.d, out_dev), s);
+        HIPCHK(d, hipGetLastError());
+        if ((rc = anim_after(rt->traj, s)) || (rc = anim_after(rt->root, s))) return rc;
+    } else {
+        AttachParams ap{};
+        ap.recs = static_cast<const uint32_t*>(recs_dev);
+        ap.src_mats = r.v.d; ap.src_pals = r.v.d + (size_t)r.b->n * 16;
+        ap.out = out_dev;
+        ap.n = (uint32_t)n; ap.n_src = r.b->n; ap.npal = r.v.npal;
+        mtr_launch_attach(ap, s);
+        HIPCHK(d, hipGetLastError());
+    }
     HIPCHK(d, hipEventRecord(r.v.read, s));
     r.recorded = true;
     return MTR_OK;
@@ -298,9 +335,11 @@ struct PoseSrc {
 };
 
 // the matrices of an attach call: one record per instance (device memory) against the current version of `src`
+// (a root-motion call: src is the batch itself, recs its steps, root what runs instead of k_attach)
 struct AttachSrc {
     mtr_batch* src = nullptr;
     const void* recs = nullptr;
+    const RootSrc* root = nullptr;
 };
 
 // What an update writes into a fresh version.  mats / pals: host arrays, or nullptr = keep the current version's (device
@@ -344,7 +383,7 @@ int32_t batch_write_version(mtr_batch* b, const float* mats, const float* pals, 
         if (v.read_pending) HIPCHK(d, hipStreamWaitEvent(s, v.read, 0));  // and a k_attach of another update that still reads it
         if (cur.ready) HIPCHK(d, hipStreamWaitEvent(s, cur.ready, 0));
         if (at) {
-            int32_t arc = src_read_launch(rd, at->recs, n, v.d, s);
+            int32_t arc = src_read_launch(rd, at->recs, n, v.d, s, at->root);
             if (arc) return arc;
         } else if (mats) HIPCHK(d, hipMemcpyAsync(v.d, mats, n * 64, hipMemcpyHostToDevice, s));
         else HIPCHK(d, hipMemcpyAsync(v.d, cur.d, n * 64, hipMemcpyDeviceToDevice, s));
@@ -542,6 +581,7 @@ int32_t mtr_anim_create(mtr_device* d, size_t njoints, size_t nclips, const uint
     if (rc) return rc;
     auto a = std::make_unique<mtr_anim>();
     a->dev = d; a->njoints = (uint32_t)njoints; a->nclips = (uint32_t)nclips;
+    for (size_t c = 0; c < nclips; c++) a->has_loop |= (table[c * 4 + 2] & MTR_CLIP_LOOP) != 0;
     const size_t key_words = (size_t)total * njoints * 12;
     if ((rc = dev_alloc(d, &a->d, table.size() + key_words))) return rc;
     hipError_t e = hipMemcpy(a->d, table.data(), table.size() * 4, hipMemcpyHostToDevice);
@@ -599,6 +639,7 @@ int32_t mtr_anim_create_tracks(mtr_device* d, size_t njoints, size_t nclips, con
     auto a = std::make_unique<mtr_anim>();
     a->dev = d; a->njoints = (uint32_t)njoints; a->nclips = (uint32_t)nclips;
     a->tracks = true; a->nkeys = (uint32_t)nkeys_total;
+    for (size_t c = 0; c < nclips; c++) a->has_loop |= (table[c * 4 + 2] & MTR_CLIP_LOOP) != 0;
     const size_t time_words = (nkeys_total + 1) / 2;
     if ((rc = dev_alloc(d, &a->d, table.size() + ntracks * 8 + nkeys_total * 2 + time_words))) return rc;
     uint32_t* p = a->d;
@@ -1040,6 +1081,125 @@ int32_t mtr_batch_sockets(mtr_batch* src, const mtr_attach* recs, size_t n, floa
         std::lock_guard<std::mutex> submit_lock(d->submit_mu);
         src_read_unpin(rd, d->s_copy);
     }
+    if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// root motion (SPEC.md section 19)
+// ---------------------------------------------------------------------------------------------
+static_assert(sizeof(mtr_root_step) == 16, "mtr_root_step");
+
+int32_t mtr_anim_root_create(mtr_device* d, size_t njoints, size_t nclips, uint32_t joint, const uint32_t* flags, mtr_anim_root** out) {
+    if (!d || !out) return MTR_E_INVALID;
+    *out = nullptr;
+    if (njoints == 0 || njoints > MTR_POSE_MAX_JOINTS) return fail(d, MTR_E_INVALID, "anim root: 1 to 256 joints");
+    if (nclips == 0 || nclips > 0xFFFFFFu) return fail(d, MTR_E_INVALID, "anim root: at least one clip");
+    if (joint >= njoints) return fail(d, MTR_E_INVALID, "anim root: the trajectory joint lies past the set's joints");
+    std::vector<uint32_t> img(nclips, 0u);
+    for (size_t c = 0; c < nclips && flags; c++) {
+        if (flags[c] & ~MTR_ROOT_CYCLIC) return fail(d, MTR_E_INVALID, "anim root: clip " + std::to_string(c) + " has unknown flag bits");
+        img[c] = flags[c];
+    }
+    int32_t rc = set_device(d);
+    if (rc) return rc;
+    auto r = std::make_unique<mtr_anim_root>();
+    r->dev = d; r->njoints = (uint32_t)njoints; r->nclips = (uint32_t)nclips; r->joint = joint;
+    if ((rc = dev_alloc(d, &r->d, img.size()))) return rc;
+    hipError_t e = hipMemcpy(r->d, img.data(), img.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->last, hipEventDisableTiming);
+    if (e != hipSuccess) { (void)hipFree(r->d); return fail(d, MTR_E_HIP, std::string("anim root upload: ") + hipGetErrorString(e)); }
+    *out = r.release();
+    return MTR_OK;
+}
+
+void mtr_anim_root_destroy(mtr_anim_root* r) {
+    if (!r) return;
+    mtr_device* d = r->dev;
+    {
+        // a kernel may still read the flags: parked behind the event of the last one, collected by a later submit
+        std::lock_guard<std::mutex> submit_lock(d->submit_mu);
+        d->garbage.push_back({r->d, 0, r->last});
+    }
+    delete r;
+}
+
+// what every root-motion call checks of its trajectory set, root set and step count
+static int32_t check_root(mtr_device* d, const mtr_anim* traj, const mtr_anim_root* root, size_t nsteps, bool deltas) {
+    if (!root) return fail(d, MTR_E_INVALID, "root motion: no root set");
+    if (traj->dev != d || root->dev != d) return fail(d, MTR_E_INVALID, "root motion: the trajectory set or the root set belongs to another device");
+    if (root->njoints != traj->njoints || root->nclips != traj->nclips)
+        return fail(d, MTR_E_INVALID, "root motion: the root set's joint or clip count is not the trajectory set's");
+    if (traj->has_loop) return fail(d, MTR_E_INVALID, "root motion: the trajectory set has a MTR_CLIP_LOOP clip (mark it MTR_ROOT_CYCLIC in the root set instead)");
+    if (nsteps < 1 || nsteps > MTR_ROOT_MAX_STEPS) return fail(d, MTR_E_INVALID, "root motion: 1 to 8 steps per instance");
+    if (!(deltas ? mtr_launch_root_deltas : mtr_launch_root)) return fail(d, MTR_E_UNSUPPORTED, "root motion: built without k_root");
+    return set_device(d);
+}
+
+int32_t mtr_batch_root_motion(mtr_batch* b, mtr_anim* traj, mtr_anim_root* root, const mtr_root_step* steps, size_t nsteps) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!traj || !steps) return fail(d, MTR_E_INVALID, "root motion: no trajectory set or no steps");
+    int32_t rc = check_root(d, traj, root, nsteps, false);
+    if (rc) return rc;
+    if ((rc = stage_pose(d, reinterpret_cast<const float*>(steps), (size_t)b->n * nsteps * 4))) return rc;
+    const RootSrc rs{traj, root, (uint32_t)nsteps};
+    const AttachSrc at{b, d->pose_stage, &rs};
+    return batch_write_version(b, nullptr, nullptr, 0, PoseSrc{}, d->s_copy, &at);
+}
+
+int32_t mtr_batch_root_motion_device(mtr_batch* b, mtr_anim* traj, mtr_anim_root* root, const mtr_root_step* steps_dev, size_t nsteps, void* hip_stream) {
+    if (!b) return MTR_E_INVALID;
+    mtr_device* d = b->dev;
+    if (!traj) return fail(d, MTR_E_INVALID, "root motion: no trajectory set");
+    if (!steps_dev || ((uintptr_t)steps_dev & 15u)) return fail(d, MTR_E_INVALID, "root motion: device steps must be 16-byte aligned");
+    int32_t rc = check_root(d, traj, root, nsteps, false);
+    if (rc) return rc;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    const RootSrc rs{traj, root, (uint32_t)nsteps};
+    const AttachSrc at{b, steps_dev, &rs};
+    return batch_write_version(b, nullptr, nullptr, 0, PoseSrc{}, s, &at);
+}
+
+int32_t mtr_anim_root_deltas_device(mtr_anim* traj, mtr_anim_root* root, const mtr_root_step* steps_dev, size_t nsteps, size_t n, float* out_dev,
+                                    void* hip_stream) {
+    if (!traj) return MTR_E_INVALID;
+    mtr_device* d = traj->dev;
+    if (!steps_dev || ((uintptr_t)steps_dev & 15u) || !out_dev || ((uintptr_t)out_dev & 15u))
+        return fail(d, MTR_E_INVALID, "root deltas: device steps and matrices must be 16-byte aligned");
+    if (n == 0 || n > (1u << 27)) return fail(d, MTR_E_INVALID, "root deltas: 1 to 2^27 instances");
+    int32_t rc = check_root(d, traj, root, nsteps, true);
+    if (rc) return rc;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    if ((rc = anim_before(traj, s)) || (rc = anim_before(root, s))) return rc;
+    mtr_launch_root_deltas(root_params(traj, root, steps_dev, (uint32_t)nsteps, n, nullptr, out_dev), s);
+    HIPCHK(d, hipGetLastError());
+    if ((rc = anim_after(traj, s)) || (rc = anim_after(root, s))) return rc;
+    return MTR_OK;
+}
+
+int32_t mtr_anim_root_deltas(mtr_anim* traj, mtr_anim_root* root, const mtr_root_step* steps, size_t nsteps, size_t n, float* out, size_t count) {
+    if (!traj) return MTR_E_INVALID;
+    mtr_device* d = traj->dev;
+    if (!steps || !out) return fail(d, MTR_E_INVALID, "root deltas: no steps or no room for the matrices");
+    if (n == 0 || n > (1u << 27) || count < n * 16) return fail(d, MTR_E_INVALID, "root deltas: 1 to 2^27 instances and room for n * 16 floats");
+    int32_t rc = check_root(d, traj, root, nsteps, true);
+    if (rc) return rc;
+    float* tmp = nullptr;  // the matrices, then the steps (n * 64 bytes in: 16-byte aligned)
+    if ((rc = dev_alloc(d, &tmp, n * 16 + n * nsteps * 4))) return rc;
+    auto run = [&]() -> int32_t {
+        HIPCHK(d, hipMemcpyAsync(tmp + n * 16, steps, n * nsteps * sizeof(mtr_root_step), hipMemcpyHostToDevice, d->s_copy));
+        int32_t r2 = anim_before(traj, d->s_copy);
+        if (r2 || (r2 = anim_before(root, d->s_copy))) return r2;
+        mtr_launch_root_deltas(root_params(traj, root, tmp + n * 16, (uint32_t)nsteps, n, nullptr, tmp), d->s_copy);
+        HIPCHK(d, hipGetLastError());
+        if ((r2 = anim_after(traj, d->s_copy)) || (r2 = anim_after(root, d->s_copy))) return r2;
+        HIPCHK(d, hipMemcpyAsync(out, tmp, n * 64, hipMemcpyDeviceToHost, d->s_copy));
+        return MTR_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(d->s_copy);  // also when a step failed: the buffer is freed next
+    (void)hipFree(tmp);
     if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     return rc;
 }

@@ -529,3 +529,17 @@ struct AttachParams {
     uint32_t n, n_src, npal;    // n_src >= 1
 };
 void mtr_launch_attach(const AttachParams& p, hipStream_t s);
+// root motion (k_root.hip, SPEC.md section 19): per instance the blended delta D of nsteps steps on the trajectory joint of
+// an animation set of either kind; mtr_launch_root writes M_in * D, mtr_launch_root_deltas (mats_in unused) D itself
+struct RootParams {
+    AnimParams anim;            // the trajectory set: clips, keys or tracks / values / times, nclips, pose.njoints; the rest unused
+    const uint32_t* root_flags; // nclips words of the root set (MTR_ROOT_CYCLIC)
+    const uint32_t* steps;      // n x nsteps x 4 words (mtr_root_step: clip, x, dx, w (f32 bits)); 16-byte aligned
+    const float* mats_in;       // n x 16: the instance matrices D is applied to
+    float* out;                 // n x 16
+    uint32_t joint;             // < pose.njoints, a validated host value
+    uint32_t nsteps;            // 1..MTR_ROOT_MAX_STEPS, a validated host value
+    uint32_t n;
+};
+void mtr_launch_root(const RootParams& p, hipStream_t s);
+void mtr_launch_root_deltas(const RootParams& p, hipStream_t s);

@@ -70,7 +70,7 @@ pub const MTR_OWN_SUPERTILES: u32 = 2;
 pub const MTR_TEXRES_DECODED: u32 = 0;
 pub const MTR_TEXRES_BLOCKS: u32 = 1;
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik);
+opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root);
 
 /// animation clips (mtr.h, SPEC.md section 14): one key of one joint, 48 bytes
 pub const MTR_CLIP_LOOP: u32 = 1;
@@ -138,6 +138,17 @@ pub struct mtr_attach {
     pub flags: u32,
     pub pad: u32,
     pub offset: [f32; 16],
+}
+/// root motion (mtr.h, SPEC.md section 19): one step of an instance, 16 bytes; x and dx in keys / ticks
+pub const MTR_ROOT_MAX_STEPS: usize = 8;
+pub const MTR_ROOT_CYCLIC: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_root_step {
+    pub clip: u32,
+    pub x: f32,
+    pub dx: f32,
+    pub w: f32,
 }
 /// what one instance plays: clip A at x_a cross-faded by w with clip B at x_b, positions in keys; 24 bytes
 #[repr(C)]
@@ -271,5 +282,15 @@ extern "C" {
     pub fn mtr_batch_sockets(src: *mut mtr_batch, recs: *const mtr_attach, n: usize, out: *mut f32, count: usize) -> i32;
     pub fn mtr_batch_sockets_device(src: *mut mtr_batch, recs_dev: *const mtr_attach, n: usize, out_dev: *mut f32, hip_stream: *mut c_void) -> i32;
     pub fn mtr_batch_read_model_mats(batch: *mut mtr_batch, out: *mut f32, count: usize) -> i32;
+    // root motion (SPEC.md section 19): declarations only
+    pub fn mtr_anim_root_create(dev: *mut mtr_device, njoints: usize, nclips: usize, joint: u32, flags: *const u32, out: *mut *mut mtr_anim_root) -> i32;
+    pub fn mtr_anim_root_destroy(root: *mut mtr_anim_root);
+    pub fn mtr_batch_root_motion(batch: *mut mtr_batch, traj: *mut mtr_anim, root: *mut mtr_anim_root, steps: *const mtr_root_step, nsteps: usize) -> i32;
+    pub fn mtr_batch_root_motion_device(batch: *mut mtr_batch, traj: *mut mtr_anim, root: *mut mtr_anim_root, steps_dev: *const mtr_root_step,
+                                        nsteps: usize, hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_root_deltas(traj: *mut mtr_anim, root: *mut mtr_anim_root, steps: *const mtr_root_step, nsteps: usize, n: usize, out: *mut f32,
+                                count: usize) -> i32;
+    pub fn mtr_anim_root_deltas_device(traj: *mut mtr_anim, root: *mut mtr_anim_root, steps_dev: *const mtr_root_step, nsteps: usize, n: usize,
+                                       out_dev: *mut f32, hip_stream: *mut c_void) -> i32;
 }
 pub mod files;

@@ -1,0 +1,95 @@
+"""CPU: the entry points of root motion (SPEC.md section 19) are declared in include/mtr.h, exported by libmtr.so and bound by
+api.py with the argument counts of their prototypes; mtr_root_step has its stated size and field offsets, in C and in
+api.ROOT_STEP; the constants agree; the error table of include/mtr.h holds where no GPU is needed; the ABI version stays 2."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HDR = os.path.join(ROOT, "include", "mtr.h")
+NAMES = {"mtr_anim_root_create": 6, "mtr_anim_root_destroy": 1, "mtr_batch_root_motion": 5, "mtr_batch_root_motion_device": 6,
+         "mtr_anim_root_deltas": 7, "mtr_anim_root_deltas_device": 7}
+
+
+def _prototypes():
+    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+    out = {}
+    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
+        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
+    return out
+
+
+def test_prototypes_declared_exported_and_bound():
+    from mt_renderer_amd import api
+    protos = _prototypes()
+    so = ctypes.CDLL(api.LIB_PATH)
+    hpp = open(os.path.join(ROOT, "include", "mtr.hpp")).read()
+    rs = open(os.path.join(ROOT, "rust", "mtr-sys", "src", "lib.rs")).read()
+    for name, nargs in NAMES.items():
+        assert protos.get(name) == nargs, f"include/mtr.h: {name} with {nargs} arguments"
+        assert hasattr(so, name), f"libmtr.so does not export {name}"
+        assert name in api.EXPORTED_SYMBOLS
+        fn = getattr(api.lib, name)
+        assert len(fn.argtypes) == nargs and fn.restype is (None if name.endswith("_destroy") else ctypes.c_int32)
+        assert name in hpp, f"mtr.hpp: {name}"
+        assert name in rs, f"mtr-sys: {name}"
+    assert "mtr_root_step" in rs and "MTR_ROOT_CYCLIC" in rs and "MTR_ROOT_MAX_STEPS" in rs and "mtr_anim_root" in rs
+    assert api.lib.mtr_abi_version() == 2
+
+
+def test_step_layout(tmp_path):
+    from mt_renderer_amd import api
+    from tests import root_model as rm
+    for dt in (api.ROOT_STEP, rm.STEP):
+        assert dt.itemsize == 16 and dt.names == ("clip", "x", "dx", "w")
+        assert [dt.fields[n][1] for n in dt.names] == [0, 4, 8, 12]
+        assert dt.fields["clip"][0] == np.dtype("<u4") and all(dt.fields[n][0] == np.dtype("<f4") for n in ("x", "dx", "w"))
+    assert (api.ROOT_MAX_STEPS, api.ROOT_CYCLIC) == (8, 1) == (rm.MAX_STEPS, rm.CYCLIC)
+    if shutil.which("g++") is None:
+        pytest.skip("no host compiler")
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stddef.h>\n#include "mtr.h"\n'
+                   '_Static_assert(sizeof(mtr_root_step) == 16 && _Alignof(mtr_root_step) == 4, "size");\n'
+                   '_Static_assert(offsetof(mtr_root_step, clip) == 0 && offsetof(mtr_root_step, x) == 4, "clip, x");\n'
+                   '_Static_assert(offsetof(mtr_root_step, dx) == 8 && offsetof(mtr_root_step, w) == 12, "dx, w");\n'
+                   '_Static_assert(MTR_ROOT_MAX_STEPS == 8 && MTR_ROOT_CYCLIC == 1u, "constants");\n'
+                   '_Static_assert(MTR_ABI_VERSION == 2, "ABI version");\n'
+                   'int main(void) { return 0; }\n')
+    subprocess.check_call(["g++", "-x", "c", "-std=c11", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)])
+
+
+def test_null_handles_are_rejected_without_a_device():
+    """the rows of the error table that need no device: a NULL device, batch or trajectory set is MTR_E_INVALID before anything
+    is touched (the rest of the table is held on the host build by tests/test_root_host_sanitizer.py and on the GPU by
+    tests/test_gpu_root.py)"""
+    from mt_renderer_amd import api
+    L = api.lib
+    st = np.zeros(3, dtype=api.ROOT_STEP)
+    out = np.zeros(48, dtype=np.float32)
+    h = ctypes.c_void_p()
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    assert L.mtr_anim_root_create(None, 1, 1, 0, None, ctypes.byref(h)) == api.MTR_E_INVALID and not h
+    assert L.mtr_batch_root_motion(None, None, None, p(st), 1) == api.MTR_E_INVALID
+    assert L.mtr_batch_root_motion_device(None, None, None, p(st), 1, None) == api.MTR_E_INVALID
+    assert L.mtr_anim_root_deltas(None, None, p(st), 1, 3, p(out), out.size) == api.MTR_E_INVALID
+    assert L.mtr_anim_root_deltas_device(None, None, p(st), 1, 3, p(out), None) == api.MTR_E_INVALID
+    L.mtr_anim_root_destroy(None)
+
+
+def test_python_builds_steps():
+    from mt_renderer_amd import api
+    s = api.root_steps(dict(clip=[0, 1, 2], x=[0.5, 1.5, 2.5], dx=[0.37] * 3), 3)
+    assert s.dtype == api.ROOT_STEP and s.shape == (3, 1) and s.flags.c_contiguous and (s["w"] == 0).all() and list(s["clip"][:, 0]) == [0, 1, 2]
+    s = api.root_steps(dict(clip=np.zeros((2, 4)), x=np.ones((2, 4)), dx=np.ones((2, 4)), w=np.full((2, 4), 0.5)), 2)
+    assert s.shape == (2, 4) and (s["w"] == 0.5).all()
+    assert api.root_steps(np.zeros((5, 2), dtype=api.ROOT_STEP), 5).shape == (5, 2)
+    assert api.root_steps(np.zeros(5, dtype=api.ROOT_STEP), None).shape == (5, 1)
+    for bad in (lambda: api.root_steps(np.zeros((5, 2), dtype=api.ROOT_STEP), 4), lambda: api.root_steps(dict(clip=[1], x=[0.0]), 1),
+                lambda: api.root_steps(dict(clip=[0], x=[0.0], dx=[0.0], y=1), 1), lambda: api.root_steps(np.zeros(4, dtype=api.ANIM_LAYER), 4)):
+        with pytest.raises(api.MtrError):
+            bad()
