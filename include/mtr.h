@@ -218,7 +218,7 @@ int32_t mtr_batch_read_palettes(mtr_batch *batch, float *out, size_t count);
  * translation, a rotation quaternion (x, y, z, w) and a scale.  keys: clip after clip, inside a clip key after key, inside
  * a key joint after joint (sum(nkeys) * njoints entries); flags: MTR_CLIP_* per clip, NULL = 0 for all.  The library copies.
  * An animation state says, for one instance: clip A at position x_a cross-faded by w (0 = A alone .. 1 = B alone) with clip
- * B at x_b.  Positions are in KEYS (seconds times the clip's key rate; the library defines no clock); a LOOP clip wraps
+ * B at x_b.  Positions are in KEYS (seconds times the clip's key rate; a player, section 20 below, keeps them on the device); a LOOP clip wraps
  * them (the last key interpolates towards the first), any other clip holds its first / last key.  Clip indices are
  * clamped to nclips - 1, never rejected (device states cannot be validated; host and device paths agree); with w == 0
  * clip B is not read.  The local matrix of a joint is from_scale_rotation_translation of the interpolated key, the
@@ -409,7 +409,8 @@ int32_t mtr_batch_read_model_mats(mtr_batch *batch, float *out, size_t count);
  *   w     : steps 1 .. nsteps - 1 are blended over step 0 in order by their clamped weight, as section 16's OVERRIDE layers
  *           (a cross-fade of walk into run); step 0's w is not read, and a step of weight 0 does not read its clip.
  * The blended delta D is a local matrix of section 14 and M_new[i] = M_old[i] * D_i in section 12's fma chain, so a numpy
- * model reproduces the matrices bit for bit.  The library defines no clock: the host advances x by dx itself.
+ * model reproduces the matrices bit for bit.  These calls define no clock: the host advances x by dx itself, or a player
+ * (section 20, below) writes the steps.
  * mtr_batch_root_motion* is ONE SHOT with the frame semantics of mtr_batch_attach with batch == src: it reads the batch's
  * current version (after its pending write) and writes a fresh one; palettes and npal are kept; a draw uses what was current
  * when it was recorded.  The batch's model needs no skeleton.  A mount moved this way and then mtr_batch_attach carries its
@@ -437,6 +438,57 @@ int32_t mtr_anim_root_deltas(mtr_anim *traj, mtr_anim_root *root, const mtr_root
                              size_t count /* >= n * 16 */);
 int32_t mtr_anim_root_deltas_device(mtr_anim *traj, mtr_anim_root *root, const mtr_root_step *steps_dev, size_t nsteps, size_t n,
                                     float *out_dev /* 16-byte aligned */, void *hip_stream);
+
+/* ---- players (build extension, SPEC.md section 20): a clock that keeps playback states on the device (k_play) ----
+ * Sections 14 to 19 take positions and define no clock; a player is the clock.  A player set holds per clip the key count
+ * (or tick count of a track set), the flag word (MTR_CLIP_LOOP) and the rate in positions per second, and owns a zeroed
+ * scratch array of max_instances words.  It is not tied to an mtr_anim: the same tables drive an in-place set and its
+ * trajectory set, clip by clip (a LOOP clip of N keys and its cyclic trajectory of N + 1 keys share the period N).
+ * A play state is 32 bytes per instance in DEVICE memory, read and written by every advance:
+ *   clip_a, x_a : what plays; clip_b, x_b : what a running fade leads to; w : the fade's weight; fade : weight per second,
+ *   a fade is running iff fade > 0; speed : multiplies dt, never written; flags : bit 0 MTR_PLAY_ENDED is written by the
+ *   kernel (a one-shot clip_a stands at its end), bits 1..31 are the user's and are kept.
+ * The user may write states directly; every bit pattern has a defined outcome and clip indices are clamped.
+ * A command {instance, clip, x, seconds} starts clip at x on one instance: a cut unless seconds > 0 and 1 / seconds is
+ * positive and finite, else a cross-fade of that duration (a running fade past half its weight first becomes the base).
+ * instance >= n is ignored; of several commands to one instance the LAST in array order wins, the others have no effect.
+ * An advance moves every state by dt seconds (positions by dt * speed * rate, wrapped on a LOOP clip, clamped otherwise;
+ * the weight by max(dt, 0) * fade; a complete fade swaps B into A) and writes, each pointer optional, the records of the
+ * frame BEFORE the swap: an mtr_anim_state per instance; layers 0 and 1 of a stack of nlayers (2..8) mtr_anim_layer per
+ * instance, the others untouched; two mtr_root_step per instance (x before the advance, and the step).  They are what
+ * mtr_batch_animate_device, mtr_batch_animate_layers_device / _ik_device and mtr_batch_root_motion_device (nsteps = 2) take.
+ * Both advance calls run in stream order on hip_stream under the rules of mtr_batch_set_poses_device; host commands are
+ * copied before the call returns, device commands may be overwritten by work queued later.  Calls on one player are
+ * ordered among themselves whatever their streams.  mtr_anim_player_destroy may follow an advance directly (no host wait).
+ * MTR_E_INVALID, nothing changed: a NULL handle or states pointer, n == 0 or n > max_instances, nlayers outside 2..8 with
+ * out_layers given, a misaligned device pointer (16 bytes: states, layers, steps, commands; 8: mtr_anim_state), ncmds > 0
+ * with NULL commands, ncmds >= 2^31; at creation nclips == 0 or > 2^24, nkeys outside 1..2^24, unknown flag bits, a rate
+ * that is not finite (mtr_last_error names the clip), max_instances outside 1..2^27.
+ * MTR_E_UNSUPPORTED: a library built without k_play. */
+#define MTR_PLAY_ENDED 1u
+typedef struct mtr_anim_player mtr_anim_player;
+typedef struct mtr_play_state { uint32_t clip_a, clip_b; float x_a, x_b, w, fade, speed; uint32_t flags; } mtr_play_state; /* 32 bytes */
+typedef struct mtr_play_cmd { uint32_t instance, clip; float x, seconds; } mtr_play_cmd;                                   /* 16 bytes */
+int32_t mtr_anim_player_create(mtr_device *dev, size_t nclips, const uint32_t *nkeys /* nclips */,
+                               const uint32_t *flags /* nclips, NULL = 0 */, const float *rates /* nclips */,
+                               size_t max_instances, mtr_anim_player **out);
+void    mtr_anim_player_destroy(mtr_anim_player *player);    /* parked like mtr_anim_destroy */
+int32_t mtr_anim_player_advance_device(mtr_anim_player *player, mtr_play_state *states_dev /* n, 16-byte aligned */, size_t n,
+                                       float dt, const mtr_play_cmd *cmds /* ncmds, host, or NULL */, size_t ncmds,
+                                       mtr_anim_state *out_states_dev /* n, or NULL */,
+                                       mtr_anim_layer *out_layers_dev /* n*nlayers, or NULL */, size_t nlayers,
+                                       mtr_root_step *out_steps_dev /* n*2, or NULL */,
+                                       void *hip_stream /* as mtr_batch_set_poses_device */);
+/* the same with the commands in device memory (16-byte aligned), read in stream order */
+int32_t mtr_anim_player_advance_device_cmds(mtr_anim_player *player, mtr_play_state *states_dev, size_t n, float dt,
+                                            const mtr_play_cmd *cmds_dev, size_t ncmds, mtr_anim_state *out_states_dev,
+                                            mtr_anim_layer *out_layers_dev, size_t nlayers, mtr_root_step *out_steps_dev,
+                                            void *hip_stream);
+/* a test and debug hook: everything in host memory (any alignment), the same kernel, waits; states are read and written
+ * back, out_layers is read first so that layers 2.. come back as they went in */
+int32_t mtr_anim_player_advance_host(mtr_anim_player *player, mtr_play_state *states /* n, host, in and out */, size_t n, float dt,
+                                     const mtr_play_cmd *cmds, size_t ncmds, mtr_anim_state *out_states,
+                                     mtr_anim_layer *out_layers, size_t nlayers, mtr_root_step *out_steps);
 
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],

@@ -191,6 +191,39 @@ class AnimRoot {
     mtr_anim_root* h_ = nullptr;
 };
 
+// A player set (include/mtr.h, SPEC.md section 20), the library's clock: per clip the key count, the flag word and the rate in
+// positions per second, for up to max_instances play states that live in device memory of the caller's
+class AnimPlayer {
+  public:
+    AnimPlayer(const Device& dev, size_t nclips, const uint32_t* nkeys, const uint32_t* flags, const float* rates, size_t max_instances) : dev_(dev) {
+        dev.check(mtr_anim_player_create(dev.handle(), nclips, nkeys, flags, rates, max_instances, &h_));
+    }
+    AnimPlayer(AnimPlayer&& o) noexcept : dev_(o.dev_), h_(std::exchange(o.h_, nullptr)) {}
+    AnimPlayer(const AnimPlayer&) = delete;
+    ~AnimPlayer() { mtr_anim_player_destroy(h_); }
+    // n states advanced by dt in place in stream order, at most one of ncmds host commands applied to each (copied before the
+    // call returns); the records of the frame go where a pointer is given
+    void advance(mtr_play_state* states_dev, size_t n, float dt, const mtr_play_cmd* cmds = nullptr, size_t ncmds = 0, mtr_anim_state* out_states_dev = nullptr,
+                 mtr_anim_layer* out_layers_dev = nullptr, size_t nlayers = 0, mtr_root_step* out_steps_dev = nullptr, void* hip_stream = nullptr) const {
+        dev_.check(mtr_anim_player_advance_device(h_, states_dev, n, dt, cmds, ncmds, out_states_dev, out_layers_dev, nlayers, out_steps_dev, hip_stream));
+    }
+    // the same with the commands in device memory
+    void advance_cmds(mtr_play_state* states_dev, size_t n, float dt, const mtr_play_cmd* cmds_dev, size_t ncmds, mtr_anim_state* out_states_dev = nullptr,
+                      mtr_anim_layer* out_layers_dev = nullptr, size_t nlayers = 0, mtr_root_step* out_steps_dev = nullptr, void* hip_stream = nullptr) const {
+        dev_.check(mtr_anim_player_advance_device_cmds(h_, states_dev, n, dt, cmds_dev, ncmds, out_states_dev, out_layers_dev, nlayers, out_steps_dev, hip_stream));
+    }
+    // the test and debug hook: everything in host memory, waits
+    void advance_host(mtr_play_state* states, size_t n, float dt, const mtr_play_cmd* cmds = nullptr, size_t ncmds = 0, mtr_anim_state* out_states = nullptr,
+                      mtr_anim_layer* out_layers = nullptr, size_t nlayers = 0, mtr_root_step* out_steps = nullptr) const {
+        dev_.check(mtr_anim_player_advance_host(h_, states, n, dt, cmds, ncmds, out_states, out_layers, nlayers, out_steps));
+    }
+    mtr_anim_player* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    mtr_anim_player* h_ = nullptr;
+};
+
 class Model {
   public:
     // Model::new(model_file, material_file, shader2, resource_manager, device, queue, ..) -- src/model.rs:36-45

@@ -53,6 +53,8 @@ EXPORTED_SYMBOLS = [
     "mtr_batch_attach", "mtr_batch_attach_device", "mtr_batch_sockets", "mtr_batch_sockets_device", "mtr_batch_read_model_mats",
     "mtr_anim_root_create", "mtr_anim_root_destroy", "mtr_batch_root_motion", "mtr_batch_root_motion_device", "mtr_anim_root_deltas",
     "mtr_anim_root_deltas_device",
+    "mtr_anim_player_create", "mtr_anim_player_destroy", "mtr_anim_player_advance_device", "mtr_anim_player_advance_device_cmds",
+    "mtr_anim_player_advance_host",
 ]
 
 CLIP_LOOP = 1
@@ -81,6 +83,11 @@ ATTACH_POSITION_ONLY = 1
 ROOT_STEP = np.dtype([("clip", "<u4"), ("x", "<f4"), ("dx", "<f4"), ("w", "<f4")])
 ROOT_MAX_STEPS = 8
 ROOT_CYCLIC = 1
+# mtr_play_state, mtr_play_cmd (SPEC.md section 20): what a player keeps per instance on the device, and a command to it
+PLAY_STATE = np.dtype([("clip_a", "<u4"), ("clip_b", "<u4"), ("x_a", "<f4"), ("x_b", "<f4"), ("w", "<f4"), ("fade", "<f4"), ("speed", "<f4"),
+                       ("flags", "<u4")])
+PLAY_CMD = np.dtype([("instance", "<u4"), ("clip", "<u4"), ("x", "<f4"), ("seconds", "<f4")])
+PLAY_ENDED = 1
 
 
 class MtrError(RuntimeError):
@@ -232,6 +239,11 @@ def _load() -> C.CDLL:
         "mtr_batch_root_motion_device": (i32, [vp, vp, vp, vp, sz, vp]),
         "mtr_anim_root_deltas": (i32, [vp, vp, vp, sz, sz, vp, sz]),
         "mtr_anim_root_deltas_device": (i32, [vp, vp, vp, sz, sz, vp, vp]),
+        "mtr_anim_player_create": (i32, [vp, sz, vp, vp, vp, sz, vp]),
+        "mtr_anim_player_destroy": (None, [vp]),
+        "mtr_anim_player_advance_device": (i32, [vp, vp, sz, C.c_float, vp, sz, vp, vp, sz, vp, vp]),
+        "mtr_anim_player_advance_device_cmds": (i32, [vp, vp, sz, C.c_float, vp, sz, vp, vp, sz, vp, vp]),
+        "mtr_anim_player_advance_host": (i32, [vp, vp, sz, C.c_float, vp, sz, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -685,6 +697,123 @@ def _root_tensor(t, dev: "Device", what: str):
     if t.dim() < 2 or (t.shape[-1] * t.element_size()) != ROOT_STEP.itemsize:
         raise MtrError(MTR_E_INVALID, f"{what}: steps of 16 bytes, [n, S, 16] uint8 or [n, S, 4] int32 / float32")
     return t
+
+
+def play_cmds(cmds) -> np.ndarray:
+    """player commands as a contiguous PLAY_CMD array [m] (SPEC.md section 20): from a structured array of that dtype, a dict
+    of its fields (instance, clip, optionally x and seconds) or None (no commands)"""
+    if cmds is None:
+        return np.zeros(0, dtype=PLAY_CMD)
+    if isinstance(cmds, dict):
+        if set(cmds) - set(PLAY_CMD.names) or not {"instance", "clip"} <= set(cmds):
+            raise MtrError(MTR_E_INVALID, "player commands: instance and clip, optionally x and seconds")
+        c = np.zeros(np.asarray(cmds["instance"]).size, dtype=PLAY_CMD)
+        for k, v in cmds.items():
+            c[k] = np.asarray(v).reshape(-1)
+        return c
+    c = np.asarray(cmds)
+    if c.dtype != PLAY_CMD or c.ndim != 1:
+        raise MtrError(MTR_E_INVALID, "player commands: an array [m] of dtype PLAY_CMD or a dict of its fields")
+    return np.ascontiguousarray(c)
+
+
+def _play_tensor(t, dev: "Device", what: str, record: int, align: int, count: Optional[int]):
+    """a tensor the player reads or writes IN PLACE: on the device, contiguous, aligned, count records of `record` bytes"""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32, torch.float32):
+        raise MtrError(MTR_E_INVALID, f"{what}: a uint8 / int32 / float32 tensor on the GPU")
+    if t.get_device() != dev.hip_device:
+        raise MtrError(MTR_E_INVALID, f"{what}: the tensor is on cuda:{t.get_device()}, the device is cuda:{dev.hip_device}")
+    if not t.is_contiguous() or t.data_ptr() % align:
+        raise MtrError(MTR_E_INVALID, f"{what}: contiguous and {align}-byte aligned (it is used in place)")
+    nbytes = t.numel() * t.element_size()
+    if nbytes == 0 or nbytes % record or (count is not None and nbytes != count * record):
+        raise MtrError(MTR_E_INVALID, f"{what}: records of {record} bytes" + ("" if count is None else f", {count} of them"))
+    return nbytes // record
+
+
+class AnimPlayer:
+    """A player set (include/mtr.h, SPEC.md section 20), the library's clock: per clip the key count (ticks for a track set),
+    the flag word (0 or CLIP_LOOP; None: all 0) and the rate in positions per second, for up to ``max_instances`` play states
+    that live in a tensor of the caller's on the GPU."""
+
+    def __init__(self, dev: Device, nkeys, rates, flags=None, max_instances: int = 1):
+        nk = np.ascontiguousarray(np.asarray(nkeys, dtype=np.uint32).reshape(-1))
+        rt = np.ascontiguousarray(np.asarray(rates, dtype=np.float32).reshape(-1))
+        fl = None if flags is None else np.ascontiguousarray(np.asarray(flags, dtype=np.uint32).reshape(-1))
+        if rt.size != nk.size or (fl is not None and fl.size != nk.size):
+            raise MtrError(MTR_E_INVALID, "anim player: one key count, one rate and one flag word per clip")
+        h = C.c_void_p()
+        dev.check(lib.mtr_anim_player_create(dev._h, nk.size, _p(nk), _p(fl), _p(rt), max_instances, C.byref(h)))
+        self.dev, self._h, self.nclips, self.max_instances = dev, h, nk.size, max_instances
+
+    def advance(self, states, dt: float, cmds=None, out_states=None, out_layers=None, out_steps=None, stream=None):
+        """advances the n PLAY_STATE records of ``states`` (a torch uint8 [n, 32] / int32 / float32 [n, 8] tensor on the GPU,
+        16-byte aligned) by ``dt`` seconds IN PLACE and writes, where given, ANIM_STATE records into ``out_states`` ([n, 24]
+        bytes), layers 0 and 1 of the ANIM_LAYER stacks of ``out_layers`` ([n, L, 16] bytes, L from its size) and two
+        ROOT_STEP records per instance into ``out_steps`` ([n, 2, 16] bytes), in stream order on ``stream`` (a torch stream;
+        None: torch.cuda.current_stream()).  cmds: None, a PLAY_CMD array or a dict (host memory, copied before the call
+        returns), or a tensor of PLAY_CMD records on the GPU (read in stream order)."""
+        import torch
+        n = _play_tensor(states, self.dev, "player states", PLAY_STATE.itemsize, 16, None)
+        used = [states]
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        nl = 0
+        if out_states is not None:
+            _play_tensor(out_states, self.dev, "player out_states", ANIM_STATE.itemsize, 8, n)
+            used.append(out_states)
+        if out_layers is not None:
+            nl = _play_tensor(out_layers, self.dev, "player out_layers", ANIM_LAYER.itemsize, 16, None)
+            if nl % n:
+                raise MtrError(MTR_E_INVALID, "player out_layers: n x L layers of 16 bytes")
+            nl //= n
+            used.append(out_layers)
+        if out_steps is not None:
+            _play_tensor(out_steps, self.dev, "player out_steps", ROOT_STEP.itemsize, 16, 2 * n)
+            used.append(out_steps)
+        if isinstance(cmds, torch.Tensor):
+            m = _play_tensor(cmds, self.dev, "player commands", PLAY_CMD.itemsize, 16, None)
+            fn, cp, keep = lib.mtr_anim_player_advance_device_cmds, ptr(cmds), None
+            used.append(cmds)
+        else:
+            keep = play_cmds(cmds)
+            m, fn, cp = keep.size, lib.mtr_anim_player_advance_device, (_p(keep) if keep.size else None)
+        cur = stream if stream is not None else torch.cuda.current_stream(states.device)
+        args = (self._h, ptr(states), n, float(dt), cp, m, ptr(out_states), ptr(out_layers), nl, ptr(out_steps))
+        if cur.cuda_stream != 0:
+            self.dev.check(fn(*args, C.c_void_p(cur.cuda_stream)))
+            for t in used:
+                t.record_stream(cur)
+        else:  # torch's legacy default stream: as Batch.set_poses
+            side = _pose_stream(states.device)
+            side.wait_stream(cur)
+            self.dev.check(fn(*args, C.c_void_p(side.cuda_stream)))
+            for t in used:
+                t.record_stream(side)
+            cur.wait_stream(side)
+
+    def advance_host(self, states: np.ndarray, dt: float, cmds=None, nlayers: int = 0, layers: Optional[np.ndarray] = None, want_states: bool = True,
+                     want_steps: bool = True):
+        """the test and debug hook: PLAY_STATE records [n] in host memory through the same kernel; waits.  Returns (states,
+        out_states or None, out_layers or None, out_steps or None); ``layers`` ([n, nlayers] ANIM_LAYER) is what layers 2..
+        hold going in."""
+        st = np.ascontiguousarray(np.asarray(states)).copy()
+        if st.dtype != PLAY_STATE or st.ndim != 1:
+            raise MtrError(MTR_E_INVALID, "player states: an array [n] of dtype PLAY_STATE")
+        n = st.size
+        cm = play_cmds(cmds)
+        oa = np.zeros(n, dtype=ANIM_STATE) if want_states else None
+        ol = None
+        if nlayers:
+            ol = np.zeros((n, nlayers), dtype=ANIM_LAYER) if layers is None else np.ascontiguousarray(layers).copy().reshape(n, nlayers)
+        os_ = np.zeros((n, 2), dtype=ROOT_STEP) if want_steps else None
+        self.dev.check(lib.mtr_anim_player_advance_host(self._h, _p(st), n, float(dt), _p(cm) if cm.size else None, cm.size, _p(oa), _p(ol), nlayers, _p(os_)))
+        return st, oa, ol, os_
+
+    def close(self):
+        if self._h:
+            lib.mtr_anim_player_destroy(self._h)
+            self._h = None
 
 
 class AnimIK:

@@ -375,6 +375,21 @@ struct mtr_anim_root {
     bool recorded = false;
 };
 
+// A player set (SPEC.md section 20).  d: nclips table entries of 4 words (period, flags, rate, key count), immutable, then
+// the scratch array of max_instances words, zero between calls.  cmds: where host commands are staged, grown on demand
+// (the outgrown buffer parked behind cmd_last, the event of the last kernel that read it).  `last` as mtr_anim's, but a
+// player's kernels also WRITE d (the scratch), so it orders the calls on one player among themselves.
+struct mtr_anim_player {
+    mtr_device* dev;
+    uint32_t nclips = 0, max_instances = 0;
+    uint32_t* d = nullptr;
+    uint32_t* cmds = nullptr;
+    size_t cmd_cap = 0;  // commands
+    hipEvent_t last = nullptr, cmd_last = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool recorded = false;
+};
+
 namespace mtr_host {
 
 struct BatchDeleter {

@@ -543,3 +543,20 @@ struct RootParams {
 };
 void mtr_launch_root(const RootParams& p, hipStream_t s);
 void mtr_launch_root_deltas(const RootParams& p, hipStream_t s);
+// players (k_play.hip, SPEC.md section 20): n play states advanced by dt in place, at most one of ncmds commands applied to
+// each (resolved through the zeroed scratch array, which the call leaves zeroed), and the frame's records written
+struct PlayParams {
+    const uint32_t* table;      // nclips x 4 words (PlayClip: period (f32 bits), flags, rate (f32 bits), key count); 16-byte aligned
+    uint32_t* states;           // n x 8 words (mtr_play_state); 16-byte aligned
+    uint32_t* scratch;          // >= n words, zero between calls
+    const uint32_t* cmds;       // ncmds x 4 words (mtr_play_cmd); 16-byte aligned; unused when ncmds == 0
+    uint32_t* out_states;       // n x 6 words (mtr_anim_state), 8-byte aligned, or nullptr
+    uint32_t* out_layers;       // n x nlayers x 4 words (mtr_anim_layer; layers 0 and 1 written), 16-byte aligned, or nullptr
+    uint32_t* out_steps;        // n x 2 x 4 words (mtr_root_step), 16-byte aligned, or nullptr
+    uint32_t ncmds;
+    uint32_t nclips;            // >= 1
+    uint32_t nlayers;           // 2..8 with out_layers, a validated host value
+    uint32_t n;
+    float dt;
+};
+void mtr_launch_play(const PlayParams& p, hipStream_t s);

@@ -70,7 +70,7 @@ pub const MTR_OWN_SUPERTILES: u32 = 2;
 pub const MTR_TEXRES_DECODED: u32 = 0;
 pub const MTR_TEXRES_BLOCKS: u32 = 1;
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root);
+opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player);
 
 /// animation clips (mtr.h, SPEC.md section 14): one key of one joint, 48 bytes
 pub const MTR_CLIP_LOOP: u32 = 1;
@@ -149,6 +149,28 @@ pub struct mtr_root_step {
     pub x: f32,
     pub dx: f32,
     pub w: f32,
+}
+/// players (mtr.h, SPEC.md section 20): the play state an instance keeps on the device, 32 bytes, and a command to it, 16 bytes
+pub const MTR_PLAY_ENDED: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_play_state {
+    pub clip_a: u32,
+    pub clip_b: u32,
+    pub x_a: f32,
+    pub x_b: f32,
+    pub w: f32,
+    pub fade: f32,
+    pub speed: f32,
+    pub flags: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_play_cmd {
+    pub instance: u32,
+    pub clip: u32,
+    pub x: f32,
+    pub seconds: f32,
 }
 /// what one instance plays: clip A at x_a cross-faded by w with clip B at x_b, positions in keys; 24 bytes
 #[repr(C)]
@@ -292,5 +314,18 @@ extern "C" {
                                 count: usize) -> i32;
     pub fn mtr_anim_root_deltas_device(traj: *mut mtr_anim, root: *mut mtr_anim_root, steps_dev: *const mtr_root_step, nsteps: usize, n: usize,
                                        out_dev: *mut f32, hip_stream: *mut c_void) -> i32;
+    // players (SPEC.md section 20): declarations only
+    pub fn mtr_anim_player_create(dev: *mut mtr_device, nclips: usize, nkeys: *const u32, flags: *const u32, rates: *const f32, max_instances: usize,
+                                  out: *mut *mut mtr_anim_player) -> i32;
+    pub fn mtr_anim_player_destroy(player: *mut mtr_anim_player);
+    pub fn mtr_anim_player_advance_device(player: *mut mtr_anim_player, states_dev: *mut mtr_play_state, n: usize, dt: f32, cmds: *const mtr_play_cmd,
+                                          ncmds: usize, out_states_dev: *mut mtr_anim_state, out_layers_dev: *mut mtr_anim_layer, nlayers: usize,
+                                          out_steps_dev: *mut mtr_root_step, hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_player_advance_device_cmds(player: *mut mtr_anim_player, states_dev: *mut mtr_play_state, n: usize, dt: f32,
+                                               cmds_dev: *const mtr_play_cmd, ncmds: usize, out_states_dev: *mut mtr_anim_state,
+                                               out_layers_dev: *mut mtr_anim_layer, nlayers: usize, out_steps_dev: *mut mtr_root_step,
+                                               hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_player_advance_host(player: *mut mtr_anim_player, states: *mut mtr_play_state, n: usize, dt: f32, cmds: *const mtr_play_cmd, ncmds: usize,
+                                        out_states: *mut mtr_anim_state, out_layers: *mut mtr_anim_layer, nlayers: usize, out_steps: *mut mtr_root_step) -> i32;
 }
 pub mod files;
