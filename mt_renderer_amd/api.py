@@ -661,25 +661,11 @@ class AnimRoot:
             self.dev.check(lib.mtr_anim_root_deltas(traj._h, self._h, _p(st), st.shape[1], st.shape[0], _p(out), out.size))
             return out
         import torch
-        t = _root_tensor(steps, self.dev, "root deltas")
-        if t.dim() != 3:
-            raise MtrError(MTR_E_INVALID, "root deltas: a tensor [n, S, 16 bytes]")
-        cur = torch.cuda.current_stream(t.device)
+        t, cur = _root_tensor(steps, self.dev, "root deltas", None, None)
         with torch.cuda.stream(cur):
-            if not t.is_contiguous() or t.data_ptr() % 16:
-                t = t.contiguous().clone()
             out = torch.empty((t.shape[0], 16), dtype=torch.float32, device=t.device)
-        args = (traj._h, self._h, C.c_void_p(t.data_ptr()), t.shape[1], t.shape[0], C.c_void_p(out.data_ptr()))
-        if cur.cuda_stream != 0:
-            self.dev.check(lib.mtr_anim_root_deltas_device(*args, C.c_void_p(cur.cuda_stream)))
-            t.record_stream(cur)
-        else:  # torch's legacy default stream: as set_poses
-            side = _pose_stream(t.device)
-            side.wait_stream(cur)
-            self.dev.check(lib.mtr_anim_root_deltas_device(*args, C.c_void_p(side.cuda_stream)))
-            t.record_stream(side)
-            out.record_stream(side)
-            cur.wait_stream(side)
+        _on_stream(self.dev, cur, lib.mtr_anim_root_deltas_device,
+                   (traj._h, self._h, C.c_void_p(t.data_ptr()), t.shape[1], t.shape[0], C.c_void_p(out.data_ptr())), (t, out))
         return out
 
     def close(self):
@@ -688,15 +674,14 @@ class AnimRoot:
             self._h = None
 
 
-def _root_tensor(t, dev: "Device", what: str):
-    import torch
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32, torch.float32):
-        raise MtrError(MTR_E_INVALID, f"{what}: a numpy ROOT_STEP array, a dict, or a uint8 / int32 / float32 tensor on the GPU")
-    if t.get_device() != dev.hip_device:
-        raise MtrError(MTR_E_INVALID, f"{what}: the tensor is on cuda:{t.get_device()}, the device is cuda:{dev.hip_device}")
-    if t.dim() < 2 or (t.shape[-1] * t.element_size()) != ROOT_STEP.itemsize:
-        raise MtrError(MTR_E_INVALID, f"{what}: steps of 16 bytes, [n, S, 16] uint8 or [n, S, 4] int32 / float32")
-    return t
+def _root_tensor(t, dev: "Device", what: str, n: Optional[int], stream):
+    """ROOT_STEP records [n, S] on the GPU (n None: any count) as _device_records returns them"""
+    t, cur = _device_records(t, dev, what, "a numpy ROOT_STEP array, a dict, or a uint8 / int32 / float32 tensor on the GPU", _U8_I32_F32,
+                             size_ok=lambda t: t.dim() >= 2 and t.shape[-1] * t.element_size() == ROOT_STEP.itemsize,
+                             size_msg="steps of 16 bytes, [n, S, 16] uint8 or [n, S, 4] int32 / float32", stream=stream, owner="device is")
+    if t.dim() != 3 or (n is not None and t.shape[0] != n):
+        raise MtrError(MTR_E_INVALID, f"{what}: a tensor [n, S, 16 bytes]")
+    return t, cur
 
 
 def play_cmds(cmds) -> np.ndarray:
@@ -780,17 +765,7 @@ class AnimPlayer:
             m, fn, cp = keep.size, lib.mtr_anim_player_advance_device, (_p(keep) if keep.size else None)
         cur = stream if stream is not None else torch.cuda.current_stream(states.device)
         args = (self._h, ptr(states), n, float(dt), cp, m, ptr(out_states), ptr(out_layers), nl, ptr(out_steps))
-        if cur.cuda_stream != 0:
-            self.dev.check(fn(*args, C.c_void_p(cur.cuda_stream)))
-            for t in used:
-                t.record_stream(cur)
-        else:  # torch's legacy default stream: as Batch.set_poses
-            side = _pose_stream(states.device)
-            side.wait_stream(cur)
-            self.dev.check(fn(*args, C.c_void_p(side.cuda_stream)))
-            for t in used:
-                t.record_stream(side)
-            cur.wait_stream(side)
+        _on_stream(self.dev, cur, fn, args, used)
 
     def advance_host(self, states: np.ndarray, dt: float, cmds=None, nlayers: int = 0, layers: Optional[np.ndarray] = None, want_states: bool = True,
                      want_steps: bool = True):
@@ -967,6 +942,50 @@ def _pose_stream(device):
     return _POSE_STREAMS[device.index]
 
 
+def _nbytes(t) -> int:
+    return t.numel() * t.element_size()
+
+
+_U8_I32, _U8_I32_F32 = ("uint8", "int32"), ("uint8", "int32", "float32")  # names of the torch dtypes a record tensor may have
+
+
+def _device_records(t, dev: "Device", what: str, expect: str, dtypes, *, size_ok=None, size_msg: str = "", align: int = 16, stream=None,
+                    owner: str = "batch on"):
+    """A tensor of records that a library call reads in stream order: its type (``dtypes``: names of torch dtypes), its
+    device and, where ``size_ok`` is given, its size (``size_ok(t)``) are checked in that order.  Returns (tensor, stream):
+    ``stream`` or torch.cuda.current_stream(), and the tensor contiguous and ``align``-byte aligned -- a copy made on that
+    stream where the caller's is not.  ``owner``: the words of the device message, which the root-motion calls word otherwise."""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in [getattr(torch, name) for name in dtypes]:
+        raise MtrError(MTR_E_INVALID, f"{what}: {expect}")
+    if t.get_device() != dev.hip_device:
+        raise MtrError(MTR_E_INVALID, f"{what}: the tensor is on cuda:{t.get_device()}, the {owner} cuda:{dev.hip_device}")
+    if size_ok is not None and not size_ok(t):
+        raise MtrError(MTR_E_INVALID, f"{what}: {size_msg}")
+    cur = stream if stream is not None else torch.cuda.current_stream(t.device)
+    if not t.is_contiguous() or t.data_ptr() % align:
+        with torch.cuda.stream(cur):
+            t = t.contiguous().clone()
+    return t, cur
+
+
+def _on_stream(dev: "Device", cur, fn, args, tensors):
+    """Runs the library call ``fn(*args, stream handle)`` in stream order on the torch stream ``cur`` and tells the allocator
+    that ``tensors`` are in use on the stream the call was given.  torch's legacy default stream: its handle, 0, would name the
+    device's own stream to the library (include/mtr.h), which is not ordered with it; the call runs on a helper stream that
+    follows the current one, and the current one waits for it."""
+    run, handle = cur, cur.cuda_stream
+    if handle == 0:
+        run = _pose_stream(cur.device)
+        run.wait_stream(cur)
+        handle = run.cuda_stream
+    dev.check(fn(*args, C.c_void_p(handle)))
+    for t in tensors:
+        t.record_stream(run)
+    if run is not cur:
+        cur.wait_stream(run)
+
+
 class Batch:
     """n instances of one Model resident in HBM (the build's scheduler submission)."""
 
@@ -1002,29 +1021,10 @@ class Batch:
             self.dev.check(lib.mtr_batch_set_poses(self._h, _p(lm), lm.shape[1]))
             self.npal = lm.shape[1]
             return
-        import torch
-        t = local_mats
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise MtrError(MTR_E_INVALID, "set_poses: a numpy array or a float32 tensor on the GPU")
-        if t.get_device() != self.dev.hip_device:
-            raise MtrError(MTR_E_INVALID, f"set_poses: the tensor is on cuda:{t.get_device()}, the batch on cuda:{self.dev.hip_device}")
-        cur = torch.cuda.current_stream(t.device)
-        if not t.is_contiguous() or t.data_ptr() % 16:
-            t = t.contiguous().clone()
+        t, cur = _device_records(local_mats, self.dev, "set_poses", "a numpy array or a float32 tensor on the GPU", ("float32",),
+                                 size_ok=lambda t: t.numel() % (self.n * 16) == 0, size_msg="n x njoints x 16 local matrices")
         nj = t.numel() // (self.n * 16)
-        if nj * self.n * 16 != t.numel():
-            raise MtrError(MTR_E_INVALID, "set_poses: n x njoints x 16 local matrices")
-        if cur.cuda_stream != 0:
-            self.dev.check(lib.mtr_batch_set_poses_device(self._h, C.c_void_p(t.data_ptr()), nj, C.c_void_p(cur.cuda_stream)))
-        else:
-            # torch's legacy default stream: its handle, 0, would name the device's own stream to the library (include/mtr.h),
-            # which is not ordered with it.  Run on a helper stream that follows the current one, and make the current one
-            # (and the allocator, for the input's block) wait for it.
-            side = _pose_stream(t.device)
-            side.wait_stream(cur)
-            self.dev.check(lib.mtr_batch_set_poses_device(self._h, C.c_void_p(t.data_ptr()), nj, C.c_void_p(side.cuda_stream)))
-            t.record_stream(side)
-            cur.wait_stream(side)
+        _on_stream(self.dev, cur, lib.mtr_batch_set_poses_device, (self._h, C.c_void_p(t.data_ptr()), nj), (t,))
         self.npal = nj
 
     def animate(self, anim: Anim, states):
@@ -1036,25 +1036,9 @@ class Batch:
             self.dev.check(lib.mtr_batch_animate(self._h, anim._h, _p(st)))
             self.npal = anim.njoints
             return
-        import torch
-        t = states
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32):
-            raise MtrError(MTR_E_INVALID, "animate: a numpy ANIM_STATE array, a dict, or a uint8 / int32 tensor on the GPU")
-        if t.get_device() != self.dev.hip_device:
-            raise MtrError(MTR_E_INVALID, f"animate: the tensor is on cuda:{t.get_device()}, the batch on cuda:{self.dev.hip_device}")
-        if t.numel() * t.element_size() != self.n * ANIM_STATE.itemsize:
-            raise MtrError(MTR_E_INVALID, "animate: n states of 24 bytes")
-        cur = torch.cuda.current_stream(t.device)
-        if not t.is_contiguous() or t.data_ptr() % 8:
-            t = t.contiguous().clone()
-        if cur.cuda_stream != 0:
-            self.dev.check(lib.mtr_batch_animate_device(self._h, anim._h, C.c_void_p(t.data_ptr()), C.c_void_p(cur.cuda_stream)))
-        else:  # torch's legacy default stream: as set_poses
-            side = _pose_stream(t.device)
-            side.wait_stream(cur)
-            self.dev.check(lib.mtr_batch_animate_device(self._h, anim._h, C.c_void_p(t.data_ptr()), C.c_void_p(side.cuda_stream)))
-            t.record_stream(side)
-            cur.wait_stream(side)
+        t, cur = _device_records(states, self.dev, "animate", "a numpy ANIM_STATE array, a dict, or a uint8 / int32 tensor on the GPU", _U8_I32,
+                                 size_ok=lambda t: _nbytes(t) == self.n * ANIM_STATE.itemsize, size_msg="n states of 24 bytes", align=8)
+        _on_stream(self.dev, cur, lib.mtr_batch_animate_device, (self._h, anim._h, C.c_void_p(t.data_ptr())), (t,))
         self.npal = anim.njoints
 
     def animate_layers(self, anim: Anim, layers, masks: Optional[AnimMasks] = None, L: Optional[int] = None):
@@ -1068,28 +1052,16 @@ class Batch:
             self.dev.check(lib.mtr_batch_animate_layers(self._h, anim._h, mh, _p(ly), ly.shape[1]))
             self.npal = anim.njoints
             return
-        import torch
-        t = layers
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32):
-            raise MtrError(MTR_E_INVALID, "animate_layers: a numpy ANIM_LAYER array, a dict, or a uint8 / int32 tensor on the GPU")
-        if t.get_device() != self.dev.hip_device:
-            raise MtrError(MTR_E_INVALID, f"animate_layers: the tensor is on cuda:{t.get_device()}, the batch on cuda:{self.dev.hip_device}")
-        nbytes = t.numel() * t.element_size()
-        if nbytes == 0 or nbytes % (self.n * ANIM_LAYER.itemsize) or (L is not None and nbytes != self.n * L * ANIM_LAYER.itemsize):
-            raise MtrError(MTR_E_INVALID, "animate_layers: n x L layers of 16 bytes")
-        nl = nbytes // (self.n * ANIM_LAYER.itemsize)
-        cur = torch.cuda.current_stream(t.device)
-        if not t.is_contiguous() or t.data_ptr() % 16:
-            t = t.contiguous().clone()
-        if cur.cuda_stream != 0:
-            self.dev.check(lib.mtr_batch_animate_layers_device(self._h, anim._h, mh, C.c_void_p(t.data_ptr()), nl, C.c_void_p(cur.cuda_stream)))
-        else:  # torch's legacy default stream: as set_poses
-            side = _pose_stream(t.device)
-            side.wait_stream(cur)
-            self.dev.check(lib.mtr_batch_animate_layers_device(self._h, anim._h, mh, C.c_void_p(t.data_ptr()), nl, C.c_void_p(side.cuda_stream)))
-            t.record_stream(side)
-            cur.wait_stream(side)
+        t, cur = _device_records(layers, self.dev, "animate_layers", "a numpy ANIM_LAYER array, a dict, or a uint8 / int32 tensor on the GPU", _U8_I32,
+                                 size_ok=lambda t: self._layer_stacks(t, L), size_msg="n x L layers of 16 bytes")
+        nl = _nbytes(t) // (self.n * ANIM_LAYER.itemsize)
+        _on_stream(self.dev, cur, lib.mtr_batch_animate_layers_device, (self._h, anim._h, mh, C.c_void_p(t.data_ptr()), nl), (t,))
         self.npal = anim.njoints
+
+    def _layer_stacks(self, t, L: Optional[int]) -> bool:
+        """t holds n stacks of whole ANIM_LAYER records, of L each where L is given"""
+        nbytes = _nbytes(t)
+        return nbytes != 0 and nbytes % (self.n * ANIM_LAYER.itemsize) == 0 and (L is None or nbytes == self.n * L * ANIM_LAYER.itemsize)
 
     def animate_ik(self, anim: Anim, layers, ik: AnimIK, targets, masks: Optional[AnimMasks] = None, L: Optional[int] = None):
         """one layer stack and one target per chain of ``ik`` per instance (k_anim_ik, SPEC.md section 17).  Numpy arrays
@@ -1111,33 +1083,18 @@ class Batch:
             if isinstance(t, host):
                 raw = np.ascontiguousarray(make(t)).view(np.uint8).reshape(self.n, -1)
                 return torch.from_numpy(raw.copy()).to(device)
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32, torch.float32):
-                raise MtrError(MTR_E_INVALID, f"animate_ik: {what} as a numpy array, a dict, or a uint8 / int32 / float32 tensor on the GPU")
-            if t.get_device() != self.dev.hip_device:
-                raise MtrError(MTR_E_INVALID, f"animate_ik: the tensor is on cuda:{t.get_device()}, the batch on cuda:{self.dev.hip_device}")
-            if not t.is_contiguous() or t.data_ptr() % 16:
-                t = t.contiguous().clone()
-            return t
+            # the sizes of the pair are checked below, once both are tensors
+            return _device_records(t, self.dev, "animate_ik", f"{what} as a numpy array, a dict, or a uint8 / int32 / float32 tensor on the GPU",
+                                   _U8_I32_F32)[0]
         tl = on_device(layers, "layers", lambda a: anim_layers(a, self.n, L))
         tt = on_device(targets, "targets", lambda a: ik_targets(a, self.n, ik.nchains))
-        nbytes = tl.numel() * tl.element_size()
-        if nbytes == 0 or nbytes % (self.n * ANIM_LAYER.itemsize) or (L is not None and nbytes != self.n * L * ANIM_LAYER.itemsize):
+        if not self._layer_stacks(tl, L):
             raise MtrError(MTR_E_INVALID, "animate_ik: n x L layers of 16 bytes")
-        if tt.numel() * tt.element_size() != self.n * ik.nchains * ANIM_IK_TARGET.itemsize:
+        if _nbytes(tt) != self.n * ik.nchains * ANIM_IK_TARGET.itemsize:
             raise MtrError(MTR_E_INVALID, "animate_ik: n x nchains targets of 32 bytes")
-        nl = nbytes // (self.n * ANIM_LAYER.itemsize)
-        cur = torch.cuda.current_stream(device)
-        if cur.cuda_stream != 0:
-            self.dev.check(lib.mtr_batch_animate_ik_device(self._h, anim._h, mh, C.c_void_p(tl.data_ptr()), nl, ik._h, C.c_void_p(tt.data_ptr()),
-                                                           C.c_void_p(cur.cuda_stream)))
-        else:  # torch's legacy default stream: as set_poses
-            side = _pose_stream(device)
-            side.wait_stream(cur)
-            self.dev.check(lib.mtr_batch_animate_ik_device(self._h, anim._h, mh, C.c_void_p(tl.data_ptr()), nl, ik._h, C.c_void_p(tt.data_ptr()),
-                                                           C.c_void_p(side.cuda_stream)))
-            tl.record_stream(side)
-            tt.record_stream(side)
-            cur.wait_stream(side)
+        nl = _nbytes(tl) // (self.n * ANIM_LAYER.itemsize)
+        _on_stream(self.dev, torch.cuda.current_stream(device), lib.mtr_batch_animate_ik_device,
+                   (self._h, anim._h, mh, C.c_void_p(tl.data_ptr()), nl, ik._h, C.c_void_p(tt.data_ptr())), (tl, tt))
         self.npal = anim.njoints
 
     def attach(self, src: "Batch", recs, stream=None):
@@ -1150,27 +1107,9 @@ class Batch:
             rc = attach_records(recs, self.n)
             self.dev.check(lib.mtr_batch_attach(self._h, src._h, _p(rc)))
             return
-        import torch
-        t = recs
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.int32, torch.float32):
-            raise MtrError(MTR_E_INVALID, "attach: a numpy ATTACH array, a dict, or a uint8 / int32 / float32 tensor on the GPU")
-        if t.get_device() != self.dev.hip_device:
-            raise MtrError(MTR_E_INVALID, f"attach: the tensor is on cuda:{t.get_device()}, the batch on cuda:{self.dev.hip_device}")
-        if t.numel() * t.element_size() != self.n * ATTACH.itemsize:
-            raise MtrError(MTR_E_INVALID, "attach: n records of 80 bytes")
-        cur = stream if stream is not None else torch.cuda.current_stream(t.device)
-        if not t.is_contiguous() or t.data_ptr() % 16:
-            with torch.cuda.stream(cur):
-                t = t.contiguous().clone()
-        if cur.cuda_stream != 0:
-            self.dev.check(lib.mtr_batch_attach_device(self._h, src._h, C.c_void_p(t.data_ptr()), C.c_void_p(cur.cuda_stream)))
-            t.record_stream(cur)
-        else:  # torch's legacy default stream: as set_poses
-            side = _pose_stream(t.device)
-            side.wait_stream(cur)
-            self.dev.check(lib.mtr_batch_attach_device(self._h, src._h, C.c_void_p(t.data_ptr()), C.c_void_p(side.cuda_stream)))
-            t.record_stream(side)
-            cur.wait_stream(side)
+        t, cur = _device_records(recs, self.dev, "attach", "a numpy ATTACH array, a dict, or a uint8 / int32 / float32 tensor on the GPU", _U8_I32_F32,
+                                 size_ok=lambda t: _nbytes(t) == self.n * ATTACH.itemsize, size_msg="n records of 80 bytes", stream=stream)
+        _on_stream(self.dev, cur, lib.mtr_batch_attach_device, (self._h, src._h, C.c_void_p(t.data_ptr())), (t,))
 
     def root_motion(self, traj: "Anim", root: "AnimRoot", steps):
         """moves every instance by the blended delta of its steps on the trajectory set ``traj`` (k_root, SPEC.md section 19):
@@ -1182,24 +1121,8 @@ class Batch:
     def root_motion_device(self, traj: "Anim", root: "AnimRoot", steps, stream=None):
         """the same from a torch uint8 [n, S, 16] / int32 / float32 [n, S, 4] tensor on the batch's device holding ROOT_STEP
         records, read in stream order on ``stream`` (a torch stream; None: torch.cuda.current_stream())."""
-        import torch
-        t = _root_tensor(steps, self.dev, "root motion")
-        if t.dim() != 3 or t.shape[0] != self.n:
-            raise MtrError(MTR_E_INVALID, "root motion: a tensor [n, S, 16 bytes]")
-        nsteps = t.shape[1]
-        cur = stream if stream is not None else torch.cuda.current_stream(t.device)
-        if not t.is_contiguous() or t.data_ptr() % 16:
-            with torch.cuda.stream(cur):
-                t = t.contiguous().clone()
-        if cur.cuda_stream != 0:
-            self.dev.check(lib.mtr_batch_root_motion_device(self._h, traj._h, root._h, C.c_void_p(t.data_ptr()), nsteps, C.c_void_p(cur.cuda_stream)))
-            t.record_stream(cur)
-        else:  # torch's legacy default stream: as set_poses
-            side = _pose_stream(t.device)
-            side.wait_stream(cur)
-            self.dev.check(lib.mtr_batch_root_motion_device(self._h, traj._h, root._h, C.c_void_p(t.data_ptr()), nsteps, C.c_void_p(side.cuda_stream)))
-            t.record_stream(side)
-            cur.wait_stream(side)
+        t, cur = _root_tensor(steps, self.dev, "root motion", self.n, stream)
+        _on_stream(self.dev, cur, lib.mtr_batch_root_motion_device, (self._h, traj._h, root._h, C.c_void_p(t.data_ptr()), t.shape[1]), (t,))
 
     def sockets(self, recs) -> np.ndarray:
         """the matrices alone, [len(recs), 16]: ATTACH records (a numpy array or a dict) against THIS batch's current

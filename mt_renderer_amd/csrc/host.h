@@ -18,6 +18,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <initializer_list>
 #include <thread>
 #include <string>
 #include <utility>
@@ -308,7 +309,7 @@ struct mtr_batch {
     // caller's stream of mtr_batch_set_poses_device); frames that draw the version wait on it.
     // read: recorded behind the last outside reader of d, a k_attach launched for ANOTHER batch's update or for a socket call
     // (SPEC.md section 18), on a stream this batch's updates need not share.  A reader queued on another stream than the one
-    // before first waits for it, so the one event covers every reader (as mtr_anim::last does).  read_pending: recorded since
+    // before first waits for it, so the one event covers every reader (as DeviceSet::last does).  read_pending: recorded since
     // the version's last write; that write's successor waits for it, and a buffer retired meanwhile is parked behind it.
     struct Ver {
         float* d = nullptr; size_t cap = 0; uint32_t npal = 0; hipEvent_t ready = nullptr; uint64_t last_frame = 0; bool used = false; uint32_t pinned = 0;
@@ -324,70 +325,60 @@ struct mtr_batch {
     uint64_t hint_key = 0;       // the ownership (table, rank) the slot's numbers were reported under
 };
 
+namespace mtr_host {
+
+// What the five set handles below share: device memory `d`, uploaded once, and the event that covers its readers.  `last` is
+// recorded behind every kernel that reads d (set_after); a kernel queued on another stream than the one before first waits
+// for it (set_before), so the one event always covers every reader and the set's destroy can park d behind it (set_park).
+struct DeviceSet {
+    mtr_device* dev = nullptr;
+    uint32_t* d = nullptr;
+    hipEvent_t last = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool recorded = false;
+};
+
+}  // namespace mtr_host
+
 // An animation set (SPEC.md section 14): immutable once uploaded.  d: the clip table (nclips x 4 words: first key, key count,
-// flags, 0), then the keys.  `last` is recorded behind every kernel that reads d; a kernel queued on another stream than
-// the one before first waits for it, so the one event always covers every reader and mtr_anim_destroy can park d behind it.
-// A track set (section 15) is the same object with tracks set.  Then d holds: the clip table (0, length in ticks, flags, 0),
-// nclips * njoints * 3 descriptors of 32 bytes, nkeys key values of 8 bytes, nkeys u16 key times.
-struct mtr_anim {
-    mtr_device* dev;
+// flags, 0), then the keys.  A track set (section 15) is the same object with tracks set.  Then d holds: the clip table (0,
+// length in ticks, flags, 0), nclips * njoints * 3 descriptors of 32 bytes, nkeys key values of 8 bytes, nkeys u16 key times
+// (host_anim.cpp: ClipImage).
+struct mtr_anim : mtr_host::DeviceSet {
     uint32_t njoints = 0, nclips = 0;
     bool tracks = false;
     uint32_t nkeys = 0;          // a track set's key total
     bool has_loop = false;       // a clip carries MTR_CLIP_LOOP: no trajectory for root motion (section 19)
-    uint32_t* d = nullptr;
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool recorded = false;
 };
 
-// A mask set (SPEC.md section 16): immutable once uploaded.  d: nmasks x njoints weights (the user's masks 1..nmasks).  `last`
-// as mtr_anim's: recorded behind every kernel that reads d, so that mtr_anim_masks_destroy can park d behind it.
-struct mtr_anim_masks {
-    mtr_device* dev;
+// A mask set (SPEC.md section 16): immutable once uploaded.  d: nmasks x njoints weights (the user's masks 1..nmasks).
+struct mtr_anim_masks : mtr_host::DeviceSet {
     uint32_t njoints = 0, nmasks = 0;
-    float* d = nullptr;
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool recorded = false;
+    const float* weights() const { return reinterpret_cast<const float*>(d); }
 };
 
 // An IK set (SPEC.md section 17): immutable once uploaded.  d: nchains x 8 words of validated chains, the path table
 // (njoints u32) and the path bytes of the skeleton its parents describe (what mtr_anim_sample_ik walks; the animate calls
-// walk the model's own, after comparing the parents).  `last` as mtr_anim's.
-struct mtr_anim_ik {
-    mtr_device* dev;
+// walk the model's own, after comparing the parents).
+struct mtr_anim_ik : mtr_host::DeviceSet {
     uint32_t njoints = 0, nchains = 0, path_bytes = 0;
     std::vector<uint8_t> parents;  // a root as 255
-    uint32_t* d = nullptr;
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool recorded = false;
 };
 
-// A root set (SPEC.md section 19): immutable once uploaded.  d: nclips flag words (MTR_ROOT_CYCLIC).  `last` as mtr_anim's.
-struct mtr_anim_root {
-    mtr_device* dev;
+// A root set (SPEC.md section 19): immutable once uploaded.  d: nclips flag words (MTR_ROOT_CYCLIC).
+struct mtr_anim_root : mtr_host::DeviceSet {
     uint32_t njoints = 0, nclips = 0, joint = 0;
-    uint32_t* d = nullptr;
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool recorded = false;
 };
 
 // A player set (SPEC.md section 20).  d: nclips table entries of 4 words (period, flags, rate, key count), immutable, then
 // the scratch array of max_instances words, zero between calls.  cmds: where host commands are staged, grown on demand
-// (the outgrown buffer parked behind cmd_last, the event of the last kernel that read it).  `last` as mtr_anim's, but a
-// player's kernels also WRITE d (the scratch), so it orders the calls on one player among themselves.
-struct mtr_anim_player {
-    mtr_device* dev;
+// (the outgrown buffer parked behind cmd_last, the event of the last kernel that read it).  A player's kernels also WRITE d
+// (the scratch), so `last` orders the calls on one player among themselves.
+struct mtr_anim_player : mtr_host::DeviceSet {
     uint32_t nclips = 0, max_instances = 0;
-    uint32_t* d = nullptr;
     uint32_t* cmds = nullptr;
     size_t cmd_cap = 0;  // commands
-    hipEvent_t last = nullptr, cmd_last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool recorded = false;
+    hipEvent_t cmd_last = nullptr;
 };
 
 namespace mtr_host {
@@ -521,6 +512,7 @@ bool pose_paths(const uint8_t* parents, size_t n, std::vector<uint32_t>& paths, 
 
 // ---- host_batch.cpp ----
 int32_t stage_pose(mtr_device* d, const float* local_mats, size_t count);
+int32_t stage_ik(mtr_device* d, const mtr_anim_layer* layers, size_t nl, const mtr_ik_target* targets, size_t nt, const void** targets_dev);
 PoseParams pose_params(const mtr_model::Skeleton& sk, const float* locals, float* out);
 // Buffers and events nobody can use any more, collected under submit_mu and released after it (release_now).
 struct FreeList {
@@ -529,6 +521,54 @@ struct FreeList {
 };
 void release_now(FreeList& fl);
 void batch_unref(mtr_batch* b, FreeList& fl);
+
+// ---- host_anim.cpp ----
+// the stream of a device call: the caller's, or the device's own
+inline hipStream_t caller_stream(const mtr_device* d, void* hip_stream) { return hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream; }
+// One part of a set's device image: bytes from p, or bytes of zeroes (p == nullptr: filled on the copy stream and waited for).
+struct Part { const void* p; size_t bytes; };
+// Allocates s->d for the parts behind each other, uploads them in order and creates s->last; "<what> upload: ..." on failure
+int32_t set_upload(DeviceSet* s, const char* what, std::initializer_list<Part> parts);
+// around a kernel on `st` that reads (a player: also writes) the set: see DeviceSet::last
+int32_t set_before(DeviceSet* s, hipStream_t st);
+int32_t set_after(DeviceSet* s, hipStream_t st);
+// a kernel may still read the set: d is parked behind the event of the last one, collected by a later submit
+void set_park(DeviceSet* s);
+// Device scratch of `words` 4-byte words for one synchronous host call: run(scratch) queues copies in, kernels and copies out
+// on the copy stream, which is waited for also when a step failed, since the scratch is freed next.
+template <class F>
+int32_t round_trip(mtr_device* d, size_t words, F&& run) {
+    float* tmp = nullptr;
+    int32_t rc = dev_alloc(d, &tmp, words);
+    if (rc) return rc;
+    rc = run(tmp);
+    const hipError_t e = hipStreamSynchronize(d->s_copy);
+    (void)hipFree(tmp);
+    if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return rc;
+}
+// One animate call: which sets it reads and where its records lie in device memory.  kind says which records: one state per
+// instance, nlayers layers per instance (masks optional), or such layers and then ik->nchains targets per instance.
+struct AnimCall {
+    enum Kind { kStates, kLayers, kIk };
+    Kind kind = kStates;
+    mtr_anim* anim = nullptr;
+    mtr_anim_masks* masks = nullptr;
+    mtr_anim_ik* ik = nullptr;
+    const void* recs = nullptr;     // the states or the layers
+    size_t nlayers = 0;             // layers per instance of a layered call, as the caller gave it (anim_check: 1 to 8)
+    const void* targets = nullptr;
+};
+// What every animate call checks of its sets, in one order: against the model's skeleton, or (m == nullptr) for a sample call,
+// which has none; no_room: the message of a sample call whose size test failed, reported where that test stands
+int32_t anim_check(mtr_device* d, const mtr_model* m, const AnimCall& c, const char* no_room = nullptr);
+// The one place that runs k_anim*: the sets' events around the launcher of the call's kind and the set's kind.  sk: the
+// skeleton the palettes (out) are folded with; nullptr: a sample call, out takes the local matrices and the caller waits
+// for the stream, so no event is touched.
+int32_t anim_enqueue(const AnimCall& c, const mtr_model::Skeleton* sk, float* out, uint32_t ninst, hipStream_t s);
+// root motion (section 19): what every call checks, and k_root (mats_in * D) or k_root_deltas (mats_in == nullptr: D) on s
+int32_t root_check(mtr_device* d, const mtr_anim* traj, const mtr_anim_root* root, size_t nsteps, bool deltas);
+int32_t root_enqueue(mtr_anim* traj, mtr_anim_root* root, const void* steps_dev, size_t nsteps, size_t n, const float* mats_in, float* out, hipStream_t s);
 
 // ---- host_frame.cpp ----
 void release_palette_pins(mtr_frame* f);

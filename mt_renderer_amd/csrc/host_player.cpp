@@ -50,14 +50,7 @@ int32_t play_launch(mtr_anim_player* pl, void* states_dev, size_t n, float dt, c
     pp.ncmds = (uint32_t)ncmds; pp.nclips = pl->nclips; pp.nlayers = (uint32_t)o.nlayers; pp.n = (uint32_t)n; pp.dt = dt;
     mtr_launch_play(pp, s);
     HIPCHK(d, hipGetLastError());
-    HIPCHK(d, hipEventRecord(pl->last, s));
-    pl->last_stream = s; pl->recorded = true;
-    return MTR_OK;
-}
-
-int32_t play_before(mtr_anim_player* pl, hipStream_t s) {
-    if (pl->recorded && pl->last_stream != s) HIPCHK(pl->dev, hipStreamWaitEvent(s, pl->last, 0));
-    return MTR_OK;
+    return set_after(pl, s);
 }
 
 // room for ncmds commands in the player's staging buffer; an outgrown buffer is parked behind the last kernel that read it
@@ -86,10 +79,10 @@ int32_t play_advance_device(mtr_anim_player* pl, mtr_play_state* states_dev, siz
     if (cmds_on_device && ncmds > 0 && ((uintptr_t)cmds & 15u)) return fail(d, MTR_E_INVALID, "player advance: device commands must be 16-byte aligned");
     int32_t rc = play_check(pl, states_dev, n, cmds, ncmds, o, true);
     if (rc) return rc;
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : d->stream;
+    hipStream_t s = caller_stream(d, hip_stream);
     const void* cmds_dev = cmds;
     if (ncmds > 0 && !cmds_on_device && (rc = play_reserve_cmds(pl, ncmds))) return rc;
-    if ((rc = play_before(pl, s))) return rc;
+    if ((rc = set_before(pl, s))) return rc;
     if (ncmds > 0 && !cmds_on_device) {
         HIPCHK(d, hipMemcpyAsync(pl->cmds, cmds, ncmds * sizeof(mtr_play_cmd), hipMemcpyHostToDevice, s));
         cmds_dev = pl->cmds;
@@ -132,12 +125,7 @@ int32_t mtr_anim_player_create(mtr_device* d, size_t nclips, const uint32_t* nke
     if (rc) return rc;
     auto pl = std::make_unique<mtr_anim_player>();
     pl->dev = d; pl->nclips = (uint32_t)nclips; pl->max_instances = (uint32_t)max_instances;
-    if ((rc = dev_alloc(d, &pl->d, img.size() + max_instances))) return rc;
-    hipError_t e = hipMemcpy(pl->d, img.data(), img.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(pl->d + img.size(), 0, max_instances * 4, d->s_copy);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->s_copy);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->last, hipEventDisableTiming);
-    if (e != hipSuccess) { (void)hipFree(pl->d); return fail(d, MTR_E_HIP, std::string("anim player upload: ") + hipGetErrorString(e)); }
+    if ((rc = set_upload(pl.get(), "anim player", {{img.data(), img.size() * 4}, {nullptr, max_instances * 4}}))) return rc;  // the table, the zeroed scratch
     *out = pl.release();
     return MTR_OK;
 }
@@ -145,12 +133,10 @@ int32_t mtr_anim_player_create(mtr_device* d, size_t nclips, const uint32_t* nke
 void mtr_anim_player_destroy(mtr_anim_player* pl) {
     if (!pl) return;
     mtr_device* d = pl->dev;
-    {
-        // a kernel may still read the table, the scratch or the staged commands: parked behind the events of the last ones,
-        // collected by a later submit
+    set_park(pl);
+    if (pl->cmds || pl->cmd_last) {  // the staged commands likewise, behind the last kernel that read them
         std::lock_guard<std::mutex> submit_lock(d->submit_mu);
-        d->garbage.push_back({pl->d, 0, pl->last});
-        if (pl->cmds || pl->cmd_last) d->garbage.push_back({pl->cmds, 0, pl->cmd_last});
+        d->garbage.push_back({pl->cmds, 0, pl->cmd_last});
     }
     delete pl;
 }
@@ -177,15 +163,14 @@ int32_t mtr_anim_player_advance_host(mtr_anim_player* pl, mtr_play_state* states
     // one block of 16-byte words: the states, the commands, the steps, the layers, then the animation states (24 bytes each)
     const size_t w_states = n * 8, w_cmds = ncmds * 4, w_steps = out_steps ? n * 8 : 0, w_layers = out_layers ? n * nlayers * 4 : 0,
                  w_anim = out_states ? n * 6 : 0;
-    uint32_t* tmp = nullptr;
-    if ((rc = dev_alloc(d, &tmp, w_states + w_cmds + w_steps + w_layers + w_anim))) return rc;
-    uint32_t *t_cmds = tmp + w_states, *t_steps = t_cmds + w_cmds, *t_layers = t_steps + w_steps, *t_anim = t_layers + w_layers;
     hipStream_t s = d->s_copy;
-    auto run = [&]() -> int32_t {
+    return round_trip(d, w_states + w_cmds + w_steps + w_layers + w_anim, [&](float* scratch) -> int32_t {
+        uint32_t* tmp = reinterpret_cast<uint32_t*>(scratch);
+        uint32_t *t_cmds = tmp + w_states, *t_steps = t_cmds + w_cmds, *t_layers = t_steps + w_steps, *t_anim = t_layers + w_layers;
         HIPCHK(d, hipMemcpyAsync(tmp, states, w_states * 4, hipMemcpyHostToDevice, s));
         if (w_cmds) HIPCHK(d, hipMemcpyAsync(t_cmds, cmds, w_cmds * 4, hipMemcpyHostToDevice, s));
         if (w_layers) HIPCHK(d, hipMemcpyAsync(t_layers, out_layers, w_layers * 4, hipMemcpyHostToDevice, s));
-        int32_t r2 = play_before(pl, s);
+        int32_t r2 = set_before(pl, s);
         if (r2) return r2;
         PlayOuts o;
         o.states = w_anim ? reinterpret_cast<mtr_anim_state*>(t_anim) : nullptr;
@@ -198,12 +183,7 @@ int32_t mtr_anim_player_advance_host(mtr_anim_player* pl, mtr_play_state* states
         if (w_layers) HIPCHK(d, hipMemcpyAsync(out_layers, t_layers, w_layers * 4, hipMemcpyDeviceToHost, s));
         if (w_anim) HIPCHK(d, hipMemcpyAsync(out_states, t_anim, w_anim * 4, hipMemcpyDeviceToHost, s));
         return MTR_OK;
-    };
-    rc = run();
-    const hipError_t e = hipStreamSynchronize(s);  // also when a step failed: the buffer is freed next
-    (void)hipFree(tmp);
-    if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    return rc;
+    });
 }
 
 }  // extern "C"

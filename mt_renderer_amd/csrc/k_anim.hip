@@ -442,85 +442,57 @@ __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_layers_tracks_samp
 static bool anim_launchable(const AnimParams& p, uint32_t ninst) {
     return ninst != 0 && p.nclips != 0 && p.pose.njoints != 0 && p.pose.njoints <= MTR_POSE_MAX_JOINTS;
 }
-
-void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_launchable(p, ninst) || p.pose.path_bytes > MTR_POSE_MAX_PATH_BYTES) return;
-    const uint32_t threads = (p.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim, dim3(ninst), dim3(threads), p.pose.path_bytes, s, p);
-}
-
-void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_launchable(p, ninst)) return;
-    const uint32_t threads = (p.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_sample, dim3(ninst), dim3(threads), 0, s, p);
-}
-
-void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_launchable(p, ninst) || p.pose.path_bytes > MTR_POSE_MAX_PATH_BYTES || !p.tracks) return;
-    const uint32_t threads = (p.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_tracks, dim3(ninst), dim3(threads), p.pose.path_bytes, s, p);
-}
-
-void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_launchable(p, ninst) || !p.tracks) return;
-    const uint32_t threads = (p.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_tracks_sample, dim3(ninst), dim3(threads), 0, s, p);
-}
-
 static bool anim_layers_launchable(const AnimLayerParams& p, uint32_t ninst, bool tracks) {
     return anim_launchable(p.anim, ninst) && p.layers && p.nlayers >= 1u && p.nlayers <= MTR_ANIM_MAX_LAYERS && (p.nmasks == 0u || p.masks) &&
            (tracks ? p.anim.tracks != nullptr : p.anim.keys != nullptr);
 }
-
-void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_layers_launchable(p, ninst, false) || p.anim.pose.path_bytes > MTR_POSE_MAX_PATH_BYTES) return;
-    const uint32_t threads = (p.anim.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_layers, dim3(ninst), dim3(threads), p.anim.pose.path_bytes, s, p);
-}
-
-void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_layers_launchable(p, ninst, false)) return;
-    const uint32_t threads = (p.anim.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_layers_sample, dim3(ninst), dim3(threads), 0, s, p);
-}
-
-void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_layers_launchable(p, ninst, true) || p.anim.pose.path_bytes > MTR_POSE_MAX_PATH_BYTES) return;
-    const uint32_t threads = (p.anim.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_layers_tracks, dim3(ninst), dim3(threads), p.anim.pose.path_bytes, s, p);
-}
-
-void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_layers_launchable(p, ninst, true)) return;
-    const uint32_t threads = (p.anim.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_layers_tracks_sample, dim3(ninst), dim3(threads), 0, s, p);
-}
-
 static bool anim_ik_launchable(const AnimIkParams& p, uint32_t ninst, bool tracks) {
     return anim_layers_launchable(p.layers, ninst, tracks) && p.chains && p.targets && p.paths && p.path_words && p.nchains >= 1u &&
            p.nchains <= MTR_ANIM_MAX_IK && p.path_bytes != 0u && p.path_bytes <= MTR_POSE_MAX_PATH_BYTES;
 }
+static bool fold_fits(const PoseParams& pose) { return pose.path_bytes <= MTR_POSE_MAX_PATH_BYTES; }
 
+// the launch every kernel here takes, if its parameters pass: a block per instance, a thread per joint in whole waves, `lds`
+// bytes for the path table
+template <class P>
+static void anim_launch(void (*kernel)(P), const P& p, bool ok, uint32_t njoints, uint32_t lds, uint32_t ninst, hipStream_t s) {
+    if (ok) hipLaunchKernelGGL(kernel, dim3(ninst), dim3((njoints + 63u) & ~63u), lds, s, p);
+}
+
+void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s) {
+    anim_launch(mtr::k_anim, p, anim_launchable(p, ninst) && fold_fits(p.pose), p.pose.njoints, p.pose.path_bytes, ninst, s);
+}
+void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) {
+    anim_launch(mtr::k_anim_sample, p, anim_launchable(p, ninst), p.pose.njoints, 0, ninst, s);
+}
+void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s) {
+    anim_launch(mtr::k_anim_tracks, p, anim_launchable(p, ninst) && fold_fits(p.pose) && p.tracks, p.pose.njoints, p.pose.path_bytes, ninst, s);
+}
+void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) {
+    anim_launch(mtr::k_anim_tracks_sample, p, anim_launchable(p, ninst) && p.tracks, p.pose.njoints, 0, ninst, s);
+}
+void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
+    anim_launch(mtr::k_anim_layers, p, anim_layers_launchable(p, ninst, false) && fold_fits(p.anim.pose), p.anim.pose.njoints, p.anim.pose.path_bytes, ninst, s);
+}
+void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
+    anim_launch(mtr::k_anim_layers_sample, p, anim_layers_launchable(p, ninst, false), p.anim.pose.njoints, 0, ninst, s);
+}
+void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
+    anim_launch(mtr::k_anim_layers_tracks, p, anim_layers_launchable(p, ninst, true) && fold_fits(p.anim.pose), p.anim.pose.njoints, p.anim.pose.path_bytes, ninst, s);
+}
+void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
+    anim_launch(mtr::k_anim_layers_tracks_sample, p, anim_layers_launchable(p, ninst, true), p.anim.pose.njoints, 0, ninst, s);
+}
+// the chain walks need the path table in LDS also where nothing is folded; a fold reads the same one
 void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_ik_launchable(p, ninst, false) || p.layers.anim.pose.path_bytes != p.path_bytes) return;
-    const uint32_t threads = (p.layers.anim.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_ik, dim3(ninst), dim3(threads), p.path_bytes, s, p);
+    anim_launch(mtr::k_anim_ik, p, anim_ik_launchable(p, ninst, false) && p.layers.anim.pose.path_bytes == p.path_bytes, p.layers.anim.pose.njoints, p.path_bytes, ninst, s);
 }
-
 void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_ik_launchable(p, ninst, false)) return;
-    const uint32_t threads = (p.layers.anim.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_ik_sample, dim3(ninst), dim3(threads), p.path_bytes, s, p);
+    anim_launch(mtr::k_anim_ik_sample, p, anim_ik_launchable(p, ninst, false), p.layers.anim.pose.njoints, p.path_bytes, ninst, s);
 }
-
 void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_ik_launchable(p, ninst, true) || p.layers.anim.pose.path_bytes != p.path_bytes) return;
-    const uint32_t threads = (p.layers.anim.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_ik_tracks, dim3(ninst), dim3(threads), p.path_bytes, s, p);
+    anim_launch(mtr::k_anim_ik_tracks, p, anim_ik_launchable(p, ninst, true) && p.layers.anim.pose.path_bytes == p.path_bytes, p.layers.anim.pose.njoints, p.path_bytes, ninst, s);
 }
-
 void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
-    if (!anim_ik_launchable(p, ninst, true)) return;
-    const uint32_t threads = (p.layers.anim.pose.njoints + 63u) & ~63u;
-    hipLaunchKernelGGL(mtr::k_anim_ik_tracks_sample, dim3(ninst), dim3(threads), p.path_bytes, s, p);
+    anim_launch(mtr::k_anim_ik_tracks_sample, p, anim_ik_launchable(p, ninst, true), p.layers.anim.pose.njoints, p.path_bytes, ninst, s);
 }

@@ -1,4 +1,4 @@
-// AddressSanitizer / UBSan run of the HOST side of the animation entry points (csrc/host_batch.cpp: mtr_anim_*, mtr_*_animate*)
+// AddressSanitizer / UBSan run of the HOST side of the animation entry points (csrc/host_anim.cpp, csrc/host_batch.cpp: mtr_anim_*, mtr_*_animate*)
 // over the stand-in HIP runtime (tests/cpp/hip_stub: device memory = host heap).  The k_anim launchers here are readers: they
 // touch, for every instance, its state and the first and last word of the keys its (clamped) clips own, and the last word of
 // what they would write, so a wrong size or offset on the host side is an ASan report.   usage: anim_host_asan <iterations>

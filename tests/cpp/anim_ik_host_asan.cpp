@@ -1,4 +1,4 @@
-// AddressSanitizer / UBSan run of the HOST side of inverse kinematics (csrc/host_batch.cpp: mtr_anim_ik_create / _destroy,
+// AddressSanitizer / UBSan run of the HOST side of inverse kinematics (csrc/host_anim.cpp, csrc/host_batch.cpp: mtr_anim_ik_create / _destroy,
 // mtr_model_animate_ik, mtr_batch_animate_ik, mtr_batch_animate_ik_device, mtr_anim_sample_ik) over the stand-in HIP runtime
 // (tests/cpp/hip_stub: device memory = host heap).  The four k_anim_ik launchers here are readers: for every instance they
 // touch its first and last layer and its first and last target, every chain of the set, the path table entry of every

@@ -1,4 +1,4 @@
-// AddressSanitizer / UBSan run of the HOST side of animation layers (csrc/host_batch.cpp: mtr_anim_masks_create / _destroy,
+// AddressSanitizer / UBSan run of the HOST side of animation layers (csrc/host_anim.cpp, csrc/host_batch.cpp: mtr_anim_masks_create / _destroy,
 // mtr_model_animate_layers, mtr_batch_animate_layers, mtr_batch_animate_layers_device, mtr_anim_sample_layers) over the
 // stand-in HIP runtime (tests/cpp/hip_stub: device memory = host heap).  The four k_anim_layers launchers here are readers:
 // for every instance they touch its first and last layer and, of every layer, the first and last weight of the mask it

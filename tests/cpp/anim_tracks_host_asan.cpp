@@ -1,4 +1,4 @@
-// AddressSanitizer / UBSan run of the HOST side of animation tracks (csrc/host_batch.cpp: mtr_anim_create_tracks and the
+// AddressSanitizer / UBSan run of the HOST side of animation tracks (csrc/host_anim.cpp, csrc/host_batch.cpp: mtr_anim_create_tracks and the
 // section-14 entry points on a track set) over the stand-in HIP runtime (tests/cpp/hip_stub: device memory = host heap).
 // The four k_anim launchers here are readers: for every instance they touch its state and, of every clip the state names
 // (clamped), the first and last key of the uniform set, or the first and last descriptor of the track set and the first

@@ -4,7 +4,9 @@
 #include "../../mt_renderer_amd/csrc/host_device.cpp"
 #include "../../mt_renderer_amd/csrc/host_texture.cpp"
 #include "../../mt_renderer_amd/csrc/host_model.cpp"
+#include "../../mt_renderer_amd/csrc/host_anim.cpp"
 #include "../../mt_renderer_amd/csrc/host_batch.cpp"
+#include "../../mt_renderer_amd/csrc/host_player.cpp"
 #include "../../mt_renderer_amd/csrc/host_frame.cpp"
 #include "../../mt_renderer_amd/csrc/host_submit.cpp"
 #include "../../mt_renderer_amd/csrc/host_shard.cpp"

@@ -9,7 +9,6 @@
 // the player's, zero between calls, and freed once (a second free is an ASan report when the devices are destroyed).
 //   usage: player_host_asan <iterations>
 #include "host_all.h"
-#include "../../mt_renderer_amd/csrc/host_player.cpp"
 #include "../../mt_renderer_amd/csrc/play_math.h"
 using namespace mtr_host;
 

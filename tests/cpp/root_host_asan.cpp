@@ -1,4 +1,4 @@
-// AddressSanitizer / UBSan run of the HOST side of root motion (csrc/host_batch.cpp: mtr_anim_root_create / _destroy,
+// AddressSanitizer / UBSan run of the HOST side of root motion (csrc/host_anim.cpp, csrc/host_batch.cpp: mtr_anim_root_create / _destroy,
 // mtr_batch_root_motion(_device), mtr_anim_root_deltas(_device)) over the stand-in HIP runtime (tests/cpp/hip_stub: device
 // memory = host heap), a stand-alone program.  The two k_root launchers here are readers: they touch the first and last
 // step, the first and last word of the clip table, of the root flags and of the keys (or descriptors, values and times),

@@ -1,0 +1,33 @@
+"""CPU: the stream traffic of every animation entry point (SPEC.md sections 13 to 20): tests/cpp/anim_call_trace.cpp, a
+stand-alone program over the stand-in HIP runtime (tests/cpp/hip_stub) built by g++ with AddressSanitizer and UBSan, makes
+each call once and prints every wait, record, copy, sync and launch with its streams, events and buffers named by first
+appearance.  The text must equal tests/golden/anim_call_trace.txt, which was recorded before the animation host code was
+moved into csrc/host_anim.cpp and is not regenerated: a reordered wait, a lost record or a changed offset in a set's device
+image is a difference here, not a wrong pose on the GPU."""
+import difflib
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_anim_call_trace_matches_the_recorded_one(tmp_path):
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "anim_call_trace")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "anim_call_trace.cpp"), "-o", exe, "-lz"])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-6000:]
+    m = re.search(r"anim_call_trace: ops=(\d+) rejected=(\d+) failed=(\d+)", r.stdout)
+    assert m and int(m.group(1)) > 400 and int(m.group(2)) >= 34 and int(m.group(3)) == 0, r.stdout[-2000:]
+    with open(os.path.join(ROOT, "tests", "golden", "anim_call_trace.txt")) as f:
+        want = f.read()
+    if r.stdout != want:
+        diff = "\n".join(list(difflib.unified_diff(want.splitlines(), r.stdout.splitlines(), "golden", "now", lineterm="", n=6))[:200])
+        pytest.fail("the trace differs from tests/golden/anim_call_trace.txt:\n" + diff)

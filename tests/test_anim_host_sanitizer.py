@@ -1,4 +1,4 @@
-"""CPU: the HOST side of the animation entry points (mtr_anim_*, mtr_*_animate*: csrc/host_batch.cpp) compiled by g++ with
+"""CPU: the HOST side of the animation entry points (mtr_anim_*, mtr_*_animate*: csrc/host_anim.cpp, csrc/host_batch.cpp) compiled by g++ with
 AddressSanitizer and UBSan over the stand-in HIP runtime (tests/cpp/hip_stub), with launchers that read the first and last
 key of every clip a state names and write the last output word: clip tables, key offsets, staged state counts, every
 invalid call of include/mtr.h's list, and an animation set destroyed while frames that were animated from it are in flight."""

@@ -1,4 +1,4 @@
-"""CPU: the HOST side of inverse kinematics (mtr_anim_ik_create / _destroy and the four IK entry points: csrc/host_batch.cpp)
+"""CPU: the HOST side of inverse kinematics (mtr_anim_ik_create / _destroy and the four IK entry points: csrc/host_anim.cpp, csrc/host_batch.cpp)
 compiled by g++ with AddressSanitizer and UBSan over the stand-in HIP runtime (tests/cpp/hip_stub), as a stand-alone
 program whose launchers read the first and last layer and target of every instance, every chain of the set and the path of
 every chain's first joint: every invalid call and every creation rule of SPEC.md section 17 (the error names the chain, or

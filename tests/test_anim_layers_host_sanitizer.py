@@ -1,5 +1,5 @@
 """CPU: the HOST side of animation layers (mtr_anim_masks_create / _destroy and the four layered entry points:
-csrc/host_batch.cpp) compiled by g++ with AddressSanitizer and UBSan over the stand-in HIP runtime (tests/cpp/hip_stub),
+csrc/host_anim.cpp, csrc/host_batch.cpp) compiled by g++ with AddressSanitizer and UBSan over the stand-in HIP runtime (tests/cpp/hip_stub),
 as a stand-alone program whose launchers read the first and last layer of every instance and the first and last mask
 weight and clip entry each layer names: every invalid call, both kinds of set with and without masks, and one batch
 animated by all kinds of call with frames in flight while mask sets come and go."""

@@ -1,5 +1,5 @@
 """CPU: the HOST side of animation tracks (mtr_anim_create_tracks and the section-14 entry points on a track set:
-csrc/host_batch.cpp) compiled by g++ with AddressSanitizer and UBSan over the stand-in HIP runtime (tests/cpp/hip_stub),
+csrc/host_anim.cpp, csrc/host_batch.cpp) compiled by g++ with AddressSanitizer and UBSan over the stand-in HIP runtime (tests/cpp/hip_stub),
 as a stand-alone program whose four launchers read the first and last descriptor, time and value of every clip a state
 names: every invalid creation, sets of both kinds created and destroyed around animate calls and frames in flight, and one
 batch animated alternately from a uniform and a track set."""

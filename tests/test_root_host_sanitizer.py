@@ -1,5 +1,5 @@
 """CPU: the HOST side of root motion (mtr_anim_root_create / _destroy, mtr_batch_root_motion(_device) and
-mtr_anim_root_deltas(_device): csrc/host_batch.cpp) compiled by g++ with AddressSanitizer and UBSan over the stand-in HIP
+mtr_anim_root_deltas(_device): csrc/host_anim.cpp, csrc/host_batch.cpp) compiled by g++ with AddressSanitizer and UBSan over the stand-in HIP
 runtime (tests/cpp/hip_stub), as a stand-alone program with its own main whose launchers read the first and last word of
 everything k_root is handed: every rejected call of SPEC.md section 19 (the error names the clip with unknown flag bits, and the
 LOOP clip of a trajectory set) leaves the batch's version ring as it was, both kinds of set with host and device steps, root
