@@ -56,7 +56,7 @@ enum { TF_LARGE = 1, TF_TEX = 2, TF_BLEND = 4, TF_ADD = 8, TF_NODW = 128, TF_NOD
 template <bool TEX>
 __device__ __forceinline__ void setup_entry(const TileParams& P, uint32_t r, int32_t binx0, int32_t biny0, TriC& t, TriX* x,
                                             int4& chi, uint32_t& submask) {
-    const RecA a = load_rec(P.fb, r);
+    const RecA a = load_rec(P.fb.rec_a, P.fb.rec_l, r);
     // a solid record carries its colour and replaces the pixel; anything else names its material
     const bool solid = (a.pad1 & 1u) != 0;
     DMat mat = {};
@@ -143,14 +143,13 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
     __shared__ uint32_t s_pm[TRI_PASS];         // pair prefix | magic(bbox width) << 12
     __shared__ uint8_t s_tmap[TRI_PASS];        // compacted index -> triangle of the pass
 
-    const uint32_t ovf = tile_prologue(P);
     const uint32_t lane = threadIdx.x;
-    uint32_t bin;
-    if (!block_to_bin(P, bin)) return;
+    TileEntry te;  // the shared entry (tile_common.h): the head of the parameters in one fetch, the bin, its queue bounds
+    if (!tile_enter<64, false>(P, 0u, lane, te)) return;
+    const TileHead& hd = te.h;
+    const uint32_t ovf = te.ovf, bin = te.bin;
     if (P.mixed && !P.bin_flag[bin]) return;  // mixed frame: k_tile_vis has rendered this bin (only opaque triangles in it)
-    uint32_t bin_x, bin_y;
-    bin_xy(P, bin, bin_x, bin_y);
-    const int32_t binx0 = (int32_t)bin_x * MTR_BIN, biny0 = (int32_t)bin_y * MTR_BIN;
+    const int32_t binx0 = (int32_t)te.bin_x * MTR_BIN, biny0 = (int32_t)te.bin_y * MTR_BIN;
 
     float dep[4];
     uint32_t col[4];
@@ -158,12 +157,12 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
     for (int i = 0; i < 4; i++) { dep[i] = P.clear_depth; col[i] = P.clear_rgba8; }
     for (uint32_t i = lane; i < MTR_BIN * MTR_BIN; i += 64) s_cnt[i] = 0u;
 
-    uint32_t seg_lo, S, ent_lo, n_ent;
-    bin_queue(P.fb, bin, ent_lo, n_ent, seg_lo, S);
-    if (ovf) { n_ent = 0; S = 0; }  // incomplete queues: read nothing, the bin stays cleared (tile_prologue)
-    if (P.fb.direct && lane == 0 && n_ent) {  // queue statistics (direct mode has no scan to count them)
-        atomicAdd(&P.fb.counters[MTR_CTR(CTR_ENT, bin)], n_ent);
-        atomicAdd(&P.fb.counters[MTR_CTR(CTR_SEG, bin)], S);
+    const uint32_t seg_lo = te.seg_lo, ent_lo = te.ent_lo;
+    uint32_t S = te.n_seg, n_ent = te.n_ent;
+    if (ovf) { n_ent = 0; S = 0; }  // incomplete queues: read nothing, the bin stays cleared (tile_enter)
+    if (hd.direct && lane == 0 && n_ent) {  // queue statistics (direct mode has no scan to count them)
+        atomicAdd(&hd.counters[MTR_CTR(CTR_ENT, bin)], n_ent);
+        atomicAdd(&hd.counters[MTR_CTR(CTR_SEG, bin)], S);
     }
     const Seg* segs = P.fb.segs + seg_lo;
 
@@ -248,7 +247,7 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
                         const uint32_t mid = (a + b) >> 1;
                         if (s_pre[mid] <= e) a = mid; else b = mid;
                     }
-                    const uint32_t ord = P.fb.entries[ent_lo + s_off[a] + (e - s_pre[a])];
+                    const uint32_t ord = hd.entries[ent_lo + s_off[a] + (e - s_pre[a])];
                     const uint32_t r = (ord >> 7) * MTR_CHUNK_SLOTS + (ord & 127u);
                     setup_entry<TEX>(P, r, binx0, biny0, s_tc[lane], TEX ? &s_tx[lane] : nullptr, s_chi[lane], s_mask[lane]);
                 }
@@ -308,7 +307,7 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
                             for (int i = 0; i < 4; i++) {
                                 const int32_t lx = (int32_t)((i & 1) * 8 + (lane & 7)), ly = (int32_t)((i >> 1) * 8 + (lane >> 3));
                                 const uint32_t pix = (uint32_t)(ly * MTR_BIN + lx);
-                                const bool in_vp = (uint32_t)(binx0 + lx) < P.fb.W && (uint32_t)(biny0 + ly) < P.fb.H;
+                                const bool in_vp = (uint32_t)(binx0 + lx) < hd.W && (uint32_t)(biny0 + ly) < hd.H;
                                 uint32_t fw[FRAG_K / 4];
 #pragma unroll
                                 for (uint32_t j = 0; j < FRAG_K / 4; j++) fw[j] = reinterpret_cast<const uint32_t*>(&s_frag[pix * FRAG_K])[j];
@@ -347,7 +346,7 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
                     const int32_t lx = (int32_t)((i & 1) * 8 + (lane & 7)), ly = (int32_t)((i >> 1) * 8 + (lane >> 3));
-                    const bool in_vp = (uint32_t)(binx0 + lx) < P.fb.W && (uint32_t)(biny0 + ly) < P.fb.H;
+                    const bool in_vp = (uint32_t)(binx0 + lx) < hd.W && (uint32_t)(biny0 + ly) < hd.H;
                     uint64_t m = __ballot(lane < cntp && ((s_mask[lane] >> i) & 1u));
                     while (m) {
                         const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)__ffsll((long long)m) - 1);
@@ -394,8 +393,8 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const uint32_t x = (uint32_t)binx0 + (i & 1) * 8 + (lane & 7), y = (uint32_t)biny0 + (i >> 1) * 8 + (lane >> 3);
-        if (x < P.fb.W && y < P.fb.H) {
-            const size_t pi = (size_t)y * P.fb.W + x;
+        if (x < hd.W && y < hd.H) {
+            const size_t pi = (size_t)y * hd.W + x;
             reinterpret_cast<uint32_t*>(P.color)[pi] = col[i];
             P.depth[pi] = dep[i];
         }
@@ -406,11 +405,9 @@ __global__ __launch_bounds__(64) void k_tile(TileParams P) {
 
 void mtr_launch_tile(const TileParams& p_in, bool textured, hipStream_t s) {
     TileParams p = p_in;
-    tile_set_divisors(p);
-    const uint32_t mine = p.fb.own.own_count;
+    tile_fill_head(p);
+    const uint32_t mine = p.fb.own.own_count, grid = p.head.grid;
     if (mine == 0) return;
-    uint32_t grid = (mine + 7) / 8 * 8;
-    if (p.xcd_run) grid = (grid / 8 + p.xcd_run - 1) / p.xcd_run * p.xcd_run * 8;  // whole runs
     if (textured) hipLaunchKernelGGL(mtr::k_tile<true>, dim3(grid), dim3(64), 0, s, p);
     else hipLaunchKernelGGL(mtr::k_tile<false>, dim3(grid), dim3(64), 0, s, p);
 }

@@ -153,28 +153,21 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
     static_assert(!QW, "the quad walk is retired");
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t ovf = tile_prologue(P);
-    uint32_t bin;
-    if (!block_to_bin(P, bin)) return;  // uniform over the workgroup, before any barrier
-    uint32_t bin_x, bin_y;
-    bin_xy(P, bin, bin_x, bin_y);
-    const int32_t binx0 = (int32_t)bin_x * MTR_BIN, biny0 = (int32_t)bin_y * MTR_BIN;
+    // the shared entry (tile_common.h): the head of the parameters in one fetch, this workgroup's bin, and -- direct mode --
+    // this wave's first two entry loads issued together with the fill-count load instead of after it
+    const uint32_t stride = 64 * VIS_WAVES, first = wv * 64;
+    TileEntry te;
+    if (!tile_enter<64 * VIS_WAVES, true>(P, first, lane, te)) return;  // uniform over the workgroup, before any barrier
+    const TileHead& hd = te.h;
+    const uint32_t ovf = te.ovf, bin = te.bin, ent_lo = te.ent_lo, n_seg = te.n_seg;
+    const uint32_t spec0 = te.spec0, spec1 = te.spec1;
+    uint32_t N = te.n_ent;
+    const int32_t binx0 = (int32_t)te.bin_x * MTR_BIN, biny0 = (int32_t)te.bin_y * MTR_BIN;
     const float cd = P.clear_depth;
     // fragments pass 0 <= z <= 1 and z <= clear depth (nothing else is in the depth buffer before the resolve)
     const bool zlim_ok = cd >= 0.0f;
     const uint32_t zlim = __float_as_uint(fminf(cd, 1.0f));
-    const int32_t vw = (int32_t)P.fb.W - binx0, vh = (int32_t)P.fb.H - biny0;  // viewport edge in bin coordinates
-    // direct mode: bin b's queue starts at b * qcap whatever its fill, so this wave's first two entry loads are
-    // issued together with the fill-count load instead of after it (one dependent round trip less per bin)
-    const uint32_t stride = 64 * VIS_WAVES, first = wv * 64;
-    uint32_t spec0 = 0, spec1 = 0;
-    if (P.fb.direct) {
-        const uint32_t qb = bin * P.fb.qcap;
-        if (first + lane < P.fb.qcap) spec0 = P.fb.entries[qb + first + lane];
-        if (first + stride + lane < P.fb.qcap) spec1 = P.fb.entries[qb + first + stride + lane];
-    }
-    uint32_t ent_lo, N, seg_lo_unused, n_seg;
-    bin_queue(P.fb, bin, ent_lo, N, seg_lo_unused, n_seg);  // the same word for every thread of the workgroup
+    const int32_t vw = (int32_t)hd.W - binx0, vh = (int32_t)hd.H - biny0;  // viewport edge in bin coordinates
     if (ovf) {  // incomplete queues: read nothing, leave the bin cleared and its fill word parked for the next frame
         N = 0;
         __syncthreads();  // every thread has read the fill word
@@ -185,43 +178,43 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
         for (uint32_t pidx = threadIdx.x; pidx < MTR_BIN * MTR_BIN; pidx += 64 * VIS_WAVES) {
             const int32_t lx = (int32_t)(pidx & (MTR_BIN - 1)), ly = (int32_t)(pidx >> MTR_BIN_SHIFT);
             if (lx >= vw || ly >= vh) continue;
-            const size_t pi = (size_t)(biny0 + ly) * P.fb.W + (size_t)(binx0 + lx);
+            const size_t pi = (size_t)(biny0 + ly) * hd.W + (size_t)(binx0 + lx);
             reinterpret_cast<uint32_t*>(P.color)[pi] = P.clear_rgba8;
             P.depth[pi] = cd;
         }
         if (P.mixed && threadIdx.x == 0) P.bin_flag[bin] = 0;
         // the parked count of an empty bin is 0 too (mtr_frame_read_bin_counts: what bench.py balances bands by); without
         // this store the word keeps whatever the allocation, or an earlier scene, left there
-        if (P.fb.direct && threadIdx.x == 0 && !ovf) P.fb.bin_count[bin] = 0ull;
+        if (hd.direct && threadIdx.x == 0 && !ovf) P.fb.bin_count[bin] = 0ull;
         return;
     }
+    const RecA zero_rec = {0, 0, 0, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0u, 0u, 0u};
+    // two-deep software pipeline over the dependent loads entries[] -> rec_a[]: while pass k is rasterised the
+    // record loads of this wave's next pass and the entry loads of the one after are in flight.  The record of an
+    // entry is addressable from its submission order: chunk run base = chunk * MTR_CHUNK_SLOTS.
+    uint32_t ord_cur = 0, ord_nxt = 0;
+    if (hd.direct) {
+        if (first + lane < N) ord_cur = spec0;
+        if (first + stride + lane < N) ord_nxt = spec1;
+    } else {
+        if (first + lane < N) ord_cur = hd.entries[ent_lo + first + lane];
+        if (first + stride + lane < N) ord_nxt = hd.entries[ent_lo + first + stride + lane];
+    }
+    RecA a_cur = zero_rec;
+    if (first + lane < N) a_cur = load_rec(hd.rec_a, P.fb.rec_l, (ord_cur >> 7) * MTR_CHUNK_SLOTS + (ord_cur & 127u));
+    // ... and the first record load is in flight while the workgroup clears its keys and meets
     for (uint32_t i = threadIdx.x; i < MTR_BIN * MTR_BIN; i += 64 * VIS_WAVES) {
         s_key[i] = 0ull;
         if (STAIR) s_cnt[i] = 0u;
     }
     if (threadIdx.x == 0) { s_trans = 0u; s_hard = 0u; }
     __syncthreads();
-
-    const RecA zero_rec = {0, 0, 0, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0u, 0u, 0u};
-    // two-deep software pipeline over the dependent loads entries[] -> rec_a[]: while pass k is rasterised the
-    // record loads of this wave's next pass and the entry loads of the one after are in flight.  The record of an
-    // entry is addressable from its submission order: chunk run base = chunk * MTR_CHUNK_SLOTS.
-    uint32_t ord_cur = 0, ord_nxt = 0;
-    if (P.fb.direct) {
-        if (first + lane < N) ord_cur = spec0;
-        if (first + stride + lane < N) ord_nxt = spec1;
-    } else {
-        if (first + lane < N) ord_cur = P.fb.entries[ent_lo + first + lane];
-        if (first + stride + lane < N) ord_nxt = P.fb.entries[ent_lo + first + stride + lane];
-    }
-    RecA a_cur = zero_rec;
-    if (first + lane < N) a_cur = load_rec(P.fb, (ord_cur >> 7) * MTR_CHUNK_SLOTS + (ord_cur & 127u));
     for (uint32_t e0 = first; e0 < N; e0 += stride) {
         const bool valid = e0 + lane < N;
         RecA a_nxt = zero_rec;
-        if (e0 + stride + lane < N) a_nxt = load_rec(P.fb, (ord_nxt >> 7) * MTR_CHUNK_SLOTS + (ord_nxt & 127u));
+        if (e0 + stride + lane < N) a_nxt = load_rec(hd.rec_a, P.fb.rec_l, (ord_nxt >> 7) * MTR_CHUNK_SLOTS + (ord_nxt & 127u));
         uint32_t ord_nn = 0;
-        if (e0 + 2 * stride + lane < N) ord_nn = P.fb.entries[ent_lo + e0 + 2 * stride + lane];
+        if (e0 + 2 * stride + lane < N) ord_nn = hd.entries[ent_lo + e0 + 2 * stride + lane];
 
         if (P.mixed && valid && (a_cur.pad1 >> 16)) {  // benign races: every writer stores 1
             s_trans = 1u;
@@ -341,9 +334,10 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
         ord_cur = ord_nxt;
         ord_nxt = ord_nn;
     }
+    const TileLate Q = tile_late();  // what the resolve reads: fetched here, under the barrier, not carried across the raster loop
     __syncthreads();
     bool stair = false;  // this bin resolves through its per-pixel order lists
-    if (P.mixed) {  // an order-dependent triangle in the queue
+    if (Q.mixed) {  // an order-dependent triangle in the queue
         bool leave = s_hard != 0u;  // leave the bin (and its queue) to the ordered kernel
         if (STAIR && !leave && s_trans) {
             bool over = false;
@@ -351,15 +345,15 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
             leave = __syncthreads_or(over ? 1 : 0) != 0;  // a pixel listed more orders than it has room for
             stair = !leave;
         }
-        if (threadIdx.x == 0) P.bin_flag[bin] = leave ? 1 : 0;
+        if (threadIdx.x == 0) Q.bin_flag[bin] = leave ? 1 : 0;
         if (leave) return;
     }
     if (threadIdx.x == 0) {
-        if (P.fb.direct && N) {  // queue statistics (direct mode has no scan to count them)
-            atomicAdd(&P.fb.counters[MTR_CTR(CTR_ENT, bin)], N);
-            atomicAdd(&P.fb.counters[MTR_CTR(CTR_SEG, bin)], n_seg);
+        if (Q.direct && N) {  // queue statistics (direct mode has no scan to count them)
+            atomicAdd(&Q.counters[MTR_CTR(CTR_ENT, bin)], N);
+            atomicAdd(&Q.counters[MTR_CTR(CTR_SEG, bin)], n_seg);
         }
-        bin_queue_done(P.fb, bin);  // every wave has read its queue bounds by now
+        bin_queue_done(Q, bin);  // every wave has read its queue bounds by now
     }
 
     // ---- resolve: deferred shading of each pixel's winner, the only framebuffer traffic of the frame;
@@ -371,7 +365,7 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
         if (lx >= vw || ly >= vh) continue;
         const uint32_t x = (uint32_t)(binx0 + lx), y = (uint32_t)(biny0 + ly);
         const unsigned long long key = s_key[ly * MTR_BIN + lx];
-        uint32_t col = P.clear_rgba8;
+        uint32_t col = Q.clear_rgba8;
         float dep = cd;
         if (STAIR && stair) {
             // the pixel's listed fragments in submission order; those that pass the depth test (z <= every earlier one's:
@@ -390,16 +384,16 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
                 last = best;
                 const uint32_t ord = best - 1u;
                 const uint32_t r = (ord >> 7) * MTR_CHUNK_SLOTS + (ord & 127u);
-                const RecA a = load_rec(P.fb, r);
+                const RecA a = load_rec(Q.rec_a, Q.rec_l, r);
                 const float z = z_at(a, (int32_t)x, (int32_t)y);
                 if (!(z <= dep)) continue;  // fails LessEqual against the nearest of its predecessors
                 dep = z;
                 if (a.pad1 & 1u) {  // solid: its colour replaces the pixel
                     col = a.pad0;
                 } else {
-                    const DMat mat = P.mats[a.mat];
+                    const DMat mat = Q.mats[a.mat];
                     if (TEX && mat.shader == MTR_SH_TEXTURED) {
-                        const RecB b = P.fb.rec_b[r];
+                        const RecB b = Q.rec_b[r];
                         float src[4];
                         sample_textured(a, b, mat, (int32_t)x, (int32_t)y, src);
                         col = blend_store(col, src, mat.blend == MTR_DB_ALPHA ? 1u : 0u);
@@ -413,12 +407,12 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
             const uint32_t ord = (uint32_t)key - 1u;
             const uint32_t r = (ord >> 7) * MTR_CHUNK_SLOTS + (ord & 127u);
             // the last word of the record: the source colour of a solid triangle (top byte 0xFF) or a material id
-            const uint32_t payload = P.fb.rec_a[r].q1.w;
+            const uint32_t payload = Q.rec_a[r].q1.w;
             if ((payload >> 24) != 0xFFu) {  // needs its material: in this kernel (order-free triangles only) a textured one
-                const DMat mat = P.mats[payload & 0xFFFFFFu];
+                const DMat mat = Q.mats[payload & 0xFFFFFFu];
                 if (TEX && mat.shader == MTR_SH_TEXTURED) {
-                    const RecA a = load_rec(P.fb, r);
-                    const RecB b = P.fb.rec_b[r];
+                    const RecA a = load_rec(Q.rec_a, Q.rec_l, r);
+                    const RecB b = Q.rec_b[r];
                     float src[4];
                     sample_textured(a, b, mat, (int32_t)x, (int32_t)y, src);
                     col = blend_store(0u, src, 0u);  // order-free: blending is off, or the texture is opaque (a == 1 exactly) and the blend a replace
@@ -429,9 +423,9 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
                 col = payload;
             }
         }
-        const size_t pi = (size_t)y * P.fb.W + x;
-        reinterpret_cast<uint32_t*>(P.color)[pi] = col;
-        P.depth[pi] = dep;
+        const size_t pi = (size_t)y * Q.W + x;
+        reinterpret_cast<uint32_t*>(Q.color)[pi] = col;
+        Q.depth[pi] = dep;
     }
 }
 
@@ -439,11 +433,9 @@ __global__ __launch_bounds__(64 * VIS_WAVES, VIS_OCC) void k_tile_vis(TileParams
 
 void mtr_launch_tile_vis(const TileParams& p_in, bool textured, hipStream_t s) {
     TileParams p = p_in;
-    tile_set_divisors(p);
-    const uint32_t mine = p.fb.own.own_count;
+    tile_fill_head(p);
+    const uint32_t mine = p.fb.own.own_count, grid = p.head.grid;
     if (mine == 0) return;
-    uint32_t grid = (mine + 7) / 8 * 8;
-    if (p.xcd_run) grid = (grid / 8 + p.xcd_run - 1) / p.xcd_run * p.xcd_run * 8;  // whole runs
     const int waves = (int)mtr_vis_waves_for(p.vis_waves, mine);
 #define MTR_LAUNCH_VIS(T, W, S) hipLaunchKernelGGL((mtr::k_tile_vis<T, W, S, false>), dim3(grid), dim3(64 * W), 0, s, p)
 #define MTR_LAUNCH_VIS_W(T, S) do { if (waves >= 8) MTR_LAUNCH_VIS(T, 8, S); else if (waves >= 4) MTR_LAUNCH_VIS(T, 4, S); else MTR_LAUNCH_VIS(T, 2, S); } while (0)

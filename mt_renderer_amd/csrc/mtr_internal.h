@@ -355,7 +355,34 @@ struct GeomParams {
     FrameBuffers fb;
 };
 
+// What a tile workgroup reads between its start and its first queue loads, as one contiguous block at the front of the
+// kernel's arguments: the kernels fetch it in wide scalar loads with one wait (tile_common.h: tile_head) instead of one
+// argument per round trip.  Every field mirrors one elsewhere in TileParams or is computed from them; tile_fill_head
+// (tile_common.h) writes them all in both launchers, whatever the caller left here.
+struct alignas(64) TileHead {
+    uint32_t grid;                      // workgroups of the launch (whole runs of xcd_run bins per XCD)
+    uint32_t own_count;                 // fb.own.own_count
+    uint32_t nbx, nbins;                // fb.nbx, fb.nbx * fb.nby
+    uint32_t W, H;                      // fb.W, fb.H
+    uint32_t direct, qcap, scap;        // fb.direct, fb.qcap, fb.scap
+    uint32_t xcd_run;
+    uint32_t nbx_mul, nbx_shift, run_mul, run_shift;  // n / nbx and n / xcd_run as multiply-highs (udiv_apply)
+    uint32_t zero_nwords, nhint;
+    const uint32_t* own_list;           // fb.own.own_list
+    uint32_t* entries;                  // fb.entries
+    unsigned long long* bin_fill;       // fb.bin_fill
+    uint32_t* bin_start;                // fb.bin_start, fb.seg_start: the two-pass queues
+    uint32_t* seg_start;
+    uint32_t* counters;                 // fb.counters
+    RecP* rec_a;                        // fb.rec_a
+    uint32_t* zero_next;
+    uint32_t* zero_words;
+    uint32_t* host_status;
+};
+static_assert(sizeof(TileHead) == 192 && alignof(TileHead) == 64, "TileHead is three 64-byte lines");
+
 struct TileParams {
+    TileHead head;
     FrameBuffers fb;
     const DMat* mats;
     uint8_t* color;  // RGBA8
@@ -386,10 +413,8 @@ struct TileParams {
     uint32_t* hint_out;
     uint32_t nhint;
     uint16_t hint_word[4], hint_slot[4];
-    // n / nbx and n / xcd_run as multiply-highs (tile_common.h: udiv_apply); filled in by the launchers, whatever the
-    // caller left here
-    uint32_t nbx_mul, nbx_shift, run_mul, run_shift;
 };
+#define MTR_TILE_PARAMS 1  // tile_common.h: TileParams is declared, so its plain-C++ part can define tile_fill_head
 
 // waves per bin of k_tile_vis for a rank that owns own_count bins: `forced` (TileParams::vis_waves) when set, else by how
 // many bins there are.  Up to 1536 bins (256 CUs) every bin is resident at once and the heaviest bin bounds the frame: 8

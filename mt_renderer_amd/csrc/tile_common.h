@@ -52,37 +52,87 @@ MTR_DIV_HD uint32_t row_magic(uint32_t iw) { return (65536u + iw - 1u) / iw; }
 
 namespace mtr {
 
-// every workgroup of a tile kernel clears its slice of the counter block the next frame on these framebuffers will use
-__device__ __forceinline__ void zero_next_counters(const TileParams& P) {
-    if (P.zero_words)
-        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < P.zero_nwords; i += gridDim.x * blockDim.x) {
-            for (uint32_t k = 0; k < P.nhint; k++)  // the thread that clears a word the host wants to see publishes it first
-                if (i - P.hint_word[k] < 2u)
-                    __hip_atomic_store(&P.hint_out[2u * P.hint_slot[k] + (i - P.hint_word[k])], 0x80000000u | P.zero_words[i], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_SYSTEM);
-            P.zero_words[i] = 0u;
-        }
-    if (!P.zero_next) return;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < (uint32_t)CTR_NUM; i += gridDim.x * blockDim.x) P.zero_next[i] = 0u;
+// The head of the parameters (mtr_internal.h: TileHead) in scalar registers.  Naming every field in one empty asm makes the
+// compiler fetch them together at the top of the kernel -- wide scalar loads, one wait -- where it would otherwise fetch each
+// argument alone in the block that first uses it and wait for it at once: some sixteen dependent round trips in front of a
+// wave's first queue load, and most of the life of the waves of an empty bin.  The kernels read these copies, not P.fb, up
+// to the end of their raster loops; what k_tile_vis reads after its loop it fetches there (tile_late).
+__device__ __forceinline__ TileHead tile_head(const TileParams& P) {
+    const TileHead h = P.head;
+    asm volatile("" ::"s"(h.grid), "s"(h.own_count), "s"(h.nbx), "s"(h.nbins), "s"(h.W), "s"(h.H), "s"(h.direct), "s"(h.qcap), "s"(h.scap),
+                 "s"(h.xcd_run), "s"(h.nbx_mul), "s"(h.nbx_shift), "s"(h.run_mul), "s"(h.run_shift), "s"(h.zero_nwords), "s"(h.nhint),
+                 "s"(h.own_list), "s"(h.entries), "s"(h.bin_fill), "s"(h.bin_start), "s"(h.seg_start), "s"(h.counters), "s"(h.rec_a),
+                 "s"(h.zero_next), "s"(h.zero_words), "s"(h.host_status));
+    return h;
 }
 
-// Start of every tile workgroup.  Returns the frame's overflow flags (final: the kernels that raise them precede this
-// one on the stream) and publishes them to the host's status word.  A frame with a flag set has incomplete queues --
-// slots that were reserved and never written -- so the tile kernels must not read them: they clear their bin, park the
-// fill word and leave; the host re-runs the frame (mtr_frame_wait, the exchange thread) or latches an error.
-__device__ __forceinline__ uint32_t tile_prologue(const TileParams& P) {
-    zero_next_counters(P);
-    const uint32_t ovf = P.fb.counters[CTR_OVERFLOW];
-    if (blockIdx.x == 0 && threadIdx.x == 0 && P.host_status)
-        __hip_atomic_store(P.host_status, 0x80000000u | ovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    return ovf;
+// every workgroup of a tile kernel clears its slice of the counter blocks the next frame on these framebuffers will use.
+// BLOCK: threads per workgroup (the kernel's template knows it; blockDim.x is a vector load from the implicit arguments).
+// A workgroup first tests, on the scalar unit, whether it owns a word at all: of the headline's 8 160 only the first 33 do.
+// The grid-stride loops stay: a launch with fewer threads than words (a rank that owns one bin) still clears them all.
+template <uint32_t BLOCK>
+__device__ __forceinline__ void zero_next_counters(const TileParams& P, const TileHead& h) {
+    const uint32_t b0 = blockIdx.x * BLOCK, step = h.grid * BLOCK;  // < 2^30: at most 2^20 + 2^19 workgroups of 512
+    if (h.zero_words && b0 < h.zero_nwords) {
+        const auto pack4 = [](const uint16_t (&a)[4]) { return (uint64_t)a[0] | (uint64_t)a[1] << 16 | (uint64_t)a[2] << 32 | (uint64_t)a[3] << 48; };
+        const uint64_t hint_words = pack4(P.hint_word), hint_slots = pack4(P.hint_slot);
+        for (uint32_t i = b0 + threadIdx.x; i < h.zero_nwords; i += step) {
+            for (uint32_t k = 0; k < h.nhint; k++) {  // the thread that clears a word the host wants to see publishes it first
+                // (the 16-bit arguments picked out of their words on the scalar unit: indexed by k they are vector loads)
+                const uint32_t hw = (uint32_t)(hint_words >> (16u * k)) & 0xffffu, hs = (uint32_t)(hint_slots >> (16u * k)) & 0xffffu;
+                if (i - hw < 2u)
+                    __hip_atomic_store(&P.hint_out[2u * hs + (i - hw)], 0x80000000u | h.zero_words[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+            h.zero_words[i] = 0u;
+        }
+    }
+    if (h.zero_next && b0 < (uint32_t)CTR_NUM)
+        for (uint32_t i = b0 + threadIdx.x; i < (uint32_t)CTR_NUM; i += step) h.zero_next[i] = 0u;
+}
+
+// What k_tile_vis reads after its raster loop, fetched once more where the loop ends.  An argument read through P is a load the
+// compiler may hoist to the top of the kernel (the segment is known to be readable), and what the resolve reads -- the material
+// table, the colour and depth planes, rec_b, ... -- then sits in scalar registers across the whole raster loop, next to the
+// head: the allocator ran out and spilled to vector lanes, which cost the kernel a wave per SIMD.  Through a pointer whose
+// origin the compiler does not see they are fetched where this is called -- together, with one wait, like the head: left to
+// the blocks that use them they were eight round trips one after another.  (The tile kernels take one argument: it starts the
+// kernel-argument segment.)
+struct TileLate {
+    const DMat* mats;
+    uint8_t* color;
+    float* depth;
+    uint8_t* bin_flag;
+    RecP* rec_a;
+    int4* rec_l;
+    RecB* rec_b;
+    unsigned long long* bin_count;
+    unsigned long long* bin_fill;
+    uint32_t* counters;
+    uint32_t W, clear_rgba8, mixed, direct;
+};
+__device__ __forceinline__ TileLate tile_late() {
+    typedef const TileParams __attribute__((address_space(4)))* TileArgs;
+    TileArgs q = (TileArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(q));
+    const TileLate t = {q->mats,         q->color,        q->depth,       q->bin_flag, q->fb.rec_a,    q->fb.rec_l, q->fb.rec_b,
+                        q->fb.bin_count, q->fb.bin_fill,  q->fb.counters, q->fb.W,     q->clear_rgba8, q->mixed,    q->fb.direct};
+    asm volatile("" ::"s"(t.mats), "s"(t.color), "s"(t.depth), "s"(t.bin_flag), "s"(t.rec_a), "s"(t.rec_l), "s"(t.rec_b), "s"(t.bin_count),
+                 "s"(t.bin_fill), "s"(t.counters), "s"(t.W), "s"(t.clear_rgba8), "s"(t.mixed), "s"(t.direct));
+    return t;
+}
+// bin_queue_done (mtr_internal.h) on them
+__device__ __forceinline__ void bin_queue_done(const TileLate& t, uint32_t bin) {
+    if (t.direct) {
+        t.bin_count[bin] = t.bin_fill[bin];
+        t.bin_fill[bin] = 0ull;
+    }
 }
 
 // one record, decoded (the rare long-edged triangle costs a second, dependent load)
-__device__ __forceinline__ RecA load_rec(const FrameBuffers& fb, uint32_t r) {
-    const RecP p = fb.rec_a[r];
+__device__ __forceinline__ RecA load_rec(const RecP* rec_a, const int4* rec_l, uint32_t r) {
+    const RecP p = rec_a[r];
     int4 l = make_int4(0, 0, 0, 0);
-    if ((p.q0.z & 0xFFFFu) == MTR_REC_LARGE_SENTINEL) l = fb.rec_l[r];
+    if ((p.q0.z & 0xFFFFu) == MTR_REC_LARGE_SENTINEL) l = rec_l[r];
     return rec_unpack(p, l);
 }
 
@@ -272,36 +322,114 @@ __device__ __forceinline__ QuadUV quad_uv(const UVPlanes& p, int32_t x, int32_t 
 // XCD-aware bin order: blocks b, b+8, ... share an XCD's L2: give each XCD a contiguous run of this rank's bins
 // (own_list is row-major for interleaved / band ownership and super-tile-major for super-tiles).
 // Returns false when this block has no bin.  The divisions by the run length and (bin_xy) by the bins per row are
-// multiply-highs by the launcher's multipliers (tile_set_divisors): every value here is uniform over the workgroup, and
+// multiply-highs by the launcher's multipliers (tile_fill_head): every value here is uniform over the workgroup, and
 // a scalar division is a float-reciprocal sequence of some 25 instructions that every wave of every bin would pay.
-__device__ __forceinline__ bool block_to_bin(const TileParams& P, uint32_t& bin) {
-    const FrameBuffers& fb = P.fb;
-    const uint32_t run = P.xcd_run;
-    const uint32_t per = (gridDim.x + 7) / 8;
+__device__ __forceinline__ bool block_to_bin(const TileHead& h, uint32_t& bin) {
+    const uint32_t run = h.xcd_run;
+    const uint32_t per = (h.grid + 7) / 8;
     const uint32_t x = blockIdx.x & 7, i = blockIdx.x >> 3;
     // run == 0: XCD x takes one contiguous eighth of the bins; run > 0: runs of `run` consecutive bins are dealt to the
     // XCDs in turn (the launch covers whole runs), so every XCD sees every region of the frame
     uint32_t slot = x * per + i;
     if (run) {
-        const uint32_t q = udiv_apply(i, P.run_mul, P.run_shift);  // i / run
+        const uint32_t q = udiv_apply(i, h.run_mul, h.run_shift);  // i / run
         slot = (q * 8 + x) * run + (i - q * run);
     }
-    if (slot >= fb.own.own_count) return false;
-    bin = fb.own.own_list ? fb.own.own_list[slot] : slot;
-    return bin < fb.nbx * fb.nby;
+    bin = 0;
+    if (slot >= h.own_count) return false;
+    bin = h.own_list ? h.own_list[slot] : slot;
+    return bin < h.nbins;
 }
 // bin -> its column and row in the grid of bins
-__device__ __forceinline__ void bin_xy(const TileParams& P, uint32_t bin, uint32_t& bx, uint32_t& by) {
-    by = udiv_apply(bin, P.nbx_mul, P.nbx_shift);  // bin / nbx
-    bx = bin - by * P.fb.nbx;
+__device__ __forceinline__ void bin_xy(const TileHead& h, uint32_t bin, uint32_t& bx, uint32_t& by) {
+    by = udiv_apply(bin, h.nbx_mul, h.nbx_shift);  // bin / nbx
+    bx = bin - by * h.nbx;
+}
+
+// Start of every tile workgroup, shared by both kernels.  Fetches the head, finds the workgroup's bin and issues everything
+// the bin's first pass waits for back to back -- the frame's overflow flags, the bin's fill word (or its two-pass bounds)
+// and, SPEC, this wave's first two entry loads (direct mode: bin b's queue starts at b * qcap whatever its fill, so they
+// need not wait for the fill word) -- then does the workgroup's bookkeeping, the counter clearing and the host's status
+// word, while those loads are in flight.
+//   ovf      the frame's overflow flags (final: the kernels that raise them precede this one on the stream), also published
+//            to the host's status word.  A frame with a flag set has incomplete queues -- slots that were reserved and never
+//            written -- so the tile kernels must not read them: they clear their bin, park the fill word and leave; the
+//            host re-runs the frame (mtr_frame_wait, the exchange thread) or latches an error.
+//   spec0/1  entries [first + lane] and [first + BLOCK + lane] of the bin's queue where they are below qcap (direct mode),
+//            valid where they are below n_ent
+// Returns false when the workgroup has no bin (uniform over the workgroup; no barrier has been met).
+struct TileEntry {
+    TileHead h;
+    uint32_t ovf, bin, bin_x, bin_y;
+    uint32_t ent_lo, n_ent, seg_lo, n_seg;
+    uint32_t spec0, spec1;
+};
+template <uint32_t BLOCK, bool SPEC>
+__device__ __forceinline__ bool tile_enter(const TileParams& P, uint32_t first, uint32_t lane, TileEntry& e) {
+    e.h = tile_head(P);
+    const TileHead& h = e.h;
+    const bool has_bin = block_to_bin(h, e.bin);
+    const uint32_t bin = e.bin;
+    const uint32_t ovf_v = h.counters[CTR_OVERFLOW];
+    unsigned long long fill = 0ull;
+    uint32_t e0 = 0, e1 = 0, s0 = 0, s1 = 0;
+    e.spec0 = e.spec1 = 0u;
+    if (has_bin) {
+        if (h.direct) {
+            // every lane of the bin's workgroup reads the same word; the caller cleans it afterwards (bin_queue_done)
+            fill = h.bin_fill[bin];
+            if (SPEC) {
+                const uint32_t qb = bin * h.qcap;
+                if (first + lane < h.qcap) e.spec0 = h.entries[qb + first + lane];
+                if (first + BLOCK + lane < h.qcap) e.spec1 = h.entries[qb + first + BLOCK + lane];
+            }
+        } else {
+            e0 = h.bin_start[bin]; e1 = h.bin_start[bin + 1];
+            s0 = h.seg_start[bin]; s1 = h.seg_start[bin + 1];
+        }
+    }
+    zero_next_counters<BLOCK>(P, h);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && h.host_status)
+        __hip_atomic_store(h.host_status, 0x80000000u | ovf_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (!has_bin) return false;
+    bin_xy(h, bin, e.bin_x, e.bin_y);
+    // every lane has loaded the same words: the bounds go on in scalar registers
+    const auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+    e.ovf = uni(ovf_v);
+    if (h.direct) {
+        e.ent_lo = bin * h.qcap; e.seg_lo = bin * h.scap;
+        e.n_ent = min(uni((uint32_t)fill), h.qcap); e.n_seg = min(uni((uint32_t)(fill >> 32)), h.scap);
+    } else {
+        e.ent_lo = uni(e0); e.n_ent = uni(e1) - e.ent_lo;
+        e.seg_lo = uni(s0); e.n_seg = uni(s1) - e.seg_lo;
+    }
+    return true;
 }
 
 }  // namespace mtr
 
-// what both launchers do to their copy of the parameters: the multipliers of the two launch-invariant divisors
-inline void tile_set_divisors(TileParams& p) {
-    const mtr::UDiv n = mtr::udiv_make(p.fb.nbx), r = mtr::udiv_make(p.xcd_run);
-    p.nbx_mul = n.mul; p.nbx_shift = n.shift;
-    p.run_mul = r.mul; p.run_shift = r.shift;
-}
 #endif  // __HIPCC__
+
+#if defined(MTR_TILE_PARAMS)  // mtr_internal.h has been included: always above, and by the host test in front of this header
+// What both launchers do to their copy of the parameters: the workgroups of the launch, the multipliers of the two
+// launch-invariant divisors, and a copy of everything else the kernels' entry path reads.  Plain C++
+// (tests/cpp/tile_head_fill.cpp holds every field to its source).
+inline void tile_fill_head(TileParams& p) {
+    TileHead& h = p.head;
+    const uint32_t mine = p.fb.own.own_count;
+    h.grid = (mine + 7) / 8 * 8;
+    if (p.xcd_run) h.grid = (h.grid / 8 + p.xcd_run - 1) / p.xcd_run * p.xcd_run * 8;  // whole runs
+    h.own_count = mine; h.own_list = p.fb.own.own_list;
+    h.nbx = p.fb.nbx; h.nbins = p.fb.nbx * p.fb.nby;
+    h.W = p.fb.W; h.H = p.fb.H;
+    h.direct = p.fb.direct; h.qcap = p.fb.qcap; h.scap = p.fb.scap;
+    h.xcd_run = p.xcd_run;
+    const mtr::UDiv n = mtr::udiv_make(p.fb.nbx), r = mtr::udiv_make(p.xcd_run);
+    h.nbx_mul = n.mul; h.nbx_shift = n.shift;
+    h.run_mul = r.mul; h.run_shift = r.shift;
+    h.zero_nwords = p.zero_nwords; h.nhint = p.nhint;
+    h.entries = p.fb.entries; h.bin_fill = p.fb.bin_fill; h.bin_start = p.fb.bin_start; h.seg_start = p.fb.seg_start;
+    h.counters = p.fb.counters; h.rec_a = p.fb.rec_a;
+    h.zero_next = p.zero_next; h.zero_words = p.zero_words; h.host_status = p.host_status;
+}
+#endif
