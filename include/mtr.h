@@ -490,6 +490,68 @@ int32_t mtr_anim_player_advance_host(mtr_anim_player *player, mtr_play_state *st
                                      const mtr_play_cmd *cmds, size_t ncmds, mtr_anim_state *out_states,
                                      mtr_anim_layer *out_layers, size_t nlayers, mtr_root_step *out_steps);
 
+/* ---- controllers (build extension, SPEC.md section 21): per-instance state machines that decide what plays (k_ctrl) ----
+ * A player takes commands; a controller writes them on the device.  It is a graph shared by all instances: nodes, each
+ * with a clip and a range [first, first + count) of its own transitions, and transitions, the first nany of which are
+ * any-state transitions that every node tries first.  A transition has a target node, flags, the seconds and x of the
+ * command it issues, and up to 3 conditions `v op value`, v being a user parameter (param < nparams) or a built-in:
+ *   MTR_CTRL_TIME seconds in the node; MTR_CTRL_POS, MTR_CTRL_PHASE the position of what plays and position / period;
+ *   MTR_CTRL_ENDED 1.0 where a one-shot clip stands at its end; MTR_CTRL_FADING 1.0 while a fade runs.
+ * "What plays" is clip B while a fade runs (fade > 0), clip A otherwise.  Per instance there are 16 bytes of state
+ * (node; t, seconds since the node was entered; fired, the transition of the last step or MTR_CTRL_NONE; user, kept) and a
+ * row of nparams floats, both in DEVICE memory and free for the user to write: every bit pattern has a defined outcome.
+ * A step tries, per instance, transitions 0..nany-1 and then the node's own, in array order, and fires the first that is
+ * not skipped (a fade runs and it lacks INTERRUPT; an any-state transition whose target is the current node and that lacks
+ * SELF) and whose conditions all hold (NaN compares false, NE is true against NaN, no conditions always pass).  Firing writes
+ * command slot i = {i, clip of the target, x (with SYNC: phase of what plays times the target clip's period), seconds},
+ * enters the target with t = 0, with CONSUME stores 0 into the user parameters its conditions name, and adds 1 to
+ * counts[transition] when counts is given (never cleared by the call).  Otherwise slot i = {0xFFFFFFFF, 0, 0, 0}, which a
+ * player ignores, and t += max(dt, 0).  The play states are read and never written.  Pass the n slots as cmds_dev, ncmds = n
+ * to the next mtr_anim_player_advance_device_cmds; a host that overrules the controller appends its commands behind slot
+ * n - 1 (the last in array order wins) and writes state.node itself.
+ * nkeys and clip_flags are what mtr_anim_player_create was given; the controller makes the same periods from them and is
+ * not tied to a player handle.  Its tables are immutable.  A step runs in stream order on hip_stream under the rules of
+ * mtr_batch_set_poses_device; mtr_anim_ctrl_destroy may follow a step directly (no host wait).
+ * MTR_E_INVALID, nothing created (mtr_last_error names the clip, node or transition): nclips == 0 or > 2^24, nkeys outside
+ * 1..2^24, clip flag bits other than MTR_CLIP_LOOP, nnodes outside 1..65535, ntrans > 2^20, nany > ntrans, nparams > 16, a
+ * NULL array that is counted; a node whose clip >= nclips or whose range leaves [nany, ntrans] (count == 0 is allowed); a
+ * transition whose target >= nnodes, with unknown flag bits or ncond > 3; a used condition whose op > 5 or whose param is
+ * neither < nparams nor a built-in.  seconds, x and value are any floats.
+ * MTR_E_INVALID, nothing changed, at a step: a NULL handle, states, play or cmds pointer, n == 0 or n > 2^27, NULL params with
+ * nparams > 0, a misaligned device pointer (16 bytes: states, play, cmds; 4: params, counts).
+ * MTR_E_UNSUPPORTED: a library built without k_ctrl. */
+#define MTR_CTRL_MAX_COND 3
+enum { MTR_OP_LT, MTR_OP_LE, MTR_OP_GT, MTR_OP_GE, MTR_OP_EQ, MTR_OP_NE };          /* 0..5 */
+#define MTR_TR_INTERRUPT 1u   /* may fire while a fade runs */
+#define MTR_TR_SELF      2u   /* an any-state transition may target the current node */
+#define MTR_TR_SYNC      4u   /* start the target at the phase of what plays */
+#define MTR_TR_CONSUME   8u   /* firing clears the user parameters its conditions name */
+#define MTR_CTRL_TIME   0xFFFFu  /* built-in "parameters" a condition may name */
+#define MTR_CTRL_POS    0xFFFEu
+#define MTR_CTRL_PHASE  0xFFFDu
+#define MTR_CTRL_ENDED  0xFFFCu
+#define MTR_CTRL_FADING 0xFFFBu
+#define MTR_CTRL_NONE   0xFFFFFFFFu
+typedef struct mtr_anim_ctrl mtr_anim_ctrl;
+typedef struct mtr_ctrl_node  { uint32_t clip, first, count, pad; } mtr_ctrl_node;                 /* 16 bytes */
+typedef struct mtr_ctrl_cond  { uint16_t param, op; float value; } mtr_ctrl_cond;                  /*  8 bytes */
+typedef struct mtr_ctrl_trans { uint32_t target, flags; float seconds, x; uint32_t ncond, pad;
+                                mtr_ctrl_cond cond[MTR_CTRL_MAX_COND]; } mtr_ctrl_trans;           /* 48 bytes */
+typedef struct mtr_ctrl_state { uint32_t node; float t; uint32_t fired, user; } mtr_ctrl_state;    /* 16 bytes */
+int32_t mtr_anim_ctrl_create(mtr_device *dev, size_t nclips, const uint32_t *nkeys /* nclips */,
+                             const uint32_t *clip_flags /* nclips, NULL = 0 */, const mtr_ctrl_node *nodes, size_t nnodes,
+                             const mtr_ctrl_trans *trans, size_t ntrans, size_t nany, size_t nparams, mtr_anim_ctrl **out);
+void    mtr_anim_ctrl_destroy(mtr_anim_ctrl *ctrl);          /* parked like mtr_anim_destroy */
+int32_t mtr_anim_ctrl_step_device(mtr_anim_ctrl *ctrl, mtr_ctrl_state *states_dev /* n, 16-byte aligned */,
+                                  const mtr_play_state *play_dev /* n, 16-byte aligned */,
+                                  float *params_dev /* n*nparams, or NULL when nparams == 0 */, size_t n, float dt,
+                                  mtr_play_cmd *cmds_out_dev /* n, 16-byte aligned */,
+                                  uint32_t *counts_dev /* ntrans, or NULL */, void *hip_stream);
+/* a test and debug hook: everything in host memory (any alignment), the same kernel, waits; states, params and counts are
+ * read and written back */
+int32_t mtr_anim_ctrl_step_host(mtr_anim_ctrl *ctrl, mtr_ctrl_state *states, const mtr_play_state *play, float *params, size_t n,
+                                float dt, mtr_play_cmd *cmds_out, uint32_t *counts);
+
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],
                         float clear_depth, mtr_frame **out);

@@ -224,6 +224,34 @@ class AnimPlayer {
     mtr_anim_player* h_ = nullptr;
 };
 
+// A controller (include/mtr.h, SPEC.md section 21): per-instance state machines over one graph of nodes and transitions that
+// write a player's commands on the device; nkeys and clip_flags are what the player was created with
+class AnimCtrl {
+  public:
+    AnimCtrl(const Device& dev, size_t nclips, const uint32_t* nkeys, const uint32_t* clip_flags, const mtr_ctrl_node* nodes, size_t nnodes,
+             const mtr_ctrl_trans* trans, size_t ntrans, size_t nany, size_t nparams) : dev_(dev) {
+        dev.check(mtr_anim_ctrl_create(dev.handle(), nclips, nkeys, clip_flags, nodes, nnodes, trans, ntrans, nany, nparams, &h_));
+    }
+    AnimCtrl(AnimCtrl&& o) noexcept : dev_(o.dev_), h_(std::exchange(o.h_, nullptr)) {}
+    AnimCtrl(const AnimCtrl&) = delete;
+    ~AnimCtrl() { mtr_anim_ctrl_destroy(h_); }
+    // n states stepped in place in stream order against their play states and parameter rows; command slot i of cmds_out_dev is
+    // instance i's, for the player's advance_cmds(states, n, dt, cmds_out_dev, n, ...)
+    void step(mtr_ctrl_state* states_dev, const mtr_play_state* play_dev, float* params_dev, size_t n, float dt, mtr_play_cmd* cmds_out_dev,
+              uint32_t* counts_dev = nullptr, void* hip_stream = nullptr) const {
+        dev_.check(mtr_anim_ctrl_step_device(h_, states_dev, play_dev, params_dev, n, dt, cmds_out_dev, counts_dev, hip_stream));
+    }
+    // the test and debug hook: everything in host memory, waits
+    void step_host(mtr_ctrl_state* states, const mtr_play_state* play, float* params, size_t n, float dt, mtr_play_cmd* cmds_out, uint32_t* counts = nullptr) const {
+        dev_.check(mtr_anim_ctrl_step_host(h_, states, play, params, n, dt, cmds_out, counts));
+    }
+    mtr_anim_ctrl* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    mtr_anim_ctrl* h_ = nullptr;
+};
+
 class Model {
   public:
     // Model::new(model_file, material_file, shader2, resource_manager, device, queue, ..) -- src/model.rs:36-45

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "mtr_anim_root_deltas_device",
     "mtr_anim_player_create", "mtr_anim_player_destroy", "mtr_anim_player_advance_device", "mtr_anim_player_advance_device_cmds",
     "mtr_anim_player_advance_host",
+    "mtr_anim_ctrl_create", "mtr_anim_ctrl_destroy", "mtr_anim_ctrl_step_device", "mtr_anim_ctrl_step_host",
 ]
 
 CLIP_LOOP = 1
@@ -88,6 +89,16 @@ PLAY_STATE = np.dtype([("clip_a", "<u4"), ("clip_b", "<u4"), ("x_a", "<f4"), ("x
                        ("flags", "<u4")])
 PLAY_CMD = np.dtype([("instance", "<u4"), ("clip", "<u4"), ("x", "<f4"), ("seconds", "<f4")])
 PLAY_ENDED = 1
+# mtr_ctrl_node, mtr_ctrl_trans, mtr_ctrl_state (SPEC.md section 21): the tables of a controller and what it keeps per instance
+CTRL_NODE = np.dtype([("clip", "<u4"), ("first", "<u4"), ("count", "<u4"), ("pad", "<u4")])
+CTRL_COND = np.dtype([("param", "<u2"), ("op", "<u2"), ("value", "<f4")])
+CTRL_TRANS = np.dtype([("target", "<u4"), ("flags", "<u4"), ("seconds", "<f4"), ("x", "<f4"), ("ncond", "<u4"), ("pad", "<u4"), ("cond", CTRL_COND, (3,))])
+CTRL_STATE = np.dtype([("node", "<u4"), ("t", "<f4"), ("fired", "<u4"), ("user", "<u4")])
+CTRL_MAX_COND = 3
+OP_LT, OP_LE, OP_GT, OP_GE, OP_EQ, OP_NE = range(6)
+TR_INTERRUPT, TR_SELF, TR_SYNC, TR_CONSUME = 1, 2, 4, 8
+CTRL_TIME, CTRL_POS, CTRL_PHASE, CTRL_ENDED, CTRL_FADING = 0xFFFF, 0xFFFE, 0xFFFD, 0xFFFC, 0xFFFB
+CTRL_NONE = 0xFFFFFFFF
 
 
 class MtrError(RuntimeError):
@@ -244,6 +255,10 @@ def _load() -> C.CDLL:
         "mtr_anim_player_advance_device": (i32, [vp, vp, sz, C.c_float, vp, sz, vp, vp, sz, vp, vp]),
         "mtr_anim_player_advance_device_cmds": (i32, [vp, vp, sz, C.c_float, vp, sz, vp, vp, sz, vp, vp]),
         "mtr_anim_player_advance_host": (i32, [vp, vp, sz, C.c_float, vp, sz, vp, vp, sz, vp]),
+        "mtr_anim_ctrl_create": (i32, [vp, sz, vp, vp, vp, sz, vp, sz, sz, sz, vp]),
+        "mtr_anim_ctrl_destroy": (None, [vp]),
+        "mtr_anim_ctrl_step_device": (i32, [vp, vp, vp, vp, sz, C.c_float, vp, vp, vp]),
+        "mtr_anim_ctrl_step_host": (i32, [vp, vp, vp, vp, sz, C.c_float, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -788,6 +803,80 @@ class AnimPlayer:
     def close(self):
         if self._h:
             lib.mtr_anim_player_destroy(self._h)
+            self._h = None
+
+
+class AnimCtrl:
+    """A controller (include/mtr.h, SPEC.md section 21): per-instance state machines that write a player's commands on the
+    GPU.  ``nkeys`` and ``clip_flags`` are what the AnimPlayer was given; ``nodes`` a CTRL_NODE array, ``trans`` a CTRL_TRANS
+    array whose first ``nany`` entries are the any-state transitions (``anim_ctrl.build`` makes the three from a readable
+    description), ``nparams`` the floats per instance that conditions may name."""
+
+    def __init__(self, dev: Device, nkeys, clip_flags, nodes, trans, nany: int = 0, nparams: int = 0):
+        nk = np.ascontiguousarray(np.asarray(nkeys, dtype=np.uint32).reshape(-1))
+        fl = None if clip_flags is None else np.ascontiguousarray(np.asarray(clip_flags, dtype=np.uint32).reshape(-1))
+        nd, tr = np.asarray(nodes), np.asarray(trans)
+        if (fl is not None and fl.size != nk.size) or nd.dtype != CTRL_NODE or tr.dtype != CTRL_TRANS or nd.ndim != 1 or tr.ndim != 1:
+            raise MtrError(MTR_E_INVALID, "anim ctrl: one flag word per clip, nodes of dtype CTRL_NODE [S] and transitions of dtype CTRL_TRANS [T]")
+        nd, tr = np.ascontiguousarray(nd), np.ascontiguousarray(tr)
+        h = C.c_void_p()
+        dev.check(lib.mtr_anim_ctrl_create(dev._h, nk.size, _p(nk), _p(fl), _p(nd), nd.size, _p(tr) if tr.size else None, tr.size, nany, nparams, C.byref(h)))
+        self.dev, self._h, self.nclips, self.nnodes, self.ntrans, self.nany, self.nparams = dev, h, nk.size, nd.size, tr.size, nany, nparams
+
+    def step(self, states, play, params, dt: float, cmds_out, counts=None, stream=None):
+        """one step of the n CTRL_STATE records of ``states`` ([n, 16] bytes on the GPU, 16-byte aligned) IN PLACE against the
+        PLAY_STATE records of ``play`` ([n, 32] bytes, read only) and the rows of ``params`` (float32 [n, nparams], None when
+        nparams == 0; CONSUME writes it); writes PLAY_CMD slot i of ``cmds_out`` (at least n slots of 16 bytes; a longer
+        tensor leaves room for the host's own commands behind slot n - 1) and adds to ``counts`` (int32 [ntrans]) where
+        given, in stream order on ``stream`` (a torch stream; None: torch.cuda.current_stream())."""
+        import torch
+        n = _play_tensor(states, self.dev, "ctrl states", CTRL_STATE.itemsize, 16, None)
+        _play_tensor(play, self.dev, "ctrl play states", PLAY_STATE.itemsize, 16, n)
+        if _play_tensor(cmds_out, self.dev, "ctrl commands", PLAY_CMD.itemsize, 16, None) < n:
+            raise MtrError(MTR_E_INVALID, "ctrl commands: at least n slots of 16 bytes")
+        used = [states, play, cmds_out]
+        if self.nparams:
+            if params is None or getattr(params, "dtype", None) != torch.float32:
+                raise MtrError(MTR_E_INVALID, "ctrl params: a float32 tensor [n, nparams] on the GPU")
+            _play_tensor(params, self.dev, "ctrl params", 4 * self.nparams, 4, n)
+            used.append(params)
+        else:
+            params = None
+        if counts is not None:
+            if getattr(counts, "dtype", None) != torch.int32:
+                raise MtrError(MTR_E_INVALID, "ctrl counts: an int32 tensor [ntrans] on the GPU")
+            if self.ntrans == 0 or _play_tensor(counts, self.dev, "ctrl counts", 4, 4, None) < self.ntrans:
+                raise MtrError(MTR_E_INVALID, "ctrl counts: one word per transition")
+            used.append(counts)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        cur = stream if stream is not None else torch.cuda.current_stream(states.device)
+        _on_stream(self.dev, cur, lib.mtr_anim_ctrl_step_device, (self._h, ptr(states), ptr(play), ptr(params), n, float(dt), ptr(cmds_out), ptr(counts)), used)
+
+    def step_host(self, states: np.ndarray, play: np.ndarray, params, dt: float, counts: Optional[np.ndarray] = None):
+        """the test and debug hook: CTRL_STATE [n], PLAY_STATE [n] and float32 [n, nparams] in host memory through the same
+        kernel; waits.  Returns (states, params or None, PLAY_CMD [n], counts or None); ``counts`` (uint32 [ntrans]) is added to."""
+        st = np.ascontiguousarray(np.asarray(states)).copy()
+        pl = np.ascontiguousarray(np.asarray(play))
+        if st.dtype != CTRL_STATE or st.ndim != 1 or pl.dtype != PLAY_STATE or pl.shape != st.shape:
+            raise MtrError(MTR_E_INVALID, "ctrl states: arrays [n] of dtype CTRL_STATE and PLAY_STATE")
+        n = st.size
+        pr = None
+        if self.nparams:
+            pr = np.ascontiguousarray(np.asarray(params, dtype=np.float32)).copy()
+            if pr.shape != (n, self.nparams):
+                raise MtrError(MTR_E_INVALID, "ctrl params: float32 [n, nparams]")
+        ct = None
+        if counts is not None:
+            ct = np.ascontiguousarray(np.asarray(counts, dtype=np.uint32)).copy()
+            if ct.shape != (self.ntrans,):
+                raise MtrError(MTR_E_INVALID, "ctrl counts: uint32 [ntrans]")
+        cm = np.zeros(n, dtype=PLAY_CMD)
+        self.dev.check(lib.mtr_anim_ctrl_step_host(self._h, _p(st), _p(pl), _p(pr), n, float(dt), _p(cm), _p(ct) if ct is not None and ct.size else None))
+        return st, pr, cm, ct
+
+    def close(self):
+        if self._h:
+            lib.mtr_anim_ctrl_destroy(self._h)
             self._h = None
 
 

@@ -381,6 +381,13 @@ struct mtr_anim_player : mtr_host::DeviceSet {
     hipEvent_t cmd_last = nullptr;
 };
 
+// A controller (SPEC.md section 21): immutable once uploaded and only read by its kernels.  d: nclips table entries of 4
+// words (period, flags, 0, key count), then nnodes nodes of 4 words, then ntrans transitions of 12 words, each part a
+// multiple of 16 bytes.
+struct mtr_anim_ctrl : mtr_host::DeviceSet {
+    uint32_t nclips = 0, nnodes = 0, ntrans = 0, nany = 0, nparams = 0;
+};
+
 namespace mtr_host {
 
 struct BatchDeleter {

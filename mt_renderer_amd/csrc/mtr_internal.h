@@ -585,3 +585,22 @@ struct PlayParams {
     float dt;
 };
 void mtr_launch_play(const PlayParams& p, hipStream_t s);
+// controllers (k_ctrl.hip, SPEC.md section 21): n controller states stepped in place against their play states and
+// parameter rows, command slot i of cmds written for instance i, counts[t] += 1 for every instance whose transition t fired
+struct CtrlParams {
+    const uint32_t* nodes;      // nnodes x 4 words (mtr_ctrl_node), validated at creation; 16-byte aligned
+    const uint32_t* trans;      // ntrans x 12 words (mtr_ctrl_trans), validated at creation; 16-byte aligned
+    const uint32_t* clips;      // nclips x 4 words (PlayClip: period (f32 bits), flags, 0, key count); 16-byte aligned
+    uint32_t* states;           // n x 4 words (mtr_ctrl_state); 16-byte aligned
+    const uint32_t* play;       // n x 8 words (mtr_play_state), read only; 16-byte aligned
+    float* params;              // n x nparams floats, written by CONSUME only; nullptr when nparams == 0
+    uint32_t* cmds;             // n x 4 words (mtr_play_cmd); 16-byte aligned
+    uint32_t* counts;           // ntrans words, or nullptr
+    uint32_t nnodes;            // >= 1
+    uint32_t nany;              // <= ntrans
+    uint32_t nclips;            // >= 1
+    uint32_t nparams;           // 0..16
+    uint32_t n;
+    float dt;
+};
+void mtr_launch_ctrl(const CtrlParams& p, hipStream_t s);

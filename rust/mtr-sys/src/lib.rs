@@ -70,7 +70,7 @@ pub const MTR_OWN_SUPERTILES: u32 = 2;
 pub const MTR_TEXRES_DECODED: u32 = 0;
 pub const MTR_TEXRES_BLOCKS: u32 = 1;
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player);
+opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player, mtr_anim_ctrl);
 
 /// animation clips (mtr.h, SPEC.md section 14): one key of one joint, 48 bytes
 pub const MTR_CLIP_LOOP: u32 = 1;
@@ -171,6 +171,59 @@ pub struct mtr_play_cmd {
     pub clip: u32,
     pub x: f32,
     pub seconds: f32,
+}
+/// controllers (mtr.h, SPEC.md section 21): the tables of a controller (a node 16 bytes, a condition 8, a transition 48) and
+/// the state an instance keeps on the device, 16 bytes
+pub const MTR_CTRL_MAX_COND: usize = 3;
+pub const MTR_OP_LT: u16 = 0;
+pub const MTR_OP_LE: u16 = 1;
+pub const MTR_OP_GT: u16 = 2;
+pub const MTR_OP_GE: u16 = 3;
+pub const MTR_OP_EQ: u16 = 4;
+pub const MTR_OP_NE: u16 = 5;
+pub const MTR_TR_INTERRUPT: u32 = 1;
+pub const MTR_TR_SELF: u32 = 2;
+pub const MTR_TR_SYNC: u32 = 4;
+pub const MTR_TR_CONSUME: u32 = 8;
+pub const MTR_CTRL_TIME: u16 = 0xFFFF;
+pub const MTR_CTRL_POS: u16 = 0xFFFE;
+pub const MTR_CTRL_PHASE: u16 = 0xFFFD;
+pub const MTR_CTRL_ENDED: u16 = 0xFFFC;
+pub const MTR_CTRL_FADING: u16 = 0xFFFB;
+pub const MTR_CTRL_NONE: u32 = 0xFFFF_FFFF;
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_ctrl_node {
+    pub clip: u32,
+    pub first: u32,
+    pub count: u32,
+    pub pad: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_ctrl_cond {
+    pub param: u16,
+    pub op: u16,
+    pub value: f32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_ctrl_trans {
+    pub target: u32,
+    pub flags: u32,
+    pub seconds: f32,
+    pub x: f32,
+    pub ncond: u32,
+    pub pad: u32,
+    pub cond: [mtr_ctrl_cond; MTR_CTRL_MAX_COND],
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_ctrl_state {
+    pub node: u32,
+    pub t: f32,
+    pub fired: u32,
+    pub user: u32,
 }
 /// what one instance plays: clip A at x_a cross-faded by w with clip B at x_b, positions in keys; 24 bytes
 #[repr(C)]
@@ -327,5 +380,13 @@ extern "C" {
                                                hip_stream: *mut c_void) -> i32;
     pub fn mtr_anim_player_advance_host(player: *mut mtr_anim_player, states: *mut mtr_play_state, n: usize, dt: f32, cmds: *const mtr_play_cmd, ncmds: usize,
                                         out_states: *mut mtr_anim_state, out_layers: *mut mtr_anim_layer, nlayers: usize, out_steps: *mut mtr_root_step) -> i32;
+    // controllers (SPEC.md section 21): declarations only
+    pub fn mtr_anim_ctrl_create(dev: *mut mtr_device, nclips: usize, nkeys: *const u32, clip_flags: *const u32, nodes: *const mtr_ctrl_node, nnodes: usize,
+                                trans: *const mtr_ctrl_trans, ntrans: usize, nany: usize, nparams: usize, out: *mut *mut mtr_anim_ctrl) -> i32;
+    pub fn mtr_anim_ctrl_destroy(ctrl: *mut mtr_anim_ctrl);
+    pub fn mtr_anim_ctrl_step_device(ctrl: *mut mtr_anim_ctrl, states_dev: *mut mtr_ctrl_state, play_dev: *const mtr_play_state, params_dev: *mut f32, n: usize,
+                                     dt: f32, cmds_out_dev: *mut mtr_play_cmd, counts_dev: *mut u32, hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_ctrl_step_host(ctrl: *mut mtr_anim_ctrl, states: *mut mtr_ctrl_state, play: *const mtr_play_state, params: *mut f32, n: usize, dt: f32,
+                                   cmds_out: *mut mtr_play_cmd, counts: *mut u32) -> i32;
 }
 pub mod files;
