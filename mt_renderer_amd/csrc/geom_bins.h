@@ -234,9 +234,13 @@ __device__ __forceinline__ void emit_bins_unordered(const FrameBuffers& fb, RecH
             const uint32_t c = slot[lane];
             if (c) {
                 const uint32_t bin = (wy0 + (lane >> 3)) * fb.nbx + wx0 + (lane & 7u);
-                uint32_t o = (uint32_t)atomicAdd(&fb.bin_fill[bin], (unsigned long long)c | (1ull << 32));
-                if (o + c > fb.qcap) { atomicOr(&fb.counters[CTR_OVERFLOW], 4u); o = 0x80000000u; }
-                slot[64 + lane] = o;
+                const uint32_t o = (uint32_t)atomicAdd(&fb.bin_fill[bin], (unsigned long long)c | (1ull << 32));
+                // the entry index of the reservation's first place, worked out here, once per bin of the window: the stores
+                // below add their rank to it (the multiply by qcap issues at a quarter of the rate, and every store carried
+                // one).  No entry has index 2^32 - 1 (the index is 32 bits wide and counts from 0), so it marks an overflow
+                uint32_t q0 = bin * fb.qcap + o;
+                if (o + c > fb.qcap) { atomicOr(&fb.counters[CTR_OVERFLOW], 4u); q0 = 0xFFFFFFFFu; }
+                slot[64 + lane] = q0;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -245,8 +249,8 @@ __device__ __forceinline__ void emit_bins_unordered(const FrameBuffers& fb, RecH
                 const uint32_t dx = w == 1u ? 0u : (w == 2u ? (j & 1u) : j), dy = w == 1u ? j : (w == 2u ? (j >> 1) : 0u);
                 const uint32_t bx = h.bx0 + dx, by = h.by0 + dy;
                 if ((own >> j) & 1u) {
-                    const uint32_t o = slot[64 + (by - wy0) * 8u + (bx - wx0)];
-                    if (!(o & 0x80000000u)) fb.entries[(by * fb.nbx + bx) * fb.qcap + o + ((ranks >> (8u * j)) & 0xffu)] = ord0 + lane;
+                    const uint32_t q0 = slot[64 + (by - wy0) * 8u + (bx - wx0)];
+                    if (q0 != 0xFFFFFFFFu) fb.entries[q0 + ((ranks >> (8u * j)) & 0xffu)] = ord0 + lane;
                 }
             }
             // the next round (or the caller) may reuse the slots at once: LDS operations of one wave are ordered

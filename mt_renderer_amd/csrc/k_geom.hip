@@ -287,7 +287,10 @@ __device__ __forceinline__ void geom_chunk(const GeomParams& P, uint32_t inst, u
     }
 
     // lanes l-1 and l-2 by DPP wave_shr:1 (VALU moves instead of the 14 ds_bpermute behind __shfl_up; same speed in an
-    // A/B run, tools/sweep_ab.sh, but the LDS pipe stays free for the palette reads)
+    // A/B run, tools/sweep_ab.sh, but the LDS pipe stays free for the palette reads).  Reading the two neighbours back from
+    // s_pv instead (two more ds_read_b128, four for textured materials; 61 VALU instructions fewer in the code of
+    // k_geom<2, false, 7>) left the headline frame where it was and made the kernel 19-22 % slower on the instanced configs
+    // (C3 0.109 -> 0.130 ms, C5 0.76 -> 0.93 ms): DESIGN.md section 7, profiles/hot_slots_ab.txt
     PV v1, v2;
     v1.iw = v1.up = v1.vp = v2.iw = v2.up = v2.vp = 0.0f;
 #define MTR_SHR1(x) __builtin_amdgcn_update_dpp((int)(x), (int)(x), 0x138, 0xf, 0xf, false)

@@ -40,8 +40,8 @@ namespace mtr {
 
 // LDS triangle record of one pass (64 B): everything a (triangle, pixel) work item needs
 struct VisTri {
-    int32_t A0, B0, C0, A1;  // edge i: E_i(lx,ly) = C_i + A_i*lx + B_i*ly, top-left bias folded into C_i
-    int32_t B1, C1, A2, B2;  // small class: i32, A/B pre-scaled by 256; large class: unscaled, C high words in s_chi
+    int32_t A0, B0, C0, A1;  // edge i: E_i = C_i + A_i*x + B_i*y, top-left bias folded into C_i
+    int32_t B1, C1, A2, B2;  // small class: i32, A/B pre-scaled by 256, (x, y) from the bbox origin; large class: unscaled, from the bin's first pixel, C high words in chi
     int32_t C2;
     uint32_t flags;          // bit0 large, bits 4..6: 1 - tl_i
     float z0, dz1;
@@ -59,15 +59,17 @@ struct Setup {
 };
 
 // the shared set-up (tri_setup.h) plus this kernel's own: the bbox clipped to the bin and the viewport, and the order.
-// A triangle whose bbox misses the bin gets npx == 0: its coefficients (meaningless, tri_setup.h) are never read
+// A triangle whose bbox misses the bin gets npx == 0: its coefficients (meaningless, tri_setup.h) are never read.
+// An i32-class triangle's C_i are taken at the bbox origin (box bits 0..7), where the flat walks evaluate them; a
+// large-class one's at the bin's first pixel, for the whole-wave walk (tri_setup_box)
 __device__ __forceinline__ void setup_tri(const RecA& a, uint32_t ord, int32_t binx0, int32_t biny0, int32_t vw, int32_t vh, Setup& s) {
     const int32_t X[3] = {a.X0, a.X1, a.X2}, Y[3] = {a.Y0, a.Y1, a.Y2};
     TriSetup g;
-    tri_setup(X, Y, a.z0, a.z1, a.z2, binx0, biny0, g);
+    tri_setup_box(X, Y, a.z0, a.z1, a.z2, binx0, biny0, g);
     const int32_t px0 = max(g.px0, 0), px1 = min(g.px1, min(MTR_BIN, vw) - 1);
     const int32_t py0 = max(g.py0, 0), py1 = min(g.py1, min(MTR_BIN, vh) - 1);
     const int32_t bw = px1 - px0 + 1, bh = py1 - py0 + 1;
-    s.npx = (bw > 0 && bh > 0) ? bw * bh : 0;  // pixels of the bbox in this bin; the caller turns it into work items (walk_items)
+    s.npx = (bw > 0 && bh > 0) ? MTR_MAD24(bw, bh, 0) : 0;  // pixels of the bbox in this bin (both <= 16: no full-width multiply); the caller turns it into work items
     s.bhm1 = (uint32_t)max(bh - 1, 0);
     s.t.A0 = g.A[0]; s.t.B0 = g.B[0]; s.t.C0 = g.Clo[0];
     s.t.A1 = g.A[1]; s.t.B1 = g.B[1]; s.t.C1 = g.Clo[1];
@@ -79,14 +81,12 @@ __device__ __forceinline__ void setup_tri(const RecA& a, uint32_t ord, int32_t b
     s.chi = make_int4(g.Chi[0], g.Chi[1], g.Chi[2], 0);
 }
 
-// a triangle of the flattened walks in s_flat: its record with the edge functions rebased to the bbox origin (an item
+// a triangle of the flattened walks in s_flat: its record, whose edge functions setup_tri took at the bbox origin (an item
 // evaluates E(col, row) with no bin coordinates), `pre` in place of flags, whose bits 5 / 6 (1 - tl) go to box bits 29 / 30
 __device__ __forceinline__ void stage_flat(uint4* dst, const VisTri& t, uint32_t pre) {
-    const int32_t ox = (int32_t)(t.box & 15u), oy = (int32_t)((t.box >> 4) & 15u);
-    const int32_t c0 = tri_edge(t.C0, t.A0, t.B0, ox, oy), c1 = tri_edge(t.C1, t.A1, t.B1, ox, oy), c2 = tri_edge(t.C2, t.A2, t.B2, ox, oy);
-    dst[0] = make_uint4((uint32_t)t.A0, (uint32_t)t.B0, (uint32_t)c0, (uint32_t)t.A1);
-    dst[1] = make_uint4((uint32_t)t.B1, (uint32_t)c1, (uint32_t)t.A2, (uint32_t)t.B2);
-    dst[2] = make_uint4((uint32_t)c2, pre, __float_as_uint(t.z0), __float_as_uint(t.dz1));
+    dst[0] = make_uint4((uint32_t)t.A0, (uint32_t)t.B0, (uint32_t)t.C0, (uint32_t)t.A1);
+    dst[1] = make_uint4((uint32_t)t.B1, (uint32_t)t.C1, (uint32_t)t.A2, (uint32_t)t.B2);
+    dst[2] = make_uint4((uint32_t)t.C2, pre, __float_as_uint(t.z0), __float_as_uint(t.dz1));
     dst[3] = make_uint4(__float_as_uint(t.dz2), __float_as_uint(t.rcpA), t.ordk, t.box | ((t.flags & 0x60u) << 24));
 }
 

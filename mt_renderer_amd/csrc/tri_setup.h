@@ -66,14 +66,20 @@ struct TriSetup {
 // overlapping the bbox: then every operand is < 2^16 and every product < 2^31.  A queued triangle whose bbox misses the
 // bin may get meaningless C values from the 24-bit multiplies; its bbox says so (k_tile: submask == 0 and pad == 0,
 // k_tile_vis: npx == 0) and its coefficients are never read.
-MTR_TRI_HD void tri_setup(const int32_t (&X)[3], const int32_t (&Y)[3], float z0, float z1, float z2, int32_t binx0, int32_t biny0, TriSetup& s) {
+// BOX (tri_setup_box below): the small class's C_i are taken at the first pixel of the bbox inside the bin instead.
+template <bool BOX>
+MTR_TRI_HD void tri_setup_at(const int32_t (&X)[3], const int32_t (&Y)[3], float z0, float z1, float z2, int32_t binx0, int32_t biny0, TriSetup& s) {
     const int32_t xmin = tri_min3(X[0], X[1], X[2]), xmax = tri_max3(X[0], X[1], X[2]);
     const int32_t ymin = tri_min3(Y[0], Y[1], Y[2]), ymax = tri_max3(Y[0], Y[1], Y[2]);
     const bool large = tri_is_large(xmax - xmin, ymax - ymin);
     s.flags = large ? 1u : 0u;
     // edge 0: v1->v2, edge 1: v2->v0, edge 2: v0->v1;  E = dy*(Px-Xa) - dx*(Py-Ya)
     if (!large) {
-        const int32_t Px = binx0 * 256 + 128, Py = biny0 * 256 + 128;
+        int32_t Px = binx0 * 256 + 128, Py = biny0 * 256 + 128;
+        if (BOX) {  // px0 / py0 below, clipped to the bin
+            const int32_t bx = ((xmin + 127) >> 8) - binx0, by = ((ymin + 127) >> 8) - biny0;
+            Px += ((bx > 0 ? bx : 0) & 15) * 256; Py += ((by > 0 ? by : 0) & 15) * 256;
+        }
 #pragma unroll
         for (int i = 0; i < 3; i++) {
             const int ia = (i + 1) % 3, ib = (i + 2) % 3;
@@ -104,6 +110,18 @@ MTR_TRI_HD void tri_setup(const int32_t (&X)[3], const int32_t (&Y)[3], float z0
     s.z0 = z0; s.dz1 = z1 - z0; s.dz2 = z2 - z0;
     s.px0 = ((xmin + 127) >> 8) - binx0; s.px1 = ((xmax - 128) >> 8) - binx0;
     s.py0 = ((ymin + 127) >> 8) - biny0; s.py1 = ((ymax - 128) >> 8) - biny0;
+}
+MTR_TRI_HD void tri_setup(const int32_t (&X)[3], const int32_t (&Y)[3], float z0, float z1, float z2, int32_t binx0, int32_t biny0, TriSetup& s) {
+    tri_setup_at<false>(X, Y, z0, z1, z2, binx0, biny0, s);
+}
+// tri_setup for the walks that evaluate E_i(col, row) in bbox coordinates (k_tile_vis.hip's flat walks): every output as
+// tri_setup's, except that a small-class triangle's Clo[i] is E_i at the bbox's first pixel inside the bin, (ox, oy) =
+// (max(px0, 0) & 15, max(py0, 0) & 15): the same integer expression at another point, so it equals tri_edge(C_i, A_i,
+// B_i, ox, oy) of tri_setup's C_i in 32-bit arithmetic (tests/test_tri_setup_box_exact.py), with operands that are
+// offsets inside the triangle's own extent (<= 2^14 + 2^8) rather than from the bin's corner.  The large class is left at
+// the bin's first pixel, as its whole-wave walk reads it.
+MTR_TRI_HD void tri_setup_box(const int32_t (&X)[3], const int32_t (&Y)[3], float z0, float z1, float z2, int32_t binx0, int32_t biny0, TriSetup& s) {
+    tri_setup_at<true>(X, Y, z0, z1, z2, binx0, biny0, s);
 }
 
 struct TriEdges {  // the nine edge words as both kernels' LDS records lay them out
