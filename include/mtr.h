@@ -552,6 +552,58 @@ int32_t mtr_anim_ctrl_step_device(mtr_anim_ctrl *ctrl, mtr_ctrl_state *states_de
 int32_t mtr_anim_ctrl_step_host(mtr_anim_ctrl *ctrl, mtr_ctrl_state *states, const mtr_play_state *play, float *params, size_t n,
                                 float dt, mtr_play_cmd *cmds_out, uint32_t *counts);
 
+/* ---- animation events (build extension, SPEC.md section 22): markers on clips fire into a device list (k_events) ----
+ * The return channel of the players: which markers did each instance arrive at or pass this frame (a footstep, the hit frame
+ * of an attack, the end of a one-shot).  An event set holds per clip count_c >= 0 markers {x, id}, clip after clip in one
+ * array, x non-decreasing within a clip (ties keep array order), id any word.  nkeys and clip_flags are what
+ * mtr_anim_player_create was given; the set makes the same periods P from them and is not tied to a player handle.  It owns
+ * a scratch array of ceil(max_instances / 256) words, so calls on one set are ordered among themselves whatever their streams.
+ * A collect call reads nsteps (1..8) mtr_root_step per instance, steps[inst * nsteps + i]: exactly what a player's advance
+ * writes into out_steps_dev (nsteps = 2) and mtr_batch_root_motion_device reads.  Every bit pattern has a defined outcome
+ * and the clip index is clamped.  Per step:
+ *   weight    : E_i = e_i * (1 - e_{i+1}) * ... * (1 - e_{nsteps-1}), e_0 = 1 and e_i the clamped w of step i: the share the
+ *               step's clip has in the blend.  A step i >= 1 with e_i == 0 fires nothing; a step fires only if
+ *               E_i >= min_weight (0 lets everything else through, NaN nothing).
+ *   direction : dx > 0 forward, dx < 0 backward, anything else fires nothing.  A marker fires when the position arrives at
+ *               it or passes it, not when it leaves it: forward over (a, b] in array order, backward over [b, a) in reverse.
+ *   one-shot  : a and b are x and x + dx clamped to [0, P], so a marker at P fires once on arrival.
+ *   LOOP      : x is wrapped into [0, P) first; across the seam the markers behind the start fire, then those up to where
+ *               the player lands; |dx| >= P fires every marker of the clip once.
+ * Consecutive frames of a player abut: a marker fires exactly once per passage.  A clip started AT a marker does not fire it.
+ * The list holds mtr_anim_event {instance, id, where, w}: where = clip | step << 24 | MTR_EVENT_BACKWARD, w = E_i; ordered
+ * by instance, then step, then firing order, whichever thread ran first.  count_dev[0] = events fired, count_dev[1] =
+ * min(count_dev[0], capacity) records written, the first in that order; a longer list is truncated, not an error, and the
+ * list behind count_dev[1] is untouched.  bits_dev (optional) takes per instance the OR of 1u << (id & 31) over its fired
+ * events, written (not OR-ed into) for every instance on every call, whatever capacity is.
+ * The call runs in stream order on hip_stream under the rules of mtr_batch_set_poses_device;
+ * mtr_anim_events_destroy may follow a call directly (no host wait).
+ * MTR_E_INVALID, nothing created (mtr_last_error names the clip and the marker): a NULL device, out or nkeys pointer,
+ * nclips == 0 or > 2^24, nkeys outside 1..2^24, clip flag bits other than MTR_CLIP_LOOP, max_instances outside 1..2^27, more
+ * than 2^24 markers in all, NULL counts or markers with a marker counted; a marker whose x is not finite, is negative, lies
+ * above P (on a LOOP clip: at or above P) or below the marker before it in its clip.
+ * MTR_E_INVALID, nothing changed, at a call: a NULL handle, steps or count pointer, nsteps outside 1..8, n == 0 or
+ * n > max_instances, capacity > 0 with a NULL list, a misaligned device pointer (16 bytes: steps, list; 4: count, bits),
+ * n * nsteps * (the largest count_c) > 2^32 - 1, a capacity of 2^32 or more at the host hook.
+ * MTR_E_UNSUPPORTED: a library built without k_events. */
+#define MTR_EVENT_BACKWARD 0x80000000u   /* in mtr_anim_event::where */
+typedef struct mtr_anim_events mtr_anim_events;
+typedef struct mtr_event_marker { float x; uint32_t id; } mtr_event_marker;                        /*  8 bytes */
+typedef struct mtr_anim_event { uint32_t instance, id, where; float w; } mtr_anim_event;           /* 16 bytes */
+int32_t mtr_anim_events_create(mtr_device *dev, size_t nclips, const uint32_t *nkeys /* nclips */,
+                               const uint32_t *clip_flags /* nclips, NULL = 0 */, const uint32_t *counts /* nclips, NULL = 0 */,
+                               const mtr_event_marker *markers /* sum of counts */, size_t max_instances,
+                               mtr_anim_events **out);
+void    mtr_anim_events_destroy(mtr_anim_events *ev);        /* parked like mtr_anim_destroy */
+int32_t mtr_anim_events_collect_device(mtr_anim_events *ev, const mtr_root_step *steps_dev /* n*nsteps, 16-byte aligned */,
+                                       size_t nsteps, size_t n, float min_weight,
+                                       mtr_anim_event *out_dev /* capacity, 16-byte aligned, or NULL */, size_t capacity,
+                                       uint32_t *count_dev /* 2 words */, uint32_t *bits_dev /* n, or NULL */,
+                                       void *hip_stream);
+/* a test and debug hook: everything in host memory (any alignment), the same kernels, waits; the list and bits are read
+ * first so that what the kernels leave untouched comes back as it went in */
+int32_t mtr_anim_events_collect_host(mtr_anim_events *ev, const mtr_root_step *steps, size_t nsteps, size_t n, float min_weight,
+                                     mtr_anim_event *out, size_t capacity, uint32_t *count, uint32_t *bits);
+
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],
                         float clear_depth, mtr_frame **out);

@@ -252,6 +252,35 @@ class AnimCtrl {
     mtr_anim_ctrl* h_ = nullptr;
 };
 
+// An event set (include/mtr.h, SPEC.md section 22): sorted markers per clip that fire into a list on the device; nkeys and
+// clip_flags are what the player was created with, counts[c] markers per clip lie behind each other in markers
+class AnimEvents {
+  public:
+    AnimEvents(const Device& dev, size_t nclips, const uint32_t* nkeys, const uint32_t* clip_flags, const uint32_t* counts, const mtr_event_marker* markers,
+               size_t max_instances) : dev_(dev) {
+        dev.check(mtr_anim_events_create(dev.handle(), nclips, nkeys, clip_flags, counts, markers, max_instances, &h_));
+    }
+    AnimEvents(AnimEvents&& o) noexcept : dev_(o.dev_), h_(std::exchange(o.h_, nullptr)) {}
+    AnimEvents(const AnimEvents&) = delete;
+    ~AnimEvents() { mtr_anim_events_destroy(h_); }
+    // the markers that the nsteps steps of each of n instances passed, in stream order: up to capacity records into out_dev,
+    // count_dev[0] = fired, count_dev[1] = written, bits_dev[i] = the mask of instance i (optional)
+    void collect(const mtr_root_step* steps_dev, size_t nsteps, size_t n, float min_weight, mtr_anim_event* out_dev, size_t capacity, uint32_t* count_dev,
+                 uint32_t* bits_dev = nullptr, void* hip_stream = nullptr) const {
+        dev_.check(mtr_anim_events_collect_device(h_, steps_dev, nsteps, n, min_weight, out_dev, capacity, count_dev, bits_dev, hip_stream));
+    }
+    // the test and debug hook: everything in host memory, waits
+    void collect_host(const mtr_root_step* steps, size_t nsteps, size_t n, float min_weight, mtr_anim_event* out, size_t capacity, uint32_t* count,
+                      uint32_t* bits = nullptr) const {
+        dev_.check(mtr_anim_events_collect_host(h_, steps, nsteps, n, min_weight, out, capacity, count, bits));
+    }
+    mtr_anim_events* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    mtr_anim_events* h_ = nullptr;
+};
+
 class Model {
   public:
     // Model::new(model_file, material_file, shader2, resource_manager, device, queue, ..) -- src/model.rs:36-45

@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "mtr_anim_player_create", "mtr_anim_player_destroy", "mtr_anim_player_advance_device", "mtr_anim_player_advance_device_cmds",
     "mtr_anim_player_advance_host",
     "mtr_anim_ctrl_create", "mtr_anim_ctrl_destroy", "mtr_anim_ctrl_step_device", "mtr_anim_ctrl_step_host",
+    "mtr_anim_events_create", "mtr_anim_events_destroy", "mtr_anim_events_collect_device", "mtr_anim_events_collect_host",
 ]
 
 CLIP_LOOP = 1
@@ -99,6 +100,10 @@ OP_LT, OP_LE, OP_GT, OP_GE, OP_EQ, OP_NE = range(6)
 TR_INTERRUPT, TR_SELF, TR_SYNC, TR_CONSUME = 1, 2, 4, 8
 CTRL_TIME, CTRL_POS, CTRL_PHASE, CTRL_ENDED, CTRL_FADING = 0xFFFF, 0xFFFE, 0xFFFD, 0xFFFC, 0xFFFB
 CTRL_NONE = 0xFFFFFFFF
+# mtr_event_marker, mtr_anim_event (SPEC.md section 22): a marker on a clip, and one record of the list a collect call writes
+EVENT_MARKER = np.dtype([("x", "<f4"), ("id", "<u4")])
+EVENT = np.dtype([("instance", "<u4"), ("id", "<u4"), ("where", "<u4"), ("w", "<f4")])
+EVENT_BACKWARD = 0x80000000
 
 
 class MtrError(RuntimeError):
@@ -259,6 +264,10 @@ def _load() -> C.CDLL:
         "mtr_anim_ctrl_destroy": (None, [vp]),
         "mtr_anim_ctrl_step_device": (i32, [vp, vp, vp, vp, sz, C.c_float, vp, vp, vp]),
         "mtr_anim_ctrl_step_host": (i32, [vp, vp, vp, vp, sz, C.c_float, vp, vp]),
+        "mtr_anim_events_create": (i32, [vp, sz, vp, vp, vp, vp, sz, vp]),
+        "mtr_anim_events_destroy": (None, [vp]),
+        "mtr_anim_events_collect_device": (i32, [vp, vp, sz, sz, C.c_float, vp, sz, vp, vp, vp]),
+        "mtr_anim_events_collect_host": (i32, [vp, vp, sz, sz, C.c_float, vp, sz, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -877,6 +886,79 @@ class AnimCtrl:
     def close(self):
         if self._h:
             lib.mtr_anim_ctrl_destroy(self._h)
+            self._h = None
+
+
+class AnimEvents:
+    """An event set (include/mtr.h, SPEC.md section 22): markers on clips that fire into a list on the GPU.  ``nkeys`` and
+    ``clip_flags`` are what the AnimPlayer was given; ``counts`` holds the markers per clip and ``markers`` an EVENT_MARKER
+    array of them, clip after clip, sorted by x within a clip (``anim_events.build`` makes the two from a dict), for calls of
+    up to ``max_instances`` instances."""
+
+    def __init__(self, dev: Device, nkeys, clip_flags, counts, markers, max_instances: int = 1):
+        nk = np.ascontiguousarray(np.asarray(nkeys, dtype=np.uint32).reshape(-1))
+        fl = None if clip_flags is None else np.ascontiguousarray(np.asarray(clip_flags, dtype=np.uint32).reshape(-1))
+        ct = np.ascontiguousarray(np.asarray(counts, dtype=np.uint32).reshape(-1))
+        mk = np.asarray(markers)
+        if (fl is not None and fl.size != nk.size) or ct.size != nk.size or mk.dtype != EVENT_MARKER or mk.ndim != 1 or mk.size != int(ct.sum(dtype=np.uint64)):
+            raise MtrError(MTR_E_INVALID, "anim events: one flag word and one marker count per clip, markers of dtype EVENT_MARKER [sum of counts]")
+        mk = np.ascontiguousarray(mk)
+        h = C.c_void_p()
+        dev.check(lib.mtr_anim_events_create(dev._h, nk.size, _p(nk), _p(fl), _p(ct), _p(mk) if mk.size else None, max_instances, C.byref(h)))
+        self.dev, self._h, self.nclips, self.nmarkers, self.max_instances = dev, h, nk.size, mk.size, max_instances
+
+    def collect(self, steps, min_weight: float, out, count, bits=None, stream=None):
+        """the markers that the S steps of each of n instances arrived at or passed: ``steps`` holds ROOT_STEP records ([n, S,
+        16] bytes on the GPU, 16-byte aligned: a player's out_steps), ``out`` takes up to its size of EVENT records (16 bytes
+        each, 16-byte aligned; None: capacity 0), ``count`` (int32 [2]) the number fired and the number written, ``bits``
+        (int32 [n], optional) the mask of each instance, in stream order on ``stream`` (a torch stream; None:
+        torch.cuda.current_stream())."""
+        import torch
+        if not isinstance(steps, torch.Tensor) or steps.dim() != 3 or steps.shape[1] < 1 or steps.shape[2] * steps.element_size() != ROOT_STEP.itemsize:
+            raise MtrError(MTR_E_INVALID, "events steps: a tensor [n, S, 16 bytes] on the GPU")
+        n, S = steps.shape[0], steps.shape[1]
+        _play_tensor(steps, self.dev, "events steps", ROOT_STEP.itemsize, 16, n * S)
+        used = [steps]
+        cap = 0
+        if out is not None:
+            cap = _play_tensor(out, self.dev, "events list", EVENT.itemsize, 16, None)
+            used.append(out)
+        if getattr(count, "dtype", None) != torch.int32:
+            raise MtrError(MTR_E_INVALID, "events count: an int32 tensor [2] on the GPU")
+        _play_tensor(count, self.dev, "events count", 4, 4, 2)
+        used.append(count)
+        if bits is not None:
+            if getattr(bits, "dtype", None) != torch.int32:
+                raise MtrError(MTR_E_INVALID, "events bits: an int32 tensor [n] on the GPU")
+            _play_tensor(bits, self.dev, "events bits", 4, 4, n)
+            used.append(bits)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        cur = stream if stream is not None else torch.cuda.current_stream(steps.device)
+        _on_stream(self.dev, cur, lib.mtr_anim_events_collect_device, (self._h, ptr(steps), S, n, float(min_weight), ptr(out), cap, ptr(count), ptr(bits)), used)
+
+    def collect_host(self, steps: np.ndarray, min_weight: float, capacity: int, out: Optional[np.ndarray] = None, bits: Optional[np.ndarray] = None,
+                     want_bits: bool = True):
+        """the test and debug hook: ROOT_STEP [n, S] in host memory through the same kernels; waits.  Returns (EVENT [capacity],
+        uint32 [2], uint32 [n] or None); ``out`` and ``bits`` are what the list and the masks hold going in."""
+        sp = np.ascontiguousarray(np.asarray(steps))
+        if sp.dtype != ROOT_STEP or sp.ndim != 2 or sp.shape[1] < 1:
+            raise MtrError(MTR_E_INVALID, "events steps: an array [n, S] of dtype ROOT_STEP")
+        n, S = sp.shape
+        ol = np.zeros(capacity, dtype=EVENT) if out is None else np.ascontiguousarray(np.asarray(out)).copy()
+        if ol.dtype != EVENT or ol.shape != (capacity,):
+            raise MtrError(MTR_E_INVALID, "events list: EVENT [capacity]")
+        bt = None
+        if want_bits:
+            bt = np.zeros(n, dtype=np.uint32) if bits is None else np.ascontiguousarray(np.asarray(bits, dtype=np.uint32)).copy()
+            if bt.shape != (n,):
+                raise MtrError(MTR_E_INVALID, "events bits: uint32 [n]")
+        ct = np.zeros(2, dtype=np.uint32)
+        self.dev.check(lib.mtr_anim_events_collect_host(self._h, _p(sp), S, n, float(min_weight), _p(ol) if capacity else None, capacity, _p(ct), _p(bt)))
+        return ol, ct, bt
+
+    def close(self):
+        if self._h:
+            lib.mtr_anim_events_destroy(self._h)
             self._h = None
 
 

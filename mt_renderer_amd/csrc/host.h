@@ -388,6 +388,15 @@ struct mtr_anim_ctrl : mtr_host::DeviceSet {
     uint32_t nclips = 0, nnodes = 0, ntrans = 0, nany = 0, nparams = 0;
 };
 
+// An event set (SPEC.md section 22).  d: nclips table entries of 4 words (period, flags, 0, key count), then nclips ranges of
+// 2 words (first marker, marker count), then the markers of 2 words, each part padded to a multiple of 16 bytes, all
+// immutable; then the scratch array of ceil(max_instances / 256) block sums.  Its kernels WRITE the scratch, so `last`
+// orders the calls on one set among themselves, as a player's.
+struct mtr_anim_events : mtr_host::DeviceSet {
+    uint32_t nclips = 0, max_instances = 0, nmarkers = 0, max_count = 0;
+    size_t w_ranges = 0, w_markers = 0;  // words of the padded range and marker parts
+};
+
 namespace mtr_host {
 
 struct BatchDeleter {

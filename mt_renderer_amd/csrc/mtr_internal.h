@@ -604,3 +604,23 @@ struct CtrlParams {
     float dt;
 };
 void mtr_launch_ctrl(const CtrlParams& p, hipStream_t s);
+// animation events (k_events.hip, SPEC.md section 22): the markers that the nsteps steps of each of n instances arrive at or
+// pass, compacted in (instance, step, firing order) into out; count[0] = how many fired, count[1] = how many were written
+#define MTR_EVENTS_BLOCK 256u   // instances per workgroup of the count and fill passes: one word of sums each
+#define MTR_EVENTS_SCAN 1024u   // width of the one workgroup that scans the sums
+struct EventParams {
+    const uint32_t* clips;      // nclips x 4 words (PlayClip: period (f32 bits), flags, 0, key count); 16-byte aligned
+    const uint32_t* ranges;     // nclips x 2 words: first marker, marker count; validated at creation; 8-byte aligned
+    const uint32_t* markers;    // (total markers) x 2 words (mtr_event_marker), sorted per clip; 8-byte aligned
+    uint32_t* sums;             // ceil(n / MTR_EVENTS_BLOCK) words of the set's scratch
+    const uint32_t* steps;      // n x nsteps x 4 words (mtr_root_step); 16-byte aligned
+    uint32_t* out;              // capacity x 4 words (mtr_anim_event), 16-byte aligned; nullptr when capacity == 0
+    uint32_t* count;            // 2 words
+    uint32_t* bits;             // n words, or nullptr
+    uint32_t nclips;            // >= 1
+    uint32_t nsteps;            // 1..8, a validated host value
+    uint32_t n;
+    uint32_t capacity;
+    float min_weight;
+};
+void mtr_launch_events(const EventParams& p, hipStream_t s);

@@ -70,7 +70,7 @@ pub const MTR_OWN_SUPERTILES: u32 = 2;
 pub const MTR_TEXRES_DECODED: u32 = 0;
 pub const MTR_TEXRES_BLOCKS: u32 = 1;
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player, mtr_anim_ctrl);
+opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player, mtr_anim_ctrl, mtr_anim_events);
 
 /// animation clips (mtr.h, SPEC.md section 14): one key of one joint, 48 bytes
 pub const MTR_CLIP_LOOP: u32 = 1;
@@ -224,6 +224,22 @@ pub struct mtr_ctrl_state {
     pub t: f32,
     pub fired: u32,
     pub user: u32,
+}
+// animation events (SPEC.md section 22)
+pub const MTR_EVENT_BACKWARD: u32 = 0x8000_0000;
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_event_marker {
+    pub x: f32,
+    pub id: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_anim_event {
+    pub instance: u32,
+    pub id: u32,
+    pub where_: u32,
+    pub w: f32,
 }
 /// what one instance plays: clip A at x_a cross-faded by w with clip B at x_b, positions in keys; 24 bytes
 #[repr(C)]
@@ -388,5 +404,14 @@ extern "C" {
                                      dt: f32, cmds_out_dev: *mut mtr_play_cmd, counts_dev: *mut u32, hip_stream: *mut c_void) -> i32;
     pub fn mtr_anim_ctrl_step_host(ctrl: *mut mtr_anim_ctrl, states: *mut mtr_ctrl_state, play: *const mtr_play_state, params: *mut f32, n: usize, dt: f32,
                                    cmds_out: *mut mtr_play_cmd, counts: *mut u32) -> i32;
+    // animation events (SPEC.md section 22): declarations only
+    pub fn mtr_anim_events_create(dev: *mut mtr_device, nclips: usize, nkeys: *const u32, clip_flags: *const u32, counts: *const u32,
+                                  markers: *const mtr_event_marker, max_instances: usize, out: *mut *mut mtr_anim_events) -> i32;
+    pub fn mtr_anim_events_destroy(ev: *mut mtr_anim_events);
+    pub fn mtr_anim_events_collect_device(ev: *mut mtr_anim_events, steps_dev: *const mtr_root_step, nsteps: usize, n: usize, min_weight: f32,
+                                          out_dev: *mut mtr_anim_event, capacity: usize, count_dev: *mut u32, bits_dev: *mut u32,
+                                          hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_events_collect_host(ev: *mut mtr_anim_events, steps: *const mtr_root_step, nsteps: usize, n: usize, min_weight: f32,
+                                        out: *mut mtr_anim_event, capacity: usize, count: *mut u32, bits: *mut u32) -> i32;
 }
 pub mod files;
