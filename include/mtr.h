@@ -604,6 +604,62 @@ int32_t mtr_anim_events_collect_device(mtr_anim_events *ev, const mtr_root_step 
 int32_t mtr_anim_events_collect_host(mtr_anim_events *ev, const mtr_root_step *steps, size_t nsteps, size_t n, float min_weight,
                                      mtr_anim_event *out, size_t capacity, uint32_t *count, uint32_t *bits);
 
+/* ---- blend spaces (build extension, SPEC.md section 23): parameters mix phase-locked clips (k_blend) ----
+ * Plays a character AT a speed or IN a direction: sample points in a 1-D or 2-D parameter space each carry a LOOP clip, and
+ * one call per frame turns one or two floats per instance into the layers and steps the animate, root-motion and event calls
+ * take.  A blend set holds the clips (nkeys, clip_flags, rates as mtr_anim_player_create takes them; it is not tied to a
+ * player or an mtr_anim), K = 1..32 samples {clip, px, py} and T = 0..64 triangles of sample indices.  T == 0 is a 1-D space
+ * over px (strictly increasing); T >= 1 a 2-D space whose triangles are counter-clockwise: the doubled area
+ * (x1-x0)*(y2-y0) - (x2-x0)*(y1-y0), in binary32 in that order, is finite and > 0 (mt_renderer_amd/anim_blend.py triangulates
+ * a point set).  param_x / param_y name the floats of an instance's row params[inst * nparams + p] (a controller's rows),
+ * damp is the smoothing rate in 1/seconds (+inf: none).
+ * The state is mtr_blend_state {phase, px, py, speed}, 16 bytes in device memory; speed is never written, and every bit
+ * pattern has a defined outcome.  Per instance and call:
+ *   smooth : a = clamp(max(dt, 0) * damp); px' = px + a * (target - px), or the target itself when a == 1 or the stored px
+ *            is not finite (so a NaN parameter heals); py likewise in 2-D.
+ *   slots  : three sample indices and two sequential weights e1, e2 (e0 = +0).  1-D: at or below the first sample
+ *            (0, 0, 0), at or above the last (K-1, K-1, K-1), else (j, j+1, j) with e1 = (p - px[j]) / (px[j+1] - px[j]).
+ *            2-D: the first triangle in array order whose barycentric l0, l1, l2 are all >= 0: (v0, v1, v2), e2 = l2,
+ *            e1 = l1 / (1 - l2); where none holds the point (outside the hull, a rounding crack, a NaN) the closest point on
+ *            any edge (a, b): (a, b, a), e1 = t.  The shares E0 = (1-e1)(1-e2), E1 = e1(1-e2), E2 = e2 are the barycentric
+ *            weights and what section 22 calls E_i.
+ *   phase  : one phase in [0, 1) for all three clips, advanced by dt * speed * f, f the rates over the periods blended with
+ *            e1, e2, and wrapped; a stored phase outside [0, 1) counts as 0.
+ *   out    : layer i = {clip_i, phase' * P_i, e_i, mask 0, OVERRIDE} for i = 0..2 of nlayers (3..8) per instance, layers 3..
+ *            untouched; step i = {clip_i, phase * P_i, dphase * P_i, e_i} (three per instance: nsteps = 3 for
+ *            mtr_batch_root_motion_device and mtr_anim_events_collect_device); optionally the three shares.
+ * Steps of consecutive frames abut only to within a unit in the last place of the position (SPEC.md section 23).
+ * The call runs in stream order on hip_stream under the rules of mtr_batch_set_poses_device;
+ * mtr_anim_blend_destroy may follow a call directly (no host wait).
+ * MTR_E_INVALID, nothing created (mtr_last_error names the clip, the sample or the triangle): a NULL device, out, nkeys, rates
+ * or samples pointer, nclips == 0 or > 2^24, nkeys outside 1..2^24, clip flag bits other than MTR_CLIP_LOOP, a rate that is not
+ * finite, nsamples outside 1..32, ntris > 64 or NULL tris with ntris > 0, nparams outside 1..16, param_x >= nparams (2-D:
+ * or param_y), damp not above 0 (NaN included), max_instances outside 1..2^27; a sample whose clip is >= nclips or not LOOP or
+ * whose px (2-D: or py) is not finite; in 1-D a px that does not lie above the one before it by a finite step; a triangle
+ * with an index >= nsamples, with two equal indices, or whose doubled area is not finite and > 0.
+ * MTR_E_INVALID, nothing changed, at a call: a NULL handle, states or params pointer, n == 0 or n > max_instances, nlayers
+ * outside 3..8 with layers given, a misaligned device pointer (16 bytes: states, layers, steps; 4: params, shares).
+ * MTR_E_UNSUPPORTED: a library built without k_blend. */
+typedef struct mtr_anim_blend mtr_anim_blend;
+typedef struct mtr_blend_sample { uint32_t clip; float px, py; uint32_t pad; } mtr_blend_sample;     /* 16 bytes */
+typedef struct mtr_blend_tri { uint32_t v[3]; uint32_t pad; } mtr_blend_tri;                        /* 16 bytes */
+typedef struct mtr_blend_state { float phase, px, py, speed; } mtr_blend_state;                     /* 16 bytes */
+int32_t mtr_anim_blend_create(mtr_device *dev, size_t nclips, const uint32_t *nkeys /* nclips */,
+                              const uint32_t *clip_flags /* nclips */, const float *rates /* nclips */,
+                              const mtr_blend_sample *samples, size_t nsamples, const mtr_blend_tri *tris /* NULL: 1-D */,
+                              size_t ntris, size_t nparams, uint32_t param_x, uint32_t param_y, float damp,
+                              size_t max_instances, mtr_anim_blend **out);
+void    mtr_anim_blend_destroy(mtr_anim_blend *blend);       /* parked like mtr_anim_destroy */
+int32_t mtr_anim_blend_advance_device(mtr_anim_blend *blend, mtr_blend_state *states_dev /* n, 16-byte aligned */,
+                                      const float *params_dev /* n*nparams, read only */, size_t n, float dt,
+                                      mtr_anim_layer *out_layers_dev /* n*nlayers, 16-byte aligned, or NULL */, size_t nlayers,
+                                      mtr_root_step *out_steps_dev /* n*3, 16-byte aligned, or NULL */,
+                                      float *out_shares_dev /* n*3, or NULL */, void *hip_stream);
+/* a test and debug hook: everything in host memory (any alignment), the same kernel, waits; the layers are read first so
+ * that layers 3.. come back as they went in */
+int32_t mtr_anim_blend_advance_host(mtr_anim_blend *blend, mtr_blend_state *states, const float *params, size_t n, float dt,
+                                    mtr_anim_layer *out_layers, size_t nlayers, mtr_root_step *out_steps, float *out_shares);
+
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],
                         float clear_depth, mtr_frame **out);

@@ -281,6 +281,37 @@ class AnimEvents {
     mtr_anim_events* h_ = nullptr;
 };
 
+// A blend set (include/mtr.h, SPEC.md section 23): samples in a 1-D (ntris == 0) or 2-D parameter space, each with a LOOP
+// clip; nkeys, clip_flags and rates are what a player is created with
+class AnimBlend {
+  public:
+    AnimBlend(const Device& dev, size_t nclips, const uint32_t* nkeys, const uint32_t* clip_flags, const float* rates, const mtr_blend_sample* samples,
+              size_t nsamples, const mtr_blend_tri* tris, size_t ntris, size_t nparams, uint32_t param_x, uint32_t param_y, float damp, size_t max_instances)
+        : dev_(dev) {
+        dev.check(mtr_anim_blend_create(dev.handle(), nclips, nkeys, clip_flags, rates, samples, nsamples, tris, ntris, nparams, param_x, param_y, damp,
+                                        max_instances, &h_));
+    }
+    AnimBlend(AnimBlend&& o) noexcept : dev_(o.dev_), h_(std::exchange(o.h_, nullptr)) {}
+    AnimBlend(const AnimBlend&) = delete;
+    ~AnimBlend() { mtr_anim_blend_destroy(h_); }
+    // n blend states advanced by dt against their parameter rows, in stream order: layers 0..2 of nlayers per instance, three
+    // steps and three shares per instance, each optional
+    void advance(mtr_blend_state* states_dev, const float* params_dev, size_t n, float dt, mtr_anim_layer* out_layers_dev, size_t nlayers,
+                 mtr_root_step* out_steps_dev, float* out_shares_dev = nullptr, void* hip_stream = nullptr) const {
+        dev_.check(mtr_anim_blend_advance_device(h_, states_dev, params_dev, n, dt, out_layers_dev, nlayers, out_steps_dev, out_shares_dev, hip_stream));
+    }
+    // the test and debug hook: everything in host memory, waits
+    void advance_host(mtr_blend_state* states, const float* params, size_t n, float dt, mtr_anim_layer* out_layers, size_t nlayers, mtr_root_step* out_steps,
+                      float* out_shares = nullptr) const {
+        dev_.check(mtr_anim_blend_advance_host(h_, states, params, n, dt, out_layers, nlayers, out_steps, out_shares));
+    }
+    mtr_anim_blend* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    mtr_anim_blend* h_ = nullptr;
+};
+
 class Model {
   public:
     // Model::new(model_file, material_file, shader2, resource_manager, device, queue, ..) -- src/model.rs:36-45

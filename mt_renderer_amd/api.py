@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "mtr_anim_player_advance_host",
     "mtr_anim_ctrl_create", "mtr_anim_ctrl_destroy", "mtr_anim_ctrl_step_device", "mtr_anim_ctrl_step_host",
     "mtr_anim_events_create", "mtr_anim_events_destroy", "mtr_anim_events_collect_device", "mtr_anim_events_collect_host",
+    "mtr_anim_blend_create", "mtr_anim_blend_destroy", "mtr_anim_blend_advance_device", "mtr_anim_blend_advance_host",
 ]
 
 CLIP_LOOP = 1
@@ -104,6 +105,11 @@ CTRL_NONE = 0xFFFFFFFF
 EVENT_MARKER = np.dtype([("x", "<f4"), ("id", "<u4")])
 EVENT = np.dtype([("instance", "<u4"), ("id", "<u4"), ("where", "<u4"), ("w", "<f4")])
 EVENT_BACKWARD = 0x80000000
+# mtr_blend_sample, mtr_blend_tri, mtr_blend_state (SPEC.md section 23): a sample point with its clip, a triangle of sample
+# indices, and what one instance of a blend space keeps on the GPU
+BLEND_SAMPLE = np.dtype([("clip", "<u4"), ("px", "<f4"), ("py", "<f4"), ("pad", "<u4")])
+BLEND_TRI = np.dtype([("v", "<u4", (3,)), ("pad", "<u4")])
+BLEND_STATE = np.dtype([("phase", "<f4"), ("px", "<f4"), ("py", "<f4"), ("speed", "<f4")])
 
 
 class MtrError(RuntimeError):
@@ -268,6 +274,10 @@ def _load() -> C.CDLL:
         "mtr_anim_events_destroy": (None, [vp]),
         "mtr_anim_events_collect_device": (i32, [vp, vp, sz, sz, C.c_float, vp, sz, vp, vp, vp]),
         "mtr_anim_events_collect_host": (i32, [vp, vp, sz, sz, C.c_float, vp, sz, vp, vp]),
+        "mtr_anim_blend_create": (i32, [vp, sz, vp, vp, vp, vp, sz, vp, sz, sz, C.c_uint32, C.c_uint32, C.c_float, sz, vp]),
+        "mtr_anim_blend_destroy": (None, [vp]),
+        "mtr_anim_blend_advance_device": (i32, [vp, vp, vp, sz, C.c_float, vp, sz, vp, vp, vp]),
+        "mtr_anim_blend_advance_host": (i32, [vp, vp, vp, sz, C.c_float, vp, sz, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -959,6 +969,87 @@ class AnimEvents:
     def close(self):
         if self._h:
             lib.mtr_anim_events_destroy(self._h)
+            self._h = None
+
+
+class AnimBlend:
+    """A blend set (include/mtr.h, SPEC.md section 23): sample points in a 1-D or 2-D parameter space that each carry a LOOP
+    clip.  ``nkeys``, ``rates`` and ``clip_flags`` are what an AnimPlayer takes; ``samples`` a BLEND_SAMPLE array, ``tris`` a
+    BLEND_TRI array or None for a 1-D space (``anim_blend.build_1d`` / ``build_2d`` make them from points); ``param_x`` and
+    ``param_y`` name the floats of an instance's row of ``nparams`` parameters, ``damp`` is the smoothing rate in 1/seconds
+    (inf: none), for calls of up to ``max_instances`` instances."""
+
+    def __init__(self, dev: Device, nkeys, rates, clip_flags, samples, tris=None, nparams: int = 1, param_x: int = 0, param_y: int = 0,
+                 damp: float = float("inf"), max_instances: int = 1):
+        nk = np.ascontiguousarray(np.asarray(nkeys, dtype=np.uint32).reshape(-1))
+        rt = np.ascontiguousarray(np.asarray(rates, dtype=np.float32).reshape(-1))
+        fl = None if clip_flags is None else np.ascontiguousarray(np.asarray(clip_flags, dtype=np.uint32).reshape(-1))
+        sm = np.asarray(samples)
+        tr = np.zeros(0, dtype=BLEND_TRI) if tris is None else np.asarray(tris)
+        if rt.size != nk.size or (fl is not None and fl.size != nk.size) or sm.dtype != BLEND_SAMPLE or sm.ndim != 1 or tr.dtype != BLEND_TRI or tr.ndim != 1:
+            raise MtrError(MTR_E_INVALID, "anim blend: one key count, rate and flag word per clip, samples of dtype BLEND_SAMPLE [K], triangles of dtype BLEND_TRI [T]")
+        if not (0 <= param_x < 1 << 32 and 0 <= param_y < 1 << 32):
+            raise MtrError(MTR_E_INVALID, "anim blend: param_x and param_y are parameter indices")
+        sm, tr = np.ascontiguousarray(sm), np.ascontiguousarray(tr)
+        h = C.c_void_p()
+        dev.check(lib.mtr_anim_blend_create(dev._h, nk.size, _p(nk), _p(fl), _p(rt), _p(sm) if sm.size else None, sm.size, _p(tr) if tr.size else None, tr.size,
+                                            nparams, param_x, param_y, float(damp), max_instances, C.byref(h)))
+        self.dev, self._h, self.nclips, self.nsamples, self.ntris, self.nparams, self.max_instances = dev, h, nk.size, sm.size, tr.size, nparams, max_instances
+
+    def advance(self, states, params, dt: float, out_layers=None, out_steps=None, out_shares=None, stream=None):
+        """advances the n BLEND_STATE records of ``states`` (a torch uint8 [n, 16] / int32 / float32 [n, 4] tensor on the GPU,
+        16-byte aligned) by ``dt`` seconds IN PLACE against the rows of ``params`` (float32 [n, nparams], read only) and writes,
+        where given, layers 0 to 2 of the ANIM_LAYER stacks of ``out_layers`` ([n, L, 16] bytes, L from its size), three
+        ROOT_STEP records per instance into ``out_steps`` ([n, 3, 16] bytes) and the three shares into ``out_shares`` (float32
+        [n, 3]), in stream order on ``stream`` (a torch stream; None: torch.cuda.current_stream())."""
+        import torch
+        n = _play_tensor(states, self.dev, "blend states", BLEND_STATE.itemsize, 16, None)
+        if getattr(params, "dtype", None) != torch.float32:
+            raise MtrError(MTR_E_INVALID, "blend params: a float32 tensor [n, nparams] on the GPU")
+        _play_tensor(params, self.dev, "blend params", 4, 4, n * self.nparams)
+        used = [states, params]
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        nl = 0
+        if out_layers is not None:
+            nl = _play_tensor(out_layers, self.dev, "blend out_layers", ANIM_LAYER.itemsize, 16, None)
+            if nl % n:
+                raise MtrError(MTR_E_INVALID, "blend out_layers: n x L layers of 16 bytes")
+            nl //= n
+            used.append(out_layers)
+        if out_steps is not None:
+            _play_tensor(out_steps, self.dev, "blend out_steps", ROOT_STEP.itemsize, 16, 3 * n)
+            used.append(out_steps)
+        if out_shares is not None:
+            if getattr(out_shares, "dtype", None) != torch.float32:
+                raise MtrError(MTR_E_INVALID, "blend out_shares: a float32 tensor [n, 3] on the GPU")
+            _play_tensor(out_shares, self.dev, "blend out_shares", 4, 4, 3 * n)
+            used.append(out_shares)
+        cur = stream if stream is not None else torch.cuda.current_stream(states.device)
+        _on_stream(self.dev, cur, lib.mtr_anim_blend_advance_device, (self._h, ptr(states), ptr(params), n, float(dt), ptr(out_layers), nl, ptr(out_steps), ptr(out_shares)), used)
+
+    def advance_host(self, states: np.ndarray, params: np.ndarray, dt: float, nlayers: int = 0, layers: Optional[np.ndarray] = None, want_steps: bool = True,
+                     want_shares: bool = True):
+        """the test and debug hook: BLEND_STATE records [n] and float32 rows [n, nparams] in host memory through the same kernel;
+        waits.  Returns (states, out_layers or None, out_steps or None, out_shares or None); ``layers`` ([n, nlayers]
+        ANIM_LAYER) is what layers 3.. hold going in."""
+        st = np.ascontiguousarray(np.asarray(states)).copy()
+        if st.dtype != BLEND_STATE or st.ndim != 1:
+            raise MtrError(MTR_E_INVALID, "blend states: an array [n] of dtype BLEND_STATE")
+        n = st.size
+        pr = np.ascontiguousarray(np.asarray(params, dtype=np.float32))
+        if pr.shape != (n, self.nparams):
+            raise MtrError(MTR_E_INVALID, "blend params: float32 [n, nparams]")
+        ol = None
+        if nlayers:
+            ol = np.zeros((n, nlayers), dtype=ANIM_LAYER) if layers is None else np.ascontiguousarray(layers).copy().reshape(n, nlayers)
+        os_ = np.zeros((n, 3), dtype=ROOT_STEP) if want_steps else None
+        sh = np.zeros((n, 3), dtype=np.float32) if want_shares else None
+        self.dev.check(lib.mtr_anim_blend_advance_host(self._h, _p(st), _p(pr), n, float(dt), _p(ol), nlayers, _p(os_), _p(sh)))
+        return st, ol, os_, sh
+
+    def close(self):
+        if self._h:
+            lib.mtr_anim_blend_destroy(self._h)
             self._h = None
 
 

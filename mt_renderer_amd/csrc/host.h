@@ -397,6 +397,13 @@ struct mtr_anim_events : mtr_host::DeviceSet {
     size_t w_ranges = 0, w_markers = 0;  // words of the padded range and marker parts
 };
 
+// A blend set (SPEC.md section 23): immutable once uploaded and only read by its kernel.  d: nclips table entries of 4 words
+// (period, flags, rate, key count), then nsamples samples of 4 words, then ntris triangles of 4 words.
+struct mtr_anim_blend : mtr_host::DeviceSet {
+    uint32_t nclips = 0, nsamples = 0, ntris = 0, nparams = 0, param_x = 0, param_y = 0, max_instances = 0;
+    float damp = 0.0f;
+};
+
 namespace mtr_host {
 
 struct BatchDeleter {

@@ -624,3 +624,25 @@ struct EventParams {
     float min_weight;
 };
 void mtr_launch_events(const EventParams& p, hipStream_t s);
+// blend spaces (k_blend.hip, SPEC.md section 23): n blend states advanced by dt in place against their parameter rows, and
+// layers 0..2, three steps and three shares written per instance
+struct BlendParams {
+    const uint32_t* clips;      // nclips x 4 words (PlayClip: period (f32 bits), flags, rate (f32 bits), key count); 16-byte aligned
+    const uint32_t* samples;    // nsamples x 4 words (mtr_blend_sample), validated at creation; 16-byte aligned
+    const uint32_t* tris;       // ntris x 4 words (mtr_blend_tri), validated at creation; 16-byte aligned
+    uint32_t* states;           // n x 4 words (mtr_blend_state); 16-byte aligned
+    const float* params;        // n x nparams floats, read only
+    uint32_t* out_layers;       // n x nlayers x 4 words (mtr_anim_layer; layers 0..2 written), 16-byte aligned, or nullptr
+    uint32_t* out_steps;        // n x 3 x 4 words (mtr_root_step), 16-byte aligned, or nullptr
+    float* out_shares;          // n x 3 floats, or nullptr
+    uint32_t nclips;            // >= 1
+    uint32_t nsamples;          // 1..32
+    uint32_t ntris;             // 0 (a 1-D space) .. 64
+    uint32_t nparams;           // 1..16
+    uint32_t param_x, param_y;  // < nparams
+    uint32_t nlayers;           // 3..8 with out_layers, a validated host value
+    uint32_t n;
+    float damp;
+    float dt;
+};
+void mtr_launch_blend(const BlendParams& p, hipStream_t s);

@@ -70,7 +70,7 @@ pub const MTR_OWN_SUPERTILES: u32 = 2;
 pub const MTR_TEXRES_DECODED: u32 = 0;
 pub const MTR_TEXRES_BLOCKS: u32 = 1;
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player, mtr_anim_ctrl, mtr_anim_events);
+opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player, mtr_anim_ctrl, mtr_anim_events, mtr_anim_blend);
 
 /// animation clips (mtr.h, SPEC.md section 14): one key of one joint, 48 bytes
 pub const MTR_CLIP_LOOP: u32 = 1;
@@ -240,6 +240,29 @@ pub struct mtr_anim_event {
     pub id: u32,
     pub where_: u32,
     pub w: f32,
+}
+// blend spaces (SPEC.md section 23)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_blend_sample {
+    pub clip: u32,
+    pub px: f32,
+    pub py: f32,
+    pub pad: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_blend_tri {
+    pub v: [u32; 3],
+    pub pad: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_blend_state {
+    pub phase: f32,
+    pub px: f32,
+    pub py: f32,
+    pub speed: f32,
 }
 /// what one instance plays: clip A at x_a cross-faded by w with clip B at x_b, positions in keys; 24 bytes
 #[repr(C)]
@@ -413,5 +436,15 @@ extern "C" {
                                           hip_stream: *mut c_void) -> i32;
     pub fn mtr_anim_events_collect_host(ev: *mut mtr_anim_events, steps: *const mtr_root_step, nsteps: usize, n: usize, min_weight: f32,
                                         out: *mut mtr_anim_event, capacity: usize, count: *mut u32, bits: *mut u32) -> i32;
+    // blend spaces (SPEC.md section 23): declarations only
+    pub fn mtr_anim_blend_create(dev: *mut mtr_device, nclips: usize, nkeys: *const u32, clip_flags: *const u32, rates: *const f32,
+                                 samples: *const mtr_blend_sample, nsamples: usize, tris: *const mtr_blend_tri, ntris: usize, nparams: usize,
+                                 param_x: u32, param_y: u32, damp: f32, max_instances: usize, out: *mut *mut mtr_anim_blend) -> i32;
+    pub fn mtr_anim_blend_destroy(blend: *mut mtr_anim_blend);
+    pub fn mtr_anim_blend_advance_device(blend: *mut mtr_anim_blend, states_dev: *mut mtr_blend_state, params_dev: *const f32, n: usize, dt: f32,
+                                         out_layers_dev: *mut mtr_anim_layer, nlayers: usize, out_steps_dev: *mut mtr_root_step,
+                                         out_shares_dev: *mut f32, hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_blend_advance_host(blend: *mut mtr_anim_blend, states: *mut mtr_blend_state, params: *const f32, n: usize, dt: f32,
+                                       out_layers: *mut mtr_anim_layer, nlayers: usize, out_steps: *mut mtr_root_step, out_shares: *mut f32) -> i32;
 }
 pub mod files;
