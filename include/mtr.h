@@ -660,6 +660,58 @@ int32_t mtr_anim_blend_advance_device(mtr_anim_blend *blend, mtr_blend_state *st
 int32_t mtr_anim_blend_advance_host(mtr_anim_blend *blend, mtr_blend_state *states, const float *params, size_t n, float dt,
                                     mtr_anim_layer *out_layers, size_t nlayers, mtr_root_step *out_steps, float *out_shares);
 
+/* ---- spring bones (SPEC.md section 24): joints that lag and sway behind the animated pose ----
+ * A spring set belongs to a skeleton, as an IK set does: it holds the skeleton's parents (the rules of
+ * mtr_model_set_skeleton) and 1..16 springs.  A spring aims its joint (mtr_ik_chain's AIM, weight 1, axis = tail) at a
+ * particle that the library simulates: tail is where the particle rests, in the joint's own space (usually the bind
+ * translation of the joint's child); stiffness (per second) pulls it there, drag in [0, 1] is the share of its velocity
+ * it loses per step, gravity is a displacement per second in the instance's model space (the space of the IK targets;
+ * exact for instances that stay upright).  flags must be 0.  The order of the list is the order of the state records and
+ * nothing else: a spring whose joint has spring ancestors sees what they changed, whatever the order.
+ *
+ * The particle of instance i and spring k lives in states[i * nsprings + k], caller-owned DEVICE memory that every call
+ * reads and writes.  cur and prev are its position at this and at the previous step, in the instance's model space.  Every
+ * bit pattern has a defined outcome; a ZEROED record means "not started" (live == 0, or a component that is not finite:
+ * the particle starts at rest, cur = prev = its rest position).  The user may write states directly.
+ *
+ * Each call is one simulation step of dt seconds between the IK chains (ik may be NULL: none) and the fold; a dt that is
+ * not positive and finite pauses the springs (the particle is carried, constrained and aimed at, not integrated).  motion:
+ * n x 16 floats, the rigid delta D every instance moved by this frame (M_new = M_old o D), exactly what
+ * mtr_anim_root_deltas_device writes: the particles are carried by its inverse, so that they stay where they were in the
+ * world.  NULL: the instances did not move, or moved in a way the springs should ignore (a teleport).  Only rotations
+ * change; like IK, the rule ignores scales above the joint.
+ *
+ * Frame semantics and ordering: mtr_batch_animate_ik_device's.  Calls on one spring set are ordered among themselves by
+ * the set's event, whatever their streams.  No host-memory batch call and no mtr_model_* call: a single character is a
+ * batch of one.
+ *
+ * Errors: MTR_E_INVALID, and nothing changes (no kernel runs, the states stay as they were), for everything the IK call
+ * rejects, a NULL spring set, one of another device or joint count or whose parents differ from the model's skeleton
+ * (mtr_last_error names the joint), NULL or misaligned states, misaligned motion, targets without an IK set or an IK set
+ * without targets; at mtr_anim_spring_create (mtr_last_error names the spring): njoints outside 1..256, invalid parents,
+ * nsprings outside 1..MTR_ANIM_MAX_SPRINGS, a joint >= njoints, a joint named twice, flag bits, a tail that is not finite
+ * or all zero, a stiffness that is not finite or < 0, a drag outside [0, 1] (NaN included), a gravity that is not finite.
+ * MTR_E_UNSUPPORTED when the library was built without the spring kernels. */
+#define MTR_ANIM_MAX_SPRINGS 16
+typedef struct mtr_anim_spring mtr_anim_spring;
+typedef struct mtr_spring { uint32_t joint, flags; float stiffness, drag; float tail[3], pad0; float gravity[3], pad1; } mtr_spring; /* 48 bytes */
+typedef struct mtr_spring_state { float cur[3]; uint32_t live; float prev[3]; uint32_t pad; } mtr_spring_state;                 /* 32 bytes */
+int32_t mtr_anim_spring_create(mtr_device *dev, size_t njoints, const uint8_t *parents, size_t nsprings,
+                               const mtr_spring *springs, mtr_anim_spring **out);
+/* may follow an animate call directly: parked like mtr_anim_destroy */
+void    mtr_anim_spring_destroy(mtr_anim_spring *spring);
+int32_t mtr_batch_animate_spring_device(mtr_batch *batch, mtr_anim *anim, mtr_anim_masks *masks /* or NULL */,
+                                        const mtr_anim_layer *layers_dev /* 16-byte aligned */, size_t nlayers,
+                                        mtr_anim_ik *ik /* or NULL */, const mtr_ik_target *targets_dev /* NULL iff ik is NULL */,
+                                        mtr_anim_spring *spring, mtr_spring_state *states_dev /* n*nsprings, in and out, 16-byte aligned */,
+                                        const float *motion_dev /* n*16 or NULL, 16-byte aligned */, float dt, void *hip_stream);
+/* a test and debug hook: everything in host memory (any alignment), the same kernels, waits; the states are read and
+ * written back; the local matrices of n instances as mtr_anim_sample_ik gives them */
+int32_t mtr_anim_sample_spring(mtr_anim *anim, mtr_anim_masks *masks /* or NULL */, mtr_anim_ik *ik /* or NULL */,
+                               mtr_anim_spring *spring, const mtr_anim_layer *layers, size_t nlayers,
+                               const mtr_ik_target *targets /* or NULL */, mtr_spring_state *states, const float *motion /* or NULL */,
+                               float dt, size_t n, float *out_locals, size_t count);
+
 /* ---- frame = one render pass (src/bin/modelviewer.rs:190-210: clear colour / clear depth) ---- */
 int32_t mtr_frame_begin(mtr_device *dev, uint32_t width, uint32_t height, const float clear_rgba[4],
                         float clear_depth, mtr_frame **out);

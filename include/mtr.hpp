@@ -116,6 +116,14 @@ class Anim {
         dev_.check(mtr_anim_sample_layers(h_, masks, layers, nlayers, n, out.data(), out.size()));
         return out;
     }
+    // one step of the springs of a spring set after the chains of ik (or nullptr, then targets is nullptr too), everything
+    // in host memory (SPEC.md section 24): states (n * nsprings) are read and written back, motion is n * 16 floats or nullptr
+    std::vector<float> sample_spring(mtr_anim_masks* masks, mtr_anim_ik* ik, mtr_anim_spring* spring, const mtr_anim_layer* layers, size_t nlayers,
+                                     const mtr_ik_target* targets, mtr_spring_state* states, const float* motion, float dt, size_t n) const {
+        std::vector<float> out(n * njoints_ * 16);
+        dev_.check(mtr_anim_sample_spring(h_, masks, ik, spring, layers, nlayers, targets, states, motion, dt, n, out.data(), out.size()));
+        return out;
+    }
     // the same after the chains of an IK set, against n * nchains targets (SPEC.md section 17)
     std::vector<float> sample_ik(mtr_anim_masks* masks, mtr_anim_ik* ik, const mtr_anim_layer* layers, size_t nlayers, const mtr_ik_target* targets,
                                  size_t n) const {
@@ -312,6 +320,24 @@ class AnimBlend {
     mtr_anim_blend* h_ = nullptr;
 };
 
+// A spring set (include/mtr.h, SPEC.md section 24): the parents of a skeleton and 1..MTR_ANIM_MAX_SPRINGS springs over it
+class AnimSpring {
+  public:
+    AnimSpring(const Device& dev, size_t njoints, const uint8_t* parents, size_t nsprings, const mtr_spring* springs) : dev_(dev), nsprings_(nsprings) {
+        dev.check(mtr_anim_spring_create(dev.handle(), njoints, parents, nsprings, springs, &h_));
+    }
+    AnimSpring(AnimSpring&& o) noexcept : dev_(o.dev_), nsprings_(o.nsprings_), h_(std::exchange(o.h_, nullptr)) {}
+    AnimSpring(const AnimSpring&) = delete;
+    ~AnimSpring() { mtr_anim_spring_destroy(h_); }
+    size_t nsprings() const { return nsprings_; }
+    mtr_anim_spring* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    size_t nsprings_;
+    mtr_anim_spring* h_ = nullptr;
+};
+
 class Model {
   public:
     // Model::new(model_file, material_file, shader2, resource_manager, device, queue, ..) -- src/model.rs:36-45
@@ -404,6 +430,16 @@ class Batch {
     void animate_ik_device(const Anim& anim, const AnimMasks* masks, const mtr_anim_layer* layers_dev, size_t nlayers, const AnimIK& ik,
                            const mtr_ik_target* targets_dev, void* hip_stream = nullptr) {
         dev_.check(mtr_batch_animate_ik_device(h_, anim.handle(), masks ? masks->handle() : nullptr, layers_dev, nlayers, ik.handle(), targets_dev, hip_stream));
+        npal_ = anim.njoints();
+    }
+    // the same and then one step of dt seconds of the springs of `spring` (SPEC.md section 24): ik may be nullptr (then
+    // targets_dev is nullptr too); states_dev (n * nsprings records, device memory) is read and written in stream order;
+    // motion_dev is n * 16 floats (mtr_anim_root_deltas_device) or nullptr
+    void animate_spring_device(const Anim& anim, const AnimMasks* masks, const mtr_anim_layer* layers_dev, size_t nlayers, const AnimIK* ik,
+                               const mtr_ik_target* targets_dev, const AnimSpring& spring, mtr_spring_state* states_dev, const float* motion_dev, float dt,
+                               void* hip_stream = nullptr) {
+        dev_.check(mtr_batch_animate_spring_device(h_, anim.handle(), masks ? masks->handle() : nullptr, layers_dev, nlayers, ik ? ik->handle() : nullptr,
+                                                   targets_dev, spring.handle(), states_dev, motion_dev, dt, hip_stream));
         npal_ = anim.njoints();
     }
     // instance matrices from the joints of src's current version (SPEC.md section 18): one record per instance, host memory

@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "mtr_batch_animate_layers_device", "mtr_anim_sample_layers",
     "mtr_anim_ik_create", "mtr_anim_ik_destroy", "mtr_model_animate_ik", "mtr_batch_animate_ik", "mtr_batch_animate_ik_device",
     "mtr_anim_sample_ik",
+    "mtr_anim_spring_create", "mtr_anim_spring_destroy", "mtr_batch_animate_spring_device", "mtr_anim_sample_spring",
     "mtr_batch_attach", "mtr_batch_attach_device", "mtr_batch_sockets", "mtr_batch_sockets_device", "mtr_batch_read_model_mats",
     "mtr_anim_root_create", "mtr_anim_root_destroy", "mtr_batch_root_motion", "mtr_batch_root_motion_device", "mtr_anim_root_deltas",
     "mtr_anim_root_deltas_device",
@@ -75,6 +76,11 @@ LAYER_ADDITIVE = 1
 ANIM_IK_CHAIN = np.dtype([("kind", "<u4"), ("joint", "<u4", 3), ("axis", "<f4", 3), ("flags", "<u4")])
 ANIM_IK_TARGET = np.dtype([("pos", "<f4", 3), ("w", "<f4"), ("pole", "<f4", 3), ("pad", "<u4")])
 ANIM_MAX_IK = 4
+# mtr_spring / mtr_spring_state (SPEC.md section 24)
+SPRING = np.dtype([("joint", "<u4"), ("flags", "<u4"), ("stiffness", "<f4"), ("drag", "<f4"), ("tail", "<f4", 3), ("pad0", "<f4"),
+                   ("gravity", "<f4", 3), ("pad1", "<f4")])
+SPRING_STATE = np.dtype([("cur", "<f4", 3), ("live", "<u4"), ("prev", "<f4", 3), ("pad", "<u4")])
+ANIM_MAX_SPRINGS = 16
 IK_TWO_BONE = 0
 IK_AIM = 1
 IK_POLE = 1
@@ -250,6 +256,10 @@ def _load() -> C.CDLL:
         "mtr_batch_animate_ik": (i32, [vp, vp, vp, vp, sz, vp, vp]),
         "mtr_batch_animate_ik_device": (i32, [vp, vp, vp, vp, sz, vp, vp, vp]),
         "mtr_anim_sample_ik": (i32, [vp, vp, vp, vp, sz, vp, sz, vp, sz]),
+        "mtr_anim_spring_create": (i32, [vp, sz, vp, sz, vp, vp]),
+        "mtr_anim_spring_destroy": (None, [vp]),
+        "mtr_batch_animate_spring_device": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.c_float, vp]),
+        "mtr_anim_sample_spring": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp, C.c_float, sz, vp, sz]),
         "mtr_batch_attach": (i32, [vp, vp, vp]),
         "mtr_batch_attach_device": (i32, [vp, vp, vp, vp]),
         "mtr_batch_sockets": (i32, [vp, vp, sz, vp, sz]),
@@ -1082,6 +1092,34 @@ class AnimIK:
             self._h = None
 
 
+class AnimSpring:
+    """A spring set (include/mtr.h, SPEC.md section 24): the parents of a skeleton of ``njoints`` joints (a root: 255 or itself)
+    and 1 to 16 springs, a SPRING array or a list of dicts of its fields (joint and tail, optionally stiffness, drag and
+    gravity).  mt_renderer_amd.anim_spring.chain makes the records of a chain of joints."""
+
+    def __init__(self, dev: Device, parents, springs):
+        par = np.ascontiguousarray(np.asarray(parents, dtype=np.uint8).reshape(-1))
+        if isinstance(springs, np.ndarray):
+            if springs.dtype != SPRING:
+                raise MtrError(MTR_E_INVALID, "anim spring: springs of dtype SPRING or a list of dicts of its fields")
+            sp = np.ascontiguousarray(springs).reshape(-1)
+        else:
+            sp = np.zeros(len(springs), dtype=SPRING)
+            for k, c in enumerate(springs):
+                if set(c) - set(SPRING.names) or "joint" not in c or "tail" not in c:
+                    raise MtrError(MTR_E_INVALID, "anim spring: a spring has joint and tail, optionally stiffness, drag, gravity and flags")
+                for name, v in c.items():
+                    sp[name][k] = v
+        h = C.c_void_p()
+        dev.check(lib.mtr_anim_spring_create(dev._h, par.size, _p(par), sp.size, _p(sp) if sp.size else None, C.byref(h)))
+        self.dev, self._h, self.njoints, self.nsprings = dev, h, par.size, sp.size
+
+    def close(self):
+        if self._h:
+            lib.mtr_anim_spring_destroy(self._h)
+            self._h = None
+
+
 class AnimMasks:
     """A mask set for animation layers (include/mtr.h, SPEC.md section 16): weights [nmasks, njoints] in [0, 1], resident
     in HBM.  A layer's mask index 0 is the built-in mask of ones, index k >= 1 is weights[k - 1]."""
@@ -1152,6 +1190,22 @@ class Anim:
         self.dev.check(lib.mtr_anim_sample_ik(self._h, masks._h if masks is not None else None, ik._h, _p(ly), ly.shape[1], _p(tg), ly.shape[0],
                                               _p(out), out.size))
         return out
+
+    def sample_spring(self, layers, spring: "AnimSpring", states, dt: float, ik: Optional["AnimIK"] = None, targets=None, motion=None,
+                      masks: Optional[AnimMasks] = None):
+        """one step of the springs of ``spring`` (SPEC.md section 24) over the given layer stacks ([n, L]) after the chains of
+        ``ik`` (or None), everything in host memory: (the local matrices [n, njoints, 16], the new SPRING_STATE [n, nsprings]).
+        states: a SPRING_STATE array [n, nsprings], left as it is; motion: [n, 16] float32 or None"""
+        ly = anim_layers(layers)
+        n = ly.shape[0]
+        st = np.array(states, dtype=SPRING_STATE, copy=True).reshape(n, spring.nsprings)
+        tg = ik_targets(targets, n, ik.nchains) if ik is not None and targets is not None else None
+        mo = _f32(motion, (n, 16)) if motion is not None else None
+        out = np.zeros((n, self.njoints, 16), dtype=np.float32)
+        self.dev.check(lib.mtr_anim_sample_spring(self._h, masks._h if masks is not None else None, ik._h if ik is not None else None, spring._h,
+                                                  _p(ly), ly.shape[1], _p(tg) if tg is not None else None, _p(st), _p(mo) if mo is not None else None,
+                                                  float(dt), n, _p(out), out.size))
+        return out, st
 
     def close(self):
         if self._h:
@@ -1357,6 +1411,53 @@ class Batch:
         nl = _nbytes(tl) // (self.n * ANIM_LAYER.itemsize)
         _on_stream(self.dev, torch.cuda.current_stream(device), lib.mtr_batch_animate_ik_device,
                    (self._h, anim._h, mh, C.c_void_p(tl.data_ptr()), nl, ik._h, C.c_void_p(tt.data_ptr())), (tl, tt))
+        self.npal = anim.njoints
+
+    def animate_spring(self, anim: Anim, layers, spring: "AnimSpring", states, dt: float, ik: Optional[AnimIK] = None, targets=None, motion=None,
+                       masks: Optional[AnimMasks] = None, L: Optional[int] = None):
+        """one layer stack per instance, the chains of ``ik`` (or None) against ``targets``, then one step of ``dt`` seconds of
+        the springs of ``spring`` (k_anim_spring, SPEC.md section 24).  states: a torch uint8 / int32 / float32 tensor on the
+        batch's device holding n x nsprings SPRING_STATE records, contiguous and 16-byte aligned; it is read AND written in
+        stream order on torch.cuda.current_stream(), so no copy is made of it.  motion: None, or such a float32 tensor
+        [n, 16] as Anim.root_deltas_device gives.  layers and targets: numpy arrays or dicts (uploaded on that stream first)
+        or record tensors on the device."""
+        import torch
+        mh = masks._h if masks is not None else None
+        host = (np.ndarray, dict)
+        device = torch.device("cuda", self.dev.hip_device)
+        what = "animate_spring"
+
+        def on_device(t, name, make):
+            if isinstance(t, host):
+                raw = np.ascontiguousarray(make(t)).view(np.uint8).reshape(self.n, -1)
+                return torch.from_numpy(raw.copy()).to(device)
+            return _device_records(t, self.dev, what, f"{name} as a numpy array, a dict, or a uint8 / int32 / float32 tensor on the GPU", _U8_I32_F32)[0]
+        if (ik is None) != (targets is None):
+            raise MtrError(MTR_E_INVALID, f"{what}: targets go with an IK set, and an IK set with targets")
+        tl = on_device(layers, "layers", lambda a: anim_layers(a, self.n, L))
+        if not self._layer_stacks(tl, L):
+            raise MtrError(MTR_E_INVALID, f"{what}: n x L layers of 16 bytes")
+        keep = [tl]
+        tt = None
+        if ik is not None:
+            tt = on_device(targets, "targets", lambda a: ik_targets(a, self.n, ik.nchains))
+            if _nbytes(tt) != self.n * ik.nchains * ANIM_IK_TARGET.itemsize:
+                raise MtrError(MTR_E_INVALID, f"{what}: n x nchains targets of 32 bytes")
+            keep.append(tt)
+        # the states are written: the caller's own memory or nothing
+        st = _device_records(states, self.dev, what, "spring states as a uint8 / int32 / float32 tensor on the GPU", _U8_I32_F32,
+                             size_ok=lambda t: _nbytes(t) == self.n * spring.nsprings * SPRING_STATE.itemsize and t.is_contiguous() and t.data_ptr() % 16 == 0,
+                             size_msg="n x nsprings states of 32 bytes, contiguous and 16-byte aligned")[0]
+        keep.append(st)
+        mo = None
+        if motion is not None:
+            mo = _device_records(motion, self.dev, what, "motion as a float32 tensor on the GPU", ("float32",),
+                                 size_ok=lambda t: t.numel() == self.n * 16, size_msg="n x 16 floats")[0]
+            keep.append(mo)
+        nl = _nbytes(tl) // (self.n * ANIM_LAYER.itemsize)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        _on_stream(self.dev, torch.cuda.current_stream(device), lib.mtr_batch_animate_spring_device,
+                   (self._h, anim._h, mh, ptr(tl), nl, ik._h if ik is not None else None, ptr(tt), spring._h, ptr(st), ptr(mo), float(dt)), keep)
         self.npal = anim.njoints
 
     def attach(self, src: "Batch", recs, stream=None):

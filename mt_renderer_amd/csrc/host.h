@@ -365,6 +365,14 @@ struct mtr_anim_ik : mtr_host::DeviceSet {
     std::vector<uint8_t> parents;  // a root as 255
 };
 
+// A spring set (SPEC.md section 24): immutable once uploaded.  d: nsprings x 12 words of validated springs, the joint table
+// (njoints u32: the joint's spring | its round << 8, or MTR_SPRING_NONE), then the path table and the path bytes as in an IK
+// set.  Its kernels write the caller's states, not d; `last` orders the calls on one set among themselves all the same.
+struct mtr_anim_spring : mtr_host::DeviceSet {
+    uint32_t njoints = 0, nsprings = 0, nrounds = 0, path_bytes = 0;
+    std::vector<uint8_t> parents;  // a root as 255
+};
+
 // A root set (SPEC.md section 19): immutable once uploaded.  d: nclips flag words (MTR_ROOT_CYCLIC).
 struct mtr_anim_root : mtr_host::DeviceSet {
     uint32_t njoints = 0, nclips = 0, joint = 0;
@@ -571,9 +579,10 @@ int32_t round_trip(mtr_device* d, size_t words, F&& run) {
     return rc;
 }
 // One animate call: which sets it reads and where its records lie in device memory.  kind says which records: one state per
-// instance, nlayers layers per instance (masks optional), or such layers and then ik->nchains targets per instance.
+// instance, nlayers layers per instance (masks optional), such layers and then ik->nchains targets per instance, or such
+// layers, targets where there is an IK set (optional here) and spring->nsprings spring states per instance, read and written.
 struct AnimCall {
-    enum Kind { kStates, kLayers, kIk };
+    enum Kind { kStates, kLayers, kIk, kSpring };
     Kind kind = kStates;
     mtr_anim* anim = nullptr;
     mtr_anim_masks* masks = nullptr;
@@ -581,6 +590,10 @@ struct AnimCall {
     const void* recs = nullptr;     // the states or the layers
     size_t nlayers = 0;             // layers per instance of a layered call, as the caller gave it (anim_check: 1 to 8)
     const void* targets = nullptr;
+    mtr_anim_spring* spring = nullptr;
+    void* spring_states = nullptr;
+    const float* motion = nullptr;  // or nullptr
+    float dt = 0.0f;
 };
 // What every animate call checks of its sets, in one order: against the model's skeleton, or (m == nullptr) for a sample call,
 // which has none; no_room: the message of a sample call whose size test failed, reported where that test stands
@@ -589,6 +602,15 @@ int32_t anim_check(mtr_device* d, const mtr_model* m, const AnimCall& c, const c
 // skeleton the palettes (out) are folded with; nullptr: a sample call, out takes the local matrices and the caller waits
 // for the stream, so no event is touched.
 int32_t anim_enqueue(const AnimCall& c, const mtr_model::Skeleton* sk, float* out, uint32_t ninst, hipStream_t s);
+// host_batch.cpp: the palettes of an animate call, its records in device memory -- a fresh version of the batch, written on s
+int32_t batch_animate(mtr_batch* b, const AnimCall& c, hipStream_t s);
+// a set's destroy: parked behind its event, the handle freed
+template <class Set>
+void set_destroy(Set* s) {
+    if (!s) return;
+    set_park(s);
+    delete s;
+}
 // root motion (section 19): what every call checks, and k_root (mats_in * D) or k_root_deltas (mats_in == nullptr: D) on s
 int32_t root_check(mtr_device* d, const mtr_anim* traj, const mtr_anim_root* root, size_t nsteps, bool deltas);
 int32_t root_enqueue(mtr_anim* traj, mtr_anim_root* root, const void* steps_dev, size_t nsteps, size_t n, const float* mats_in, float* out, hipStream_t s);

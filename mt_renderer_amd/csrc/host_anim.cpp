@@ -18,6 +18,10 @@ void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __
 void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_spring(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_spring_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_spring_tracks(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_spring_tracks_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
 // k_root.hip, weak for the same reason
 void mtr_launch_root(const RootParams& p, hipStream_t s) __attribute__((weak));
 void mtr_launch_root_deltas(const RootParams& p, hipStream_t s) __attribute__((weak));
@@ -101,24 +105,32 @@ struct AnimLaunch {
     void (*states)(const AnimParams&, uint32_t, hipStream_t);
     void (*layers)(const AnimLayerParams&, uint32_t, hipStream_t);
     void (*ik)(const AnimIkParams&, uint32_t, hipStream_t);
-    bool has(int kind) const { return kind == AnimCall::kStates ? states != nullptr : kind == AnimCall::kLayers ? layers != nullptr : ik != nullptr; }
+    void (*spring)(const AnimSpringParams&, uint32_t, hipStream_t);
+    bool has(int kind) const {
+        return kind == AnimCall::kStates ? states != nullptr : kind == AnimCall::kLayers ? layers != nullptr : kind == AnimCall::kIk ? ik != nullptr : spring != nullptr;
+    }
 };
 const AnimLaunch kAnimLaunch[2][2] = {
-    {{mtr_launch_anim, mtr_launch_anim_layers, mtr_launch_anim_ik}, {mtr_launch_anim_sample, mtr_launch_anim_layers_sample, mtr_launch_anim_ik_sample}},
-    {{mtr_launch_anim_tracks, mtr_launch_anim_layers_tracks, mtr_launch_anim_ik_tracks},
-     {mtr_launch_anim_tracks_sample, mtr_launch_anim_layers_tracks_sample, mtr_launch_anim_ik_tracks_sample}}};
-const char* const kAnimWhat[2][3] = {{"animate", "animate layers", "animate ik"}, {"anim sample", "anim sample layers", "anim sample ik"}};
-const char* const kAnimKernel[3] = {"k_anim", "k_anim_layers", "k_anim_ik"};
+    {{mtr_launch_anim, mtr_launch_anim_layers, mtr_launch_anim_ik, mtr_launch_anim_spring},
+     {mtr_launch_anim_sample, mtr_launch_anim_layers_sample, mtr_launch_anim_ik_sample, mtr_launch_anim_spring_sample}},
+    {{mtr_launch_anim_tracks, mtr_launch_anim_layers_tracks, mtr_launch_anim_ik_tracks, mtr_launch_anim_spring_tracks},
+     {mtr_launch_anim_tracks_sample, mtr_launch_anim_layers_tracks_sample, mtr_launch_anim_ik_tracks_sample, mtr_launch_anim_spring_tracks_sample}}};
+const char* const kAnimWhat[2][4] = {{"animate", "animate layers", "animate ik", "animate spring"},
+                                     {"anim sample", "anim sample layers", "anim sample ik", "anim sample spring"}};
+const char* const kAnimKernel[4] = {"k_anim", "k_anim_layers", "k_anim_ik", "k_anim_spring"};
 
 }  // namespace
 
-// A layered call makes the checks of a plain one too, an IK call those of a layered one: `stage` names the kind a message
-// speaks for.  A sample call speaks under its own name throughout.
+// A layered call makes the checks of a plain one too, an IK call those of a layered one, a spring call those of an IK call
+// where it has an IK set and those of a layered one where it has none: `stage` names the kind a message speaks for.  A
+// sample call speaks under its own name throughout.
 int32_t anim_check(mtr_device* d, const mtr_model* m, const AnimCall& c, const char* no_room) {
     const bool sample = !m;
     const mtr_anim* a = c.anim;
     const mtr_anim_masks* mk = c.masks;
     const mtr_anim_ik* ik = c.ik;
+    const mtr_anim_spring* sp = c.spring;
+    const bool springs = c.kind == AnimCall::kSpring;
     auto what = [&](int stage) { return std::string(kAnimWhat[sample][sample ? c.kind : stage]) + ": "; };
     auto bad = [&](int stage, const std::string& msg) { return fail(d, MTR_E_INVALID, what(stage) + msg); };
     auto built = [&](int stage) {
@@ -136,7 +148,11 @@ int32_t anim_check(mtr_device* d, const mtr_model* m, const AnimCall& c, const c
     }
     int32_t rc;
     if (sample) {
-        if (c.kind == AnimCall::kIk && (!ik || ik->dev != d || ik->njoints != a->njoints)) return bad(c.kind, "an IK set of this device and joint count");
+        if ((c.kind == AnimCall::kIk || (springs && ik)) && (!ik || ik->dev != d || ik->njoints != a->njoints))
+            return bad(c.kind, "an IK set of this device and joint count");
+        if (springs && (!sp || sp->dev != d || sp->njoints != a->njoints)) return bad(c.kind, "a spring set of this device and joint count");
+        // the chains walk the spring set's copy of the paths here
+        if (springs && ik && ik->parents != sp->parents) return bad(c.kind, "the IK set's parents are not the spring set's");
         if (no_room) return bad(c.kind, no_room);
         return (rc = built(c.kind)) ? rc : set_device(d);
     }
@@ -147,23 +163,33 @@ int32_t anim_check(mtr_device* d, const mtr_model* m, const AnimCall& c, const c
     if ((rc = built(AnimCall::kStates)) || (rc = set_device(d))) return rc;
     if (c.kind == AnimCall::kStates) return MTR_OK;
     if ((rc = built(AnimCall::kLayers)) || c.kind == AnimCall::kLayers) return rc;
-    if (!ik) return bad(AnimCall::kIk, "no IK set");
-    if (ik->dev != d) return bad(AnimCall::kIk, "the IK set belongs to another device");
-    if (ik->njoints != m->skel.njoints) return bad(AnimCall::kIk, "the IK set's joint count is not the skeleton's");
-    for (uint32_t j = 0; j < ik->njoints; j++)
-        if (ik->parents[j] != m->skel.parents[j]) return bad(AnimCall::kIk, "the IK set's parent of joint " + std::to_string(j) + " is not the skeleton's");
-    return built(AnimCall::kIk);
+    if (ik || !springs) {
+        if (!ik) return bad(AnimCall::kIk, "no IK set");
+        if (ik->dev != d) return bad(AnimCall::kIk, "the IK set belongs to another device");
+        if (ik->njoints != m->skel.njoints) return bad(AnimCall::kIk, "the IK set's joint count is not the skeleton's");
+        for (uint32_t j = 0; j < ik->njoints; j++)
+            if (ik->parents[j] != m->skel.parents[j]) return bad(AnimCall::kIk, "the IK set's parent of joint " + std::to_string(j) + " is not the skeleton's");
+        if ((rc = built(AnimCall::kIk)) || !springs) return rc;
+    }
+    if (!sp) return bad(AnimCall::kSpring, "no spring set");
+    if (sp->dev != d) return bad(AnimCall::kSpring, "the spring set belongs to another device");
+    if (sp->njoints != m->skel.njoints) return bad(AnimCall::kSpring, "the spring set's joint count is not the skeleton's");
+    for (uint32_t j = 0; j < sp->njoints; j++)
+        if (sp->parents[j] != m->skel.parents[j])
+            return bad(AnimCall::kSpring, "the spring set's parent of joint " + std::to_string(j) + " is not the skeleton's");
+    return built(AnimCall::kSpring);
 }
 
 int32_t anim_enqueue(const AnimCall& c, const mtr_model::Skeleton* sk, float* out, uint32_t ninst, hipStream_t s) {
     mtr_anim* a = c.anim;
     mtr_device* d = a->dev;
-    DeviceSet* const sets[3] = {a, c.masks, c.ik};
+    DeviceSet* const sets[4] = {a, c.masks, c.ik, c.spring};
     int32_t rc;
     for (DeviceSet* x : sets)
         if (sk && x && (rc = set_before(x, s))) return rc;
-    // the parameters of the three kinds nest: each kernel is handed the part it knows
-    AnimIkParams ip{};
+    // the parameters of the four kinds nest: each kernel is handed the part it knows
+    AnimSpringParams sp{};
+    AnimIkParams& ip = sp.ik;
     AnimLayerParams& lp = ip.layers;
     AnimParams& ap = lp.anim;
     if (sk) ap.pose = pose_params(*sk, nullptr, out);
@@ -180,14 +206,29 @@ int32_t anim_enqueue(const AnimCall& c, const mtr_model::Skeleton* sk, float* ou
         if (c.kind == AnimCall::kLayers) {
             launch.layers(lp, ninst, s);
         } else {
-            // the chain walks read the skeleton's path table as the fold does; a sample call has none and reads the IK set's copy
+            // the chain walks read the skeleton's path table as the fold does; a sample call has none and reads the IK set's
+            // copy, or the spring set's
             const mtr_anim_ik* ik = c.ik;
-            ip.chains = ik->d;
-            ip.targets = static_cast<const uint32_t*>(c.targets);
-            ip.nchains = ik->nchains;
+            const mtr_anim_spring* ss = c.kind == AnimCall::kSpring ? c.spring : nullptr;
+            if (ik) {
+                ip.chains = ik->d;
+                ip.targets = static_cast<const uint32_t*>(c.targets);
+                ip.nchains = ik->nchains;
+            }
             if (sk) { ip.paths = ap.pose.paths; ip.path_words = ap.pose.path_words; ip.path_bytes = sk->path_bytes; }
+            else if (ss) { ip.paths = ss->d + (size_t)ss->nsprings * 12 + ss->njoints; ip.path_words = ip.paths + ss->njoints; ip.path_bytes = ss->path_bytes; }
             else { ip.paths = ik->d + (size_t)ik->nchains * 8; ip.path_words = ip.paths + ik->njoints; ip.path_bytes = ik->path_bytes; }
-            launch.ik(ip, ninst, s);
+            if (ss) {
+                sp.springs = ss->d;
+                sp.joint_tab = ss->d + (size_t)ss->nsprings * 12;
+                sp.states = static_cast<uint32_t*>(c.spring_states);
+                sp.motion = c.motion;
+                sp.dt = c.dt;
+                sp.nsprings = ss->nsprings; sp.nrounds = ss->nrounds;
+                launch.spring(sp, ninst, s);
+            } else {
+                launch.ik(ip, ninst, s);
+            }
         }
     }
     HIPCHK(d, hipGetLastError());
@@ -262,13 +303,6 @@ int32_t anim_sample(AnimCall c, size_t rec_words, size_t target_words, size_t n,
 // n instances and room for their local matrices?
 bool sample_room(const mtr_anim* a, size_t n, bool records, const float* out_locals, size_t count) {
     return n <= 0xFFFFFFu && (!n || (records && out_locals)) && count >= n * a->njoints * 16;
-}
-
-template <class Set>
-void set_destroy(Set* s) {
-    if (!s) return;
-    set_park(s);
-    delete s;
 }
 
 }  // namespace

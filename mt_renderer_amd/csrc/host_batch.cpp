@@ -309,12 +309,16 @@ int32_t batch_pose(mtr_batch* b, const float* locals_dev, size_t njoints, hipStr
     return batch_write_version(b, MatSrc{}, ps, s);
 }
 
-// the palettes of an animate call, its records in device memory
+}  // namespace
+
+// the palettes of an animate call, its records in device memory (host_spring.cpp calls in too)
 int32_t batch_animate(mtr_batch* b, const AnimCall& c, hipStream_t s) {
     PalSrc ps;
     ps.from = PalSrc::kAnim; ps.npal = c.anim->njoints; ps.anim = c;
     return batch_write_version(b, MatSrc{}, ps, s);
 }
+
+namespace {
 
 // the matrices of an attach call: one record per instance (device memory) against the current version of src
 int32_t batch_attach(mtr_batch* b, mtr_batch* src, const void* recs_dev, hipStream_t s) {

@@ -17,8 +17,12 @@
 // Inverse kinematics (section 17): the k_anim_ik kernels evaluate the same stack through the same code, keep each joint's
 // (T, Q, S) in registers and, between the stack and the fold, solve up to 4 chains per instance (two-bone reach, aim) in
 // order over the local matrices and rotations in LDS.  The scalar solve lives in anim_ik.h.
+//
+// Spring bones (section 24): the k_anim_spring kernels go on from there -- after the chains, joints that carry a spring are
+// aimed at a particle whose state lives in device memory from call to call.  The scalar rule lives in spring_math.h.
 #include "anim_blend.h"
 #include "anim_ik.h"
+#include "spring_math.h"
 #include "anim_tracks.h"
 #include "pose_common.h"
 
@@ -349,24 +353,11 @@ __device__ __forceinline__ void ik_walk(const float4* loc, const float4* rot, co
 // nothing writes afterwards; a, b and c index loc[], rot[] and paths[], all of njoints entries.  paths[] and the path bytes
 // were built on the host from validated parents: an offset plus a length stays inside path_bytes, and every path byte is
 // a joint < njoints.  No device-side value forms an address.
-template <bool TRACKS, bool FOLD>
-__device__ __forceinline__ void anim_ik(const AnimIkParams& p) {
-    const PoseParams& pose = p.layers.anim.pose;
-    __shared__ float4 loc[MTR_POSE_MAX_JOINTS * 4];
-    __shared__ float4 rot[MTR_POSE_MAX_JOINTS];
-    extern __shared__ uint32_t path_lds[];  // p.path_bytes / 4 words
-    const uint32_t inst = blockIdx.x, t = threadIdx.x, J = pose.njoints, K = p.nchains;
-    AnimKey r = {};
-    if (t < J) {
-        r = anim_layer_tqs<TRACKS>(p.layers, inst, t);
-        float4 M[4];
-        anim_matrix(r, M);
-#pragma unroll
-        for (int c = 0; c < 4; c++) loc[t * 4 + c] = M[c];
-        rot[t] = r.q;
-    }
-    for (uint32_t i = t; i < p.path_bytes / 4; i += blockDim.x) path_lds[i] = p.path_words[i];
-    __syncthreads();
+//
+// ik_chains is that chain loop, shared with the spring kernels (section 24): r is the calling thread's (T, Q, S), every
+// thread of the workgroup calls it (the barriers), and nchains == 0 (a spring call without an IK set) reads nothing.
+__device__ __forceinline__ void ik_chains(const AnimIkParams& p, float4* loc, float4* rot, const uint32_t* path_lds, AnimKey& r, uint32_t inst, uint32_t t) {
+    const uint32_t K = p.nchains;
     const uint4* chains = reinterpret_cast<const uint4*>(p.chains);
     const uint4* targets = reinterpret_cast<const uint4*>(p.targets) + (size_t)inst * K * 2;
     for (uint32_t k = 0; k < K; k++) {  // uniform for the workgroup: every barrier below is met by every wave
@@ -413,20 +404,131 @@ __device__ __forceinline__ void anim_ik(const AnimIkParams& p) {
         }
         __syncthreads();
     }
-    if (t >= J) return;
+}
+
+// what the IK and the spring kernels begin with: thread t's (T, Q, S) after the layer stack, its matrix and rotation in LDS,
+// the path table in LDS, a barrier
+template <bool TRACKS>
+__device__ __forceinline__ AnimKey anim_stack_to_lds(const AnimIkParams& p, float4* loc, float4* rot, uint32_t* path_lds, uint32_t inst, uint32_t t) {
+    AnimKey r = {};
+    if (t < p.layers.anim.pose.njoints) {
+        r = anim_layer_tqs<TRACKS>(p.layers, inst, t);
+        float4 M[4];
+        anim_matrix(r, M);
+#pragma unroll
+        for (int c = 0; c < 4; c++) loc[t * 4 + c] = M[c];
+        rot[t] = r.q;
+    }
+    for (uint32_t i = t; i < p.path_bytes / 4; i += blockDim.x) path_lds[i] = p.path_words[i];
+    __syncthreads();
+    return r;
+}
+
+// and what they end with: the fold, or the local matrices themselves
+template <bool FOLD>
+__device__ __forceinline__ void anim_lds_out(const PoseParams& pose, const float4* loc, const uint32_t* path_lds, uint32_t inst, uint32_t t) {
+    if (t >= pose.njoints) return;
     if constexpr (FOLD) {
         pose_fold_store(pose, loc, path_lds, inst, t);
     } else {
-        float4* out = reinterpret_cast<float4*>(pose.out + ((size_t)inst * J + t) * 16);
+        float4* out = reinterpret_cast<float4*>(pose.out + ((size_t)inst * pose.njoints + t) * 16);
 #pragma unroll
         for (int c = 0; c < 4; c++) out[c] = loc[t * 4 + c];
     }
+}
+
+template <bool TRACKS, bool FOLD>
+__device__ __forceinline__ void anim_ik(const AnimIkParams& p) {
+    __shared__ float4 loc[MTR_POSE_MAX_JOINTS * 4];
+    __shared__ float4 rot[MTR_POSE_MAX_JOINTS];
+    extern __shared__ uint32_t path_lds[];  // p.path_bytes / 4 words
+    const uint32_t inst = blockIdx.x, t = threadIdx.x;
+    AnimKey r = anim_stack_to_lds<TRACKS>(p, loc, rot, path_lds, inst, t);
+    ik_chains(p, loc, rot, path_lds, r, inst, t);
+    anim_lds_out<FOLD>(p.layers.anim.pose, loc, path_lds, inst, t);
 }
 
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_ik(AnimIkParams p) { anim_ik<false, true>(p); }
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_ik_sample(AnimIkParams p) { anim_ik<false, false>(p); }
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_ik_tracks(AnimIkParams p) { anim_ik<true, true>(p); }
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_ik_tracks_sample(AnimIkParams p) { anim_ik<true, false>(p); }
+
+// ---- spring bones (section 24) ----
+// The shape of anim_ik: the layer stack, then the chains (ik_chains; none without an IK set), then the springs, then the
+// fold.  A joint carries at most one spring, so thread t owns at most one: it simulates it itself -- it holds the joint's
+// (T, Q, S) in registers, walks its own path (ik_walk), runs the rule of spring_math.h on its state record, writes rot[t]
+// and rebuilds loc[t].  The springs run by ROUNDS: a spring's round is the number of spring joints among its joint's
+// ancestors (the host counted it), R = 1 + the largest one is the same for the whole workgroup, and one barrier ends a
+// round.  That suffices: within a round no spring joint is an ancestor of another (an ancestor has fewer spring ancestors),
+// so no thread reads an entry of loc[] or rot[] that another thread of the round writes -- a walk reads the joint's ancestors
+// and the joint itself --, and the joints without a spring read loc[] only in the fold, behind the last barrier.  Four
+// strands of three joints cost three rounds, not twelve steps.  The spring record, the state record, the path word and the
+// instance's delta depend on nothing computed, so their loads are issued ahead of the layer stack.
+//
+// Memory safety, extending the argument at anim_ik: joint_tab holds njoints words and t < njoints; the host built it from
+// the validated springs (a spring index k < nsprings, nsprings validated to 1..16, each joint named once), so the record
+// k * 3 lies inside the nsprings records of the set and the state (inst * nsprings + k) * 2 inside the ninst * nsprings
+// records of 32 bytes the caller owns; two threads never share a state record.  motion is indexed by inst alone and holds
+// ninst * 16 floats.  From the spring and state records, dt and motion come positions, rotations and factors, which reach
+// no address; paths[t] is the host's, as for a chain.  No device-side value forms an address.
+template <bool TRACKS, bool FOLD>
+__device__ __forceinline__ void anim_spring(const AnimSpringParams& p) {
+    const AnimIkParams& ip = p.ik;
+    __shared__ float4 loc[MTR_POSE_MAX_JOINTS * 4];
+    __shared__ float4 rot[MTR_POSE_MAX_JOINTS];
+    extern __shared__ uint32_t path_lds[];  // ip.path_bytes / 4 words
+    const uint32_t inst = blockIdx.x, t = threadIdx.x, J = ip.layers.anim.pose.njoints, R = p.nrounds;
+    const uint32_t tab = t < J ? p.joint_tab[t] : MTR_SPRING_NONE;
+    const bool mine = tab != MTR_SPRING_NONE;
+    uint4 s0 = {}, s1 = {}, s2 = {}, st0 = {}, st1 = {};
+    float4 d0 = {}, d1 = {}, d2 = {}, d3 = {};
+    uint4* state = nullptr;
+    uint32_t pw = 0u;
+    if (mine) {
+        const uint32_t k = tab & 0xFFu;
+        const uint4* sp = reinterpret_cast<const uint4*>(p.springs) + k * 3;
+        s0 = sp[0]; s1 = sp[1]; s2 = sp[2];  // joint, flags, stiffness, drag | tail, pad | gravity, pad
+        state = reinterpret_cast<uint4*>(p.states) + ((size_t)inst * p.nsprings + k) * 2;
+        st0 = state[0]; st1 = state[1];  // cur, live | prev, pad
+        pw = ip.paths[t];
+        if (p.motion) {
+            const float4* D = reinterpret_cast<const float4*>(p.motion) + (size_t)inst * 4;
+            d0 = D[0]; d1 = D[1]; d2 = D[2]; d3 = D[3];
+        }
+    }
+    AnimKey r = anim_stack_to_lds<TRACKS>(ip, loc, rot, path_lds, inst, t);
+    ik_chains(ip, loc, rot, path_lds, r, inst, t);
+    for (uint32_t rd = 0; rd < R; rd++) {  // uniform for the workgroup: the barrier is met by every wave
+        if (mine && (tab >> 8) == rd) {
+            float4 W[4];
+            AnimVec P;
+            ik_walk(loc, rot, path_lds, pw, W, P);
+            SpringMotion D;
+            D.c0 = ik_vec3(d0.x, d0.y, d0.z); D.c1 = ik_vec3(d1.x, d1.y, d1.z); D.c2 = ik_vec3(d2.x, d2.y, d2.z); D.t = ik_vec3(d3.x, d3.y, d3.z);
+            SpringState st;
+            st.cur = ik_vec3(__uint_as_float(st0.x), __uint_as_float(st0.y), __uint_as_float(st0.z));
+            st.live = st0.w;
+            st.prev = ik_vec3(__uint_as_float(st1.x), __uint_as_float(st1.y), __uint_as_float(st1.z));
+            spring_step(ik_vec3(W[3].x, W[3].y, W[3].z), P, r.q, ik_vec3(__uint_as_float(s1.x), __uint_as_float(s1.y), __uint_as_float(s1.z)),
+                        ik_vec3(__uint_as_float(s2.x), __uint_as_float(s2.y), __uint_as_float(s2.z)), __uint_as_float(s0.z), __uint_as_float(s0.w), p.dt,
+                        p.motion != nullptr, D, st);
+            state[0] = make_uint4(__float_as_uint(st.cur.x), __float_as_uint(st.cur.y), __float_as_uint(st.cur.z), st.live);
+            state[1] = make_uint4(__float_as_uint(st.prev.x), __float_as_uint(st.prev.y), __float_as_uint(st.prev.z), 0u);
+            rot[t] = r.q;  // a failed guard left r.q as it was: the same matrix again
+            float4 M[4];
+            anim_matrix(r, M);
+#pragma unroll
+            for (int c = 0; c < 4; c++) loc[t * 4 + c] = M[c];
+        }
+        __syncthreads();
+    }
+    anim_lds_out<FOLD>(ip.layers.anim.pose, loc, path_lds, inst, t);
+}
+
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_spring(AnimSpringParams p) { anim_spring<false, true>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_spring_sample(AnimSpringParams p) { anim_spring<false, false>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_spring_tracks(AnimSpringParams p) { anim_spring<true, true>(p); }
+__global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_spring_tracks_sample(AnimSpringParams p) { anim_spring<true, false>(p); }
 
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim(AnimParams p) { anim_palettes<false>(p); }
 __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_sample(AnimParams p) { anim_locals<false>(p); }
@@ -449,6 +551,14 @@ static bool anim_layers_launchable(const AnimLayerParams& p, uint32_t ninst, boo
 static bool anim_ik_launchable(const AnimIkParams& p, uint32_t ninst, bool tracks) {
     return anim_layers_launchable(p.layers, ninst, tracks) && p.chains && p.targets && p.paths && p.path_words && p.nchains >= 1u &&
            p.nchains <= MTR_ANIM_MAX_IK && p.path_bytes != 0u && p.path_bytes <= MTR_POSE_MAX_PATH_BYTES;
+}
+// the IK part may be empty here (no chains, no targets); the states are written, 16 bytes at a time
+static bool anim_spring_launchable(const AnimSpringParams& p, uint32_t ninst, bool tracks) {
+    const AnimIkParams& ip = p.ik;
+    return anim_layers_launchable(ip.layers, ninst, tracks) && ip.nchains <= MTR_ANIM_MAX_IK && (ip.nchains == 0u || (ip.chains && ip.targets)) && ip.paths &&
+           ip.path_words && ip.path_bytes != 0u && ip.path_bytes <= MTR_POSE_MAX_PATH_BYTES && p.springs && p.joint_tab && p.states &&
+           ((uintptr_t)p.states & 15u) == 0u && ((uintptr_t)p.motion & 15u) == 0u && p.nsprings >= 1u && p.nsprings <= MTR_ANIM_MAX_SPRINGS &&
+           p.nrounds >= 1u && p.nrounds <= p.nsprings;
 }
 static bool fold_fits(const PoseParams& pose) { return pose.path_bytes <= MTR_POSE_MAX_PATH_BYTES; }
 
@@ -495,4 +605,19 @@ void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_
 }
 void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
     anim_launch(mtr::k_anim_ik_tracks_sample, p, anim_ik_launchable(p, ninst, true), p.layers.anim.pose.njoints, p.path_bytes, ninst, s);
+}
+// the springs walk the same path table as the chains
+void mtr_launch_anim_spring(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) {
+    const AnimIkParams& ip = p.ik;
+    anim_launch(mtr::k_anim_spring, p, anim_spring_launchable(p, ninst, false) && ip.layers.anim.pose.path_bytes == ip.path_bytes, ip.layers.anim.pose.njoints, ip.path_bytes, ninst, s);
+}
+void mtr_launch_anim_spring_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) {
+    anim_launch(mtr::k_anim_spring_sample, p, anim_spring_launchable(p, ninst, false), p.ik.layers.anim.pose.njoints, p.ik.path_bytes, ninst, s);
+}
+void mtr_launch_anim_spring_tracks(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) {
+    const AnimIkParams& ip = p.ik;
+    anim_launch(mtr::k_anim_spring_tracks, p, anim_spring_launchable(p, ninst, true) && ip.layers.anim.pose.path_bytes == ip.path_bytes, ip.layers.anim.pose.njoints, ip.path_bytes, ninst, s);
+}
+void mtr_launch_anim_spring_tracks_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) {
+    anim_launch(mtr::k_anim_spring_tracks_sample, p, anim_spring_launchable(p, ninst, true), p.ik.layers.anim.pose.njoints, p.ik.path_bytes, ninst, s);
 }

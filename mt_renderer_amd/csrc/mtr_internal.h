@@ -545,6 +545,25 @@ void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
 void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
+// spring bones after the IK chains (k_anim.hip, SPEC.md section 24): per instance nsprings state records, read and written,
+// over the springs of a spring set.  ik.nchains may be 0 here (ik.chains and ik.targets are then unused); ik.paths,
+// ik.path_words and ik.path_bytes are what the chain walks and the spring walks read.
+#define MTR_ANIM_MAX_SPRINGS 16
+#define MTR_SPRING_NONE 0xFFFFFFFFu
+struct AnimSpringParams {
+    AnimIkParams ik;
+    const uint32_t* springs;    // nsprings x 12 words (mtr_spring: joint, flags, stiffness, drag, tail[3], pad, gravity[3], pad), validated on the host
+    const uint32_t* joint_tab;  // njoints: the index of the joint's spring | its round << 8, or MTR_SPRING_NONE; built on the host
+    uint32_t* states;           // ninst x nsprings x 8 words (mtr_spring_state: cur[3], live, prev[3], pad); 16-byte aligned
+    const float* motion;        // ninst x 16, the rigid delta of every instance (column-major), 16-byte aligned, or nullptr
+    float dt;
+    uint32_t nsprings;          // 1..MTR_ANIM_MAX_SPRINGS, a validated host value
+    uint32_t nrounds;           // 1 + the largest round, a host value
+};
+void mtr_launch_anim_spring(const AnimSpringParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_spring_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_spring_tracks(const AnimSpringParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_spring_tracks_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s);
 // attachments (k_attach.hip, SPEC.md section 18): n instance matrices from the matrices and palettes of a source batch's version
 struct AttachParams {
     const uint32_t* recs;       // n x 20 words (mtr_attach: src_instance, joint, flags, pad, offset[16]); 16-byte aligned

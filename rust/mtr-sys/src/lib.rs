@@ -70,7 +70,7 @@ pub const MTR_OWN_SUPERTILES: u32 = 2;
 pub const MTR_TEXRES_DECODED: u32 = 0;
 pub const MTR_TEXRES_BLOCKS: u32 = 1;
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player, mtr_anim_ctrl, mtr_anim_events, mtr_anim_blend);
+opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player, mtr_anim_ctrl, mtr_anim_events, mtr_anim_blend, mtr_anim_spring);
 
 /// animation clips (mtr.h, SPEC.md section 14): one key of one joint, 48 bytes
 pub const MTR_CLIP_LOOP: u32 = 1;
@@ -125,6 +125,28 @@ pub struct mtr_ik_target {
     pub pos: [f32; 3],
     pub w: f32,
     pub pole: [f32; 3],
+    pub pad: u32,
+}
+/// spring bones (mtr.h, SPEC.md section 24): a spring of a spring set, 48 bytes, and one instance's particle for it, 32 bytes
+pub const MTR_ANIM_MAX_SPRINGS: usize = 16;
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_spring {
+    pub joint: u32,
+    pub flags: u32,
+    pub stiffness: f32,
+    pub drag: f32,
+    pub tail: [f32; 3],
+    pub pad0: f32,
+    pub gravity: [f32; 3],
+    pub pad1: f32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_spring_state {
+    pub cur: [f32; 3],
+    pub live: u32,
+    pub prev: [f32; 3],
     pub pad: u32,
 }
 /// attachments (mtr.h, SPEC.md section 18): one attached instance, 80 bytes; offset is column-major, in the source model's bind space
@@ -446,5 +468,16 @@ extern "C" {
                                          out_shares_dev: *mut f32, hip_stream: *mut c_void) -> i32;
     pub fn mtr_anim_blend_advance_host(blend: *mut mtr_anim_blend, states: *mut mtr_blend_state, params: *const f32, n: usize, dt: f32,
                                        out_layers: *mut mtr_anim_layer, nlayers: usize, out_steps: *mut mtr_root_step, out_shares: *mut f32) -> i32;
+    // spring bones (SPEC.md section 24): declarations only
+    pub fn mtr_anim_spring_create(dev: *mut mtr_device, njoints: usize, parents: *const u8, nsprings: usize, springs: *const mtr_spring,
+                                  out: *mut *mut mtr_anim_spring) -> i32;
+    pub fn mtr_anim_spring_destroy(spring: *mut mtr_anim_spring);
+    pub fn mtr_batch_animate_spring_device(batch: *mut mtr_batch, anim: *mut mtr_anim, masks: *mut mtr_anim_masks,
+                                           layers_dev: *const mtr_anim_layer, nlayers: usize, ik: *mut mtr_anim_ik,
+                                           targets_dev: *const mtr_ik_target, spring: *mut mtr_anim_spring, states_dev: *mut mtr_spring_state,
+                                           motion_dev: *const f32, dt: f32, hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_sample_spring(anim: *mut mtr_anim, masks: *mut mtr_anim_masks, ik: *mut mtr_anim_ik, spring: *mut mtr_anim_spring,
+                                  layers: *const mtr_anim_layer, nlayers: usize, targets: *const mtr_ik_target, states: *mut mtr_spring_state,
+                                  motion: *const f32, dt: f32, n: usize, out_locals: *mut f32, count: usize) -> i32;
 }
 pub mod files;
