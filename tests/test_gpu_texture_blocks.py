@@ -1,7 +1,12 @@
 """BC textures kept block-compressed in HBM and decoded per fetch (mtr_device_set_texture_residency(MTR_TEXRES_BLOCKS),
-csrc/bc_sample.h): the same pixels as the default decode-at-upload path and as the oracle, for every BC7 mode /
-partition / rotation a few thousand random blocks reach, BC1 with and without its punch-through alpha, mip chains,
-magnified (linear, four texels from up to four blocks) and minified (nearest) samples, both tile kernels."""
+csrc/bc_sample.h): the same pixels as the default decode-at-upload path and as the oracle, on random blocks: BC1 with and
+without its punch-through alpha, mip chains, magnified (linear, four texels from up to four blocks) and minified (nearest)
+samples, both tile kernels.  What the random blocks reach is not every layout: the 1716 BC7 blocks of
+test_every_texel_one_to_one[bc7] hold 273 of the 285 (mode, partition, rotation, index selection) combinations -- they miss
+mode 1 partitions 9, 23, 41, 61, mode 2 partitions 23, 54, mode 3 partition 25 and mode 7 partitions 12, 18, 24, 29, 31 -- no
+reserved block and no BC1 block with c0 == c1, and the default blend hides the colour of a texel with alpha near 0
+(tests/test_bc_block_premises.py::test_what_the_random_textures_reach keeps that list).  Every layout, the reserved mode,
+every BC1 endpoint ordering and every byte of every texel are tests/test_gpu_bc_blocks.py's."""
 import numpy as np
 import pytest
 
