@@ -680,9 +680,32 @@ def root_steps(steps, n: Optional[int]) -> np.ndarray:
     return np.ascontiguousarray(st)
 
 
-class AnimRoot:
+class _Set:
+    """What the animation set classes share: the device ``dev``, the library's handle ``_h`` and the name of the library
+    function that destroys it."""
+    _destroy = ""
+
+    def close(self):
+        if self._h:
+            getattr(lib, self._destroy)(self._h)
+            self._h = None
+
+
+def _clip_arrays(size_msg: str, nkeys, flags, *rates):
+    """The per-clip arrays of a set's create as contiguous arrays: (uint32 key counts, uint32 flag words or None), and the
+    float32 rates behind them for a set that has rates.  ``size_msg``: what to say when they do not hold one entry per clip."""
+    nk = np.ascontiguousarray(np.asarray(nkeys, dtype=np.uint32).reshape(-1))
+    rt = [np.ascontiguousarray(np.asarray(r, dtype=np.float32).reshape(-1)) for r in rates]
+    fl = None if flags is None else np.ascontiguousarray(np.asarray(flags, dtype=np.uint32).reshape(-1))
+    if any(r.size != nk.size for r in rt) or (fl is not None and fl.size != nk.size):
+        raise MtrError(MTR_E_INVALID, size_msg)
+    return (nk, fl, *rt)
+
+
+class AnimRoot(_Set):
     """A root set (include/mtr.h, SPEC.md section 19) for trajectory sets of ``njoints`` joints and ``nclips`` clips: the
     trajectory joint and one flag word per clip (0 or ROOT_CYCLIC; None: all 0)."""
+    _destroy = "mtr_anim_root_destroy"
 
     def __init__(self, dev: Device, njoints: int, nclips: int, joint: int = 0, flags=None):
         fl = None if flags is None else np.ascontiguousarray(np.asarray(flags, dtype=np.uint32).reshape(-1))
@@ -711,11 +734,6 @@ class AnimRoot:
         _on_stream(self.dev, cur, lib.mtr_anim_root_deltas_device,
                    (traj._h, self._h, C.c_void_p(t.data_ptr()), t.shape[1], t.shape[0], C.c_void_p(out.data_ptr())), (t, out))
         return out
-
-    def close(self):
-        if self._h:
-            lib.mtr_anim_root_destroy(self._h)
-            self._h = None
 
 
 def _root_tensor(t, dev: "Device", what: str, n: Optional[int], stream):
@@ -761,17 +779,62 @@ def _play_tensor(t, dev: "Device", what: str, record: int, align: int, count: Op
     return nbytes // record
 
 
-class AnimPlayer:
+def _want_dtype(t, dtype, msg: str):
+    if getattr(t, "dtype", None) != dtype:
+        raise MtrError(MTR_E_INVALID, msg)
+
+
+class _InPlaceArgs:
+    """The tensors that one device call of a player, controller, event set or blend set reads or writes IN PLACE: each is
+    checked as it is added (_play_tensor, after its dtype where one is required) and kept, so that the call can tell the
+    allocator which stream uses them."""
+
+    def __init__(self, dev: "Device"):
+        self.dev, self.used = dev, []
+
+    def add(self, t, what: str, record: int, align: int, count: Optional[int], dtype=None, dtype_msg: str = "") -> int:
+        """checks ``t`` and returns the number of records it holds"""
+        if dtype is not None:
+            _want_dtype(t, dtype, dtype_msg)
+        k = _play_tensor(t, self.dev, what, record, align, count)
+        self.used.append(t)
+        return k
+
+    def layers(self, t, what: str, n: int) -> int:
+        """``t``: None or n x L ANIM_LAYER records; returns L, 0 for None"""
+        if t is None:
+            return 0
+        nl = self.add(t, what, ANIM_LAYER.itemsize, 16, None)
+        if nl % n:
+            raise MtrError(MTR_E_INVALID, f"{what}: n x L layers of 16 bytes")
+        return nl // n
+
+    @staticmethod
+    def ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    def call(self, fn, args, stream):
+        """``fn(*args, stream handle)`` in stream order on ``stream`` (None: the current stream of the first tensor's device)"""
+        import torch
+        cur = stream if stream is not None else torch.cuda.current_stream(self.used[0].device)
+        _on_stream(self.dev, cur, fn, args, self.used)
+
+
+def _layers_in(n: int, nlayers: int, layers) -> Optional[np.ndarray]:
+    """the ANIM_LAYER stacks [n, nlayers] a host hook sends in and gets back: a copy of ``layers``, zeroes, or None (no layers)"""
+    if not nlayers:
+        return None
+    return np.zeros((n, nlayers), dtype=ANIM_LAYER) if layers is None else np.ascontiguousarray(layers).copy().reshape(n, nlayers)
+
+
+class AnimPlayer(_Set):
     """A player set (include/mtr.h, SPEC.md section 20), the library's clock: per clip the key count (ticks for a track set),
     the flag word (0 or CLIP_LOOP; None: all 0) and the rate in positions per second, for up to ``max_instances`` play states
     that live in a tensor of the caller's on the GPU."""
+    _destroy = "mtr_anim_player_destroy"
 
     def __init__(self, dev: Device, nkeys, rates, flags=None, max_instances: int = 1):
-        nk = np.ascontiguousarray(np.asarray(nkeys, dtype=np.uint32).reshape(-1))
-        rt = np.ascontiguousarray(np.asarray(rates, dtype=np.float32).reshape(-1))
-        fl = None if flags is None else np.ascontiguousarray(np.asarray(flags, dtype=np.uint32).reshape(-1))
-        if rt.size != nk.size or (fl is not None and fl.size != nk.size):
-            raise MtrError(MTR_E_INVALID, "anim player: one key count, one rate and one flag word per clip")
+        nk, fl, rt = _clip_arrays("anim player: one key count, one rate and one flag word per clip", nkeys, flags, rates)
         h = C.c_void_p()
         dev.check(lib.mtr_anim_player_create(dev._h, nk.size, _p(nk), _p(fl), _p(rt), max_instances, C.byref(h)))
         self.dev, self._h, self.nclips, self.max_instances = dev, h, nk.size, max_instances
@@ -784,32 +847,20 @@ class AnimPlayer:
         None: torch.cuda.current_stream()).  cmds: None, a PLAY_CMD array or a dict (host memory, copied before the call
         returns), or a tensor of PLAY_CMD records on the GPU (read in stream order)."""
         import torch
-        n = _play_tensor(states, self.dev, "player states", PLAY_STATE.itemsize, 16, None)
-        used = [states]
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        nl = 0
+        a = _InPlaceArgs(self.dev)
+        n = a.add(states, "player states", PLAY_STATE.itemsize, 16, None)
         if out_states is not None:
-            _play_tensor(out_states, self.dev, "player out_states", ANIM_STATE.itemsize, 8, n)
-            used.append(out_states)
-        if out_layers is not None:
-            nl = _play_tensor(out_layers, self.dev, "player out_layers", ANIM_LAYER.itemsize, 16, None)
-            if nl % n:
-                raise MtrError(MTR_E_INVALID, "player out_layers: n x L layers of 16 bytes")
-            nl //= n
-            used.append(out_layers)
+            a.add(out_states, "player out_states", ANIM_STATE.itemsize, 8, n)
+        nl = a.layers(out_layers, "player out_layers", n)
         if out_steps is not None:
-            _play_tensor(out_steps, self.dev, "player out_steps", ROOT_STEP.itemsize, 16, 2 * n)
-            used.append(out_steps)
+            a.add(out_steps, "player out_steps", ROOT_STEP.itemsize, 16, 2 * n)
         if isinstance(cmds, torch.Tensor):
-            m = _play_tensor(cmds, self.dev, "player commands", PLAY_CMD.itemsize, 16, None)
-            fn, cp, keep = lib.mtr_anim_player_advance_device_cmds, ptr(cmds), None
-            used.append(cmds)
+            m = a.add(cmds, "player commands", PLAY_CMD.itemsize, 16, None)
+            fn, cp, keep = lib.mtr_anim_player_advance_device_cmds, a.ptr(cmds), None
         else:
             keep = play_cmds(cmds)
             m, fn, cp = keep.size, lib.mtr_anim_player_advance_device, (_p(keep) if keep.size else None)
-        cur = stream if stream is not None else torch.cuda.current_stream(states.device)
-        args = (self._h, ptr(states), n, float(dt), cp, m, ptr(out_states), ptr(out_layers), nl, ptr(out_steps))
-        _on_stream(self.dev, cur, fn, args, used)
+        a.call(fn, (self._h, a.ptr(states), n, float(dt), cp, m, a.ptr(out_states), a.ptr(out_layers), nl, a.ptr(out_steps)), stream)
 
     def advance_host(self, states: np.ndarray, dt: float, cmds=None, nlayers: int = 0, layers: Optional[np.ndarray] = None, want_states: bool = True,
                      want_steps: bool = True):
@@ -822,31 +873,26 @@ class AnimPlayer:
         n = st.size
         cm = play_cmds(cmds)
         oa = np.zeros(n, dtype=ANIM_STATE) if want_states else None
-        ol = None
-        if nlayers:
-            ol = np.zeros((n, nlayers), dtype=ANIM_LAYER) if layers is None else np.ascontiguousarray(layers).copy().reshape(n, nlayers)
+        ol = _layers_in(n, nlayers, layers)
         os_ = np.zeros((n, 2), dtype=ROOT_STEP) if want_steps else None
         self.dev.check(lib.mtr_anim_player_advance_host(self._h, _p(st), n, float(dt), _p(cm) if cm.size else None, cm.size, _p(oa), _p(ol), nlayers, _p(os_)))
         return st, oa, ol, os_
 
-    def close(self):
-        if self._h:
-            lib.mtr_anim_player_destroy(self._h)
-            self._h = None
 
-
-class AnimCtrl:
+class AnimCtrl(_Set):
     """A controller (include/mtr.h, SPEC.md section 21): per-instance state machines that write a player's commands on the
     GPU.  ``nkeys`` and ``clip_flags`` are what the AnimPlayer was given; ``nodes`` a CTRL_NODE array, ``trans`` a CTRL_TRANS
     array whose first ``nany`` entries are the any-state transitions (``anim_ctrl.build`` makes the three from a readable
     description), ``nparams`` the floats per instance that conditions may name."""
 
+    _destroy = "mtr_anim_ctrl_destroy"
+
     def __init__(self, dev: Device, nkeys, clip_flags, nodes, trans, nany: int = 0, nparams: int = 0):
-        nk = np.ascontiguousarray(np.asarray(nkeys, dtype=np.uint32).reshape(-1))
-        fl = None if clip_flags is None else np.ascontiguousarray(np.asarray(clip_flags, dtype=np.uint32).reshape(-1))
+        msg = "anim ctrl: one flag word per clip, nodes of dtype CTRL_NODE [S] and transitions of dtype CTRL_TRANS [T]"
+        nk, fl = _clip_arrays(msg, nkeys, clip_flags)
         nd, tr = np.asarray(nodes), np.asarray(trans)
-        if (fl is not None and fl.size != nk.size) or nd.dtype != CTRL_NODE or tr.dtype != CTRL_TRANS or nd.ndim != 1 or tr.ndim != 1:
-            raise MtrError(MTR_E_INVALID, "anim ctrl: one flag word per clip, nodes of dtype CTRL_NODE [S] and transitions of dtype CTRL_TRANS [T]")
+        if nd.dtype != CTRL_NODE or tr.dtype != CTRL_TRANS or nd.ndim != 1 or tr.ndim != 1:
+            raise MtrError(MTR_E_INVALID, msg)
         nd, tr = np.ascontiguousarray(nd), np.ascontiguousarray(tr)
         h = C.c_void_p()
         dev.check(lib.mtr_anim_ctrl_create(dev._h, nk.size, _p(nk), _p(fl), _p(nd), nd.size, _p(tr) if tr.size else None, tr.size, nany, nparams, C.byref(h)))
@@ -859,27 +905,20 @@ class AnimCtrl:
         tensor leaves room for the host's own commands behind slot n - 1) and adds to ``counts`` (int32 [ntrans]) where
         given, in stream order on ``stream`` (a torch stream; None: torch.cuda.current_stream())."""
         import torch
-        n = _play_tensor(states, self.dev, "ctrl states", CTRL_STATE.itemsize, 16, None)
-        _play_tensor(play, self.dev, "ctrl play states", PLAY_STATE.itemsize, 16, n)
-        if _play_tensor(cmds_out, self.dev, "ctrl commands", PLAY_CMD.itemsize, 16, None) < n:
+        a = _InPlaceArgs(self.dev)
+        n = a.add(states, "ctrl states", CTRL_STATE.itemsize, 16, None)
+        a.add(play, "ctrl play states", PLAY_STATE.itemsize, 16, n)
+        if a.add(cmds_out, "ctrl commands", PLAY_CMD.itemsize, 16, None) < n:
             raise MtrError(MTR_E_INVALID, "ctrl commands: at least n slots of 16 bytes")
-        used = [states, play, cmds_out]
         if self.nparams:
-            if params is None or getattr(params, "dtype", None) != torch.float32:
-                raise MtrError(MTR_E_INVALID, "ctrl params: a float32 tensor [n, nparams] on the GPU")
-            _play_tensor(params, self.dev, "ctrl params", 4 * self.nparams, 4, n)
-            used.append(params)
+            a.add(params, "ctrl params", 4 * self.nparams, 4, n, torch.float32, "ctrl params: a float32 tensor [n, nparams] on the GPU")
         else:
             params = None
         if counts is not None:
-            if getattr(counts, "dtype", None) != torch.int32:
-                raise MtrError(MTR_E_INVALID, "ctrl counts: an int32 tensor [ntrans] on the GPU")
-            if self.ntrans == 0 or _play_tensor(counts, self.dev, "ctrl counts", 4, 4, None) < self.ntrans:
+            _want_dtype(counts, torch.int32, "ctrl counts: an int32 tensor [ntrans] on the GPU")
+            if self.ntrans == 0 or a.add(counts, "ctrl counts", 4, 4, None) < self.ntrans:
                 raise MtrError(MTR_E_INVALID, "ctrl counts: one word per transition")
-            used.append(counts)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        cur = stream if stream is not None else torch.cuda.current_stream(states.device)
-        _on_stream(self.dev, cur, lib.mtr_anim_ctrl_step_device, (self._h, ptr(states), ptr(play), ptr(params), n, float(dt), ptr(cmds_out), ptr(counts)), used)
+        a.call(lib.mtr_anim_ctrl_step_device, (self._h, a.ptr(states), a.ptr(play), a.ptr(params), n, float(dt), a.ptr(cmds_out), a.ptr(counts)), stream)
 
     def step_host(self, states: np.ndarray, play: np.ndarray, params, dt: float, counts: Optional[np.ndarray] = None):
         """the test and debug hook: CTRL_STATE [n], PLAY_STATE [n] and float32 [n, nparams] in host memory through the same
@@ -903,25 +942,22 @@ class AnimCtrl:
         self.dev.check(lib.mtr_anim_ctrl_step_host(self._h, _p(st), _p(pl), _p(pr), n, float(dt), _p(cm), _p(ct) if ct is not None and ct.size else None))
         return st, pr, cm, ct
 
-    def close(self):
-        if self._h:
-            lib.mtr_anim_ctrl_destroy(self._h)
-            self._h = None
 
-
-class AnimEvents:
+class AnimEvents(_Set):
     """An event set (include/mtr.h, SPEC.md section 22): markers on clips that fire into a list on the GPU.  ``nkeys`` and
     ``clip_flags`` are what the AnimPlayer was given; ``counts`` holds the markers per clip and ``markers`` an EVENT_MARKER
     array of them, clip after clip, sorted by x within a clip (``anim_events.build`` makes the two from a dict), for calls of
     up to ``max_instances`` instances."""
 
+    _destroy = "mtr_anim_events_destroy"
+
     def __init__(self, dev: Device, nkeys, clip_flags, counts, markers, max_instances: int = 1):
-        nk = np.ascontiguousarray(np.asarray(nkeys, dtype=np.uint32).reshape(-1))
-        fl = None if clip_flags is None else np.ascontiguousarray(np.asarray(clip_flags, dtype=np.uint32).reshape(-1))
+        msg = "anim events: one flag word and one marker count per clip, markers of dtype EVENT_MARKER [sum of counts]"
+        nk, fl = _clip_arrays(msg, nkeys, clip_flags)
         ct = np.ascontiguousarray(np.asarray(counts, dtype=np.uint32).reshape(-1))
         mk = np.asarray(markers)
-        if (fl is not None and fl.size != nk.size) or ct.size != nk.size or mk.dtype != EVENT_MARKER or mk.ndim != 1 or mk.size != int(ct.sum(dtype=np.uint64)):
-            raise MtrError(MTR_E_INVALID, "anim events: one flag word and one marker count per clip, markers of dtype EVENT_MARKER [sum of counts]")
+        if ct.size != nk.size or mk.dtype != EVENT_MARKER or mk.ndim != 1 or mk.size != int(ct.sum(dtype=np.uint64)):
+            raise MtrError(MTR_E_INVALID, msg)
         mk = np.ascontiguousarray(mk)
         h = C.c_void_p()
         dev.check(lib.mtr_anim_events_create(dev._h, nk.size, _p(nk), _p(fl), _p(ct), _p(mk) if mk.size else None, max_instances, C.byref(h)))
@@ -937,24 +973,13 @@ class AnimEvents:
         if not isinstance(steps, torch.Tensor) or steps.dim() != 3 or steps.shape[1] < 1 or steps.shape[2] * steps.element_size() != ROOT_STEP.itemsize:
             raise MtrError(MTR_E_INVALID, "events steps: a tensor [n, S, 16 bytes] on the GPU")
         n, S = steps.shape[0], steps.shape[1]
-        _play_tensor(steps, self.dev, "events steps", ROOT_STEP.itemsize, 16, n * S)
-        used = [steps]
-        cap = 0
-        if out is not None:
-            cap = _play_tensor(out, self.dev, "events list", EVENT.itemsize, 16, None)
-            used.append(out)
-        if getattr(count, "dtype", None) != torch.int32:
-            raise MtrError(MTR_E_INVALID, "events count: an int32 tensor [2] on the GPU")
-        _play_tensor(count, self.dev, "events count", 4, 4, 2)
-        used.append(count)
+        a = _InPlaceArgs(self.dev)
+        a.add(steps, "events steps", ROOT_STEP.itemsize, 16, n * S)
+        cap = a.add(out, "events list", EVENT.itemsize, 16, None) if out is not None else 0
+        a.add(count, "events count", 4, 4, 2, torch.int32, "events count: an int32 tensor [2] on the GPU")
         if bits is not None:
-            if getattr(bits, "dtype", None) != torch.int32:
-                raise MtrError(MTR_E_INVALID, "events bits: an int32 tensor [n] on the GPU")
-            _play_tensor(bits, self.dev, "events bits", 4, 4, n)
-            used.append(bits)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        cur = stream if stream is not None else torch.cuda.current_stream(steps.device)
-        _on_stream(self.dev, cur, lib.mtr_anim_events_collect_device, (self._h, ptr(steps), S, n, float(min_weight), ptr(out), cap, ptr(count), ptr(bits)), used)
+            a.add(bits, "events bits", 4, 4, n, torch.int32, "events bits: an int32 tensor [n] on the GPU")
+        a.call(lib.mtr_anim_events_collect_device, (self._h, a.ptr(steps), S, n, float(min_weight), a.ptr(out), cap, a.ptr(count), a.ptr(bits)), stream)
 
     def collect_host(self, steps: np.ndarray, min_weight: float, capacity: int, out: Optional[np.ndarray] = None, bits: Optional[np.ndarray] = None,
                      want_bits: bool = True):
@@ -976,28 +1001,23 @@ class AnimEvents:
         self.dev.check(lib.mtr_anim_events_collect_host(self._h, _p(sp), S, n, float(min_weight), _p(ol) if capacity else None, capacity, _p(ct), _p(bt)))
         return ol, ct, bt
 
-    def close(self):
-        if self._h:
-            lib.mtr_anim_events_destroy(self._h)
-            self._h = None
 
-
-class AnimBlend:
+class AnimBlend(_Set):
     """A blend set (include/mtr.h, SPEC.md section 23): sample points in a 1-D or 2-D parameter space that each carry a LOOP
     clip.  ``nkeys``, ``rates`` and ``clip_flags`` are what an AnimPlayer takes; ``samples`` a BLEND_SAMPLE array, ``tris`` a
     BLEND_TRI array or None for a 1-D space (``anim_blend.build_1d`` / ``build_2d`` make them from points); ``param_x`` and
     ``param_y`` name the floats of an instance's row of ``nparams`` parameters, ``damp`` is the smoothing rate in 1/seconds
     (inf: none), for calls of up to ``max_instances`` instances."""
+    _destroy = "mtr_anim_blend_destroy"
 
     def __init__(self, dev: Device, nkeys, rates, clip_flags, samples, tris=None, nparams: int = 1, param_x: int = 0, param_y: int = 0,
                  damp: float = float("inf"), max_instances: int = 1):
-        nk = np.ascontiguousarray(np.asarray(nkeys, dtype=np.uint32).reshape(-1))
-        rt = np.ascontiguousarray(np.asarray(rates, dtype=np.float32).reshape(-1))
-        fl = None if clip_flags is None else np.ascontiguousarray(np.asarray(clip_flags, dtype=np.uint32).reshape(-1))
+        msg = "anim blend: one key count, rate and flag word per clip, samples of dtype BLEND_SAMPLE [K], triangles of dtype BLEND_TRI [T]"
+        nk, fl, rt = _clip_arrays(msg, nkeys, clip_flags, rates)
         sm = np.asarray(samples)
         tr = np.zeros(0, dtype=BLEND_TRI) if tris is None else np.asarray(tris)
-        if rt.size != nk.size or (fl is not None and fl.size != nk.size) or sm.dtype != BLEND_SAMPLE or sm.ndim != 1 or tr.dtype != BLEND_TRI or tr.ndim != 1:
-            raise MtrError(MTR_E_INVALID, "anim blend: one key count, rate and flag word per clip, samples of dtype BLEND_SAMPLE [K], triangles of dtype BLEND_TRI [T]")
+        if sm.dtype != BLEND_SAMPLE or sm.ndim != 1 or tr.dtype != BLEND_TRI or tr.ndim != 1:
+            raise MtrError(MTR_E_INVALID, msg)
         if not (0 <= param_x < 1 << 32 and 0 <= param_y < 1 << 32):
             raise MtrError(MTR_E_INVALID, "anim blend: param_x and param_y are parameter indices")
         sm, tr = np.ascontiguousarray(sm), np.ascontiguousarray(tr)
@@ -1013,29 +1033,16 @@ class AnimBlend:
         ROOT_STEP records per instance into ``out_steps`` ([n, 3, 16] bytes) and the three shares into ``out_shares`` (float32
         [n, 3]), in stream order on ``stream`` (a torch stream; None: torch.cuda.current_stream())."""
         import torch
-        n = _play_tensor(states, self.dev, "blend states", BLEND_STATE.itemsize, 16, None)
-        if getattr(params, "dtype", None) != torch.float32:
-            raise MtrError(MTR_E_INVALID, "blend params: a float32 tensor [n, nparams] on the GPU")
-        _play_tensor(params, self.dev, "blend params", 4, 4, n * self.nparams)
-        used = [states, params]
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        nl = 0
-        if out_layers is not None:
-            nl = _play_tensor(out_layers, self.dev, "blend out_layers", ANIM_LAYER.itemsize, 16, None)
-            if nl % n:
-                raise MtrError(MTR_E_INVALID, "blend out_layers: n x L layers of 16 bytes")
-            nl //= n
-            used.append(out_layers)
+        a = _InPlaceArgs(self.dev)
+        n = a.add(states, "blend states", BLEND_STATE.itemsize, 16, None)
+        a.add(params, "blend params", 4, 4, n * self.nparams, torch.float32, "blend params: a float32 tensor [n, nparams] on the GPU")
+        nl = a.layers(out_layers, "blend out_layers", n)
         if out_steps is not None:
-            _play_tensor(out_steps, self.dev, "blend out_steps", ROOT_STEP.itemsize, 16, 3 * n)
-            used.append(out_steps)
+            a.add(out_steps, "blend out_steps", ROOT_STEP.itemsize, 16, 3 * n)
         if out_shares is not None:
-            if getattr(out_shares, "dtype", None) != torch.float32:
-                raise MtrError(MTR_E_INVALID, "blend out_shares: a float32 tensor [n, 3] on the GPU")
-            _play_tensor(out_shares, self.dev, "blend out_shares", 4, 4, 3 * n)
-            used.append(out_shares)
-        cur = stream if stream is not None else torch.cuda.current_stream(states.device)
-        _on_stream(self.dev, cur, lib.mtr_anim_blend_advance_device, (self._h, ptr(states), ptr(params), n, float(dt), ptr(out_layers), nl, ptr(out_steps), ptr(out_shares)), used)
+            a.add(out_shares, "blend out_shares", 4, 4, 3 * n, torch.float32, "blend out_shares: a float32 tensor [n, 3] on the GPU")
+        a.call(lib.mtr_anim_blend_advance_device,
+               (self._h, a.ptr(states), a.ptr(params), n, float(dt), a.ptr(out_layers), nl, a.ptr(out_steps), a.ptr(out_shares)), stream)
 
     def advance_host(self, states: np.ndarray, params: np.ndarray, dt: float, nlayers: int = 0, layers: Optional[np.ndarray] = None, want_steps: bool = True,
                      want_shares: bool = True):
@@ -1049,23 +1056,17 @@ class AnimBlend:
         pr = np.ascontiguousarray(np.asarray(params, dtype=np.float32))
         if pr.shape != (n, self.nparams):
             raise MtrError(MTR_E_INVALID, "blend params: float32 [n, nparams]")
-        ol = None
-        if nlayers:
-            ol = np.zeros((n, nlayers), dtype=ANIM_LAYER) if layers is None else np.ascontiguousarray(layers).copy().reshape(n, nlayers)
+        ol = _layers_in(n, nlayers, layers)
         os_ = np.zeros((n, 3), dtype=ROOT_STEP) if want_steps else None
         sh = np.zeros((n, 3), dtype=np.float32) if want_shares else None
         self.dev.check(lib.mtr_anim_blend_advance_host(self._h, _p(st), _p(pr), n, float(dt), _p(ol), nlayers, _p(os_), _p(sh)))
         return st, ol, os_, sh
 
-    def close(self):
-        if self._h:
-            lib.mtr_anim_blend_destroy(self._h)
-            self._h = None
 
-
-class AnimIK:
+class AnimIK(_Set):
     """An IK set (include/mtr.h, SPEC.md section 17): the parents of a skeleton of ``njoints`` joints (a root: 255 or itself)
     and 1 to 4 chains, an ANIM_IK_CHAIN array or a list of dicts of its fields (kind, joint, optionally axis and flags)."""
+    _destroy = "mtr_anim_ik_destroy"
 
     def __init__(self, dev: Device, parents, chains):
         par = np.ascontiguousarray(np.asarray(parents, dtype=np.uint8).reshape(-1))
@@ -1086,16 +1087,11 @@ class AnimIK:
         dev.check(lib.mtr_anim_ik_create(dev._h, par.size, _p(par), ch.size, _p(ch) if ch.size else None, C.byref(h)))
         self.dev, self._h, self.njoints, self.nchains = dev, h, par.size, ch.size
 
-    def close(self):
-        if self._h:
-            lib.mtr_anim_ik_destroy(self._h)
-            self._h = None
-
-
-class AnimSpring:
+class AnimSpring(_Set):
     """A spring set (include/mtr.h, SPEC.md section 24): the parents of a skeleton of ``njoints`` joints (a root: 255 or itself)
     and 1 to 16 springs, a SPRING array or a list of dicts of its fields (joint and tail, optionally stiffness, drag and
     gravity).  mt_renderer_amd.anim_spring.chain makes the records of a chain of joints."""
+    _destroy = "mtr_anim_spring_destroy"
 
     def __init__(self, dev: Device, parents, springs):
         par = np.ascontiguousarray(np.asarray(parents, dtype=np.uint8).reshape(-1))
@@ -1114,15 +1110,10 @@ class AnimSpring:
         dev.check(lib.mtr_anim_spring_create(dev._h, par.size, _p(par), sp.size, _p(sp) if sp.size else None, C.byref(h)))
         self.dev, self._h, self.njoints, self.nsprings = dev, h, par.size, sp.size
 
-    def close(self):
-        if self._h:
-            lib.mtr_anim_spring_destroy(self._h)
-            self._h = None
-
-
-class AnimMasks:
+class AnimMasks(_Set):
     """A mask set for animation layers (include/mtr.h, SPEC.md section 16): weights [nmasks, njoints] in [0, 1], resident
     in HBM.  A layer's mask index 0 is the built-in mask of ones, index k >= 1 is weights[k - 1]."""
+    _destroy = "mtr_anim_masks_destroy"
 
     def __init__(self, dev: Device, njoints: int, weights):
         w = _f32(weights)
@@ -1133,16 +1124,11 @@ class AnimMasks:
         dev.check(lib.mtr_anim_masks_create(dev._h, njoints, w.shape[0], _p(w), C.byref(h)))
         self.dev, self._h, self.njoints, self.nmasks = dev, h, njoints, w.shape[0]
 
-    def close(self):
-        if self._h:
-            lib.mtr_anim_masks_destroy(self._h)
-            self._h = None
-
-
-class Anim:
+class Anim(_Set):
     """An animation set (include/mtr.h, SPEC.md section 14): clips of uniformly spaced keys for ``njoints`` joints, resident
     in HBM.  clips: a list of (keys, flags); keys is [nkeys, njoints, 12] float32 (t.xyz 0 | q.xyzw | s.xyz 0) or an
     ANIM_KEY array [nkeys, njoints]; flags 0 or CLIP_LOOP."""
+    _destroy = "mtr_anim_destroy"
 
     def __init__(self, dev: Device, njoints: int, clips, _handle=None):
         if _handle is not None:  # AnimTracks: created already
@@ -1206,12 +1192,6 @@ class Anim:
                                                   _p(ly), ly.shape[1], _p(tg) if tg is not None else None, _p(st), _p(mo) if mo is not None else None,
                                                   float(dt), n, _p(out), out.size))
         return out, st
-
-    def close(self):
-        if self._h:
-            lib.mtr_anim_destroy(self._h)
-            self._h = None
-
 
 def anim_track_arrays(njoints: int, clips):
     """The arrays of mtr_anim_create_tracks from a list of track clips (nticks, flags, tracks, times, values): tracks an

@@ -327,7 +327,7 @@ struct mtr_batch {
 
 namespace mtr_host {
 
-// What the five set handles below share: device memory `d`, uploaded once, and the event that covers its readers.  `last` is
+// What the nine set handles below share: device memory `d`, uploaded once, and the event that covers its readers.  `last` is
 // recorded behind every kernel that reads d (set_after); a kernel queued on another stream than the one before first waits
 // for it (set_before), so the one event always covers every reader and the set's destroy can park d behind it (set_park).
 struct DeviceSet {
@@ -560,24 +560,60 @@ inline hipStream_t caller_stream(const mtr_device* d, void* hip_stream) { return
 struct Part { const void* p; size_t bytes; };
 // Allocates s->d for the parts behind each other, uploads them in order and creates s->last; "<what> upload: ..." on failure
 int32_t set_upload(DeviceSet* s, const char* what, std::initializer_list<Part> parts);
+// One entry of the clip table the clock sets share (players, controllers, event sets, blend sets; play_math.h: PlayClip),
+// validated and written: out = period, flags, rate (rates == nullptr: 0, and no rate check), key count.  The one place that
+// forms the period, so the sets' periods are bit-equal (SPEC.md sections 21 to 23).  "<who>: clip <c> has ..." on failure.
+constexpr size_t kClipMaxKeys = (size_t)1 << 24;
+int32_t clip_entry(mtr_device* d, const char* who, size_t c, const uint32_t* nkeys, uint32_t flags, const float* rates, uint32_t* out);
 // around a kernel on `st` that reads (a player: also writes) the set: see DeviceSet::last
 int32_t set_before(DeviceSet* s, hipStream_t st);
 int32_t set_after(DeviceSet* s, hipStream_t st);
 // a kernel may still read the set: d is parked behind the event of the last one, collected by a later submit
 void set_park(DeviceSet* s);
-// Device scratch of `words` 4-byte words for one synchronous host call: run(scratch) queues copies in, kernels and copies out
-// on the copy stream, which is waited for also when a step failed, since the scratch is freed next.
-template <class F>
-int32_t round_trip(mtr_device* d, size_t words, F&& run) {
-    float* tmp = nullptr;
-    int32_t rc = dev_alloc(d, &tmp, words);
-    if (rc) return rc;
-    rc = run(tmp);
-    const hipError_t e = hipStreamSynchronize(d->s_copy);
-    (void)hipFree(tmp);
-    if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    return rc;
-}
+// Device scratch for one synchronous host call: the caller's arrays as parts of one block, part behind part in the order they
+// were named.  A part of 0 words is absent: it takes no room, dev() is nullptr and up / down skip it.
+struct StagedPart {
+    void* host;
+    size_t words;  // 4-byte words
+    char* at;      // where the part starts in the block (an absent part: where the next one does), set by StagedBlock::run
+    template <class T>
+    T* dev() const { return words ? reinterpret_cast<T*>(at) : nullptr; }
+};
+struct StagedBlock {
+    mtr_device* d;
+    StagedPart parts[6];
+    int nparts = 0;
+    explicit StagedBlock(mtr_device* dev) : d(dev) {}
+    StagedPart& part(const void* host, size_t words) { return parts[nparts++] = StagedPart{const_cast<void*>(host), words, nullptr}; }
+    // copies on the copy stream, in the order given: host to device, device to host
+    int32_t up(std::initializer_list<const StagedPart*> ps) {
+        for (const StagedPart* p : ps)
+            if (p->words) HIPCHK(d, hipMemcpyAsync(p->at, p->host, p->words * 4, hipMemcpyHostToDevice, d->s_copy));
+        return MTR_OK;
+    }
+    int32_t down(std::initializer_list<const StagedPart*> ps) {
+        for (const StagedPart* p : ps)
+            if (p->words) HIPCHK(d, hipMemcpyAsync(p->host, p->at, p->words * 4, hipMemcpyDeviceToHost, d->s_copy));
+        return MTR_OK;
+    }
+    // Allocates the block and places the parts; call() queues copies in, kernels and copies out on the copy stream, which is
+    // waited for also when a step failed, since the block is freed next.
+    template <class F>
+    int32_t run(F&& call) {
+        size_t words = 0;
+        for (int i = 0; i < nparts; i++) words += parts[i].words;
+        uint32_t* block = nullptr;
+        int32_t rc = dev_alloc(d, &block, words);
+        if (rc) return rc;
+        char* at = reinterpret_cast<char*>(block);
+        for (int i = 0; i < nparts; i++) { parts[i].at = at; at += parts[i].words * 4; }
+        rc = call();
+        const hipError_t e = hipStreamSynchronize(d->s_copy);
+        (void)hipFree(block);
+        if (!rc && e != hipSuccess) rc = fail(d, MTR_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+        return rc;
+    }
+};
 // One animate call: which sets it reads and where its records lie in device memory.  kind says which records: one state per
 // instance, nlayers layers per instance (masks optional), such layers and then ik->nchains targets per instance, or such
 // layers, targets where there is an IK set (optional here) and spring->nsprings spring states per instance, read and written.

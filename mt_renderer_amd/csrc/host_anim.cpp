@@ -52,6 +52,20 @@ int32_t set_upload(DeviceSet* s, const char* what, std::initializer_list<Part> p
     return fail(d, MTR_E_HIP, std::string(what) + " upload: " + hipGetErrorString(e));
 }
 
+int32_t clip_entry(mtr_device* d, const char* who, size_t c, const uint32_t* nkeys, uint32_t flags, const float* rates, uint32_t* out) {
+    auto bad = [&](const char* what) { return fail(d, MTR_E_INVALID, std::string(who) + ": clip " + std::to_string(c) + " " + what); };
+    if (nkeys[c] == 0 || nkeys[c] > kClipMaxKeys) return bad("has no keys or more than 2^24");
+    if (flags & ~MTR_CLIP_LOOP) return bad("has unknown flag bits");
+    if (rates && !std::isfinite(rates[c])) return bad("has a rate that is not finite");
+    const float period = (flags & MTR_CLIP_LOOP) ? (float)nkeys[c] : (float)(nkeys[c] - 1u);  // exact: at most 2^24
+    std::memcpy(&out[0], &period, 4);
+    out[1] = flags;
+    out[2] = 0u;
+    if (rates) std::memcpy(&out[2], &rates[c], 4);
+    out[3] = nkeys[c];
+    return MTR_OK;
+}
+
 int32_t set_before(DeviceSet* s, hipStream_t st) {
     if (s->recorded && s->last_stream != st) HIPCHK(s->dev, hipStreamWaitEvent(st, s->last, 0));
     return MTR_OK;
@@ -287,16 +301,14 @@ int32_t anim_sample(AnimCall c, size_t rec_words, size_t target_words, size_t n,
     mtr_device* d = c.anim->dev;
     int32_t rc = anim_check(d, nullptr, c, no_room);
     if (rc || !n) return rc;
-    const size_t need = n * c.anim->njoints * 16, rw = n * rec_words, tw = n * target_words;
-    return round_trip(d, need + rw + tw, [&](float* tmp) -> int32_t {
-        HIPCHK(d, hipMemcpyAsync(tmp + need, c.recs, rw * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
-        if (tw) HIPCHK(d, hipMemcpyAsync(tmp + need + rw, c.targets, tw * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
-        c.recs = tmp + need;
-        c.targets = tmp + need + rw;
-        int32_t r2 = anim_enqueue(c, nullptr, tmp, (uint32_t)n, d->s_copy);
+    StagedBlock blk(d);
+    StagedPart &p_locals = blk.part(out_locals, n * c.anim->njoints * 16), &p_recs = blk.part(c.recs, n * rec_words), &p_targets = blk.part(c.targets, n * target_words);
+    return blk.run([&]() -> int32_t {
+        int32_t r2 = blk.up({&p_recs, &p_targets});
         if (r2) return r2;
-        HIPCHK(d, hipMemcpyAsync(out_locals, tmp, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
-        return MTR_OK;
+        c.recs = p_recs.at; c.targets = p_targets.dev<void>();
+        if ((r2 = anim_enqueue(c, nullptr, p_locals.dev<float>(), (uint32_t)n, d->s_copy))) return r2;
+        return blk.down({&p_locals});
     });
 }
 
@@ -592,12 +604,12 @@ int32_t mtr_anim_root_deltas(mtr_anim* traj, mtr_anim_root* root, const mtr_root
     int32_t rc = root_check(d, traj, root, nsteps, true);
     if (rc) return rc;
     // the matrices, then the steps (n * 64 bytes in: 16-byte aligned)
-    return round_trip(d, n * 16 + n * nsteps * 4, [&](float* tmp) -> int32_t {
-        HIPCHK(d, hipMemcpyAsync(tmp + n * 16, steps, n * nsteps * sizeof(mtr_root_step), hipMemcpyHostToDevice, d->s_copy));
-        int32_t r2 = root_enqueue(traj, root, tmp + n * 16, nsteps, n, nullptr, tmp, d->s_copy);
-        if (r2) return r2;
-        HIPCHK(d, hipMemcpyAsync(out, tmp, n * 64, hipMemcpyDeviceToHost, d->s_copy));
-        return MTR_OK;
+    StagedBlock blk(d);
+    StagedPart &p_out = blk.part(out, n * 16), &p_steps = blk.part(steps, n * nsteps * 4);
+    return blk.run([&]() -> int32_t {
+        int32_t r2;
+        if ((r2 = blk.up({&p_steps})) || (r2 = root_enqueue(traj, root, p_steps.at, nsteps, n, nullptr, p_out.dev<float>(), d->s_copy))) return r2;
+        return blk.down({&p_out});
     });
 }
 

@@ -579,13 +579,15 @@ int32_t mtr_batch_sockets(mtr_batch* src, const mtr_attach* recs, size_t n, floa
     // the matrices, then the records (n * 64 bytes in: 16-byte aligned).  The version is pinned once the scratch is there
     // and stays pinned until the stream has drained.
     SrcRead rd;
-    rc = round_trip(d, n * 16 + n * MTR_ATTACH_WORDS, [&](float* tmp) -> int32_t {
+    StagedBlock blk(d);
+    StagedPart &p_out = blk.part(out, n * 16), &p_recs = blk.part(recs, n * MTR_ATTACH_WORDS);
+    rc = blk.run([&]() -> int32_t {
         sockets_pin(src, rd);
-        HIPCHK(d, hipMemcpyAsync(tmp + n * 16, recs, n * sizeof(mtr_attach), hipMemcpyHostToDevice, s));
-        int32_t r2 = src_read_launch(rd, s, [&](const mtr_batch::Ver& sv) { return attach_launch(src, sv, tmp + n * 16, n, tmp, s); });
-        if (r2) return r2;
-        HIPCHK(d, hipMemcpyAsync(out, tmp, n * 64, hipMemcpyDeviceToHost, s));
-        return MTR_OK;
+        int32_t r2;
+        if ((r2 = blk.up({&p_recs})) ||
+            (r2 = src_read_launch(rd, s, [&](const mtr_batch::Ver& sv) { return attach_launch(src, sv, p_recs.at, n, p_out.dev<float>(), s); })))
+            return r2;
+        return blk.down({&p_out});
     });
     if (rd.b) sockets_unpin(rd, s);  // not pinned only where the scratch could not be allocated
     return rc;

@@ -11,7 +11,7 @@ namespace mtr_host {
 
 namespace {
 
-constexpr size_t kBlendMaxInstances = (size_t)1 << 27, kBlendMaxKeys = (size_t)1 << 24, kBlendMaxSamples = 32, kBlendMaxTris = 64, kBlendMaxParams = 16;
+constexpr size_t kBlendMaxInstances = (size_t)1 << 27, kBlendMaxSamples = 32, kBlendMaxTris = 64, kBlendMaxParams = 16;
 
 // what every advance call checks before it touches anything; device: the pointers are device memory and must be aligned
 int32_t blend_check(const mtr_anim_blend* bl, const void* states, const void* params, size_t n, const void* layers, size_t nlayers, const void* steps,
@@ -69,7 +69,7 @@ int32_t mtr_anim_blend_create(mtr_device* d, size_t nclips, const uint32_t* nkey
                               size_t max_instances, mtr_anim_blend** out) {
     if (!d || !out) return MTR_E_INVALID;
     *out = nullptr;
-    if (nclips == 0 || nclips > kBlendMaxKeys) return fail(d, MTR_E_INVALID, "anim blend: 1 to 2^24 clips");
+    if (nclips == 0 || nclips > kClipMaxKeys) return fail(d, MTR_E_INVALID, "anim blend: 1 to 2^24 clips");
     if (!nkeys || !rates) return fail(d, MTR_E_INVALID, "anim blend: no key counts or no rates");
     if (!samples || nsamples == 0 || nsamples > kBlendMaxSamples) return fail(d, MTR_E_INVALID, "anim blend: 1 to 32 samples");
     if (ntris > kBlendMaxTris || (ntris > 0 && !tris)) return fail(d, MTR_E_INVALID, "anim blend: 0 to 64 triangles");
@@ -78,18 +78,9 @@ int32_t mtr_anim_blend_create(mtr_device* d, size_t nclips, const uint32_t* nkey
     if (!(damp > 0.0f)) return fail(d, MTR_E_INVALID, "anim blend: damp must be above 0 (+inf: no smoothing)");
     if (max_instances == 0 || max_instances > kBlendMaxInstances) return fail(d, MTR_E_INVALID, "anim blend: 1 to 2^27 instances");
     std::vector<uint32_t> img((nclips + nsamples + ntris) * 4);
-    for (size_t c = 0; c < nclips; c++) {
-        const uint32_t fl = clip_flags ? clip_flags[c] : 0u;
-        const std::string who = "anim blend: clip " + std::to_string(c) + " ";
-        if (nkeys[c] == 0 || nkeys[c] > kBlendMaxKeys) return fail(d, MTR_E_INVALID, who + "has no keys or more than 2^24");
-        if (fl & ~MTR_CLIP_LOOP) return fail(d, MTR_E_INVALID, who + "has unknown flag bits");
-        if (!std::isfinite(rates[c])) return fail(d, MTR_E_INVALID, who + "has a rate that is not finite");
-        const float period = (fl & MTR_CLIP_LOOP) ? (float)nkeys[c] : (float)(nkeys[c] - 1u);  // exact: at most 2^24; the player's
-        std::memcpy(&img[c * 4], &period, 4);
-        img[c * 4 + 1] = fl;
-        std::memcpy(&img[c * 4 + 2], &rates[c], 4);
-        img[c * 4 + 3] = nkeys[c];
-    }
+    int32_t rc;
+    for (size_t c = 0; c < nclips; c++)
+        if ((rc = clip_entry(d, "anim blend", c, nkeys, clip_flags ? clip_flags[c] : 0u, rates, &img[c * 4]))) return rc;
     for (size_t k = 0; k < nsamples; k++) {
         const mtr_blend_sample& sm = samples[k];
         const std::string who = "anim blend: sample " + std::to_string(k) + " ";
@@ -115,8 +106,7 @@ int32_t mtr_anim_blend_create(mtr_device* d, size_t nclips, const uint32_t* nkey
         for (int j = 0; j < 3; j++) img[(nclips + nsamples + k) * 4 + j] = v[j];
         img[(nclips + nsamples + k) * 4 + 3] = 0u;
     }
-    int32_t rc = set_device(d);
-    if (rc) return rc;
+    if ((rc = set_device(d))) return rc;
     auto bl = std::make_unique<mtr_anim_blend>();
     bl->dev = d; bl->nclips = (uint32_t)nclips; bl->nsamples = (uint32_t)nsamples; bl->ntris = (uint32_t)ntris; bl->nparams = (uint32_t)nparams;
     bl->param_x = param_x; bl->param_y = ntris ? param_y : 0u; bl->damp = damp; bl->max_instances = (uint32_t)max_instances;
@@ -125,11 +115,7 @@ int32_t mtr_anim_blend_create(mtr_device* d, size_t nclips, const uint32_t* nkey
     return MTR_OK;
 }
 
-void mtr_anim_blend_destroy(mtr_anim_blend* bl) {
-    if (!bl) return;
-    set_park(bl);
-    delete bl;
-}
+void mtr_anim_blend_destroy(mtr_anim_blend* bl) { set_destroy(bl); }
 
 int32_t mtr_anim_blend_advance_device(mtr_anim_blend* bl, mtr_blend_state* states_dev, const float* params_dev, size_t n, float dt, mtr_anim_layer* out_layers_dev,
                                       size_t nlayers, mtr_root_step* out_steps_dev, float* out_shares_dev, void* hip_stream) {
@@ -146,23 +132,16 @@ int32_t mtr_anim_blend_advance_host(mtr_anim_blend* bl, mtr_blend_state* states,
     int32_t rc = blend_check(bl, states, params, n, out_layers, nlayers, out_steps, out_shares, false);
     if (rc) return rc;
     // one block: the states, the layers and the steps (16-byte words), then the parameter rows and the shares
-    const size_t w_states = n * 4, w_layers = out_layers ? n * nlayers * 4 : 0, w_steps = out_steps ? n * 12 : 0, w_params = n * bl->nparams,
-                 w_shares = out_shares ? n * 3 : 0;
-    hipStream_t s = d->s_copy;
-    return round_trip(d, w_states + w_layers + w_steps + w_params + w_shares, [&](float* scratch) -> int32_t {
-        uint32_t* tmp = reinterpret_cast<uint32_t*>(scratch);
-        uint32_t *t_layers = tmp + w_states, *t_steps = t_layers + w_layers, *t_params = t_steps + w_steps, *t_shares = t_params + w_params;
-        HIPCHK(d, hipMemcpyAsync(tmp, states, w_states * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(d, hipMemcpyAsync(t_params, params, w_params * 4, hipMemcpyHostToDevice, s));
-        if (w_layers) HIPCHK(d, hipMemcpyAsync(t_layers, out_layers, w_layers * 4, hipMemcpyHostToDevice, s));  // layers 3.. come back as they went in
-        int32_t r2 = blend_launch(bl, tmp, reinterpret_cast<const float*>(t_params), n, dt, w_layers ? t_layers : nullptr, nlayers, w_steps ? t_steps : nullptr,
-                                  w_shares ? reinterpret_cast<float*>(t_shares) : nullptr, s);
-        if (r2) return r2;
-        HIPCHK(d, hipMemcpyAsync(states, tmp, w_states * 4, hipMemcpyDeviceToHost, s));
-        if (w_layers) HIPCHK(d, hipMemcpyAsync(out_layers, t_layers, w_layers * 4, hipMemcpyDeviceToHost, s));
-        if (w_steps) HIPCHK(d, hipMemcpyAsync(out_steps, t_steps, w_steps * 4, hipMemcpyDeviceToHost, s));
-        if (w_shares) HIPCHK(d, hipMemcpyAsync(out_shares, t_shares, w_shares * 4, hipMemcpyDeviceToHost, s));
-        return MTR_OK;
+    StagedBlock blk(d);
+    StagedPart &p_states = blk.part(states, n * 4), &p_layers = blk.part(out_layers, out_layers ? n * nlayers * 4 : 0),
+               &p_steps = blk.part(out_steps, out_steps ? n * 12 : 0), &p_params = blk.part(params, n * bl->nparams),
+               &p_shares = blk.part(out_shares, out_shares ? n * 3 : 0);
+    return blk.run([&]() -> int32_t {
+        int32_t r2;
+        if ((r2 = blk.up({&p_states, &p_params, &p_layers})) ||  // layers 3.. come back as they went in
+            (r2 = blend_launch(bl, p_states.at, p_params.dev<float>(), n, dt, p_layers.dev<void>(), nlayers, p_steps.dev<void>(), p_shares.dev<float>(), d->s_copy)))
+            return r2;
+        return blk.down({&p_states, &p_layers, &p_steps, &p_shares});
     });
 }
 

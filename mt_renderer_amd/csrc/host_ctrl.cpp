@@ -10,7 +10,7 @@ namespace mtr_host {
 
 namespace {
 
-constexpr size_t kCtrlMaxInstances = (size_t)1 << 27, kCtrlMaxKeys = (size_t)1 << 24, kCtrlMaxNodes = 65535, kCtrlMaxTrans = (size_t)1 << 20,
+constexpr size_t kCtrlMaxInstances = (size_t)1 << 27, kCtrlMaxNodes = 65535, kCtrlMaxTrans = (size_t)1 << 20,
                  kCtrlMaxParams = 16;
 constexpr uint32_t kCtrlFlags = MTR_TR_INTERRUPT | MTR_TR_SELF | MTR_TR_SYNC | MTR_TR_CONSUME;
 
@@ -67,23 +67,16 @@ int32_t mtr_anim_ctrl_create(mtr_device* d, size_t nclips, const uint32_t* nkeys
                              const mtr_ctrl_trans* trans, size_t ntrans, size_t nany, size_t nparams, mtr_anim_ctrl** out) {
     if (!d || !out) return MTR_E_INVALID;
     *out = nullptr;
-    if (nclips == 0 || nclips > kCtrlMaxKeys) return fail(d, MTR_E_INVALID, "anim ctrl: 1 to 2^24 clips");
+    if (nclips == 0 || nclips > kClipMaxKeys) return fail(d, MTR_E_INVALID, "anim ctrl: 1 to 2^24 clips");
     if (!nkeys) return fail(d, MTR_E_INVALID, "anim ctrl: no key counts");
     if (!nodes || nnodes == 0 || nnodes > kCtrlMaxNodes) return fail(d, MTR_E_INVALID, "anim ctrl: 1 to 65535 nodes");
     if (ntrans > kCtrlMaxTrans || (ntrans > 0 && !trans)) return fail(d, MTR_E_INVALID, "anim ctrl: 0 to 2^20 transitions");
     if (nany > ntrans) return fail(d, MTR_E_INVALID, "anim ctrl: more any-state transitions than transitions");
     if (nparams > kCtrlMaxParams) return fail(d, MTR_E_INVALID, "anim ctrl: 0 to 16 parameters");
     std::vector<uint32_t> img(nclips * 4);
-    for (size_t c = 0; c < nclips; c++) {
-        const uint32_t fl = clip_flags ? clip_flags[c] : 0u;
-        if (nkeys[c] == 0 || nkeys[c] > kCtrlMaxKeys) return fail(d, MTR_E_INVALID, "anim ctrl: clip " + std::to_string(c) + " has no keys or more than 2^24");
-        if (fl & ~MTR_CLIP_LOOP) return fail(d, MTR_E_INVALID, "anim ctrl: clip " + std::to_string(c) + " has unknown flag bits");
-        const float period = (fl & MTR_CLIP_LOOP) ? (float)nkeys[c] : (float)(nkeys[c] - 1u);  // exact: at most 2^24; the player's
-        std::memcpy(&img[c * 4], &period, 4);
-        img[c * 4 + 1] = fl;
-        img[c * 4 + 2] = 0u;
-        img[c * 4 + 3] = nkeys[c];
-    }
+    int32_t rc;
+    for (size_t c = 0; c < nclips; c++)
+        if ((rc = clip_entry(d, "anim ctrl", c, nkeys, clip_flags ? clip_flags[c] : 0u, nullptr, &img[c * 4]))) return rc;
     for (size_t i = 0; i < nnodes; i++) {
         const mtr_ctrl_node& nd = nodes[i];
         const std::string who = "anim ctrl: node " + std::to_string(i) + " ";
@@ -103,8 +96,7 @@ int32_t mtr_anim_ctrl_create(mtr_device* d, size_t nclips, const uint32_t* nkeys
                 return fail(d, MTR_E_INVALID, who + "has a condition on a parameter the controller does not have");
         }
     }
-    int32_t rc = set_device(d);
-    if (rc) return rc;
+    if ((rc = set_device(d))) return rc;
     auto c = std::make_unique<mtr_anim_ctrl>();
     c->dev = d; c->nclips = (uint32_t)nclips; c->nnodes = (uint32_t)nnodes; c->ntrans = (uint32_t)ntrans; c->nany = (uint32_t)nany; c->nparams = (uint32_t)nparams;
     const Part p_clips{img.data(), img.size() * 4}, p_nodes{nodes, nnodes * sizeof(mtr_ctrl_node)}, p_trans{trans, ntrans * sizeof(mtr_ctrl_trans)};
@@ -114,11 +106,7 @@ int32_t mtr_anim_ctrl_create(mtr_device* d, size_t nclips, const uint32_t* nkeys
     return MTR_OK;
 }
 
-void mtr_anim_ctrl_destroy(mtr_anim_ctrl* c) {
-    if (!c) return;
-    set_park(c);
-    delete c;
-}
+void mtr_anim_ctrl_destroy(mtr_anim_ctrl* c) { set_destroy(c); }
 
 int32_t mtr_anim_ctrl_step_device(mtr_anim_ctrl* c, mtr_ctrl_state* states_dev, const mtr_play_state* play_dev, float* params_dev, size_t n, float dt,
                                   mtr_play_cmd* cmds_out_dev, uint32_t* counts_dev, void* hip_stream) {
@@ -135,22 +123,15 @@ int32_t mtr_anim_ctrl_step_host(mtr_anim_ctrl* c, mtr_ctrl_state* states, const 
     int32_t rc = ctrl_check(c, states, play, params, n, cmds_out, counts, false);
     if (rc) return rc;
     // one block: the states, the play states and the commands (16-byte words), then the parameter rows and the counts
-    const size_t w_states = n * 4, w_play = n * 8, w_cmds = n * 4, w_params = n * c->nparams, w_counts = counts ? c->ntrans : 0;
-    hipStream_t s = d->s_copy;
-    return round_trip(d, w_states + w_play + w_cmds + w_params + w_counts, [&](float* scratch) -> int32_t {
-        uint32_t* tmp = reinterpret_cast<uint32_t*>(scratch);
-        uint32_t *t_play = tmp + w_states, *t_cmds = t_play + w_play, *t_params = t_cmds + w_cmds, *t_counts = t_params + w_params;
-        HIPCHK(d, hipMemcpyAsync(tmp, states, w_states * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(d, hipMemcpyAsync(t_play, play, w_play * 4, hipMemcpyHostToDevice, s));
-        if (w_params) HIPCHK(d, hipMemcpyAsync(t_params, params, w_params * 4, hipMemcpyHostToDevice, s));
-        if (w_counts) HIPCHK(d, hipMemcpyAsync(t_counts, counts, w_counts * 4, hipMemcpyHostToDevice, s));
-        int32_t r2 = ctrl_launch(c, tmp, t_play, w_params ? reinterpret_cast<float*>(t_params) : nullptr, n, dt, t_cmds, w_counts ? t_counts : nullptr, s);
-        if (r2) return r2;
-        HIPCHK(d, hipMemcpyAsync(states, tmp, w_states * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(d, hipMemcpyAsync(cmds_out, t_cmds, w_cmds * 4, hipMemcpyDeviceToHost, s));
-        if (w_params) HIPCHK(d, hipMemcpyAsync(params, t_params, w_params * 4, hipMemcpyDeviceToHost, s));
-        if (w_counts) HIPCHK(d, hipMemcpyAsync(counts, t_counts, w_counts * 4, hipMemcpyDeviceToHost, s));
-        return MTR_OK;
+    StagedBlock blk(d);
+    StagedPart &p_states = blk.part(states, n * 4), &p_play = blk.part(play, n * 8), &p_cmds = blk.part(cmds_out, n * 4),
+               &p_params = blk.part(params, n * c->nparams), &p_counts = blk.part(counts, counts ? c->ntrans : 0);
+    return blk.run([&]() -> int32_t {
+        int32_t r2;
+        if ((r2 = blk.up({&p_states, &p_play, &p_params, &p_counts})) ||
+            (r2 = ctrl_launch(c, p_states.at, p_play.at, p_params.dev<float>(), n, dt, p_cmds.at, p_counts.dev<uint32_t>(), d->s_copy)))
+            return r2;
+        return blk.down({&p_states, &p_cmds, &p_params, &p_counts});
     });
 }
 

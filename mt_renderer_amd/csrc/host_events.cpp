@@ -10,7 +10,7 @@ namespace mtr_host {
 
 namespace {
 
-constexpr size_t kEvMaxInstances = (size_t)1 << 27, kEvMaxKeys = (size_t)1 << 24, kEvMaxMarkers = (size_t)1 << 24;
+constexpr size_t kEvMaxInstances = (size_t)1 << 27, kEvMaxMarkers = (size_t)1 << 24;
 
 // what every collect call checks before it touches anything; device: the pointers are device memory and must be aligned
 int32_t events_check(const mtr_anim_events* ev, const void* steps, size_t nsteps, size_t n, const void* out, size_t capacity, const void* count,
@@ -67,7 +67,7 @@ int32_t mtr_anim_events_create(mtr_device* d, size_t nclips, const uint32_t* nke
                                const mtr_event_marker* markers, size_t max_instances, mtr_anim_events** out) {
     if (!d || !out) return MTR_E_INVALID;
     *out = nullptr;
-    if (nclips == 0 || nclips > kEvMaxKeys) return fail(d, MTR_E_INVALID, "anim events: 1 to 2^24 clips");
+    if (nclips == 0 || nclips > kClipMaxKeys) return fail(d, MTR_E_INVALID, "anim events: 1 to 2^24 clips");
     if (!nkeys) return fail(d, MTR_E_INVALID, "anim events: no key counts");
     if (max_instances == 0 || max_instances > kEvMaxInstances) return fail(d, MTR_E_INVALID, "anim events: 1 to 2^27 instances");
     size_t total = 0;
@@ -81,17 +81,14 @@ int32_t mtr_anim_events_create(mtr_device* d, size_t nclips, const uint32_t* nke
     const size_t w_ranges = (nclips * 2 + 3) / 4 * 4, w_markers = (total * 2 + 3) / 4 * 4;
     std::vector<uint32_t> img(nclips * 4 + w_ranges + w_markers);
     size_t first = 0;
-    for (size_t c = 0; c < nclips; c++) {
+    int32_t rc;
+    for (size_t c = 0; c < nclips; c++) {  // a clip's entry, then its markers, before the next clip's
         const uint32_t fl = clip_flags ? clip_flags[c] : 0u;
+        if ((rc = clip_entry(d, "anim events", c, nkeys, fl, nullptr, &img[c * 4]))) return rc;
         const std::string who = "anim events: clip " + std::to_string(c) + " ";
-        if (nkeys[c] == 0 || nkeys[c] > kEvMaxKeys) return fail(d, MTR_E_INVALID, who + "has no keys or more than 2^24");
-        if (fl & ~MTR_CLIP_LOOP) return fail(d, MTR_E_INVALID, who + "has unknown flag bits");
         const bool loop = (fl & MTR_CLIP_LOOP) != 0;
-        const float period = loop ? (float)nkeys[c] : (float)(nkeys[c] - 1u);  // exact: at most 2^24; the player's
-        std::memcpy(&img[c * 4], &period, 4);
-        img[c * 4 + 1] = fl;
-        img[c * 4 + 2] = 0u;
-        img[c * 4 + 3] = nkeys[c];
+        float period;
+        std::memcpy(&period, &img[c * 4], 4);
         const uint32_t cnt = counts ? counts[c] : 0u;
         img[nclips * 4 + c * 2] = (uint32_t)first;
         img[nclips * 4 + c * 2 + 1] = cnt;
@@ -105,8 +102,7 @@ int32_t mtr_anim_events_create(mtr_device* d, size_t nclips, const uint32_t* nke
         first += cnt;
     }
     if (total) std::memcpy(&img[nclips * 4 + w_ranges], markers, total * sizeof(mtr_event_marker));
-    int32_t rc = set_device(d);
-    if (rc) return rc;
+    if ((rc = set_device(d))) return rc;
     auto ev = std::make_unique<mtr_anim_events>();
     ev->dev = d; ev->nclips = (uint32_t)nclips; ev->max_instances = (uint32_t)max_instances; ev->nmarkers = (uint32_t)total; ev->max_count = max_count;
     ev->w_ranges = w_ranges; ev->w_markers = w_markers;
@@ -116,11 +112,7 @@ int32_t mtr_anim_events_create(mtr_device* d, size_t nclips, const uint32_t* nke
     return MTR_OK;
 }
 
-void mtr_anim_events_destroy(mtr_anim_events* ev) {
-    if (!ev) return;
-    set_park(ev);
-    delete ev;
-}
+void mtr_anim_events_destroy(mtr_anim_events* ev) { set_destroy(ev); }
 
 int32_t mtr_anim_events_collect_device(mtr_anim_events* ev, const mtr_root_step* steps_dev, size_t nsteps, size_t n, float min_weight, mtr_anim_event* out_dev,
                                        size_t capacity, uint32_t* count_dev, uint32_t* bits_dev, void* hip_stream) {
@@ -138,19 +130,15 @@ int32_t mtr_anim_events_collect_host(mtr_anim_events* ev, const mtr_root_step* s
     if (rc) return rc;
     if (capacity > 0xFFFFFFFFull) return fail(d, MTR_E_INVALID, "events collect: the host hook takes a capacity below 2^32");
     // one block: the steps and the list (16-byte words), then the bits and the two words of the count
-    const size_t w_steps = n * nsteps * 4, w_out = capacity * 4, w_bits = bits ? n : 0;
-    hipStream_t s = d->s_copy;
-    return round_trip(d, w_steps + w_out + w_bits + 2, [&](float* scratch) -> int32_t {
-        uint32_t* tmp = reinterpret_cast<uint32_t*>(scratch);
-        uint32_t *t_out = tmp + w_steps, *t_bits = t_out + w_out, *t_count = t_bits + w_bits;
-        HIPCHK(d, hipMemcpyAsync(tmp, steps, w_steps * 4, hipMemcpyHostToDevice, s));
-        if (w_out) HIPCHK(d, hipMemcpyAsync(t_out, out, w_out * 4, hipMemcpyHostToDevice, s));
-        int32_t r2 = events_launch(ev, tmp, nsteps, n, min_weight, w_out ? t_out : nullptr, capacity, t_count, w_bits ? t_bits : nullptr, s);
-        if (r2) return r2;
-        if (w_out) HIPCHK(d, hipMemcpyAsync(out, t_out, w_out * 4, hipMemcpyDeviceToHost, s));
-        if (w_bits) HIPCHK(d, hipMemcpyAsync(bits, t_bits, w_bits * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(d, hipMemcpyAsync(count, t_count, 8, hipMemcpyDeviceToHost, s));
-        return MTR_OK;
+    StagedBlock blk(d);
+    StagedPart &p_steps = blk.part(steps, n * nsteps * 4), &p_out = blk.part(out, capacity * 4), &p_bits = blk.part(bits, bits ? n : 0),
+               &p_count = blk.part(count, 2);
+    return blk.run([&]() -> int32_t {
+        int32_t r2;
+        if ((r2 = blk.up({&p_steps, &p_out})) ||
+            (r2 = events_launch(ev, p_steps.at, nsteps, n, min_weight, p_out.dev<void>(), capacity, p_count.dev<uint32_t>(), p_bits.dev<uint32_t>(), d->s_copy)))
+            return r2;
+        return blk.down({&p_out, &p_bits, &p_count});
     });
 }
 

@@ -10,7 +10,7 @@ namespace mtr_host {
 
 namespace {
 
-constexpr size_t kPlayMaxInstances = (size_t)1 << 27, kPlayMaxKeys = (size_t)1 << 24, kPlayMaxCmds = ((size_t)1 << 31) - 1;
+constexpr size_t kPlayMaxInstances = (size_t)1 << 27, kPlayMaxCmds = ((size_t)1 << 31) - 1;
 
 struct PlayOuts {
     mtr_anim_state* states = nullptr;
@@ -106,23 +106,14 @@ int32_t mtr_anim_player_create(mtr_device* d, size_t nclips, const uint32_t* nke
                                mtr_anim_player** out) {
     if (!d || !out) return MTR_E_INVALID;
     *out = nullptr;
-    if (nclips == 0 || nclips > kPlayMaxKeys) return fail(d, MTR_E_INVALID, "anim player: at least one clip");
+    if (nclips == 0 || nclips > kClipMaxKeys) return fail(d, MTR_E_INVALID, "anim player: at least one clip");
     if (!nkeys || !rates) return fail(d, MTR_E_INVALID, "anim player: no key counts or no rates");
     if (max_instances == 0 || max_instances > kPlayMaxInstances) return fail(d, MTR_E_INVALID, "anim player: 1 to 2^27 instances");
     std::vector<uint32_t> img(nclips * 4);
-    for (size_t c = 0; c < nclips; c++) {
-        const uint32_t fl = flags ? flags[c] : 0u;
-        if (nkeys[c] == 0 || nkeys[c] > kPlayMaxKeys) return fail(d, MTR_E_INVALID, "anim player: clip " + std::to_string(c) + " has no keys or more than 2^24");
-        if (fl & ~MTR_CLIP_LOOP) return fail(d, MTR_E_INVALID, "anim player: clip " + std::to_string(c) + " has unknown flag bits");
-        if (!std::isfinite(rates[c])) return fail(d, MTR_E_INVALID, "anim player: clip " + std::to_string(c) + " has a rate that is not finite");
-        const float period = (fl & MTR_CLIP_LOOP) ? (float)nkeys[c] : (float)(nkeys[c] - 1u);  // exact: at most 2^24
-        std::memcpy(&img[c * 4], &period, 4);
-        img[c * 4 + 1] = fl;
-        std::memcpy(&img[c * 4 + 2], &rates[c], 4);
-        img[c * 4 + 3] = nkeys[c];
-    }
-    int32_t rc = set_device(d);
-    if (rc) return rc;
+    int32_t rc;
+    for (size_t c = 0; c < nclips; c++)
+        if ((rc = clip_entry(d, "anim player", c, nkeys, flags ? flags[c] : 0u, rates, &img[c * 4]))) return rc;
+    if ((rc = set_device(d))) return rc;
     auto pl = std::make_unique<mtr_anim_player>();
     pl->dev = d; pl->nclips = (uint32_t)nclips; pl->max_instances = (uint32_t)max_instances;
     if ((rc = set_upload(pl.get(), "anim player", {{img.data(), img.size() * 4}, {nullptr, max_instances * 4}}))) return rc;  // the table, the zeroed scratch
@@ -161,28 +152,15 @@ int32_t mtr_anim_player_advance_host(mtr_anim_player* pl, mtr_play_state* states
     int32_t rc = play_check(pl, states, n, cmds, ncmds, host, false);
     if (rc) return rc;
     // one block of 16-byte words: the states, the commands, the steps, the layers, then the animation states (24 bytes each)
-    const size_t w_states = n * 8, w_cmds = ncmds * 4, w_steps = out_steps ? n * 8 : 0, w_layers = out_layers ? n * nlayers * 4 : 0,
-                 w_anim = out_states ? n * 6 : 0;
-    hipStream_t s = d->s_copy;
-    return round_trip(d, w_states + w_cmds + w_steps + w_layers + w_anim, [&](float* scratch) -> int32_t {
-        uint32_t* tmp = reinterpret_cast<uint32_t*>(scratch);
-        uint32_t *t_cmds = tmp + w_states, *t_steps = t_cmds + w_cmds, *t_layers = t_steps + w_steps, *t_anim = t_layers + w_layers;
-        HIPCHK(d, hipMemcpyAsync(tmp, states, w_states * 4, hipMemcpyHostToDevice, s));
-        if (w_cmds) HIPCHK(d, hipMemcpyAsync(t_cmds, cmds, w_cmds * 4, hipMemcpyHostToDevice, s));
-        if (w_layers) HIPCHK(d, hipMemcpyAsync(t_layers, out_layers, w_layers * 4, hipMemcpyHostToDevice, s));
-        int32_t r2 = set_before(pl, s);
-        if (r2) return r2;
-        PlayOuts o;
-        o.states = w_anim ? reinterpret_cast<mtr_anim_state*>(t_anim) : nullptr;
-        o.layers = w_layers ? reinterpret_cast<mtr_anim_layer*>(t_layers) : nullptr;
-        o.nlayers = nlayers;
-        o.steps = w_steps ? reinterpret_cast<mtr_root_step*>(t_steps) : nullptr;
-        if ((r2 = play_launch(pl, tmp, n, dt, t_cmds, ncmds, o, s))) return r2;
-        HIPCHK(d, hipMemcpyAsync(states, tmp, w_states * 4, hipMemcpyDeviceToHost, s));
-        if (w_steps) HIPCHK(d, hipMemcpyAsync(out_steps, t_steps, w_steps * 4, hipMemcpyDeviceToHost, s));
-        if (w_layers) HIPCHK(d, hipMemcpyAsync(out_layers, t_layers, w_layers * 4, hipMemcpyDeviceToHost, s));
-        if (w_anim) HIPCHK(d, hipMemcpyAsync(out_states, t_anim, w_anim * 4, hipMemcpyDeviceToHost, s));
-        return MTR_OK;
+    StagedBlock blk(d);
+    StagedPart &p_states = blk.part(states, n * 8), &p_cmds = blk.part(cmds, ncmds * 4), &p_steps = blk.part(out_steps, out_steps ? n * 8 : 0),
+               &p_layers = blk.part(out_layers, out_layers ? n * nlayers * 4 : 0), &p_anim = blk.part(out_states, out_states ? n * 6 : 0);
+    return blk.run([&]() -> int32_t {
+        int32_t r2;
+        if ((r2 = blk.up({&p_states, &p_cmds, &p_layers})) || (r2 = set_before(pl, d->s_copy))) return r2;
+        const PlayOuts o{p_anim.dev<mtr_anim_state>(), p_layers.dev<mtr_anim_layer>(), nlayers, p_steps.dev<mtr_root_step>()};
+        if ((r2 = play_launch(pl, p_states.at, n, dt, p_cmds.at, ncmds, o, d->s_copy))) return r2;  // no commands: where they would lie, unread
+        return blk.down({&p_states, &p_steps, &p_layers, &p_anim});
     });
 }
 

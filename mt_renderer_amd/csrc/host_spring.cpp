@@ -98,23 +98,16 @@ int32_t mtr_anim_sample_spring(mtr_anim* a, mtr_anim_masks* mk, mtr_anim_ik* ik,
         no_room = "n * nlayers layers, n * nsprings spring states and room for n * njoints * 16 floats";
     int32_t rc = anim_check(d, nullptr, c, no_room);
     if (rc || !n) return rc;
-    const size_t need = n * a->njoints * 16, lw = n * nlayers * 4, tw = ik ? n * ik->nchains * 8 : 0, sw = n * sp->nsprings * 8, mw = motion ? n * 16 : 0;
-    return round_trip(d, need + lw + tw + sw + mw, [&](float* tmp) -> int32_t {
-        float* at = tmp + need;
-        HIPCHK(d, hipMemcpyAsync(at, layers, lw * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
-        c.recs = at; at += lw;
-        if (tw) HIPCHK(d, hipMemcpyAsync(at, targets, tw * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
-        c.targets = tw ? at : nullptr; at += tw;
-        HIPCHK(d, hipMemcpyAsync(at, states, sw * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
-        float* const st = at;
-        c.spring_states = at; at += sw;
-        if (mw) HIPCHK(d, hipMemcpyAsync(at, motion, mw * sizeof(float), hipMemcpyHostToDevice, d->s_copy));
-        c.motion = mw ? at : nullptr;
-        int32_t r2 = anim_enqueue(c, nullptr, tmp, (uint32_t)n, d->s_copy);
+    StagedBlock blk(d);
+    StagedPart &p_locals = blk.part(out_locals, n * a->njoints * 16), &p_layers = blk.part(layers, n * nlayers * 4),
+               &p_targets = blk.part(targets, ik ? n * ik->nchains * 8 : 0), &p_states = blk.part(states, n * sp->nsprings * 8),
+               &p_motion = blk.part(motion, motion ? n * 16 : 0);
+    return blk.run([&]() -> int32_t {
+        int32_t r2 = blk.up({&p_layers, &p_targets, &p_states, &p_motion});
         if (r2) return r2;
-        HIPCHK(d, hipMemcpyAsync(out_locals, tmp, need * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
-        HIPCHK(d, hipMemcpyAsync(states, st, sw * sizeof(float), hipMemcpyDeviceToHost, d->s_copy));
-        return MTR_OK;
+        c.recs = p_layers.at; c.targets = p_targets.dev<void>(); c.spring_states = p_states.at; c.motion = p_motion.dev<float>();
+        if ((r2 = anim_enqueue(c, nullptr, p_locals.dev<float>(), (uint32_t)n, d->s_copy))) return r2;
+        return blk.down({&p_locals, &p_states});
     });
 }
 

@@ -11,6 +11,11 @@
 // synchronous hipMemcpy is not traced and the clip, track, mask, IK and root sets are created with the trace off, so the
 // sizes and the order of the parts a create uploads are pinned only through the launchers' offsets here, by the ASan
 // harnesses of each feature (whose launchers read the first and last word of every part) and by the GPU tests.
+// Appended behind that first recording, whose lines stay as they are (its closing line with its counts included): the other
+// clock sets (SPEC.md sections 21 to 23: controllers, event sets, blend sets) and the spring set (section 24), at 3
+// instances; their creates and destroys traced, every optional argument present and absent, a second stream after a first
+// for each set, the rejected clips of the four clock-set creates with the order their checks fire in, and a last line with
+// the counts of the whole run.
 #include "host_all.h"
 using namespace mtr_host;
 
@@ -108,6 +113,62 @@ void mtr_launch_play(const PlayParams& p, hipStream_t s) {
     t += " out_steps=" + B(p.out_steps);
     launched("play", p.n, s, t);
 }
+static std::string flt(float v) { return std::to_string(v); }
+// a synchronous host hook runs on the copy stream over one scratch block: where its parts lie from the block's first part
+static bool host_hook(hipStream_t s);
+void mtr_launch_ctrl(const CtrlParams& p, hipStream_t s) {
+    std::string t = " nnodes=" + num(p.nnodes) + " nany=" + num(p.nany) + " nclips=" + num(p.nclips) + " nparams=" + num(p.nparams) + " dt=" + flt(p.dt);
+    t += " clips=" + B(p.clips) + " nodes=" + off(p.nodes, p.clips) + " trans=" + off(p.trans, p.clips);
+    t += " states=" + B(p.states);
+    t += " play=" + B(p.play);
+    t += " params=" + B(p.params);
+    t += " cmds=" + B(p.cmds);
+    t += " counts=" + B(p.counts);
+    if (host_hook(s)) t += " block: play=" + off(p.play, p.states) + " cmds=" + off(p.cmds, p.states) + " params=" + off(p.params, p.states) + " counts=" + off(p.counts, p.states);
+    launched("ctrl", p.n, s, t);
+}
+void mtr_launch_events(const EventParams& p, hipStream_t s) {
+    std::string t = " nclips=" + num(p.nclips) + " nsteps=" + num(p.nsteps) + " capacity=" + num(p.capacity) + " min_weight=" + flt(p.min_weight);
+    t += " clips=" + B(p.clips) + " ranges=" + off(p.ranges, p.clips) + " markers=" + off(p.markers, p.clips) + " sums=" + off(p.sums, p.clips);
+    t += " steps=" + B(p.steps);
+    t += " out=" + B(p.out);
+    t += " count=" + B(p.count);
+    t += " bits=" + B(p.bits);
+    if (host_hook(s)) t += " block: out=" + off(p.out, p.steps) + " bits=" + off(p.bits, p.steps) + " count=" + off(p.count, p.steps);
+    launched("events", p.n, s, t);
+}
+void mtr_launch_blend(const BlendParams& p, hipStream_t s) {
+    std::string t = " nclips=" + num(p.nclips) + " nsamples=" + num(p.nsamples) + " ntris=" + num(p.ntris) + " nparams=" + num(p.nparams) +
+                    " param_x=" + num(p.param_x) + " param_y=" + num(p.param_y) + " nlayers=" + num(p.nlayers) + " damp=" + flt(p.damp) + " dt=" + flt(p.dt);
+    t += " clips=" + B(p.clips) + " samples=" + off(p.samples, p.clips) + " tris=" + off(p.tris, p.clips);
+    t += " states=" + B(p.states);
+    t += " params=" + B(p.params);
+    t += " out_layers=" + B(p.out_layers);
+    t += " out_steps=" + B(p.out_steps);
+    t += " out_shares=" + B(p.out_shares);
+    if (host_hook(s)) t += " block: out_layers=" + off(p.out_layers, p.states) + " out_steps=" + off(p.out_steps, p.states) + " params=" + off(p.params, p.states) +
+                           " out_shares=" + off(p.out_shares, p.states);
+    launched("blend", p.n, s, t);
+}
+static std::string spring_str(const AnimSpringParams& p) {
+    const AnimIkParams& k = p.ik;
+    std::string s = " nsprings=" + num(p.nsprings) + " nrounds=" + num(p.nrounds) + " dt=" + flt(p.dt) + " springs=" + B(p.springs) + " joint_tab=" + off(p.joint_tab, p.springs);
+    s += " spring_states=" + B(p.states);
+    s += " motion=" + B(p.motion);
+    s += " nchains=" + num(k.nchains) + " ik_path_bytes=" + num(k.path_bytes) + " chains=" + B(k.chains);
+    s += " targets=" + B(k.targets);
+    const bool own = k.paths == k.layers.anim.pose.paths;  // the model's table, or the spring set's copy behind its joint table
+    s += own ? std::string(" ik_paths=pose") : " ik_paths=" + off(k.paths, p.springs) + " ik_path_words=" + off(k.path_words, p.springs);
+    if (!k.layers.anim.pose.imats) {  // a sample call: the local matrices lead its scratch block
+        const void* base = k.layers.anim.pose.out;
+        s += " block: layers=" + off(k.layers.layers, base) + " targets=" + off(k.targets, base) + " spring_states=" + off(p.states, base) + " motion=" + off(p.motion, base);
+    }
+    return s + layers_str(k.layers);
+}
+void mtr_launch_anim_spring(const AnimSpringParams& p, uint32_t n, hipStream_t s) { launched("anim_spring", n, s, spring_str(p)); }
+void mtr_launch_anim_spring_sample(const AnimSpringParams& p, uint32_t n, hipStream_t s) { launched("anim_spring_sample", n, s, spring_str(p)); }
+void mtr_launch_anim_spring_tracks(const AnimSpringParams& p, uint32_t n, hipStream_t s) { launched("anim_spring_tracks", n, s, spring_str(p)); }
+void mtr_launch_anim_spring_tracks_sample(const AnimSpringParams& p, uint32_t n, hipStream_t s) { launched("anim_spring_tracks_sample", n, s, spring_str(p)); }
 void mtr_launch_geom(const GeomParams&, hipStream_t) {}
 void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
 void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
@@ -124,6 +185,7 @@ void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
 
 // ---- calls ----
 static mtr_device* g_dev = nullptr;
+static bool host_hook(hipStream_t s) { return s == g_dev->s_copy; }
 static int g_failed = 0;
 static long g_rejected = 0;
 
@@ -166,6 +228,211 @@ static mtr_anim* make_tracks(mtr_device* d, uint32_t J) {
     mtr_anim* a = nullptr;
     MUST(mtr_anim_create_tracks(d, J, 2, nticks, nullptr, tr.data(), times.data(), values.data(), times.size(), &a));
     return a;
+}
+
+// ---- the clock sets besides the player, and the spring set: 3 instances, 3 clips, a 4-joint chain with 2 springs ----
+static void clock_sets(mtr_device* d, hipStream_t caller) {
+    const uint32_t N = 3, J = 4;
+    const uint32_t nk[3] = {2, 3, 4}, fl[3] = {MTR_CLIP_LOOP, 0, MTR_CLIP_LOOP};
+    const float rates[3] = {30.0f, 24.0f, 12.0f};
+
+    printf("==== clock sets: created ====\n");
+    // a controller with parameters, transitions and an any-state transition, and one with neither parameters nor transitions
+    const mtr_ctrl_node nodes[2] = {{0, 1, 1, 0}, {1, 2, 0, 0}};
+    mtr_ctrl_trans trans[2];
+    memset(trans, 0, sizeof trans);
+    trans[0].target = 0; trans[0].flags = MTR_TR_SELF; trans[0].seconds = 0.25f; trans[0].ncond = 1; trans[0].cond[0] = {1, MTR_OP_GT, 0.5f};
+    trans[1].target = 1; trans[1].flags = MTR_TR_CONSUME; trans[1].ncond = 2; trans[1].cond[0] = {0, MTR_OP_GE, 1.0f}; trans[1].cond[1] = {MTR_CTRL_TIME, MTR_OP_GT, 0.0f};
+    mtr_anim_ctrl *ctl = nullptr, *ctl0 = nullptr;
+    CALL(mtr_anim_ctrl_create(d, 3, nk, fl, nodes, 2, trans, 2, 1, 2, &ctl));
+    const mtr_ctrl_node lone[1] = {{2, 0, 0, 0}};
+    CALL(mtr_anim_ctrl_create(d, 3, nk, nullptr, lone, 1, nullptr, 0, 0, 0, &ctl0));
+    // an event set: two markers on clip 0, none on clip 1, one on clip 2
+    const uint32_t counts[3] = {2, 0, 1};
+    const mtr_event_marker markers[3] = {{0.5f, 7}, {1.5f, 8}, {1.0f, 9}};
+    mtr_anim_events* evs = nullptr;
+    CALL(mtr_anim_events_create(d, 3, nk, fl, counts, markers, N, &evs));
+    // a 1-D blend set of two samples and a 2-D one of one triangle
+    const mtr_blend_sample line[2] = {{0, 0.0f, 0.0f, 0}, {2, 1.0f, 0.0f, 0}};
+    const mtr_blend_sample plane[3] = {{0, 0.0f, 0.0f, 0}, {2, 1.0f, 0.0f, 0}, {0, 0.0f, 1.0f, 0}};
+    const mtr_blend_tri tri[1] = {{{0, 1, 2}, 0}};
+    mtr_anim_blend *bl1 = nullptr, *bl2 = nullptr;
+    CALL(mtr_anim_blend_create(d, 3, nk, fl, rates, line, 2, nullptr, 0, 2, 1, 0, 4.0f, N, &bl1));
+    CALL(mtr_anim_blend_create(d, 3, nk, fl, rates, plane, 3, tri, 1, 2, 0, 1, 4.0f, N, &bl2));
+    // a spring set: the last two joints of a 4-joint chain, two rounds
+    const uint8_t parents[J] = {255, 0, 1, 2};
+    mtr_spring springs[2];
+    memset(springs, 0, sizeof springs);
+    for (uint32_t k = 0; k < 2; k++) { springs[k].joint = 2 + k; springs[k].stiffness = 1.0f; springs[k].drag = 0.5f; springs[k].tail[1] = 1.0f; }
+    mtr_anim_spring* sp = nullptr;
+    CALL(mtr_anim_spring_create(d, J, parents, 2, springs, &sp));
+
+    // what the spring calls need besides: a model of that chain, a batch of 3, a clip set, masks and an IK set over it (trace off)
+    const float verts[9] = {-0.5f, -0.5f, 0.5f, 0.5f, -0.5f, 0.5f, 0.0f, 0.5f, 0.5f};
+    const uint16_t idx[3] = {0, 1, 2};
+    mtr_primitive pr;
+    memset(&pr, 0, sizeof pr);
+    pr.w[0] = 3u << 16; pr.w[2] = 1 | (12u << 16) | (3u << 24); pr.w[7] = 3;
+    mtr_layout lay;
+    memset(&lay, 0, sizeof lay);
+    lay.elements[lay.num_elements++] = mtr_element{MTR_SEM_POSITION, MTR_IEF_F32, 3, 0, 0, 0};
+    mtr_model* m = nullptr;
+    MUST(mtr_model_create(d, verts, sizeof verts, idx, 3, &pr, 1, &lay, nullptr, nullptr, 0, nullptr, &m));
+    std::vector<float> imats((size_t)J * 16, 0.0f), mats((size_t)N * 16, 0.0f);
+    for (uint32_t j = 0; j < J; j++) imats[j * 16] = imats[j * 16 + 5] = imats[j * 16 + 10] = imats[j * 16 + 15] = 1.0f;
+    MUST(mtr_model_set_skeleton(m, parents, imats.data(), J));
+    mtr_batch* b = nullptr;
+    MUST(mtr_batch_create(d, m, N, mats.data(), nullptr, 0, nullptr, &b));
+    mtr_anim* a = make_uniform(d, J, nullptr);
+    std::vector<float> weights((size_t)J, 0.5f);
+    mtr_anim_masks* mk = nullptr;
+    MUST(mtr_anim_masks_create(d, J, 1, weights.data(), &mk));
+    mtr_ik_chain chain = mtr_ik_chain{};
+    chain.kind = MTR_IK_TWO_BONE; chain.joint[0] = 0; chain.joint[1] = 1; chain.joint[2] = 2;
+    mtr_anim_ik* ik = nullptr;
+    MUST(mtr_anim_ik_create(d, J, parents, 1, &chain, &ik));
+
+    // ---- the records, on the host and in "device" memory ----
+    std::vector<mtr_ctrl_state> cs(N, mtr_ctrl_state{0, 0.0f, MTR_CTRL_NONE, 0});
+    std::vector<mtr_play_state> ps(N, mtr_play_state{0, 1, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0});
+    std::vector<float> prm((size_t)N * 2, 0.75f), shares((size_t)N * 3, 0.0f), motion((size_t)N * 16, 0.0f), locals((size_t)N * J * 16, 0.0f);
+    std::vector<mtr_play_cmd> cmds(N, mtr_play_cmd{0, 0, 0.0f, 0.0f});
+    std::vector<uint32_t> fired(2, 0u), count(2, 0u), bits(N, 0u);
+    std::vector<mtr_root_step> steps2((size_t)N * 2, mtr_root_step{0, 0.25f, 1.0f, 1.0f}), steps3((size_t)N * 3, mtr_root_step{0, 0.0f, 0.0f, 0.0f});
+    std::vector<mtr_anim_event> list(4, mtr_anim_event{0, 0, 0, 0.0f});
+    std::vector<mtr_blend_state> bs(N, mtr_blend_state{0.0f, 0.5f, 0.25f, 1.0f});
+    std::vector<mtr_anim_layer> ly3((size_t)N * 3, mtr_anim_layer{0, 0.5f, 0.5f, 1, 0}), ly4((size_t)N * 4, mtr_anim_layer{1, 0.5f, 0.5f, 0, 0});
+    std::vector<mtr_ik_target> tg(N, mtr_ik_target{});
+    std::vector<mtr_spring_state> ss((size_t)N * 2, mtr_spring_state{});
+    mtr_ctrl_state* cs_dev = dev_copy(cs);
+    mtr_play_state* ps_dev = dev_copy(ps);
+    float *prm_dev = dev_copy(prm), *shares_dev = dev_copy(shares), *motion_dev = dev_copy(motion);
+    mtr_play_cmd* cmds_dev = dev_copy(cmds);
+    uint32_t *fired_dev = dev_copy(fired), *count_dev = dev_copy(count), *bits_dev = dev_copy(bits);
+    mtr_root_step *steps2_dev = dev_copy(steps2), *steps3_dev = dev_copy(steps3);
+    mtr_anim_event* list_dev = dev_copy(list);
+    mtr_blend_state* bs_dev = dev_copy(bs);
+    mtr_anim_layer *ly3_dev = dev_copy(ly3), *ly4_dev = dev_copy(ly4);
+    mtr_ik_target* tg_dev = dev_copy(tg);
+    mtr_spring_state* ss_dev = dev_copy(ss);
+
+    // the device variants on the device's own stream and then on the caller's: the second waits for the set's event
+    printf("==== controller ====\n");
+    CALL(mtr_anim_ctrl_step_device(ctl, cs_dev, ps_dev, prm_dev, N, 0.5f, cmds_dev, fired_dev, nullptr));
+    CALL(mtr_anim_ctrl_step_device(ctl, cs_dev, ps_dev, prm_dev, N, 0.5f, cmds_dev, nullptr, caller));
+    CALL(mtr_anim_ctrl_step_device(ctl0, cs_dev, ps_dev, nullptr, N, 0.5f, cmds_dev, nullptr, nullptr));
+    CALL(mtr_anim_ctrl_step_device(ctl0, cs_dev, ps_dev, nullptr, N, 0.5f, cmds_dev, fired_dev, caller));
+    CALL(mtr_anim_ctrl_step_host(ctl, cs.data(), ps.data(), prm.data(), N, 0.5f, cmds.data(), fired.data()));
+    CALL(mtr_anim_ctrl_step_host(ctl, cs.data(), ps.data(), prm.data(), N, 0.5f, cmds.data(), nullptr));
+    CALL(mtr_anim_ctrl_step_host(ctl0, cs.data(), ps.data(), nullptr, N, 0.5f, cmds.data(), nullptr));
+    CALL(mtr_anim_ctrl_step_host(ctl0, cs.data(), ps.data(), nullptr, N, 0.5f, cmds.data(), fired.data()));  // no transitions: no counts to copy
+
+    printf("==== events ====\n");
+    CALL(mtr_anim_events_collect_device(evs, steps2_dev, 2, N, 0.0f, list_dev, 4, count_dev, bits_dev, nullptr));
+    CALL(mtr_anim_events_collect_device(evs, steps2_dev, 2, N, 0.0f, nullptr, 0, count_dev, nullptr, caller));
+    CALL(mtr_anim_events_collect_device(evs, steps2_dev, 2, N, 0.0f, list_dev, 0, count_dev, bits_dev, caller));  // a list and no capacity
+    CALL(mtr_anim_events_collect_host(evs, steps2.data(), 2, N, 0.0f, list.data(), 4, count.data(), bits.data()));
+    CALL(mtr_anim_events_collect_host(evs, steps2.data(), 2, N, 0.0f, list.data(), 4, count.data(), nullptr));
+    CALL(mtr_anim_events_collect_host(evs, steps2.data(), 2, N, 0.0f, nullptr, 0, count.data(), bits.data()));
+    CALL(mtr_anim_events_collect_host(evs, steps2.data(), 1, N, 0.0f, nullptr, 0, count.data(), nullptr));
+
+    printf("==== blend ====\n");
+    CALL(mtr_anim_blend_advance_device(bl1, bs_dev, prm_dev, N, 0.5f, ly4_dev, 4, steps3_dev, shares_dev, nullptr));
+    CALL(mtr_anim_blend_advance_device(bl1, bs_dev, prm_dev, N, 0.5f, nullptr, 0, nullptr, nullptr, caller));
+    CALL(mtr_anim_blend_advance_device(bl2, bs_dev, prm_dev, N, 0.5f, ly4_dev, 4, nullptr, shares_dev, nullptr));
+    CALL(mtr_anim_blend_advance_device(bl2, bs_dev, prm_dev, N, 0.5f, nullptr, 0, steps3_dev, nullptr, caller));
+    CALL(mtr_anim_blend_advance_host(bl1, bs.data(), prm.data(), N, 0.5f, ly4.data(), 4, steps3.data(), shares.data()));
+    CALL(mtr_anim_blend_advance_host(bl1, bs.data(), prm.data(), N, 0.5f, nullptr, 0, nullptr, nullptr));
+    CALL(mtr_anim_blend_advance_host(bl2, bs.data(), prm.data(), N, 0.5f, ly4.data(), 4, nullptr, nullptr));
+    CALL(mtr_anim_blend_advance_host(bl2, bs.data(), prm.data(), N, 0.5f, nullptr, 0, steps3.data(), nullptr));
+    CALL(mtr_anim_blend_advance_host(bl2, bs.data(), prm.data(), N, 0.5f, nullptr, 0, nullptr, shares.data()));
+
+    printf("==== spring ====\n");
+    CALL(mtr_batch_animate_spring_device(b, a, mk, ly3_dev, 3, ik, tg_dev, sp, ss_dev, motion_dev, 0.5f, nullptr));
+    CALL(mtr_batch_animate_spring_device(b, a, nullptr, ly3_dev, 3, nullptr, nullptr, sp, ss_dev, nullptr, 0.5f, caller));
+    CALL(mtr_anim_sample_spring(a, mk, ik, sp, ly3.data(), 3, tg.data(), ss.data(), motion.data(), 0.5f, N, locals.data(), locals.size()));
+    CALL(mtr_anim_sample_spring(a, nullptr, nullptr, sp, ly3.data(), 3, nullptr, ss.data(), nullptr, 0.5f, N, locals.data(), locals.size()));
+    CALL(mtr_anim_sample_spring(a, mk, ik, sp, ly3.data(), 3, tg.data(), ss.data(), nullptr, 0.5f, N, locals.data(), locals.size()));
+    CALL(mtr_anim_sample_spring(a, nullptr, nullptr, sp, ly3.data(), 3, nullptr, ss.data(), motion.data(), 0.5f, N, locals.data(), locals.size()));
+
+    // ---- the clip checks of the four creates: each message, and the order the checks fire in ----
+    printf("==== clock sets: rejected ====\n");
+    mtr_anim_player* no_pl = nullptr;
+    mtr_anim_ctrl* no_ctl = nullptr;
+    mtr_anim_events* no_ev = nullptr;
+    mtr_anim_blend* no_bl = nullptr;
+    const uint32_t nk_none[3] = {2, 0, 4}, nk_many[3] = {2, 3, (1u << 24) + 1u}, fl_bad[3] = {MTR_CLIP_LOOP, 2, MTR_CLIP_LOOP};
+    const float rates_nan[3] = {30.0f, 24.0f, NAN}, rates_inf[3] = {INFINITY, 24.0f, 12.0f};
+    REJECT(mtr_anim_player_create(d, 3, nk_none, fl, rates, N, &no_pl));
+    REJECT(mtr_anim_player_create(d, 3, nk_many, fl, rates, N, &no_pl));
+    REJECT(mtr_anim_player_create(d, 3, nk, fl_bad, rates, N, &no_pl));
+    REJECT(mtr_anim_player_create(d, 3, nk, fl, rates_nan, N, &no_pl));
+    REJECT(mtr_anim_player_create(d, 3, nk, nullptr, rates_inf, N, &no_pl));
+    REJECT(mtr_anim_ctrl_create(d, 3, nk_none, fl, nodes, 2, trans, 2, 1, 2, &no_ctl));
+    REJECT(mtr_anim_ctrl_create(d, 3, nk_many, fl, nodes, 2, trans, 2, 1, 2, &no_ctl));
+    REJECT(mtr_anim_ctrl_create(d, 3, nk, fl_bad, nodes, 2, trans, 2, 1, 2, &no_ctl));
+    REJECT(mtr_anim_events_create(d, 3, nk_none, fl, counts, markers, N, &no_ev));
+    REJECT(mtr_anim_events_create(d, 3, nk_many, fl, counts, markers, N, &no_ev));
+    REJECT(mtr_anim_events_create(d, 3, nk, fl_bad, counts, markers, N, &no_ev));
+    REJECT(mtr_anim_blend_create(d, 3, nk_none, fl, rates, line, 2, nullptr, 0, 2, 1, 0, 4.0f, N, &no_bl));
+    REJECT(mtr_anim_blend_create(d, 3, nk_many, fl, rates, line, 2, nullptr, 0, 2, 1, 0, 4.0f, N, &no_bl));
+    REJECT(mtr_anim_blend_create(d, 3, nk, fl_bad, rates, line, 2, nullptr, 0, 2, 1, 0, 4.0f, N, &no_bl));
+    REJECT(mtr_anim_blend_create(d, 3, nk, fl, rates_nan, line, 2, nullptr, 0, 2, 1, 0, 4.0f, N, &no_bl));
+    REJECT(mtr_anim_blend_create(d, 3, nk, fl, rates_inf, plane, 3, tri, 1, 2, 0, 1, 4.0f, N, &no_bl));
+    // a clip's markers are checked before the next clip's flags: the marker of clip 0 is reported, not the flags of clip 1
+    const mtr_event_marker markers_out[3] = {{0.5f, 7}, {2.0f, 8}, {1.0f, 9}};
+    REJECT(mtr_anim_events_create(d, 3, nk, fl_bad, counts, markers_out, N, &no_ev));
+    // two bad clips: the lower index is reported, whichever of its checks comes first in a clip (clip 0: flags, a later
+    // check; clip 1: no keys, the first; a not-finite rate of clip 0 against the flags of clip 1 likewise)
+    const uint32_t fl_bad0[3] = {4, 0, MTR_CLIP_LOOP}, fl_bad1[3] = {MTR_CLIP_LOOP, 2, MTR_CLIP_LOOP};
+    REJECT(mtr_anim_player_create(d, 3, nk_none, fl_bad0, rates, N, &no_pl));
+    REJECT(mtr_anim_player_create(d, 3, nk, fl_bad1, rates_inf, N, &no_pl));
+    REJECT(mtr_anim_ctrl_create(d, 3, nk_none, fl_bad0, nodes, 2, trans, 2, 1, 2, &no_ctl));
+    REJECT(mtr_anim_events_create(d, 3, nk_none, fl_bad0, counts, markers, N, &no_ev));
+    REJECT(mtr_anim_blend_create(d, 3, nk_none, fl_bad0, rates, line, 2, nullptr, 0, 2, 1, 0, 4.0f, N, &no_bl));
+    REJECT(mtr_anim_blend_create(d, 3, nk, fl_bad1, rates_inf, line, 2, nullptr, 0, 2, 1, 0, 4.0f, N, &no_bl));
+    // the table-wide checks stand before the clips'
+    REJECT(mtr_anim_player_create(d, 0, nk, fl, rates, N, &no_pl));
+    REJECT(mtr_anim_ctrl_create(d, ((size_t)1 << 24) + 1, nk, fl, nodes, 2, trans, 2, 1, 2, &no_ctl));
+    REJECT(mtr_anim_events_create(d, 0, nk, fl, counts, markers, N, &no_ev));
+    REJECT(mtr_anim_blend_create(d, 0, nk, fl, rates, line, 2, nullptr, 0, 2, 1, 0, 4.0f, N, &no_bl));
+    // one rejected call per entry point
+    REJECT(mtr_anim_ctrl_step_device(ctl, odd(cs_dev), ps_dev, prm_dev, N, 0.5f, cmds_dev, fired_dev, caller));
+    REJECT(mtr_anim_ctrl_step_host(ctl, cs.data(), ps.data(), nullptr, N, 0.5f, cmds.data(), nullptr));
+    REJECT(mtr_anim_events_collect_device(evs, odd(steps2_dev), 2, N, 0.0f, list_dev, 4, count_dev, bits_dev, caller));
+    REJECT(mtr_anim_events_collect_host(evs, steps2.data(), 2, N, 0.0f, nullptr, 4, count.data(), nullptr));
+    REJECT(mtr_anim_blend_advance_device(bl1, bs_dev, prm_dev, N + 1, 0.5f, nullptr, 0, nullptr, nullptr, caller));
+    REJECT(mtr_anim_blend_advance_host(bl2, bs.data(), prm.data(), N, 0.5f, ly4.data(), 2, nullptr, nullptr));
+    REJECT(mtr_batch_animate_spring_device(b, a, mk, ly3_dev, 3, ik, tg_dev, sp, odd(ss_dev), nullptr, 0.5f, caller));
+    REJECT(mtr_anim_sample_spring(a, mk, nullptr, sp, ly3.data(), 3, tg.data(), ss.data(), nullptr, 0.5f, N, locals.data(), locals.size()));
+    mtr_anim_spring* no_sp = nullptr;
+    REJECT(mtr_anim_spring_create(d, J, parents, 0, springs, &no_sp));
+
+    // ---- each set destroyed with a kernel queued on the caller's stream ----
+    printf("==== clock sets: destroyed ====\n");
+    CALL(mtr_anim_ctrl_step_device(ctl, cs_dev, ps_dev, prm_dev, N, 0.5f, cmds_dev, nullptr, caller));
+    CALL(mtr_anim_events_collect_device(evs, steps2_dev, 2, N, 0.0f, list_dev, 4, count_dev, nullptr, caller));
+    CALL(mtr_anim_blend_advance_device(bl2, bs_dev, prm_dev, N, 0.5f, nullptr, 0, nullptr, nullptr, caller));
+    CALL(mtr_batch_animate_spring_device(b, a, nullptr, ly3_dev, 3, nullptr, nullptr, sp, ss_dev, nullptr, 0.5f, caller));
+    DESTROY(mtr_anim_ctrl_destroy(ctl));
+    DESTROY(mtr_anim_ctrl_destroy(ctl0));
+    DESTROY(mtr_anim_events_destroy(evs));
+    DESTROY(mtr_anim_blend_destroy(bl1));
+    DESTROY(mtr_anim_blend_destroy(bl2));
+    DESTROY(mtr_anim_spring_destroy(sp));
+    mtr_anim_ctrl_destroy(nullptr);
+    mtr_anim_events_destroy(nullptr);
+    mtr_anim_blend_destroy(nullptr);
+    mtr_anim_spring_destroy(nullptr);
+
+    for (void* p : {(void*)cs_dev, (void*)ps_dev, (void*)prm_dev, (void*)shares_dev, (void*)motion_dev, (void*)cmds_dev, (void*)fired_dev, (void*)count_dev,
+                    (void*)bits_dev, (void*)steps2_dev, (void*)steps3_dev, (void*)list_dev, (void*)bs_dev, (void*)ly3_dev, (void*)ly4_dev, (void*)tg_dev,
+                    (void*)ss_dev}) free(p);
+    mtr_anim_destroy(a);
+    mtr_anim_masks_destroy(mk);
+    mtr_anim_ik_destroy(ik);
+    mtr_batch_destroy(b);
+    mtr_model_destroy(m);
 }
 
 int main() {
@@ -369,6 +636,8 @@ int main() {
     mtr_anim_destroy(wide);
     mtr_anim_destroy(foreign);
     mtr_anim_destroy(nullptr);
+    printf("anim_call_trace: ops=%ld rejected=%ld failed=%d\n", g_ops, g_rejected, g_failed);  // where the first recording ended
+    clock_sets(d, caller);
 
     for (void* p : {(void*)st_dev, (void*)ly1_dev, (void*)ly2_dev, (void*)tg_dev, (void*)steps1_dev, (void*)steps2_dev, (void*)recs_dev, (void*)locals_dev,
                     (void*)out_dev, (void*)ps_dev, (void*)cmds_dev, (void*)oa_dev, (void*)ol_dev, (void*)os_dev}) free(p);

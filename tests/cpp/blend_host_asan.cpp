@@ -7,7 +7,6 @@
 // clip, the sample or the triangle; sets are created and destroyed with calls queued.
 //   usage: blend_host_asan <iterations>
 #include "host_all.h"
-#include "../../mt_renderer_amd/csrc/host_blend.cpp"
 using namespace mtr_host;
 
 static int g_failed = 0;

@@ -8,7 +8,6 @@
 // steps queued.
 //   usage: ctrl_host_asan <iterations>
 #include "host_all.h"
-#include "../../mt_renderer_amd/csrc/host_ctrl.cpp"
 #include "../../mt_renderer_amd/csrc/ctrl_math.h"
 using namespace mtr_host;
 

@@ -8,7 +8,6 @@
 // destroyed with calls queued.
 //   usage: events_host_asan <iterations>
 #include "host_all.h"
-#include "../../mt_renderer_amd/csrc/host_events.cpp"
 #include "../../mt_renderer_amd/csrc/event_math.h"
 using namespace mtr_host;
 

@@ -7,6 +7,10 @@
 #include "../../mt_renderer_amd/csrc/host_anim.cpp"
 #include "../../mt_renderer_amd/csrc/host_batch.cpp"
 #include "../../mt_renderer_amd/csrc/host_player.cpp"
+#include "../../mt_renderer_amd/csrc/host_ctrl.cpp"
+#include "../../mt_renderer_amd/csrc/host_events.cpp"
+#include "../../mt_renderer_amd/csrc/host_blend.cpp"
+#include "../../mt_renderer_amd/csrc/host_spring.cpp"
 #include "../../mt_renderer_amd/csrc/host_frame.cpp"
 #include "../../mt_renderer_amd/csrc/host_submit.cpp"
 #include "../../mt_renderer_amd/csrc/host_shard.cpp"

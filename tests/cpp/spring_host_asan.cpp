@@ -7,7 +7,6 @@
 // the states after a call are compared with a second run of the rule.
 //   usage: spring_host_asan <iterations>
 #include "host_all.h"
-#include "../../mt_renderer_amd/csrc/host_spring.cpp"
 using namespace mtr_host;
 #include "../../mt_renderer_amd/csrc/mtr_files.cpp"
 

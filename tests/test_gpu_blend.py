@@ -253,3 +253,39 @@ def test_invalid_calls_change_nothing(gpu_device):
         assert not t_st[n * 16:].any().item() and not t_ly[n * nl * 16:].any().item() and not t_sp[n * 48:].any().item() and t_sh[n * 3].item() == 0
     finally:
         bl.close()
+
+
+def test_argument_errors_of_advance_read_as_before(gpu_device):
+    import torch
+    from tests.test_gpu_player import _raises_saying
+    n = 3
+    u8 = lambda k: torch.zeros(k, dtype=torch.uint8, device="cuda:0")
+    f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device="cuda:0")
+    samples = np.array([(0, 0.0, 0.0, 0), (1, 1.0, 0.0, 0)], dtype=api.BLEND_SAMPLE)
+    create_msg = "anim blend: one key count, rate and flag word per clip, samples of dtype BLEND_SAMPLE [K], triangles of dtype BLEND_TRI [T]"
+    bl = api.AnimBlend(gpu_device, [30, 20], [30.0, 30.0], [1, 1], samples, nparams=2, param_x=1, max_instances=n)
+    st, pr = u8(n * 16), f32(n, 2)
+    try:
+        _raises_saying([
+            (lambda: bl.advance(st.double(), pr, 0.1), "blend states: a uint8 / int32 / float32 tensor on the GPU"),
+            (lambda: bl.advance(u8(n * 16 + 16)[8:8 + n * 16], pr, 0.1), "blend states: contiguous and 16-byte aligned (it is used in place)"),
+            (lambda: bl.advance(st, pr.int(), 0.1), "blend params: a float32 tensor [n, nparams] on the GPU"),
+            (lambda: bl.advance(st, None, 0.1), "blend params: a float32 tensor [n, nparams] on the GPU"),
+            (lambda: bl.advance(st, f32(n, 3), 0.1), "blend params: records of 4 bytes, 6 of them"),
+            (lambda: bl.advance(st, pr, 0.1, out_layers=u8((3 * n + 1) * 16)), "blend out_layers: n x L layers of 16 bytes"),
+            (lambda: bl.advance(st, pr, 0.1, out_layers=u8(n * 3 * 32).view(n * 3, 32)[:, :16]), "blend out_layers: contiguous and 16-byte aligned (it is used in place)"),
+            (lambda: bl.advance(st, pr, 0.1, out_steps=u8(n * 2 * 16)), "blend out_steps: records of 16 bytes, 9 of them"),
+            (lambda: bl.advance(st, pr, 0.1, out_shares=f32(n, 3).int()), "blend out_shares: a float32 tensor [n, 3] on the GPU"),
+            (lambda: bl.advance(st, pr, 0.1, out_shares=f32(n, 2)), "blend out_shares: records of 4 bytes, 9 of them"),
+            # the first check that fails speaks: the parameters before the layers, the layers before the steps and the shares
+            (lambda: bl.advance(st, pr.int(), 0.1, out_layers=u8((3 * n + 1) * 16)), "blend params: a float32 tensor [n, nparams] on the GPU"),
+            (lambda: bl.advance(st, pr, 0.1, out_layers=u8((3 * n + 1) * 16), out_steps=u8(16), out_shares=f32(1)), "blend out_layers: n x L layers of 16 bytes"),
+            (lambda: api.AnimBlend(gpu_device, [30, 20], [30.0], [1, 1], samples), create_msg),
+            (lambda: api.AnimBlend(gpu_device, [30, 20], [30.0, 30.0], [1], samples), create_msg),
+            (lambda: api.AnimBlend(gpu_device, [30, 20], [30.0, 30.0], [1, 1], samples.view(np.uint8)), create_msg),
+            (lambda: api.AnimBlend(gpu_device, [30, 20], [30.0, 30.0], [1, 1], samples, param_x=-1), "anim blend: param_x and param_y are parameter indices"),
+        ])
+        torch.cuda.synchronize()
+        assert not st.any().item(), "nothing ran"
+    finally:
+        bl.close()

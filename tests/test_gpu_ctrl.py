@@ -325,3 +325,40 @@ def test_invalid_calls_change_nothing(gpu_device):
         assert (t_ct.cpu().numpy().view(np.uint32)[:T] == want[3]).all() and t_ct[T].item() == 0
     finally:
         ct.close()
+
+
+def test_argument_errors_of_step_read_as_before(gpu_device):
+    import torch
+    from tests.test_gpu_player import _raises_saying
+    n = 3
+    u8 = lambda k: torch.zeros(k, dtype=torch.uint8, device="cuda:0")
+    f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device="cuda:0")
+    i32 = lambda k: torch.zeros(k, dtype=torch.int32, device="cuda:0")
+    nodes, trans = np.zeros(1, dtype=api.CTRL_NODE), np.zeros(2, dtype=api.CTRL_TRANS)
+    nodes["count"] = 2
+    create_msg = "anim ctrl: one flag word per clip, nodes of dtype CTRL_NODE [S] and transitions of dtype CTRL_TRANS [T]"
+    ct = api.AnimCtrl(gpu_device, [30, 2], [1, 0], nodes, trans, nany=0, nparams=2)
+    st, pl, pr, cmds = u8(n * 16), u8(n * 32), f32(n, 2), u8(n * 16)
+    try:
+        _raises_saying([
+            (lambda: ct.step(st.double(), pl, pr, 0.1, cmds), "ctrl states: a uint8 / int32 / float32 tensor on the GPU"),
+            (lambda: ct.step(u8(n * 16 + 16)[8:8 + n * 16], pl, pr, 0.1, cmds), "ctrl states: contiguous and 16-byte aligned (it is used in place)"),
+            (lambda: ct.step(st, u8((n - 1) * 32), pr, 0.1, cmds), "ctrl play states: records of 32 bytes, 3 of them"),
+            (lambda: ct.step(st, pl, pr, 0.1, u8((n - 1) * 16)), "ctrl commands: at least n slots of 16 bytes"),
+            (lambda: ct.step(st, pl, None, 0.1, cmds), "ctrl params: a float32 tensor [n, nparams] on the GPU"),
+            (lambda: ct.step(st, pl, pr.int(), 0.1, cmds), "ctrl params: a float32 tensor [n, nparams] on the GPU"),
+            (lambda: ct.step(st, pl, f32(n, 3), 0.1, cmds), "ctrl params: records of 8 bytes, 3 of them"),
+            (lambda: ct.step(st, pl, f32(n, 4)[:, :2], 0.1, cmds), "ctrl params: contiguous and 4-byte aligned (it is used in place)"),
+            (lambda: ct.step(st, pl, pr, 0.1, cmds, counts=f32(2)), "ctrl counts: an int32 tensor [ntrans] on the GPU"),
+            (lambda: ct.step(st, pl, pr, 0.1, cmds, counts=i32(1)), "ctrl counts: one word per transition"),
+            (lambda: ct.step(st, pl, pr, 0.1, cmds, counts=i32(4)[::2]), "ctrl counts: contiguous and 4-byte aligned (it is used in place)"),
+            # the first check that fails speaks: the commands before the parameters, the parameters before the counts
+            (lambda: ct.step(st, pl, None, 0.1, u8((n - 1) * 16), counts=f32(2)), "ctrl commands: at least n slots of 16 bytes"),
+            (lambda: ct.step(st, pl, pr.int(), 0.1, cmds, counts=f32(2)), "ctrl params: a float32 tensor [n, nparams] on the GPU"),
+            (lambda: api.AnimCtrl(gpu_device, [30, 2], [1], nodes, trans), create_msg),
+            (lambda: api.AnimCtrl(gpu_device, [30, 2], [1, 0], nodes.view(np.uint8), trans), create_msg),
+        ])
+        torch.cuda.synchronize()
+        assert not st.any().item() and not cmds.any().item(), "nothing ran"
+    finally:
+        ct.close()

@@ -254,3 +254,38 @@ def test_invalid_calls_change_nothing(gpu_device):
         assert not t_out[cap * 16:].any().item() and not t_ct[2:].any().item() and t_bits[n].item() == 0 and want[1][0] > 0
     finally:
         ev.close()
+
+
+def test_argument_errors_of_collect_read_as_before(gpu_device):
+    import torch
+    from tests.test_gpu_player import _raises_saying
+    n, S = 3, 2
+    u8 = lambda k: torch.zeros(k, dtype=torch.uint8, device="cuda:0")
+    i32 = lambda k: torch.zeros(k, dtype=torch.int32, device="cuda:0")
+    markers = np.array([(0.5, 7)], dtype=api.EVENT_MARKER)
+    create_msg = "anim events: one flag word and one marker count per clip, markers of dtype EVENT_MARKER [sum of counts]"
+    ev = api.AnimEvents(gpu_device, [30, 2], [1, 0], [1, 0], markers, max_instances=n)
+    steps, out, count, bits = u8(n * S * 16).view(n, S, 16), u8(4 * 16), i32(2), i32(n)
+    try:
+        _raises_saying([
+            (lambda: ev.collect(steps.view(n * S, 16), 0.0, out, count), "events steps: a tensor [n, S, 16 bytes] on the GPU"),
+            (lambda: ev.collect(torch.zeros((n, S, 2), dtype=torch.float64, device="cuda:0"), 0.0, out, count), "events steps: a uint8 / int32 / float32 tensor on the GPU"),
+            (lambda: ev.collect(u8(n * S * 16 + 16)[8:8 + n * S * 16].view(n, S, 16), 0.0, out, count), "events steps: contiguous and 16-byte aligned (it is used in place)"),
+            (lambda: ev.collect(u8(n * S * 32).view(n, S, 32)[:, :, :16], 0.0, out, count), "events steps: contiguous and 16-byte aligned (it is used in place)"),
+            (lambda: ev.collect(steps, 0.0, u8(24), count), "events list: records of 16 bytes"),
+            (lambda: ev.collect(steps, 0.0, out, count.float()), "events count: an int32 tensor [2] on the GPU"),
+            (lambda: ev.collect(steps, 0.0, out, None), "events count: an int32 tensor [2] on the GPU"),
+            (lambda: ev.collect(steps, 0.0, out, i32(3)), "events count: records of 4 bytes, 2 of them"),
+            (lambda: ev.collect(steps, 0.0, out, count, bits=bits.float()), "events bits: an int32 tensor [n] on the GPU"),
+            (lambda: ev.collect(steps, 0.0, out, count, bits=i32(n + 1)), "events bits: records of 4 bytes, 3 of them"),
+            # the first check that fails speaks: the list before the count, the count before the bits
+            (lambda: ev.collect(steps, 0.0, u8(24), count.float(), bits=bits.float()), "events list: records of 16 bytes"),
+            (lambda: ev.collect(steps, 0.0, out, i32(3), bits=bits.float()), "events count: records of 4 bytes, 2 of them"),
+            (lambda: api.AnimEvents(gpu_device, [30, 2], [1], [1, 0], markers), create_msg),
+            (lambda: api.AnimEvents(gpu_device, [30, 2], [1, 0], [1], markers), create_msg),
+            (lambda: api.AnimEvents(gpu_device, [30, 2], [1, 0], [2, 0], markers), create_msg),
+        ])
+        torch.cuda.synchronize()
+        assert not out.any().item() and not count.any().item() and not bits.any().item(), "nothing ran"
+    finally:
+        ev.close()

@@ -286,3 +286,44 @@ def test_invalid_calls_change_nothing(gpu_device):
         _same(_host(t_st, pm.PLAY), pm.advance(c["states"], dt, tab, cm0)[0], "after invalid calls")
     finally:
         pl.close()
+
+
+def _raises_saying(cases):
+    """each call raises MtrError MTR_E_INVALID with exactly the given text: the binding's own argument checks, before any kernel"""
+    for k, (fn, text) in enumerate(cases):
+        with pytest.raises(api.MtrError) as e:
+            fn()
+        assert e.value.code == api.MTR_E_INVALID and str(e.value) == f"mtr error {api.MTR_E_INVALID}: {text}", (k, str(e.value))
+
+
+def test_argument_errors_of_advance_read_as_before(gpu_device):
+    import torch
+    n = 3
+    u8 = lambda k: torch.zeros(k, dtype=torch.uint8, device="cuda:0")
+    st = u8(n * 32)
+    pl = api.AnimPlayer(gpu_device, [30, 2], [30.0, 1.0], [1, 0], max_instances=n)
+    try:
+        _raises_saying([
+            (lambda: pl.advance(st.double(), 0.1), "player states: a uint8 / int32 / float32 tensor on the GPU"),
+            (lambda: pl.advance(st.cpu(), 0.1), "player states: a uint8 / int32 / float32 tensor on the GPU"),
+            (lambda: pl.advance(u8(n * 32 + 16)[8:8 + n * 32], 0.1), "player states: contiguous and 16-byte aligned (it is used in place)"),
+            (lambda: pl.advance(u8(n * 64).view(n, 64)[:, :32], 0.1), "player states: contiguous and 16-byte aligned (it is used in place)"),
+            (lambda: pl.advance(u8(n * 32 + 1), 0.1), "player states: records of 32 bytes"),
+            (lambda: pl.advance(st, 0.1, out_states=u8((n + 1) * 24)), "player out_states: records of 24 bytes, 3 of them"),
+            (lambda: pl.advance(st, 0.1, out_states=u8(n * 24 + 8)[4:4 + n * 24]), "player out_states: contiguous and 8-byte aligned (it is used in place)"),
+            (lambda: pl.advance(st, 0.1, out_layers=u8((2 * n + 1) * 16)), "player out_layers: n x L layers of 16 bytes"),
+            (lambda: pl.advance(st, 0.1, out_layers=u8(n * 2 * 16).double()), "player out_layers: a uint8 / int32 / float32 tensor on the GPU"),
+            (lambda: pl.advance(st, 0.1, out_steps=u8(n * 16)), "player out_steps: records of 16 bytes, 6 of them"),
+            (lambda: pl.advance(st, 0.1, cmds=u8(24)), "player commands: records of 16 bytes"),
+            (lambda: pl.advance(st, 0.1, cmds=u8(48)[8:40]), "player commands: contiguous and 16-byte aligned (it is used in place)"),
+            # the first check that fails speaks: the states before the outputs, an output before the commands
+            (lambda: pl.advance(u8(n * 32 + 1), 0.1, out_states=u8(1), cmds=u8(24)), "player states: records of 32 bytes"),
+            (lambda: pl.advance(st, 0.1, out_steps=u8(n * 16), cmds=u8(24)), "player out_steps: records of 16 bytes, 6 of them"),
+            (lambda: api.AnimPlayer(gpu_device, [30, 2], [1.0]), "anim player: one key count, one rate and one flag word per clip"),
+            (lambda: api.AnimPlayer(gpu_device, [30, 2], [1.0, 1.0], [1]), "anim player: one key count, one rate and one flag word per clip"),
+        ])
+        torch.cuda.synchronize()
+        assert not st.any().item(), "nothing ran"
+    finally:
+        pl.close()
+        pl.close()  # a second close does nothing
