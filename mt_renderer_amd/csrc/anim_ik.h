@@ -14,28 +14,28 @@ struct IkVec3 {
     float x, y, z;
 };
 
-MTR_BLEND_HD IkVec3 ik_vec3(float x, float y, float z) {
+MTR_HD IkVec3 ik_vec3(float x, float y, float z) {
     IkVec3 r;
     r.x = x; r.y = y; r.z = z;
     return r;
 }
 
-MTR_BLEND_HD IkVec3 ik_sub(const IkVec3& u, const IkVec3& v) { return ik_vec3(u.x - v.x, u.y - v.y, u.z - v.z); }
-MTR_BLEND_HD IkVec3 ik_add(const IkVec3& u, const IkVec3& v) { return ik_vec3(u.x + v.x, u.y + v.y, u.z + v.z); }
-MTR_BLEND_HD IkVec3 ik_scale(float s, const IkVec3& v) { return ik_vec3(s * v.x, s * v.y, s * v.z); }
-MTR_BLEND_HD IkVec3 ik_div(const IkVec3& v, float s) { return ik_vec3(v.x / s, v.y / s, v.z / s); }
+MTR_HD IkVec3 ik_sub(const IkVec3& u, const IkVec3& v) { return ik_vec3(u.x - v.x, u.y - v.y, u.z - v.z); }
+MTR_HD IkVec3 ik_add(const IkVec3& u, const IkVec3& v) { return ik_vec3(u.x + v.x, u.y + v.y, u.z + v.z); }
+MTR_HD IkVec3 ik_scale(float s, const IkVec3& v) { return ik_vec3(s * v.x, s * v.y, s * v.z); }
+MTR_HD IkVec3 ik_div(const IkVec3& v, float s) { return ik_vec3(v.x / s, v.y / s, v.z / s); }
 
-MTR_BLEND_HD float ik_dot3(const IkVec3& u, const IkVec3& v) { return (u.x * v.x + u.y * v.y) + u.z * v.z; }
-MTR_BLEND_HD float ik_len(const IkVec3& v) { return sqrtf(ik_dot3(v, v)); }
+MTR_HD float ik_dot3(const IkVec3& u, const IkVec3& v) { return (u.x * v.x + u.y * v.y) + u.z * v.z; }
+MTR_HD float ik_len(const IkVec3& v) { return sqrtf(ik_dot3(v, v)); }
 
-MTR_BLEND_HD IkVec3 ik_cross(const IkVec3& u, const IkVec3& v) {
+MTR_HD IkVec3 ik_cross(const IkVec3& u, const IkVec3& v) {
     return ik_vec3(u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x);
 }
 
-MTR_BLEND_HD AnimVec ik_conj(const AnimVec& q) { return anim_vec(-q.x, -q.y, -q.z, q.w); }
+MTR_HD AnimVec ik_conj(const AnimVec& q) { return anim_vec(-q.x, -q.y, -q.z, q.w); }
 
 // section 14's renormalisation: the identity when the norm is 0 or its reciprocal root is not finite
-MTR_BLEND_HD AnimVec ik_norm4(const AnimVec& q) {
+MTR_HD AnimVec ik_norm4(const AnimVec& q) {
     const float n2 = anim_dot(q, q);
     const float rn = 1.0f / sqrtf(n2);
     if (n2 == 0.0f || !(fabsf(rn) <= 3.402823466e38f)) return anim_vec(0.0f, 0.0f, 0.0f, 1.0f);
@@ -43,7 +43,7 @@ MTR_BLEND_HD AnimVec ik_norm4(const AnimVec& q) {
 }
 
 // v rotated by q: t = 2 (q.xyz x v), v + q.w t + q.xyz x t
-MTR_BLEND_HD IkVec3 ik_qrot(const AnimVec& q, const IkVec3& v) {
+MTR_HD IkVec3 ik_qrot(const AnimVec& q, const IkVec3& v) {
     const IkVec3 a = ik_vec3(q.x, q.y, q.z);
     IkVec3 t = ik_cross(a, v);
     t = ik_add(t, t);
@@ -51,7 +51,7 @@ MTR_BLEND_HD IkVec3 ik_qrot(const AnimVec& q, const IkVec3& v) {
 }
 
 // the shortest arc that turns u towards v; exactly antiparallel vectors (and a zero vector) give the identity
-MTR_BLEND_HD AnimVec ik_fromto(const IkVec3& u, const IkVec3& v) {
+MTR_HD AnimVec ik_fromto(const IkVec3& u, const IkVec3& v) {
     const IkVec3 c = ik_cross(u, v);
     const float w = sqrtf(ik_dot3(u, u) * ik_dot3(v, v)) + ik_dot3(u, v);
     return ik_norm4(anim_vec(c.x, c.y, c.z, w));
@@ -61,7 +61,7 @@ MTR_BLEND_HD AnimVec ik_fromto(const IkVec3& u, const IkVec3& v) {
 // rotations of a and b, replaced when the guard holds; g: the target position; pole: the pole position, read only with
 // use_pole; e: the clamped weight, != 0 (the caller skips a chain with e == 0 before it reads anything).  Returns whether
 // the guard held; when it did not, qa and qb are untouched bit for bit.
-MTR_BLEND_HD bool ik_two_bone(const IkVec3& pa, const IkVec3& pb, const IkVec3& pc, const AnimVec& P, AnimVec& qa, AnimVec& qb,
+MTR_HD bool ik_two_bone(const IkVec3& pa, const IkVec3& pb, const IkVec3& pc, const AnimVec& P, AnimVec& qa, AnimVec& qb,
                               const IkVec3& g, const IkVec3& pole, bool use_pole, float e) {
     const IkVec3 ab = ik_sub(pb, pa), bc = ik_sub(pc, pb);
     const float la = ik_len(ab), lb = ik_len(bc);
@@ -96,7 +96,7 @@ MTR_BLEND_HD bool ik_two_bone(const IkVec3& pa, const IkVec3& pb, const IkVec3& 
 
 // AIM.  pa: the world position of a; P: the world rotation above a; qa: the local rotation of a, replaced when the guard
 // holds; axis: the chain's axis in a's local space; g: the target position; e != 0.
-MTR_BLEND_HD bool ik_aim(const IkVec3& pa, const AnimVec& P, AnimVec& qa, const IkVec3& axis, const IkVec3& g, float e) {
+MTR_HD bool ik_aim(const IkVec3& pa, const AnimVec& P, AnimVec& qa, const IkVec3& axis, const IkVec3& g, float e) {
     const AnimVec A0 = anim_qmul(P, qa);
     const IkVec3 cur = ik_qrot(A0, axis);
     const IkVec3 v = ik_sub(g, pa);

@@ -8,14 +8,9 @@
 // One rounded operation per operator; nothing here is fused (the including file is compiled with -ffp-contract=off; the section
 // has no fma at all) and '/' is correctly rounded.  NaN compares false, which every test below is written for.
 #pragma once
-#include <cstdint>
-#include <cmath>
-
 #include "play_math.h"
 
 namespace mtr {
-
-#define MTR_BLEND_HD MTR_PLAY_HD
 
 // mtr_blend_sample, mtr_blend_tri, mtr_blend_state: 16 bytes each
 struct alignas(16) BlendSample {
@@ -55,29 +50,29 @@ struct BlendSlots {
     float e1, e2;
 };
 
-MTR_BLEND_HD bool blend_finite(float v) { return fabsf(v) <= PLAY_FLT_MAX; }
+MTR_HD bool blend_finite(float v) { return fabsf(v) <= PLAY_FLT_MAX; }
 
 // step 2: one parameter smoothed towards its target
-MTR_BLEND_HD float blend_smooth(float p, float t, float a) {
+MTR_HD float blend_smooth(float p, float t, float a) {
     if (a == 1.0f || !blend_finite(p)) return t;
     const float d = t - p, m = a * d;
     return p + m;
 }
 
 // the doubled area of a triangle, in the operation order of the creation check
-MTR_BLEND_HD float blend_area(float x0, float y0, float x1, float y1, float x2, float y2) {
+MTR_HD float blend_area(float x0, float y0, float x1, float y1, float x2, float y2) {
     const float ax = x1 - x0, ay = y1 - y0, bx = x2 - x0, by = y2 - y0;
     const float m0 = ax * by, m1 = bx * ay;
     return m0 - m1;
 }
 
-MTR_BLEND_HD float blend_dot2(float ux, float uy, float vx, float vy) {
+MTR_HD float blend_dot2(float ux, float uy, float vx, float vy) {
     const float m0 = ux * vx, m1 = uy * vy;
     return m0 + m1;
 }
 
 // step 3 in a 1-D space
-MTR_BLEND_HD BlendSlots blend_slots_1d(float p, const BlendTables& t) {
+MTR_HD BlendSlots blend_slots_1d(float p, const BlendTables& t) {
     BlendSlots r;
     r.e1 = 0.0f; r.e2 = 0.0f;
     const uint32_t top = t.nsamples - 1u;
@@ -96,7 +91,7 @@ MTR_BLEND_HD BlendSlots blend_slots_1d(float p, const BlendTables& t) {
 // step 3 in a 2-D space.  Both loops run over every triangle with a uniform index; a lane that has its triangle skips the
 // rest of the first loop's bodies, and only a lane without one enters the second: what a lane computes does not depend on
 // where the other lanes of its wave are.
-MTR_BLEND_HD BlendSlots blend_slots_2d(float px, float py, const BlendTables& t) {
+MTR_HD BlendSlots blend_slots_2d(float px, float py, const BlendTables& t) {
     BlendSlots r;
     bool hit = false;
     for (uint32_t k = 0; k < t.ntris; k++) {
@@ -113,9 +108,9 @@ MTR_BLEND_HD BlendSlots blend_slots_2d(float px, float py, const BlendTables& t)
         if (l0 >= 0.0f && l1 >= 0.0f && l2 >= 0.0f) {
             hit = true;
             r.s[0] = tr.v[0]; r.s[1] = tr.v[1]; r.s[2] = tr.v[2];
-            r.e2 = play_weight(l2);
+            r.e2 = anim_weight(l2);
             const float om = 1.0f - l2;
-            r.e1 = om == 0.0f ? 0.0f : play_weight(l1 / om);
+            r.e1 = om == 0.0f ? 0.0f : anim_weight(l1 / om);
         }
     }
     if (hit) return r;
@@ -130,7 +125,7 @@ MTR_BLEND_HD BlendSlots blend_slots_2d(float px, float py, const BlendTables& t)
             const float ex = b.px - a.px, ey = b.py - a.py;
             const float qx = px - a.px, qy = py - a.py;
             const float num = blend_dot2(qx, qy, ex, ey), den = blend_dot2(ex, ey, ex, ey);
-            const float tt = play_weight(num / den);
+            const float tt = anim_weight(num / den);
             const float mx = tt * ex, my = tt * ey;
             const float cx = a.px + mx, cy = a.py + my;
             const float dx = px - cx, dy = py - cy;
@@ -145,11 +140,11 @@ MTR_BLEND_HD BlendSlots blend_slots_2d(float px, float py, const BlendTables& t)
 
 // Steps 1 to 6 of section 23 for one instance.  st: the stored state, rewritten (speed kept); row: the instance's nparams
 // parameters, read only.
-MTR_BLEND_HD BlendFrame blend_advance(BlendState& st, const float* row, float dt, const BlendTables& t) {
+MTR_HD BlendFrame blend_advance(BlendState& st, const float* row, float dt, const BlendTables& t) {
     const bool two_d = t.ntris != 0u;
     // 1. target, 2. smooth
     const float dtp = dt > 0.0f ? dt : 0.0f;
-    const float a = play_weight(dtp * t.damp);
+    const float a = anim_weight(dtp * t.damp);
     const float px = blend_smooth(st.px, row[t.param_x], a);
     const float py = two_d ? blend_smooth(st.py, row[t.param_y], a) : st.py;
     // 3. slots

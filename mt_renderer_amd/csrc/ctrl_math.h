@@ -11,16 +11,7 @@
 // here indexes a local array with a value known only at run time: user parameters are read from memory where a condition
 // names them and the tables are read through pointers.
 #pragma once
-#include <cstdint>
-#include <cmath>
-
 #include "play_math.h"
-
-#if defined(__HIPCC__)
-#define MTR_CTRL_HD __host__ __device__ __forceinline__
-#else
-#define MTR_CTRL_HD inline
-#endif
 
 #ifndef MTR_CTRL_MAX_COND  // include/mtr.h has the same
 #define MTR_CTRL_MAX_COND 3
@@ -69,7 +60,7 @@ struct CtrlStep {
     uint32_t fired;  // MTR_CTRL_NONE: none
 };
 
-MTR_CTRL_HD float ctrl_float(uint32_t u) {
+MTR_HD float ctrl_float(uint32_t u) {
     union { uint32_t u; float f; } c;
     c.u = u;
     return c.f;
@@ -82,7 +73,7 @@ struct CtrlLead {
 };
 
 // v op value for one condition word pair; params: the instance's row, read only where the condition names a user parameter
-MTR_CTRL_HD bool ctrl_cond(uint32_t po, uint32_t value_bits, const CtrlLead& l, const float* params) {
+MTR_HD bool ctrl_cond(uint32_t po, uint32_t value_bits, const CtrlLead& l, const float* params) {
     const uint32_t p = po & 0xFFFFu, op = po >> 16;
     const float value = ctrl_float(value_bits);
     float v;
@@ -103,14 +94,14 @@ MTR_CTRL_HD bool ctrl_cond(uint32_t po, uint32_t value_bits, const CtrlLead& l, 
 }
 
 // CONSUME: the user parameter a condition names is stored as +0.0
-MTR_CTRL_HD void ctrl_consume(uint32_t po, float* params) {
+MTR_HD void ctrl_consume(uint32_t po, float* params) {
     const uint32_t p = po & 0xFFFFu;
     if (p < MTR_CTRL_FADING) params[p] = 0.0f;
 }
 
 // Steps 1 to 6 of section 21 for one instance.  st: the stored state, rewritten; play: its play state, read only; params: its
 // row of nparams floats (nullptr when nparams == 0), written only by CONSUME.
-MTR_CTRL_HD CtrlStep ctrl_step(CtrlState& st, const PlayState& play, float* params, uint32_t inst, float dt, const CtrlTables& tb) {
+MTR_HD CtrlStep ctrl_step(CtrlState& st, const PlayState& play, float* params, uint32_t inst, float dt, const CtrlTables& tb) {
     // 1. node
     const uint32_t node = st.node < tb.nnodes - 1u ? st.node : tb.nnodes - 1u;
     // 2. lead

@@ -1,15 +1,14 @@
 // event_math.h -- the scalar rule of SPEC.md section 22 (animation events) that k_events.hip is made of: the weight of a
 // step, the positions a step starts and ends at, and per step the one or two ranges of the clip's sorted markers that the
 // position arrives at or passes, with a direction.  The ranges come from lower / upper bound searches, never from a walk.
-// Plain C++ besides the macro, like play_math.h (whose PlayClip and play_weight it reuses), so that
+// Plain C++ besides the macro, like play_math.h (whose PlayClip it reuses; the clamp and the wrap of a position and the
+// clamp of a weight are clip_math.h's), so that
 // tests/test_events_exact.py compiles this very source for the host (-ffp-contract=off) and compares it bit for bit with
 // the numpy model of section 22.
 //
 // One rounded operation per operator; nothing here is fused.  NaN compares false, which every test below is written for.
 #pragma once
 #include "play_math.h"
-
-#define MTR_EVENT_HD MTR_PLAY_HD
 
 #ifndef MTR_EVENT_MAX_STEPS  // include/mtr.h has the same (MTR_ROOT_MAX_STEPS)
 #define MTR_EVENT_MAX_STEPS 8
@@ -50,11 +49,11 @@ struct EventTables {
 struct EventSpans {
     uint32_t lo0, hi0, lo1, hi1;
     uint32_t where;
-    MTR_EVENT_HD uint32_t count() const { return (hi0 - lo0) + (hi1 - lo1); }
+    MTR_HD uint32_t count() const { return (hi0 - lo0) + (hi1 - lo1); }
 };
 
 // how many of the n markers at m lie below v (x < v), and how many do not lie above it (x <= v)
-MTR_EVENT_HD uint32_t event_lower(const EventMarker* m, uint32_t n, float v) {
+MTR_HD uint32_t event_lower(const EventMarker* m, uint32_t n, float v) {
     uint32_t lo = 0, hi = n;
     while (lo < hi) {
         const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -62,7 +61,7 @@ MTR_EVENT_HD uint32_t event_lower(const EventMarker* m, uint32_t n, float v) {
     }
     return lo;
 }
-MTR_EVENT_HD uint32_t event_upper(const EventMarker* m, uint32_t n, float v) {
+MTR_HD uint32_t event_upper(const EventMarker* m, uint32_t n, float v) {
     uint32_t lo = 0, hi = n;
     while (lo < hi) {
         const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -71,24 +70,14 @@ MTR_EVENT_HD uint32_t event_upper(const EventMarker* m, uint32_t n, float v) {
     return lo;
 }
 
-// section 14's clamp of a position to [0, P] (NaN -> 0) and its wrap into [0, P) with the fallback to 0
-MTR_EVENT_HD float event_clamp(float x, float P) {
-    const float r = x >= 0.0f ? x : 0.0f;
-    return r > P ? P : r;
-}
-MTR_EVENT_HD float event_wrap(float x, float P) {
-    const float r = x - floorf(x / P) * P;
-    return (r >= 0.0f && r < P) ? r : 0.0f;
-}
-
 // The weights of an instance's S steps (1..8): E[i] = e_i (1 - e_{i+1}) ... (1 - e_{S-1}) with e_0 = 1 and e_i the clamped
 // w of step i, the products taken in increasing index; returns the mask of the steps that fire at all: e_i != 0 (i >= 1)
 // and E_i >= min_weight.  w: the S raw weights; w[0] is not read.
-MTR_EVENT_HD uint32_t event_weights(const float* w, uint32_t S, float min_weight, float* E) {
+MTR_HD uint32_t event_weights(const float* w, uint32_t S, float min_weight, float* E) {
     float e[MTR_EVENT_MAX_STEPS];
     e[0] = 1.0f;
 #pragma unroll
-    for (uint32_t i = 1; i < MTR_EVENT_MAX_STEPS; i++) e[i] = i < S ? play_weight(w[i]) : 0.0f;
+    for (uint32_t i = 1; i < MTR_EVENT_MAX_STEPS; i++) e[i] = i < S ? anim_weight(w[i]) : 0.0f;
     uint32_t live = 0;
 #pragma unroll
     for (uint32_t i = 0; i < MTR_EVENT_MAX_STEPS; i++) {
@@ -104,7 +93,7 @@ MTR_EVENT_HD uint32_t event_weights(const float* w, uint32_t S, float min_weight
 
 // The ranges of step i of an instance.  The clip index is clamped; everything else that reaches an address is a search
 // result inside the clip's own range of markers.
-MTR_EVENT_HD EventSpans event_spans(const EventStepIn& s, uint32_t i, const EventTables& t) {
+MTR_HD EventSpans event_spans(const EventStepIn& s, uint32_t i, const EventTables& t) {
     const uint32_t top = t.nclips - 1u, c = s.clip < top ? s.clip : top;
     const float x = s.x, dx = s.dx;
     const bool fwd = dx > 0.0f, back = dx < 0.0f;
@@ -119,11 +108,11 @@ MTR_EVENT_HD EventSpans event_spans(const EventStepIn& s, uint32_t i, const Even
     const float P = pc.period;
     uint32_t lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
     if (!(pc.flags & MTR_CLIP_LOOP)) {
-        const float a = event_clamp(x, P), y = x + dx, b = event_clamp(y, P);
+        const float a = clip_clamp(x, P), y = x + dx, b = clip_clamp(y, P);
         if (fwd) { lo0 = event_upper(m, n, a); hi0 = event_upper(m, n, b); }  // (a, b]
         else { lo0 = event_lower(m, n, b); hi0 = event_lower(m, n, a); }       // [b, a)
     } else {
-        const float r0 = event_wrap(x, P), y = r0 + dx;
+        const float r0 = clip_wrap(x, P), y = r0 + dx;
         if (fabsf(dx) >= P) {  // a cycle or more: every marker once, from behind r0 round to r0
             const uint32_t k = fwd ? event_upper(m, n, r0) : event_lower(m, n, r0);
             if (fwd) { lo0 = k; hi0 = n; lo1 = 0; hi1 = k; }
@@ -145,13 +134,13 @@ MTR_EVENT_HD EventSpans event_spans(const EventStepIn& s, uint32_t i, const Even
 }
 
 // the raw weights of an instance's steps, for event_weights
-MTR_EVENT_HD void event_load_weights(const EventStepIn* steps, uint32_t S, float* w) {
+MTR_HD void event_load_weights(const EventStepIn* steps, uint32_t S, float* w) {
 #pragma unroll
     for (uint32_t i = 0; i < MTR_EVENT_MAX_STEPS; i++) w[i] = (i >= 1u && i < S) ? steps[i].w : 0.0f;
 }
 
 // how many events the S steps of an instance fire
-MTR_EVENT_HD uint32_t event_count(const EventStepIn* steps, uint32_t S, float min_weight, const EventTables& t) {
+MTR_HD uint32_t event_count(const EventStepIn* steps, uint32_t S, float min_weight, const EventTables& t) {
     float w[MTR_EVENT_MAX_STEPS], E[MTR_EVENT_MAX_STEPS];
     event_load_weights(steps, S, w);
     const uint32_t live = event_weights(w, S, min_weight, E);
@@ -164,7 +153,7 @@ MTR_EVENT_HD uint32_t event_count(const EventStepIn* steps, uint32_t S, float mi
 // The events of an instance in their order: step after step, range 0 then range 1, each in its direction.  emit(marker,
 // where, w) is called once per event; returns their number.
 template <class Emit>
-MTR_EVENT_HD uint32_t event_walk(const EventStepIn* steps, uint32_t S, float min_weight, const EventTables& t, Emit&& emit) {
+MTR_HD uint32_t event_walk(const EventStepIn* steps, uint32_t S, float min_weight, const EventTables& t, Emit&& emit) {
     float w[MTR_EVENT_MAX_STEPS], E[MTR_EVENT_MAX_STEPS];
     event_load_weights(steps, S, w);
     const uint32_t live = event_weights(w, S, min_weight, E);

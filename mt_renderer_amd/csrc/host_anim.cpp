@@ -6,22 +6,10 @@
 
 // k_anim.hip.  Weak: the host-only builds of this file (tests/cpp, over the HIP stub runtime) link no kernels and define
 // the launchers they watch; libmtr.so links k_anim.o.
-void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_spring(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_spring_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_spring_tracks(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
-void mtr_launch_anim_spring_tracks_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim(const AnimParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_layers(const AnimLayerParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_ik(const AnimIkParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s) __attribute__((weak));
+void mtr_launch_anim_spring(const AnimSpringParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s) __attribute__((weak));
 // k_root.hip, weak for the same reason
 void mtr_launch_root(const RootParams& p, hipStream_t s) __attribute__((weak));
 void mtr_launch_root_deltas(const RootParams& p, hipStream_t s) __attribute__((weak));
@@ -114,21 +102,6 @@ void anim_source(const mtr_anim* a, AnimParams& ap) {
 // ---------------------------------------------------------------------------------------------
 // one animate call
 // ---------------------------------------------------------------------------------------------
-// the launchers of k_anim.hip by the set's kind (tracks), by fold or sample, and by the call's kind (the member)
-struct AnimLaunch {
-    void (*states)(const AnimParams&, uint32_t, hipStream_t);
-    void (*layers)(const AnimLayerParams&, uint32_t, hipStream_t);
-    void (*ik)(const AnimIkParams&, uint32_t, hipStream_t);
-    void (*spring)(const AnimSpringParams&, uint32_t, hipStream_t);
-    bool has(int kind) const {
-        return kind == AnimCall::kStates ? states != nullptr : kind == AnimCall::kLayers ? layers != nullptr : kind == AnimCall::kIk ? ik != nullptr : spring != nullptr;
-    }
-};
-const AnimLaunch kAnimLaunch[2][2] = {
-    {{mtr_launch_anim, mtr_launch_anim_layers, mtr_launch_anim_ik, mtr_launch_anim_spring},
-     {mtr_launch_anim_sample, mtr_launch_anim_layers_sample, mtr_launch_anim_ik_sample, mtr_launch_anim_spring_sample}},
-    {{mtr_launch_anim_tracks, mtr_launch_anim_layers_tracks, mtr_launch_anim_ik_tracks, mtr_launch_anim_spring_tracks},
-     {mtr_launch_anim_tracks_sample, mtr_launch_anim_layers_tracks_sample, mtr_launch_anim_ik_tracks_sample, mtr_launch_anim_spring_tracks_sample}}};
 const char* const kAnimWhat[2][4] = {{"animate", "animate layers", "animate ik", "animate spring"},
                                      {"anim sample", "anim sample layers", "anim sample ik", "anim sample spring"}};
 const char* const kAnimKernel[4] = {"k_anim", "k_anim_layers", "k_anim_ik", "k_anim_spring"};
@@ -148,7 +121,8 @@ int32_t anim_check(mtr_device* d, const mtr_model* m, const AnimCall& c, const c
     auto what = [&](int stage) { return std::string(kAnimWhat[sample][sample ? c.kind : stage]) + ": "; };
     auto bad = [&](int stage, const std::string& msg) { return fail(d, MTR_E_INVALID, what(stage) + msg); };
     auto built = [&](int stage) {
-        if (kAnimLaunch[a->tracks][sample].has(stage)) return (int32_t)MTR_OK;
+        const bool linked[4] = {mtr_launch_anim != nullptr, mtr_launch_anim_layers != nullptr, mtr_launch_anim_ik != nullptr, mtr_launch_anim_spring != nullptr};
+        if (linked[stage]) return (int32_t)MTR_OK;
         return fail(d, MTR_E_UNSUPPORTED, what(stage) + "built without " + kAnimKernel[stage]);
     };
     if (c.kind != AnimCall::kStates) {
@@ -209,16 +183,16 @@ int32_t anim_enqueue(const AnimCall& c, const mtr_model::Skeleton* sk, float* ou
     if (sk) ap.pose = pose_params(*sk, nullptr, out);
     else { ap.pose.out = out; ap.pose.njoints = a->njoints; }
     anim_source(a, ap);
-    const AnimLaunch& launch = kAnimLaunch[a->tracks][!sk];
+    const bool tracks = a->tracks, fold = sk != nullptr;
     if (c.kind == AnimCall::kStates) {
         ap.states = static_cast<const uint32_t*>(c.recs);
-        launch.states(ap, ninst, s);
+        mtr_launch_anim(ap, tracks, fold, ninst, s);
     } else {
         lp.layers = static_cast<const uint32_t*>(c.recs);
         lp.nlayers = (uint32_t)c.nlayers;
         if (c.masks) { lp.masks = c.masks->weights(); lp.nmasks = c.masks->nmasks; }
         if (c.kind == AnimCall::kLayers) {
-            launch.layers(lp, ninst, s);
+            mtr_launch_anim_layers(lp, tracks, fold, ninst, s);
         } else {
             // the chain walks read the skeleton's path table as the fold does; a sample call has none and reads the IK set's
             // copy, or the spring set's
@@ -239,9 +213,9 @@ int32_t anim_enqueue(const AnimCall& c, const mtr_model::Skeleton* sk, float* ou
                 sp.motion = c.motion;
                 sp.dt = c.dt;
                 sp.nsprings = ss->nsprings; sp.nrounds = ss->nrounds;
-                launch.spring(sp, ninst, s);
+                mtr_launch_anim_spring(sp, tracks, fold, ninst, s);
             } else {
-                launch.ik(ip, ninst, s);
+                mtr_launch_anim_ik(ip, tracks, fold, ninst, s);
             }
         }
     }

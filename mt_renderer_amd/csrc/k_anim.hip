@@ -22,37 +22,12 @@
 // aimed at a particle whose state lives in device memory from call to call.  The scalar rule lives in spring_math.h.
 #include "anim_blend.h"
 #include "anim_ik.h"
+#include "anim_launch.h"
 #include "spring_math.h"
 #include "anim_tracks.h"
 #include "pose_common.h"
 
 namespace mtr {
-
-struct AnimPos {
-    uint32_t i0, i1;  // key indices inside the clip
-    float a;          // fraction towards i1
-};
-
-// Position -> keys: nkeys >= 1 keys at uniform spacing, x in keys
-__device__ __forceinline__ AnimPos anim_position(float x, uint32_t nkeys, uint32_t flags) {
-    AnimPos r;
-    float pos;
-    if (flags & 1u) {  // MTR_CLIP_LOOP
-        const float nf = (float)nkeys;
-        pos = x - floorf(x / nf) * nf;
-        if (!(pos >= 0.0f && pos < nf)) pos = 0.0f;  // NaN, +-inf, huge x, and pos == nf for a tiny negative x
-        r.i0 = (uint32_t)floorf(pos);
-        r.i1 = r.i0 + 1u == nkeys ? 0u : r.i0 + 1u;
-    } else {
-        const float last = (float)(nkeys - 1u);
-        pos = x >= 0.0f ? x : 0.0f;  // NaN -> 0
-        if (pos > last) pos = last;
-        r.i0 = (uint32_t)floorf(pos);
-        r.i1 = r.i0 + 1u < nkeys ? r.i0 + 1u : nkeys - 1u;
-    }
-    r.a = pos - (float)r.i0;
-    return r;
-}
 
 __device__ __forceinline__ AnimKey anim_load_key(const float4* keys, uint32_t key, uint32_t J, uint32_t j) {
     const float4* k = keys + ((size_t)key * J + j) * 3;
@@ -541,83 +516,27 @@ __global__ __launch_bounds__(MTR_POSE_MAX_JOINTS) void k_anim_layers_tracks_samp
 
 }  // namespace mtr
 
-static bool anim_launchable(const AnimParams& p, uint32_t ninst) {
-    return ninst != 0 && p.nclips != 0 && p.pose.njoints != 0 && p.pose.njoints <= MTR_POSE_MAX_JOINTS;
-}
-static bool anim_layers_launchable(const AnimLayerParams& p, uint32_t ninst, bool tracks) {
-    return anim_launchable(p.anim, ninst) && p.layers && p.nlayers >= 1u && p.nlayers <= MTR_ANIM_MAX_LAYERS && (p.nmasks == 0u || p.masks) &&
-           (tracks ? p.anim.tracks != nullptr : p.anim.keys != nullptr);
-}
-static bool anim_ik_launchable(const AnimIkParams& p, uint32_t ninst, bool tracks) {
-    return anim_layers_launchable(p.layers, ninst, tracks) && p.chains && p.targets && p.paths && p.path_words && p.nchains >= 1u &&
-           p.nchains <= MTR_ANIM_MAX_IK && p.path_bytes != 0u && p.path_bytes <= MTR_POSE_MAX_PATH_BYTES;
-}
-// the IK part may be empty here (no chains, no targets); the states are written, 16 bytes at a time
-static bool anim_spring_launchable(const AnimSpringParams& p, uint32_t ninst, bool tracks) {
-    const AnimIkParams& ip = p.ik;
-    return anim_layers_launchable(ip.layers, ninst, tracks) && ip.nchains <= MTR_ANIM_MAX_IK && (ip.nchains == 0u || (ip.chains && ip.targets)) && ip.paths &&
-           ip.path_words && ip.path_bytes != 0u && ip.path_bytes <= MTR_POSE_MAX_PATH_BYTES && p.springs && p.joint_tab && p.states &&
-           ((uintptr_t)p.states & 15u) == 0u && ((uintptr_t)p.motion & 15u) == 0u && p.nsprings >= 1u && p.nsprings <= MTR_ANIM_MAX_SPRINGS &&
-           p.nrounds >= 1u && p.nrounds <= p.nsprings;
-}
-static bool fold_fits(const PoseParams& pose) { return pose.path_bytes <= MTR_POSE_MAX_PATH_BYTES; }
-
-// the launch every kernel here takes, if its parameters pass: a block per instance, a thread per joint in whole waves, `lds`
-// bytes for the path table
+// One launcher per stage: the kernel by the set's kind (tracks) and by fold or sample; whether it is launched, and with how
+// many threads and how much LDS for the path table, is anim_launch.h's to say.  A block per instance.
 template <class P>
-static void anim_launch(void (*kernel)(P), const P& p, bool ok, uint32_t njoints, uint32_t lds, uint32_t ninst, hipStream_t s) {
-    if (ok) hipLaunchKernelGGL(kernel, dim3(ninst), dim3((njoints + 63u) & ~63u), lds, s, p);
+static void anim_launch(void (*const (&kernels)[2][2])(P), const P& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s) {
+    const AnimLaunchPlan plan = anim_launch_plan(p, tracks, fold, ninst);
+    if (plan.ok) hipLaunchKernelGGL(kernels[tracks][fold], dim3(ninst), dim3(plan.threads), plan.lds_bytes, s, p);
 }
 
-void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim, p, anim_launchable(p, ninst) && fold_fits(p.pose), p.pose.njoints, p.pose.path_bytes, ninst, s);
+void mtr_launch_anim(const AnimParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s) {
+    static void (*const k[2][2])(AnimParams) = {{mtr::k_anim_sample, mtr::k_anim}, {mtr::k_anim_tracks_sample, mtr::k_anim_tracks}};
+    anim_launch(k, p, tracks, fold, ninst, s);
 }
-void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_sample, p, anim_launchable(p, ninst), p.pose.njoints, 0, ninst, s);
+void mtr_launch_anim_layers(const AnimLayerParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s) {
+    static void (*const k[2][2])(AnimLayerParams) = {{mtr::k_anim_layers_sample, mtr::k_anim_layers}, {mtr::k_anim_layers_tracks_sample, mtr::k_anim_layers_tracks}};
+    anim_launch(k, p, tracks, fold, ninst, s);
 }
-void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_tracks, p, anim_launchable(p, ninst) && fold_fits(p.pose) && p.tracks, p.pose.njoints, p.pose.path_bytes, ninst, s);
+void mtr_launch_anim_ik(const AnimIkParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s) {
+    static void (*const k[2][2])(AnimIkParams) = {{mtr::k_anim_ik_sample, mtr::k_anim_ik}, {mtr::k_anim_ik_tracks_sample, mtr::k_anim_ik_tracks}};
+    anim_launch(k, p, tracks, fold, ninst, s);
 }
-void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_tracks_sample, p, anim_launchable(p, ninst) && p.tracks, p.pose.njoints, 0, ninst, s);
-}
-void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_layers, p, anim_layers_launchable(p, ninst, false) && fold_fits(p.anim.pose), p.anim.pose.njoints, p.anim.pose.path_bytes, ninst, s);
-}
-void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_layers_sample, p, anim_layers_launchable(p, ninst, false), p.anim.pose.njoints, 0, ninst, s);
-}
-void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_layers_tracks, p, anim_layers_launchable(p, ninst, true) && fold_fits(p.anim.pose), p.anim.pose.njoints, p.anim.pose.path_bytes, ninst, s);
-}
-void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_layers_tracks_sample, p, anim_layers_launchable(p, ninst, true), p.anim.pose.njoints, 0, ninst, s);
-}
-// the chain walks need the path table in LDS also where nothing is folded; a fold reads the same one
-void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_ik, p, anim_ik_launchable(p, ninst, false) && p.layers.anim.pose.path_bytes == p.path_bytes, p.layers.anim.pose.njoints, p.path_bytes, ninst, s);
-}
-void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_ik_sample, p, anim_ik_launchable(p, ninst, false), p.layers.anim.pose.njoints, p.path_bytes, ninst, s);
-}
-void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_ik_tracks, p, anim_ik_launchable(p, ninst, true) && p.layers.anim.pose.path_bytes == p.path_bytes, p.layers.anim.pose.njoints, p.path_bytes, ninst, s);
-}
-void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_ik_tracks_sample, p, anim_ik_launchable(p, ninst, true), p.layers.anim.pose.njoints, p.path_bytes, ninst, s);
-}
-// the springs walk the same path table as the chains
-void mtr_launch_anim_spring(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) {
-    const AnimIkParams& ip = p.ik;
-    anim_launch(mtr::k_anim_spring, p, anim_spring_launchable(p, ninst, false) && ip.layers.anim.pose.path_bytes == ip.path_bytes, ip.layers.anim.pose.njoints, ip.path_bytes, ninst, s);
-}
-void mtr_launch_anim_spring_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_spring_sample, p, anim_spring_launchable(p, ninst, false), p.ik.layers.anim.pose.njoints, p.ik.path_bytes, ninst, s);
-}
-void mtr_launch_anim_spring_tracks(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) {
-    const AnimIkParams& ip = p.ik;
-    anim_launch(mtr::k_anim_spring_tracks, p, anim_spring_launchable(p, ninst, true) && ip.layers.anim.pose.path_bytes == ip.path_bytes, ip.layers.anim.pose.njoints, ip.path_bytes, ninst, s);
-}
-void mtr_launch_anim_spring_tracks_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s) {
-    anim_launch(mtr::k_anim_spring_tracks_sample, p, anim_spring_launchable(p, ninst, true), p.ik.layers.anim.pose.njoints, p.ik.path_bytes, ninst, s);
+void mtr_launch_anim_spring(const AnimSpringParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s) {
+    static void (*const k[2][2])(AnimSpringParams) = {{mtr::k_anim_spring_sample, mtr::k_anim_spring}, {mtr::k_anim_spring_tracks_sample, mtr::k_anim_spring_tracks}};
+    anim_launch(k, p, tracks, fold, ninst, s);
 }

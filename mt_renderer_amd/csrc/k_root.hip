@@ -19,7 +19,7 @@
 // is clamped to n - 1 and the step index to nsteps - 1, so inst * nsteps + step lies inside it (lanes of instances past n
 // compute instance n - 1 again and store nothing).  From a record come (a) the clip index, clamped to nclips - 1 before it
 // reaches the clip table, the root flags or a descriptor, (b) x and dx, which root_positions turns into positions that are
-// -0 or lie in [0, N - 1] for every float pattern, and which root_uniform_keys / root_sample_tracks clamp once more into
+// -0 or lie in [0, N - 1] for every float pattern, and which anim_position / root_sample_tracks clamp once more into
 // key indices inside the clip (the argument at track_clip_begin in k_anim.hip holds for the search), and (c) the weight,
 // which reaches no address.  joint < njoints is validated on the host.  No device-side value forms an address unclamped.
 #include "mtr_internal.h"

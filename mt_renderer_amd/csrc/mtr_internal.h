@@ -505,16 +505,15 @@ struct AnimParams {
     const float* keys;          // (total keys) x njoints x 12 f32, key-major, joint fastest; 16-byte aligned
     const uint32_t* states;     // ninst x 6 words: clip_a, clip_b, x_a, x_b, w (f32 bits), pad; 8-byte aligned
     uint32_t nclips;            // >= 1
-    // a track set (SPEC.md section 15; the *_tracks launchers only, nullptr otherwise).  clips then holds per clip: 0, its
+    // a track set (SPEC.md section 15; launches with `tracks` only, nullptr otherwise).  clips then holds per clip: 0, its
     // length in ticks (1..65536), flags, 0; keys is nullptr
     const uint32_t* tracks;     // nclips x njoints x 3 descriptors of 8 words (mtr_anim_track: first, count, lo[3], step[3]); 16-byte aligned
     const uint32_t* values;     // (total keys) x 2 words: four 16-bit words per key; 8-byte aligned
     const uint16_t* times;      // (total keys) u16 ticks
 };
-void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t s);
+// One launcher per stage of k_anim.hip.  tracks: the set is a track set; fold: the palettes are folded (the k_anim* kernels),
+// otherwise the local matrices are stored (the *_sample kernels).  Whether a launch happens: anim_launch.h
+void mtr_launch_anim(const AnimParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s);
 // animation layers (k_anim.hip, SPEC.md section 16): per instance nlayers records over the same set; AnimParams::states unused
 #define MTR_ANIM_MAX_LAYERS 8
 struct AnimLayerParams {
@@ -524,10 +523,7 @@ struct AnimLayerParams {
     uint32_t nlayers;           // 1..MTR_ANIM_MAX_LAYERS, a validated host value
     uint32_t nmasks;            // 0 without a mask set
 };
-void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_layers(const AnimLayerParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s);
 // inverse kinematics after the layer stack (k_anim.hip, SPEC.md section 17): per instance nchains targets over the chains
 // of an IK set.  paths / path_words: the skeleton's path table and path bytes that the chain walks read -- the model's own
 // (the same memory as layers.anim.pose's) where the palettes are folded, the IK set's copy where the locals are sampled
@@ -541,10 +537,7 @@ struct AnimIkParams {
     uint32_t nchains;           // 1..MTR_ANIM_MAX_IK, a validated host value
     uint32_t path_bytes;
 };
-void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_ik(const AnimIkParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s);
 // spring bones after the IK chains (k_anim.hip, SPEC.md section 24): per instance nsprings state records, read and written,
 // over the springs of a spring set.  ik.nchains may be 0 here (ik.chains and ik.targets are then unused); ik.paths,
 // ik.path_words and ik.path_bytes are what the chain walks and the spring walks read.
@@ -560,10 +553,7 @@ struct AnimSpringParams {
     uint32_t nsprings;          // 1..MTR_ANIM_MAX_SPRINGS, a validated host value
     uint32_t nrounds;           // 1 + the largest round, a host value
 };
-void mtr_launch_anim_spring(const AnimSpringParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_spring_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_spring_tracks(const AnimSpringParams& p, uint32_t ninst, hipStream_t s);
-void mtr_launch_anim_spring_tracks_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t s);
+void mtr_launch_anim_spring(const AnimSpringParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t s);
 // attachments (k_attach.hip, SPEC.md section 18): n instance matrices from the matrices and palettes of a source batch's version
 struct AttachParams {
     const uint32_t* recs;       // n x 20 words (mtr_attach: src_instance, joint, flags, pad, offset[16]); 16-byte aligned

@@ -7,21 +7,10 @@
 // One rounded operation per operator; nothing here is fused (the including file is compiled with -ffp-contract=off) and '/'
 // is correctly rounded.  NaN compares false, which every test below is written for.
 #pragma once
-#include <cstdint>
-#include <cmath>
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define MTR_PLAY_HD __host__ __device__ __forceinline__
-#else
-#define MTR_PLAY_HD inline
-#endif
+#include "clip_math.h"
 
 #ifndef MTR_PLAY_ENDED  // include/mtr.h has the same
 #define MTR_PLAY_ENDED 1u
-#endif
-#ifndef MTR_CLIP_LOOP
-#define MTR_CLIP_LOOP 1u
 #endif
 
 namespace mtr {
@@ -58,26 +47,15 @@ struct PlayFrame {
     float x0_a, dx_a, x0_b, dx_b;
 };
 
-// section 14's clamp of a weight: NaN -> 0, then [0, 1]
-MTR_PLAY_HD float play_weight(float w) {
-    w = w > 0.0f ? w : 0.0f;
-    return w > 1.0f ? 1.0f : w;
-}
-
 // x' = adv(x, dx, clip): on a LOOP clip section 14's wrap of y = x + dx with its fallback, otherwise its clamp to [0, P]
-MTR_PLAY_HD float play_adv(float x, float dx, const PlayClip& c) {
-    const float y = x + dx, P = c.period;
-    if (c.flags & MTR_CLIP_LOOP) {
-        const float r = y - floorf(y / P) * P;
-        return (r >= 0.0f && r < P) ? r : 0.0f;
-    }
-    const float r = y >= 0.0f ? y : 0.0f;
-    return r > P ? P : r;
+MTR_HD float play_adv(float x, float dx, const PlayClip& c) {
+    const float y = x + dx;
+    return (c.flags & MTR_CLIP_LOOP) ? clip_wrap(y, c.period) : clip_clamp(y, c.period);
 }
 
 // Steps 1 to 8 of section 20 for one instance.  st: the stored state, rewritten; cmd: the one command that reaches the
 // instance, or nullptr; table: nclips >= 1 entries, read through clamped indices only.
-MTR_PLAY_HD PlayFrame play_advance(PlayState& st, const PlayCmd* cmd, float dt, const PlayClip* table, uint32_t nclips) {
+MTR_HD PlayFrame play_advance(PlayState& st, const PlayCmd* cmd, float dt, const PlayClip* table, uint32_t nclips) {
     const uint32_t top = nclips - 1u;
     // 1. clamp
     uint32_t ca = st.clip_a < top ? st.clip_a : top, cb = st.clip_b < top ? st.clip_b : top;
@@ -87,7 +65,7 @@ MTR_PLAY_HD PlayFrame play_advance(PlayState& st, const PlayCmd* cmd, float dt, 
         const uint32_t c = cmd->clip < top ? cmd->clip : top;
         const float r = 1.0f / cmd->seconds;
         if (cmd->seconds > 0.0f && r > 0.0f && r <= PLAY_FLT_MAX) {  // a fade
-            if (fade > 0.0f && play_weight(w) >= 0.5f) { ca = cb; xa = xb; }
+            if (fade > 0.0f && anim_weight(w) >= 0.5f) { ca = cb; xa = xb; }
             cb = c; xb = cmd->x; w = 0.0f; fade = r;
         } else {  // a cut
             ca = c; xa = cmd->x; w = 0.0f; fade = 0.0f;
@@ -112,7 +90,7 @@ MTR_PLAY_HD PlayFrame play_advance(PlayState& st, const PlayCmd* cmd, float dt, 
         f.dx_b = s * tb.rate;
         f.x0_b = xb;
         f.x_b = play_adv(xb, f.dx_b, tb);
-        w1 = play_weight(w) + dtp * fade;
+        w1 = anim_weight(w) + dtp * fade;
         f.w = w1 > 1.0f ? 1.0f : w1;
     } else {
         f.dx_b = 0.0f;

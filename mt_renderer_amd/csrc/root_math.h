@@ -26,7 +26,7 @@ struct RootXf {
     AnimVec q;
 };
 
-MTR_BLEND_HD RootXf root_identity() {
+MTR_HD RootXf root_identity() {
     RootXf r;
     r.t = ik_vec3(0.0f, 0.0f, 0.0f);
     r.q = anim_vec(0.0f, 0.0f, 0.0f, 1.0f);
@@ -44,7 +44,7 @@ struct RootPos {
 };
 
 // n: the clip's key count or tick count (>= 1); flags: the root set's word of the clip (bit 0 is the only one set)
-MTR_BLEND_HD RootPos root_positions(float x, float dx, uint32_t n, uint32_t flags) {
+MTR_HD RootPos root_positions(float x, float dx, uint32_t n, uint32_t flags) {
     RootPos p;
     const float L = (float)(n - 1u);
     p.r[1] = L; p.r[2] = 0.0f;
@@ -60,8 +60,7 @@ MTR_BLEND_HD RootPos root_positions(float x, float dx, uint32_t n, uint32_t flag
         p.kind = ROOT_IDENTITY;
         return p;
     }
-    float r0 = x - floorf(x / L) * L;
-    if (!(r0 >= 0.0f && r0 < L)) r0 = 0.0f;
+    const float r0 = clip_wrap(x, L);
     const float y = r0 + dx;
     float r1 = y;
     if (y < 0.0f) {
@@ -79,31 +78,17 @@ MTR_BLEND_HD RootPos root_positions(float x, float dx, uint32_t n, uint32_t flag
     return p;
 }
 
-// "one clip at r" of section 14 for one joint, under the clamp rule: the two keys and the fraction
-struct RootKeys {
-    uint32_t i0, i1;
-    float a;
-};
-
-MTR_BLEND_HD RootKeys root_uniform_keys(float r, uint32_t nkeys) {
-    RootKeys k;
-    const float pos = track_position(r, nkeys, 0u);  // idempotent on a step's positions; any float lands inside the clip
-    k.i0 = (uint32_t)floorf(pos);
-    k.i1 = k.i0 + 1u < nkeys ? k.i0 + 1u : nkeys - 1u;
-    k.a = pos - (float)k.i0;
-    return k;
-}
-
-MTR_BLEND_HD RootXf root_mix(const AnimVec& t0, const AnimVec& t1, const AnimVec& q0, const AnimVec& q1, float at, float aq) {
+MTR_HD RootXf root_mix(const AnimVec& t0, const AnimVec& t1, const AnimVec& q0, const AnimVec& q1, float at, float aq) {
     RootXf s;
     s.t = ik_vec3(anim_lerp(t0.x, t1.x, at), anim_lerp(t0.y, t1.y, at), anim_lerp(t0.z, t1.z, at));
     s.q = anim_nlerp(q0, q1, aq);
     return s;
 }
 
-// R(r) from uniform keys (12 floats per joint key, key-major, joint fastest); first: the clip's first key
-MTR_BLEND_HD RootXf root_sample_uniform(const float* keys, uint32_t first, uint32_t nkeys, uint32_t J, uint32_t j, float r) {
-    const RootKeys k = root_uniform_keys(r, nkeys);
+// R(r) from uniform keys (12 floats per joint key, key-major, joint fastest); first: the clip's first key.  "One clip at r"
+// of section 14 under the clamp rule: idempotent on a step's positions, and any float lands inside the clip
+MTR_HD RootXf root_sample_uniform(const float* keys, uint32_t first, uint32_t nkeys, uint32_t J, uint32_t j, float r) {
+    const AnimPos k = anim_position(r, nkeys, 0u);
     const float* p0 = keys + ((size_t)(first + k.i0) * J + j) * 12;
     const float* p1 = keys + ((size_t)(first + k.i1) * J + j) * 12;
     const AnimVec t0 = anim_vec(p0[0], p0[1], p0[2], 0.0f), q0 = anim_vec(p0[4], p0[5], p0[6], p0[7]);
@@ -114,7 +99,7 @@ MTR_BLEND_HD RootXf root_sample_uniform(const float* keys, uint32_t first, uint3
 // R(r) from a track set: desc points at the joint's three 8-word descriptors of the clip (translation, rotation, scale; the
 // scale's is not read).  The two searches advance together, a step's probes in flight at once; then both time loads and
 // the four value loads are issued before the first use.
-MTR_BLEND_HD RootXf root_sample_tracks(const uint32_t* desc, const uint32_t* values, const uint16_t* times, uint32_t nticks, float r) {
+MTR_HD RootXf root_sample_tracks(const uint32_t* desc, const uint32_t* values, const uint16_t* times, uint32_t nticks, float r) {
     const float pos = track_position(r, nticks, 0u);
     const uint32_t ft = desc[0], ct = desc[1], fq = desc[8], cq = desc[9];
     float lo[3], step[3];
@@ -144,7 +129,7 @@ MTR_BLEND_HD RootXf root_sample_tracks(const uint32_t* desc, const uint32_t* val
 }
 
 // delta(a -> b): b seen from a
-MTR_BLEND_HD RootXf root_delta(const RootXf& a, const RootXf& b) {
+MTR_HD RootXf root_delta(const RootXf& a, const RootXf& b) {
     const AnimVec ca = ik_conj(a.q);
     RootXf d;
     d.q = anim_qmul(ca, b.q);
@@ -153,7 +138,7 @@ MTR_BLEND_HD RootXf root_delta(const RootXf& a, const RootXf& b) {
 }
 
 // d1 o d2: d2 carried out in the frame d1 ends in
-MTR_BLEND_HD RootXf root_compose(const RootXf& d1, const RootXf& d2) {
+MTR_HD RootXf root_compose(const RootXf& d1, const RootXf& d2) {
     RootXf d;
     d.t = ik_add(d1.t, ik_qrot(d1.q, d2.t));
     d.q = anim_qmul(d1.q, d2.q);
@@ -161,7 +146,7 @@ MTR_BLEND_HD RootXf root_compose(const RootXf& d1, const RootXf& d2) {
 }
 
 // the delta of a step from the samples at its four positions; the rotation renormalised once
-MTR_BLEND_HD RootXf root_step_delta(const RootXf (&s)[4], uint32_t kind) {
+MTR_HD RootXf root_step_delta(const RootXf (&s)[4], uint32_t kind) {
     if (kind == ROOT_IDENTITY) return root_identity();
     RootXf d = kind == ROOT_SEAM ? root_compose(root_delta(s[0], s[1]), root_delta(s[2], s[3])) : root_delta(s[0], s[3]);
     d.q = ik_norm4(d.q);
@@ -170,7 +155,7 @@ MTR_BLEND_HD RootXf root_step_delta(const RootXf (&s)[4], uint32_t kind) {
 
 // one further step over the blend so far (section 16's OVERRIDE with mask 0); w as stored.  A step whose clamped weight is 0
 // changes nothing: its delta is not read.
-MTR_BLEND_HD void root_blend(RootXf& acc, const RootXf& d, float w) {
+MTR_HD void root_blend(RootXf& acc, const RootXf& d, float w) {
     const float e = anim_weight(w);
     if (e == 0.0f) return;
     acc.t = ik_vec3(anim_lerp(acc.t.x, d.t.x, e), anim_lerp(acc.t.y, d.t.y, e), anim_lerp(acc.t.z, d.t.z, e));
@@ -178,7 +163,7 @@ MTR_BLEND_HD void root_blend(RootXf& acc, const RootXf& d, float w) {
 }
 
 // section 14's local matrix of (T, Q, S = (1, 1, 1)), column-major
-MTR_BLEND_HD void root_matrix(const RootXf& d, AnimVec (&M)[4]) {
+MTR_HD void root_matrix(const RootXf& d, AnimVec (&M)[4]) {
     AnimKey k;
     k.t = anim_vec(d.t.x, d.t.y, d.t.z, 0.0f);
     k.q = d.q;

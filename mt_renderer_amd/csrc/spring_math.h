@@ -21,11 +21,11 @@ struct SpringMotion {
     IkVec3 c0, c1, c2, t;
 };
 
-MTR_BLEND_HD bool spring_finite(float x) { return fabsf(x) <= 3.402823466e38f; }  // NaN compares false
-MTR_BLEND_HD bool spring_finite3(const IkVec3& v) { return spring_finite(v.x) && spring_finite(v.y) && spring_finite(v.z); }
+MTR_HD bool spring_finite(float x) { return fabsf(x) <= 3.402823466e38f; }  // NaN compares false
+MTR_HD bool spring_finite3(const IkVec3& v) { return spring_finite(v.x) && spring_finite(v.y) && spring_finite(v.z); }
 
 // p seen from the instance's new model space: R^T (p - t), the inverse of a rigid D
-MTR_BLEND_HD IkVec3 spring_carry(const SpringMotion& D, const IkVec3& p) {
+MTR_HD IkVec3 spring_carry(const SpringMotion& D, const IkVec3& p) {
     const IkVec3 u = ik_sub(p, D.t);
     return ik_vec3(ik_dot3(D.c0, u), ik_dot3(D.c1, u), ik_dot3(D.c2, u));
 }
@@ -35,7 +35,7 @@ MTR_BLEND_HD IkVec3 spring_carry(const SpringMotion& D, const IkVec3& p) {
 // (tail finite and not zero, stiffness finite and >= 0, drag in [0, 1], gravity finite); dt: the call's, any bit pattern;
 // moved, D: whether the instance has a delta, and that delta (not read otherwise); st: the state record, any bit pattern
 // in, the new record out (live = 1).  Returns whether the aim's guard held; when it did not, qa is untouched bit for bit.
-MTR_BLEND_HD bool spring_step(const IkVec3& pa, const AnimVec& P, AnimVec& qa, const IkVec3& tail, const IkVec3& gravity, float stiffness, float drag,
+MTR_HD bool spring_step(const IkVec3& pa, const AnimVec& P, AnimVec& qa, const IkVec3& tail, const IkVec3& gravity, float stiffness, float drag,
                               float dt, bool moved, const SpringMotion& D, SpringState& st) {
     const AnimVec A0 = anim_qmul(P, qa);
     const IkVec3 d0 = ik_qrot(A0, tail);

@@ -78,18 +78,13 @@ static std::string ik_str(const AnimIkParams& k) {
     return s + layers_str(k.layers);
 }
 void mtr_launch_pose(const PoseParams& p, uint32_t n, hipStream_t s) { launched("pose", n, s, pose_str(p)); }
-void mtr_launch_anim(const AnimParams& p, uint32_t n, hipStream_t s) { launched("anim", n, s, anim_str(p)); }
-void mtr_launch_anim_sample(const AnimParams& p, uint32_t n, hipStream_t s) { launched("anim_sample", n, s, anim_str(p)); }
-void mtr_launch_anim_tracks(const AnimParams& p, uint32_t n, hipStream_t s) { launched("anim_tracks", n, s, anim_str(p)); }
-void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t n, hipStream_t s) { launched("anim_tracks_sample", n, s, anim_str(p)); }
-void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t n, hipStream_t s) { launched("anim_layers", n, s, layers_str(p)); }
-void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t n, hipStream_t s) { launched("anim_layers_sample", n, s, layers_str(p)); }
-void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t n, hipStream_t s) { launched("anim_layers_tracks", n, s, layers_str(p)); }
-void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t n, hipStream_t s) { launched("anim_layers_tracks_sample", n, s, layers_str(p)); }
-void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t n, hipStream_t s) { launched("anim_ik", n, s, ik_str(p)); }
-void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t n, hipStream_t s) { launched("anim_ik_sample", n, s, ik_str(p)); }
-void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t n, hipStream_t s) { launched("anim_ik_tracks", n, s, ik_str(p)); }
-void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t n, hipStream_t s) { launched("anim_ik_tracks_sample", n, s, ik_str(p)); }
+// a k_anim launcher's name: the stage, then the set's kind, then fold or sample, as the kernels are named
+static std::string anim_name(const char* stage, bool tracks, bool fold) { return std::string(stage) + (tracks ? "_tracks" : "") + (fold ? "" : "_sample"); }
+void mtr_launch_anim(const AnimParams& p, bool tracks, bool fold, uint32_t n, hipStream_t s) { launched(anim_name("anim", tracks, fold).c_str(), n, s, anim_str(p)); }
+void mtr_launch_anim_layers(const AnimLayerParams& p, bool tracks, bool fold, uint32_t n, hipStream_t s) {
+    launched(anim_name("anim_layers", tracks, fold).c_str(), n, s, layers_str(p));
+}
+void mtr_launch_anim_ik(const AnimIkParams& p, bool tracks, bool fold, uint32_t n, hipStream_t s) { launched(anim_name("anim_ik", tracks, fold).c_str(), n, s, ik_str(p)); }
 void mtr_launch_attach(const AttachParams& p, hipStream_t s) {
     std::string t = " n_src=" + num(p.n_src) + " npal=" + num(p.npal) + " recs=" + B(p.recs);
     t += " src_mats=" + B(p.src_mats) + " src_pals=" + off(p.src_pals, p.src_mats);
@@ -165,10 +160,9 @@ static std::string spring_str(const AnimSpringParams& p) {
     }
     return s + layers_str(k.layers);
 }
-void mtr_launch_anim_spring(const AnimSpringParams& p, uint32_t n, hipStream_t s) { launched("anim_spring", n, s, spring_str(p)); }
-void mtr_launch_anim_spring_sample(const AnimSpringParams& p, uint32_t n, hipStream_t s) { launched("anim_spring_sample", n, s, spring_str(p)); }
-void mtr_launch_anim_spring_tracks(const AnimSpringParams& p, uint32_t n, hipStream_t s) { launched("anim_spring_tracks", n, s, spring_str(p)); }
-void mtr_launch_anim_spring_tracks_sample(const AnimSpringParams& p, uint32_t n, hipStream_t s) { launched("anim_spring_tracks_sample", n, s, spring_str(p)); }
+void mtr_launch_anim_spring(const AnimSpringParams& p, bool tracks, bool fold, uint32_t n, hipStream_t s) {
+    launched(anim_name("anim_spring", tracks, fold).c_str(), n, s, spring_str(p));
+}
 void mtr_launch_geom(const GeomParams&, hipStream_t) {}
 void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
 void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}

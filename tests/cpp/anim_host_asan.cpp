@@ -1,7 +1,7 @@
 // AddressSanitizer / UBSan run of the HOST side of the animation entry points (csrc/host_anim.cpp, csrc/host_batch.cpp: mtr_anim_*, mtr_*_animate*)
-// over the stand-in HIP runtime (tests/cpp/hip_stub: device memory = host heap).  The k_anim launchers here are readers: they
-// touch, for every instance, its state and the first and last word of the keys its (clamped) clips own, and the last word of
-// what they would write, so a wrong size or offset on the host side is an ASan report.   usage: anim_host_asan <iterations>
+// over the stand-in HIP runtime (tests/cpp/hip_stub: device memory = host heap).  The k_anim launcher here is a reader: it
+// touches, for every instance, its state and the first and last word of the keys its (clamped) clips own, and the last word of
+// what it would write, so a wrong size or offset on the host side is an ASan report.   usage: anim_host_asan <iterations>
 #include "host_all.h"
 using namespace mtr_host;
 #include "../../mt_renderer_amd/csrc/mtr_files.cpp"
@@ -39,11 +39,11 @@ static float touch(const AnimParams& p, uint32_t ninst) {
     p.pose.out[(size_t)ninst * J * 16 - 1] = acc;
     return acc;
 }
-void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t) {
-    if (p.pose.imats[(size_t)p.pose.njoints * 16 - 1] != 1.0f) abort();  // the skeleton's last inverse bind element
+void mtr_launch_anim(const AnimParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t) {
+    if (tracks) abort();  // uniform sets only here
+    if (fold && p.pose.imats[(size_t)p.pose.njoints * 16 - 1] != 1.0f) abort();  // the skeleton's last inverse bind element
     touch(p, ninst);
 }
-void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t) { touch(p, ninst); }
 
 static uint64_t rs = 0x13198A2E03707344ull;
 static uint64_t rnd() {

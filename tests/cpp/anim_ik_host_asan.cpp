@@ -1,8 +1,8 @@
 // AddressSanitizer / UBSan run of the HOST side of inverse kinematics (csrc/host_anim.cpp, csrc/host_batch.cpp: mtr_anim_ik_create / _destroy,
 // mtr_model_animate_ik, mtr_batch_animate_ik, mtr_batch_animate_ik_device, mtr_anim_sample_ik) over the stand-in HIP runtime
-// (tests/cpp/hip_stub: device memory = host heap).  The four k_anim_ik launchers here are readers: for every instance they
-// touch its first and last layer and its first and last target, every chain of the set, the path table entry of every
-// chain's joint a with the first and last byte of that path, and they write the last word of the output.  A wrong size or
+// (tests/cpp/hip_stub: device memory = host heap).  The k_anim_ik launcher here is a reader: for every instance it
+// touches its first and last layer and its first and last target, every chain of the set, the path table entry of every
+// chain's joint a with the first and last byte of that path, and it writes the last word of the output.  A wrong size or
 // offset on the host side is an ASan report.
 //   usage: anim_ik_host_asan <iterations>
 #include "host_all.h"
@@ -25,12 +25,14 @@ void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t
 void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
 // the other pose sources: the plain, layered and posed calls are made here too, between the IK ones
 void mtr_launch_pose(const PoseParams& p, uint32_t ninst, hipStream_t) { p.out[(size_t)ninst * p.njoints * 16 - 1] = p.locals[(size_t)ninst * p.njoints * 16 - 1]; }
-void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t) { p.pose.out[(size_t)ninst * p.pose.njoints * 16 - 1] = (float)p.states[(size_t)ninst * 6 - 1]; }
-void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s) { mtr_launch_anim(p, ninst, s); }
-void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t) {
+void mtr_launch_anim(const AnimParams& p, bool, bool fold, uint32_t ninst, hipStream_t) {
+    if (!fold) abort();  // no plain or layered sample call is made here
+    p.pose.out[(size_t)ninst * p.pose.njoints * 16 - 1] = (float)p.states[(size_t)ninst * 6 - 1];
+}
+void mtr_launch_anim_layers(const AnimLayerParams& p, bool, bool fold, uint32_t ninst, hipStream_t) {
+    if (!fold) abort();
     p.anim.pose.out[(size_t)ninst * p.anim.pose.njoints * 16 - 1] = (float)p.layers[(size_t)ninst * p.nlayers * 4 - 1];
 }
-void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) { mtr_launch_anim_layers(p, ninst, s); }
 
 static uint64_t g_target_reads = 0, g_chain_reads = 0, g_path_reads = 0;
 static void touch_ik(const AnimIkParams& p, uint32_t ninst, bool tracks, bool fold) {
@@ -64,10 +66,7 @@ static void touch_ik(const AnimIkParams& p, uint32_t ninst, bool tracks, bool fo
     }
     a.pose.out[(size_t)ninst * J * 16 - 1] = (float)acc;
 }
-void mtr_launch_anim_ik(const AnimIkParams& p, uint32_t ninst, hipStream_t) { touch_ik(p, ninst, false, true); }
-void mtr_launch_anim_ik_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t) { touch_ik(p, ninst, false, false); }
-void mtr_launch_anim_ik_tracks(const AnimIkParams& p, uint32_t ninst, hipStream_t) { touch_ik(p, ninst, true, true); }
-void mtr_launch_anim_ik_tracks_sample(const AnimIkParams& p, uint32_t ninst, hipStream_t) { touch_ik(p, ninst, true, false); }
+void mtr_launch_anim_ik(const AnimIkParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t) { touch_ik(p, ninst, tracks, fold); }
 
 static uint64_t rs = 0x243F6A8885A308D3ull;
 static uint64_t rnd() {

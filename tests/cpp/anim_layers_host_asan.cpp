@@ -1,9 +1,9 @@
 // AddressSanitizer / UBSan run of the HOST side of animation layers (csrc/host_anim.cpp, csrc/host_batch.cpp: mtr_anim_masks_create / _destroy,
 // mtr_model_animate_layers, mtr_batch_animate_layers, mtr_batch_animate_layers_device, mtr_anim_sample_layers) over the
-// stand-in HIP runtime (tests/cpp/hip_stub: device memory = host heap).  The four k_anim_layers launchers here are readers:
-// for every instance they touch its first and last layer and, of every layer, the first and last weight of the mask it
+// stand-in HIP runtime (tests/cpp/hip_stub: device memory = host heap).  The k_anim_layers launcher here is a reader:
+// for every instance it touches its first and last layer and, of every layer, the first and last weight of the mask it
 // names (clamped) and the clip table entry with the first and last key (or descriptor) of the clip it names (clamped), and
-// they write the last word of the output.  A wrong size or offset on the host side is an ASan report.
+// it writes the last word of the output.  A wrong size or offset on the host side is an ASan report.
 //   usage: anim_layers_host_asan <iterations>
 #include "host_all.h"
 using namespace mtr_host;
@@ -24,8 +24,10 @@ void mtr_launch_unpack_shards(const uint8_t*, uint8_t*, uint32_t, uint32_t, cons
 void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t i = 0; i < p.ninst; i++) { p.strad[p.count[1]++] = *p.count; p.list[(*p.count)++] = i; } }
 void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
 // the section-14 launchers: the plain animate calls are made here too, between the layered ones
-void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t) { p.pose.out[(size_t)ninst * p.pose.njoints * 16 - 1] = (float)p.states[(size_t)ninst * 6 - 1]; }
-void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t) { p.pose.out[(size_t)ninst * p.pose.njoints * 16 - 1] = (float)p.states[(size_t)ninst * 6 - 1]; }
+void mtr_launch_anim(const AnimParams& p, bool, bool fold, uint32_t ninst, hipStream_t) {
+    if (!fold) abort();  // no plain sample call is made here
+    p.pose.out[(size_t)ninst * p.pose.njoints * 16 - 1] = (float)p.states[(size_t)ninst * 6 - 1];
+}
 
 static uint64_t g_layer_reads = 0, g_mask_reads = 0, g_clip_reads = 0;
 static void touch_layers(const AnimLayerParams& p, uint32_t ninst, bool tracks) {
@@ -64,10 +66,10 @@ static void touch_layers(const AnimLayerParams& p, uint32_t ninst, bool tracks) 
     a.pose.out[(size_t)ninst * J * 16 - 1] = acc;
 }
 static void check_skeleton(const AnimLayerParams& p) { if (p.anim.pose.imats[(size_t)p.anim.pose.njoints * 16 - 1] != 1.0f) abort(); }
-void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t) { check_skeleton(p); touch_layers(p, ninst, false); }
-void mtr_launch_anim_layers_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t) { touch_layers(p, ninst, false); }
-void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t) { check_skeleton(p); touch_layers(p, ninst, true); }
-void mtr_launch_anim_layers_tracks_sample(const AnimLayerParams& p, uint32_t ninst, hipStream_t) { touch_layers(p, ninst, true); }
+void mtr_launch_anim_layers(const AnimLayerParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t) {
+    if (fold) check_skeleton(p);
+    touch_layers(p, ninst, tracks);
+}
 
 static uint64_t rs = 0x13198A2E03707344ull;
 static uint64_t rnd() {

@@ -1,8 +1,8 @@
 // AddressSanitizer / UBSan run of the HOST side of animation tracks (csrc/host_anim.cpp, csrc/host_batch.cpp: mtr_anim_create_tracks and the
 // section-14 entry points on a track set) over the stand-in HIP runtime (tests/cpp/hip_stub: device memory = host heap).
-// The four k_anim launchers here are readers: for every instance they touch its state and, of every clip the state names
+// The k_anim launcher here is a reader: for every instance it touches its state and, of every clip the state names
 // (clamped), the first and last key of the uniform set, or the first and last descriptor of the track set and the first
-// and last time and value those descriptors own, and they write the last word of the output.  A wrong size or offset on
+// and last time and value those descriptors own, and it writes the last word of the output.  A wrong size or offset on
 // the host side is an ASan report.   usage: anim_tracks_host_asan <iterations>
 #include "host_all.h"
 using namespace mtr_host;
@@ -67,10 +67,10 @@ static void touch_tracks(const AnimParams& p, uint32_t ninst) {
     p.pose.out[(size_t)ninst * J * 16 - 1] = (float)acc;
 }
 static void check_skeleton(const AnimParams& p) { if (p.pose.imats[(size_t)p.pose.njoints * 16 - 1] != 1.0f) abort(); }
-void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t) { check_skeleton(p); touch_uniform(p, ninst); }
-void mtr_launch_anim_sample(const AnimParams& p, uint32_t ninst, hipStream_t) { touch_uniform(p, ninst); }
-void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t) { check_skeleton(p); touch_tracks(p, ninst); }
-void mtr_launch_anim_tracks_sample(const AnimParams& p, uint32_t ninst, hipStream_t) { touch_tracks(p, ninst); }
+void mtr_launch_anim(const AnimParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t) {
+    if (fold) check_skeleton(p);
+    if (tracks) touch_tracks(p, ninst); else touch_uniform(p, ninst);
+}
 
 static uint64_t rs = 0x243F6A8885A308D3ull;
 static uint64_t rnd() {

@@ -49,11 +49,11 @@ void mtr_launch_attach(const AttachParams& p, hipStream_t s) {
     p.out[(size_t)p.n * 16 - 1] = 1.0f;
     g_ops.push_back({"attach", p.out, s});
 }
-void mtr_launch_anim(const AnimParams& p, uint32_t ninst, hipStream_t s) {
+void mtr_launch_anim(const AnimParams& p, bool, bool fold, uint32_t ninst, hipStream_t s) {
+    if (!fold) abort();  // no sample call is made here
     p.pose.out[(size_t)ninst * p.pose.njoints * 16 - 1] = (float)p.states[(size_t)ninst * 6 - 1];
     g_ops.push_back({"anim", p.pose.out, s});
 }
-void mtr_launch_anim_tracks(const AnimParams& p, uint32_t ninst, hipStream_t s) { mtr_launch_anim(p, ninst, s); }
 void mtr_launch_geom(const GeomParams&, hipStream_t) {}
 void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
 void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}

@@ -1,6 +1,6 @@
 // AddressSanitizer / UBSan run of the HOST side of spring bones (csrc/host_spring.cpp, csrc/host_anim.cpp, csrc/host_batch.cpp:
 // mtr_anim_spring_create / _destroy, mtr_batch_animate_spring_device, mtr_anim_sample_spring) over the stand-in HIP runtime
-// (tests/cpp/hip_stub: device memory = host heap, everything runs at once).  The four k_anim_spring launchers here check the
+// (tests/cpp/hip_stub: device memory = host heap, everything runs at once).  The k_anim_spring launcher here checks the
 // set's image (the joint table against the springs, the path of every spring joint), touch the first and last layer, target
 // and motion matrix of every instance, and run the rule of csrc/spring_math.h on the state words they are handed, each
 // spring at a position made of its index and the instance's: a wrong size or offset on the host side is an ASan report, and
@@ -35,14 +35,12 @@ void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t
 void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
 // a spring call makes the checks of the kinds it nests over, so their kernels count as built; the layered call is made
 // here too, between the spring ones
-void mtr_launch_anim(const AnimParams&, uint32_t, hipStream_t) { abort(); }
-void mtr_launch_anim_tracks(const AnimParams&, uint32_t, hipStream_t) { abort(); }
-void mtr_launch_anim_layers(const AnimLayerParams& p, uint32_t ninst, hipStream_t) {
+void mtr_launch_anim(const AnimParams&, bool, bool, uint32_t, hipStream_t) { abort(); }
+void mtr_launch_anim_layers(const AnimLayerParams& p, bool, bool fold, uint32_t ninst, hipStream_t) {
+    if (!fold) abort();
     p.anim.pose.out[(size_t)ninst * p.anim.pose.njoints * 16 - 1] = (float)p.layers[(size_t)ninst * p.nlayers * 4 - 1];
 }
-void mtr_launch_anim_layers_tracks(const AnimLayerParams& p, uint32_t ninst, hipStream_t s) { mtr_launch_anim_layers(p, ninst, s); }
-void mtr_launch_anim_ik(const AnimIkParams&, uint32_t, hipStream_t) { abort(); }
-void mtr_launch_anim_ik_tracks(const AnimIkParams&, uint32_t, hipStream_t) { abort(); }
+void mtr_launch_anim_ik(const AnimIkParams&, bool, bool, uint32_t, hipStream_t) { abort(); }
 
 static float f32(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 static uint32_t u32(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
@@ -110,10 +108,7 @@ static void run_springs(const AnimSpringParams& p, uint32_t ninst, bool tracks, 
     }
     a.pose.out[(size_t)ninst * J * 16 - 1] = (float)acc;
 }
-void mtr_launch_anim_spring(const AnimSpringParams& p, uint32_t ninst, hipStream_t) { run_springs(p, ninst, false, true); }
-void mtr_launch_anim_spring_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t) { run_springs(p, ninst, false, false); }
-void mtr_launch_anim_spring_tracks(const AnimSpringParams& p, uint32_t ninst, hipStream_t) { run_springs(p, ninst, true, true); }
-void mtr_launch_anim_spring_tracks_sample(const AnimSpringParams& p, uint32_t ninst, hipStream_t) { run_springs(p, ninst, true, false); }
+void mtr_launch_anim_spring(const AnimSpringParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t) { run_springs(p, ninst, tracks, fold); }
 
 static uint64_t rs = 0x13198A2E03707344ull;
 static uint64_t rnd() {
