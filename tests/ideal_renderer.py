@@ -681,6 +681,8 @@ def _sample(R):
         with np.errstate(all="ignore"):
             D = lam.sum(axis=1)
             u, v = (lam * uu).sum(axis=1) / D, (lam * vv).sum(axis=1) / D
+            if R.mutate == "uv_affine":
+                u, v = (lam * uu * ww).sum(axis=1), (lam * vv * ww).sum(axis=1)
             aD = np.abs(D)
             gD = (Ainv[:, :, 0].sum(axis=1) * gx, Ainv[:, :, 1].sum(axis=1) * gy)
             out = [u, v]
