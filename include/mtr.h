@@ -660,6 +660,67 @@ int32_t mtr_anim_blend_advance_device(mtr_anim_blend *blend, mtr_blend_state *st
 int32_t mtr_anim_blend_advance_host(mtr_anim_blend *blend, mtr_blend_state *states, const float *params, size_t n, float dt,
                                     mtr_anim_layer *out_layers, size_t nlayers, mtr_root_step *out_steps, float *out_shares);
 
+/* ---- motion matching (build extension, SPEC.md section 25): nearest-pose search per instance (k_match) ----
+ * A controller is authored by hand; a match set chooses by search.  It holds the clips (nkeys, clip_flags as
+ * mtr_anim_ctrl_create takes them: the same periods P, no tie to a player handle), D features per row (D a multiple of 4 in
+ * 4..64) and R rows {clip, x, bias, tags} sorted by clip, x strictly increasing within a clip: row r says "clip at position x
+ * looks like features[r * D ..]".  The features are already normalised and weighted by whoever built the database
+ * (mt_renderer_amd/anim_match.py).  pose_dims has bit d set where dimension d describes the pose being played, the other
+ * dimensions describe where the game wants to go; mean and scale (D floats each, NULL: 0 and 1) normalise the game's raw
+ * query.  Per instance and call:
+ *   lead    : clip L and position p of what plays (clip B while fade > 0, else A; L clamped); cur = the row of L with the
+ *             largest x <= p, none when L has no rows, p is NaN or p lies below L's first row.
+ *   query   : q_d = features[cur][d] for a pose dimension with a cur, else (query[i * D + d] - mean_d) * scale_d.
+ *   score   : s_r = fma(q_{D-1}, f_r[D-1], ... fma(q_0, f_r[0], c_r)), c_r = -(0.5 * |f_r|^2 + bias_r): the greatest score is the
+ *             least 0.5 * |q - f_r|^2 + bias_r.  -0 counts as +0; a NaN score never wins.
+ *   winner  : the greatest score among the rows with (tags & require) == require and (tags & exclude) == 0 (NULL filters:
+ *             every row), the lowest row among equals.
+ *   command : slot i = {instance_base + i, clip_win, x_win, seconds}, or the ignored command {0xFFFFFFFF, 0, 0, 0} when there
+ *             is no winner, when a fade runs and the set lacks MTR_MATCH_INTERRUPT, when cur exists and the winner lies in L
+ *             within near_x of p (the test does not look across the seam of a LOOP clip), or when cur exists, its score is
+ *             not NaN and the winner's is not above it by more than margin.
+ *   result  : optionally {row, cur, score, cur_score}; MTR_MATCH_NONE and 0x7FC00000 where there is none.
+ * The n slots are what a controller writes: pass them to the next mtr_anim_player_advance_device_cmds.  instance_base lets a
+ * caller search a slice of its crowd per frame: play + k, query + k * D, cmds + k, base k.  The play states are read and never
+ * written; every bit pattern of play state, query and filter has a defined outcome.  A search runs in stream order on
+ * hip_stream under the rules of mtr_batch_set_poses_device; the set owns scratch its kernels write, so calls on one set are
+ * ordered among themselves whatever their streams; mtr_anim_match_destroy may follow a search directly (no host wait).
+ * MTR_E_INVALID, nothing created (mtr_last_error names the clip, row or dimension): the clip rules of mtr_anim_ctrl_create, D not
+ * a multiple of 4 in 4..64, nrows outside 1..2^22, max_instances outside 1..2^20, unknown flag bits, pose bits at or above D,
+ * near_x or margin negative or not finite, a NULL array that is counted; a row whose clip is >= nclips or below the row
+ * before it, whose x is not finite, below 0, above P (LOOP: at or above P) or not above the row before it in its clip, whose
+ * bias or a feature is not finite or whose c_r is not finite; a mean or scale that is not finite.
+ * MTR_E_INVALID, nothing changed, at a call: a NULL handle, play or cmds pointer, NULL query while some dimension is not a pose
+ * dimension, n == 0 or n > max_instances, instance_base + n > 2^32 - 1, a misaligned device pointer (16 bytes: play, query,
+ * cmds, results; 8: filter).
+ * MTR_E_UNSUPPORTED: a library built without k_match. */
+#define MTR_MATCH_INTERRUPT 1u   /* may command while a fade runs */
+#define MTR_MATCH_NONE 0xFFFFFFFFu
+#define MTR_MATCH_MAX_DIMS 64
+typedef struct mtr_anim_match mtr_anim_match;
+typedef struct mtr_match_row    { uint32_t clip; float x, bias; uint32_t tags; } mtr_match_row;          /* 16 bytes */
+typedef struct mtr_match_filter { uint32_t require, exclude; } mtr_match_filter;                       /*  8 bytes */
+typedef struct mtr_match_result { uint32_t row, cur; float score, cur_score; } mtr_match_result;        /* 16 bytes */
+int32_t mtr_anim_match_create(mtr_device *dev, size_t nclips, const uint32_t *nkeys /* nclips */,
+                              const uint32_t *clip_flags /* nclips, NULL = 0 */, size_t D, uint64_t pose_dims, uint32_t flags,
+                              float seconds, float near_x, float margin, const mtr_match_row *rows, size_t nrows,
+                              const float *features /* nrows*D */, const float *mean /* D, or NULL */,
+                              const float *scale /* D, or NULL */, size_t max_instances, mtr_anim_match **out);
+void    mtr_anim_match_destroy(mtr_anim_match *match);       /* parked like mtr_anim_destroy */
+int32_t mtr_anim_match_search_device(mtr_anim_match *match, const mtr_play_state *play_dev /* n, 16-byte aligned */,
+                                     const float *query_dev /* n*D, 16-byte aligned; NULL: every dimension is a pose dimension */,
+                                     const mtr_match_filter *filter_dev /* n, or NULL */, size_t n, uint32_t instance_base,
+                                     mtr_play_cmd *cmds_out_dev /* n, 16-byte aligned */,
+                                     mtr_match_result *results_dev /* n, or NULL */, void *hip_stream);
+/* a test and debug hook: everything in host memory (any alignment), the same kernels, waits */
+int32_t mtr_anim_match_search_host(mtr_anim_match *match, const mtr_play_state *play, const float *query,
+                                   const mtr_match_filter *filter, size_t n, uint32_t instance_base, mtr_play_cmd *cmds_out,
+                                   mtr_match_result *results);
+/* a test and debug hook: every score s_r of every instance, out[i * nrows + r], from the search kernel itself (a variant
+ * that also stores its accumulators); host memory, waits */
+int32_t mtr_anim_match_scores_host(mtr_anim_match *match, const mtr_play_state *play, const float *query, size_t n,
+                                   float *out /* n*nrows */);
+
 /* ---- spring bones (SPEC.md section 24): joints that lag and sway behind the animated pose ----
  * A spring set belongs to a skeleton, as an IK set does: it holds the skeleton's parents (the rules of
  * mtr_model_set_skeleton) and 1..16 springs.  A spring aims its joint (mtr_ik_chain's AIM, weight 1, axis = tail) at a

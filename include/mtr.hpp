@@ -232,6 +232,40 @@ class AnimPlayer {
     mtr_anim_player* h_ = nullptr;
 };
 
+// A match set (include/mtr.h, SPEC.md section 25): nearest-pose search per instance over a database of feature rows, writing a
+// player's commands on the device; nkeys and clip_flags are what the player was created with
+class AnimMatch {
+  public:
+    AnimMatch(const Device& dev, size_t nclips, const uint32_t* nkeys, const uint32_t* clip_flags, size_t D, uint64_t pose_dims, uint32_t flags, float seconds,
+              float near_x, float margin, const mtr_match_row* rows, size_t nrows, const float* features, const float* mean, const float* scale,
+              size_t max_instances) : dev_(dev) {
+        dev.check(mtr_anim_match_create(dev.handle(), nclips, nkeys, clip_flags, D, pose_dims, flags, seconds, near_x, margin, rows, nrows, features, mean, scale,
+                                        max_instances, &h_));
+    }
+    AnimMatch(AnimMatch&& o) noexcept : dev_(o.dev_), h_(std::exchange(o.h_, nullptr)) {}
+    AnimMatch(const AnimMatch&) = delete;
+    ~AnimMatch() { mtr_anim_match_destroy(h_); }
+    // one search for n instances in stream order; command slot i of cmds_out_dev is instance instance_base + i's, for the
+    // player's advance_cmds(states, n, dt, cmds_out_dev, n, ...)
+    void search(const mtr_play_state* play_dev, const float* query_dev, const mtr_match_filter* filter_dev, size_t n, uint32_t instance_base,
+                mtr_play_cmd* cmds_out_dev, mtr_match_result* results_dev = nullptr, void* hip_stream = nullptr) const {
+        dev_.check(mtr_anim_match_search_device(h_, play_dev, query_dev, filter_dev, n, instance_base, cmds_out_dev, results_dev, hip_stream));
+    }
+    // the test and debug hooks: everything in host memory, waits
+    void search_host(const mtr_play_state* play, const float* query, const mtr_match_filter* filter, size_t n, uint32_t instance_base, mtr_play_cmd* cmds_out,
+                     mtr_match_result* results = nullptr) const {
+        dev_.check(mtr_anim_match_search_host(h_, play, query, filter, n, instance_base, cmds_out, results));
+    }
+    void scores_host(const mtr_play_state* play, const float* query, size_t n, float* out) const {
+        dev_.check(mtr_anim_match_scores_host(h_, play, query, n, out));
+    }
+    mtr_anim_match* handle() const { return h_; }
+
+  private:
+    const Device& dev_;
+    mtr_anim_match* h_ = nullptr;
+};
+
 // A controller (include/mtr.h, SPEC.md section 21): per-instance state machines over one graph of nodes and transitions that
 // write a player's commands on the device; nkeys and clip_flags are what the player was created with
 class AnimCtrl {

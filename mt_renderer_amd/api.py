@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = [
     "mtr_anim_ctrl_create", "mtr_anim_ctrl_destroy", "mtr_anim_ctrl_step_device", "mtr_anim_ctrl_step_host",
     "mtr_anim_events_create", "mtr_anim_events_destroy", "mtr_anim_events_collect_device", "mtr_anim_events_collect_host",
     "mtr_anim_blend_create", "mtr_anim_blend_destroy", "mtr_anim_blend_advance_device", "mtr_anim_blend_advance_host",
+    "mtr_anim_match_create", "mtr_anim_match_destroy", "mtr_anim_match_search_device", "mtr_anim_match_search_host",
+    "mtr_anim_match_scores_host",
 ]
 
 CLIP_LOOP = 1
@@ -116,6 +118,13 @@ EVENT_BACKWARD = 0x80000000
 BLEND_SAMPLE = np.dtype([("clip", "<u4"), ("px", "<f4"), ("py", "<f4"), ("pad", "<u4")])
 BLEND_TRI = np.dtype([("v", "<u4", (3,)), ("pad", "<u4")])
 BLEND_STATE = np.dtype([("phase", "<f4"), ("px", "<f4"), ("py", "<f4"), ("speed", "<f4")])
+# mtr_match_row, mtr_match_filter, mtr_match_result (SPEC.md section 25): a row of a match set, what an instance admits, what a search found
+MATCH_ROW = np.dtype([("clip", "<u4"), ("x", "<f4"), ("bias", "<f4"), ("tags", "<u4")])
+MATCH_FILTER = np.dtype([("require", "<u4"), ("exclude", "<u4")])
+MATCH_RESULT = np.dtype([("row", "<u4"), ("cur", "<u4"), ("score", "<f4"), ("cur_score", "<f4")])
+MATCH_INTERRUPT = 1
+MATCH_NONE = 0xFFFFFFFF
+MATCH_MAX_DIMS = 64
 
 
 class MtrError(RuntimeError):
@@ -288,6 +297,11 @@ def _load() -> C.CDLL:
         "mtr_anim_blend_destroy": (None, [vp]),
         "mtr_anim_blend_advance_device": (i32, [vp, vp, vp, sz, C.c_float, vp, sz, vp, vp, vp]),
         "mtr_anim_blend_advance_host": (i32, [vp, vp, vp, sz, C.c_float, vp, sz, vp, vp]),
+        "mtr_anim_match_create": (i32, [vp, sz, vp, vp, sz, C.c_uint64, u32, C.c_float, C.c_float, C.c_float, vp, sz, vp, vp, vp, sz, vp]),
+        "mtr_anim_match_destroy": (None, [vp]),
+        "mtr_anim_match_search_device": (i32, [vp, vp, vp, vp, sz, u32, vp, vp, vp]),
+        "mtr_anim_match_search_host": (i32, [vp, vp, vp, vp, sz, u32, vp, vp]),
+        "mtr_anim_match_scores_host": (i32, [vp, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1061,6 +1075,97 @@ class AnimBlend(_Set):
         sh = np.zeros((n, 3), dtype=np.float32) if want_shares else None
         self.dev.check(lib.mtr_anim_blend_advance_host(self._h, _p(st), _p(pr), n, float(dt), _p(ol), nlayers, _p(os_), _p(sh)))
         return st, ol, os_, sh
+
+
+class AnimMatch(_Set):
+    """A match set (include/mtr.h, SPEC.md section 25): nearest-pose search per instance that writes a player's commands on the
+    GPU.  ``nkeys`` and ``clip_flags`` are what the AnimPlayer was given; ``rows`` a MATCH_ROW array [R] sorted by clip and by x
+    within a clip, ``features`` float32 [R, D], already normalised and weighted (``anim_match.normalise`` and ``rows_of`` make
+    them); ``pose_dims`` has bit d set where dimension d is taken from the pose being played, ``mean`` and ``scale`` (float32
+    [D], None: 0 and 1) normalise the raw query; ``seconds`` is the fade of a jump, ``near`` and ``margin`` say when a winner is
+    not worth one; for calls of up to ``max_instances`` instances."""
+
+    _destroy = "mtr_anim_match_destroy"
+
+    def __init__(self, dev: Device, nkeys, clip_flags, rows, features, pose_dims: int = 0, flags: int = 0, seconds: float = 0.2, near: float = 0.0,
+                 margin: float = 0.0, mean=None, scale=None, max_instances: int = 1):
+        msg = "anim match: one flag word per clip, rows of dtype MATCH_ROW [R], features float32 [R, D], mean and scale float32 [D]"
+        nk, fl = _clip_arrays(msg, nkeys, clip_flags)
+        rw, ft = np.asarray(rows), np.ascontiguousarray(np.asarray(features, dtype=np.float32))
+        if rw.dtype != MATCH_ROW or rw.ndim != 1 or ft.ndim != 2 or ft.shape[0] != rw.size:
+            raise MtrError(MTR_E_INVALID, msg)
+        D = ft.shape[1]
+        mn, sc = (None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape(-1)) for v in (mean, scale))
+        if any(v is not None and v.size != D for v in (mn, sc)):
+            raise MtrError(MTR_E_INVALID, msg)
+        if not (0 <= pose_dims < 1 << 64 and 0 <= flags < 1 << 32):
+            raise MtrError(MTR_E_INVALID, "anim match: pose_dims is a 64-bit and flags a 32-bit word")
+        rw = np.ascontiguousarray(rw)
+        h = C.c_void_p()
+        dev.check(lib.mtr_anim_match_create(dev._h, nk.size, _p(nk), _p(fl), D, pose_dims, flags, float(seconds), float(near), float(margin),
+                                            _p(rw) if rw.size else None, rw.size, _p(ft) if ft.size else None, _p(mn), _p(sc), max_instances, C.byref(h)))
+        self.dev, self._h, self.nclips, self.nrows, self.D, self.pose_dims, self.max_instances = dev, h, nk.size, rw.size, D, pose_dims, max_instances
+
+    @property
+    def needs_query(self) -> bool:
+        return self.pose_dims != (1 << self.D) - 1
+
+    def search(self, play, query, cmds_out, filters=None, results=None, instance_base: int = 0, stream=None):
+        """one search for the n PLAY_STATE records of ``play`` ([n, 32] bytes on the GPU, 16-byte aligned, read only) against
+        the raw queries of ``query`` (float32 [n, D]; None when every dimension is a pose dimension) and, where given, the
+        MATCH_FILTER records of ``filters`` ([n, 8] bytes); writes PLAY_CMD slot i of ``cmds_out`` (at least n slots of 16
+        bytes; a longer tensor leaves room for the host's own commands behind slot n - 1) as {instance_base + i, ...} and,
+        where given, the MATCH_RESULT records of ``results`` ([n, 16] bytes), in stream order on ``stream`` (a torch stream;
+        None: torch.cuda.current_stream()).  A slice of a crowd: play[k:k + m], query[k:k + m], cmds[k:k + m], instance_base=k."""
+        import torch
+        a = _InPlaceArgs(self.dev)
+        n = a.add(play, "match play states", PLAY_STATE.itemsize, 16, None)
+        if a.add(cmds_out, "match commands", PLAY_CMD.itemsize, 16, None) < n:
+            raise MtrError(MTR_E_INVALID, "match commands: at least n slots of 16 bytes")
+        if query is not None:
+            a.add(query, "match query", 4 * self.D, 16, n, torch.float32, "match query: a float32 tensor [n, D] on the GPU")
+        elif self.needs_query:
+            raise MtrError(MTR_E_INVALID, "match query: the set has dimensions that are not pose dimensions and no query is given")
+        if filters is not None:
+            a.add(filters, "match filters", MATCH_FILTER.itemsize, 8, n)
+        if results is not None:
+            a.add(results, "match results", MATCH_RESULT.itemsize, 16, n)
+        if not 0 <= instance_base <= 0xFFFFFFFF:
+            raise MtrError(MTR_E_INVALID, "match search: instance_base is a 32-bit index")
+        a.call(lib.mtr_anim_match_search_device, (self._h, a.ptr(play), a.ptr(query), a.ptr(filters), n, instance_base, a.ptr(cmds_out), a.ptr(results)), stream)
+
+    def _host_in(self, play, query):
+        pl = np.ascontiguousarray(np.asarray(play))
+        if pl.dtype != PLAY_STATE or pl.ndim != 1:
+            raise MtrError(MTR_E_INVALID, "match play states: an array [n] of dtype PLAY_STATE")
+        qr = None
+        if query is not None:
+            qr = np.ascontiguousarray(np.asarray(query, dtype=np.float32))
+            if qr.shape != (pl.size, self.D):
+                raise MtrError(MTR_E_INVALID, "match query: float32 [n, D]")
+        return pl, qr
+
+    def search_host(self, play: np.ndarray, query, filters: Optional[np.ndarray] = None, instance_base: int = 0, want_results: bool = True):
+        """the test and debug hook: PLAY_STATE [n], float32 [n, D] (or None) and MATCH_FILTER [n] (or None) in host memory
+        through the same kernels; waits.  Returns (PLAY_CMD [n], MATCH_RESULT [n] or None)."""
+        pl, qr = self._host_in(play, query)
+        n = pl.size
+        fl = None
+        if filters is not None:
+            fl = np.ascontiguousarray(np.asarray(filters))
+            if fl.dtype != MATCH_FILTER or fl.shape != (n,):
+                raise MtrError(MTR_E_INVALID, "match filters: an array [n] of dtype MATCH_FILTER")
+        cm = np.zeros(n, dtype=PLAY_CMD)
+        rs = np.zeros(n, dtype=MATCH_RESULT) if want_results else None
+        self.dev.check(lib.mtr_anim_match_search_host(self._h, _p(pl), _p(qr), _p(fl), n, instance_base, _p(cm), _p(rs)))
+        return cm, rs
+
+    def scores_host(self, play: np.ndarray, query) -> np.ndarray:
+        """the test and debug hook: every score, float32 [n, R], from the search kernel itself; waits"""
+        pl, qr = self._host_in(play, query)
+        out = np.zeros((pl.size, self.nrows), dtype=np.float32)
+        self.dev.check(lib.mtr_anim_match_scores_host(self._h, _p(pl), _p(qr), pl.size, _p(out)))
+        return out
 
 
 class AnimIK(_Set):

@@ -327,7 +327,7 @@ struct mtr_batch {
 
 namespace mtr_host {
 
-// What the nine set handles below share: device memory `d`, uploaded once, and the event that covers its readers.  `last` is
+// What the ten set handles below share: device memory `d`, uploaded once, and the event that covers its readers.  `last` is
 // recorded behind every kernel that reads d (set_after); a kernel queued on another stream than the one before first waits
 // for it (set_before), so the one event always covers every reader and the set's destroy can park d behind it (set_park).
 struct DeviceSet {
@@ -410,6 +410,18 @@ struct mtr_anim_events : mtr_host::DeviceSet {
 struct mtr_anim_blend : mtr_host::DeviceSet {
     uint32_t nclips = 0, nsamples = 0, ntris = 0, nparams = 0, param_x = 0, param_y = 0, max_instances = 0;
     float damp = 0.0f;
+};
+
+// A match set (SPEC.md section 25).  d: nclips table entries of 4 words (period, flags, 0, key count), nclips ranges of 2 words
+// (first row, row count), the rows of 4 words, Rp (R rounded up to 32) c_r, Rp tag words, Rp x Dp features tile-major
+// (match_math.h: match_slot), Dp means and Dp scales, each part padded to a multiple of 16 bytes, all immutable; then the
+// scratch: the queries of max_instances rounded up to 32 (tile-major), max_instances current rows and max_instances 64-bit
+// winner keys.  Its kernels WRITE the scratch, so `last` orders the calls on one set among themselves, as a player's.
+struct mtr_anim_match : mtr_host::DeviceSet {
+    uint32_t nclips = 0, R = 0, D = 0, flags = 0, max_instances = 0;
+    uint64_t pose_dims = 0;
+    float seconds = 0.0f, near_x = 0.0f, margin = 0.0f;
+    size_t w_ranges = 0;  // words of the padded range part
 };
 
 namespace mtr_host {

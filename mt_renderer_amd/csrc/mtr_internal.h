@@ -655,3 +655,33 @@ struct BlendParams {
     float dt;
 };
 void mtr_launch_blend(const BlendParams& p, hipStream_t s);
+// motion matching (k_match.hip, SPEC.md section 25): per instance the database row nearest to its query, joined over the
+// row slabs of the grid by one 64-bit atomic maximum, and the command that fades there.  Three launches in stream order.
+struct MatchParams {
+    const uint32_t* clips;      // nclips x 4 words (PlayClip: period (f32 bits), flags, 0, key count); 16-byte aligned
+    const uint32_t* ranges;     // nclips x 2 words: first row, row count; validated at creation
+    const uint32_t* rows;       // R x 4 words (mtr_match_row), validated at creation; 16-byte aligned
+    const float* c;             // Rp floats (R rounded up to 32): c_r, NaN behind R; 16-byte aligned
+    const uint32_t* tags;       // Rp words: the rows' tags, 0 behind R; 16-byte aligned
+    const float* feat;          // Rp x Dp floats, tile-major (match_math.h: match_slot); 16-byte aligned
+    const float* mean;          // Dp floats
+    const float* scale;         // Dp floats
+    float* query;               // the set's scratch: np x Dp floats (n rounded up to 32), tile-major as feat; 16-byte aligned
+    uint32_t* cur;              // the set's scratch: max_instances words
+    unsigned long long* keys;   // the set's scratch: max_instances winner keys
+    const uint32_t* play;       // n x 8 words (mtr_play_state), read only; 16-byte aligned
+    const float* raw;           // n x D floats, or nullptr when every dimension is a pose dimension; 16-byte aligned
+    const uint32_t* filter;     // n x 2 words (mtr_match_filter), or nullptr: every row is a candidate; 8-byte aligned
+    uint32_t* cmds;             // n x 4 words (mtr_play_cmd); 16-byte aligned
+    uint32_t* results;          // n x 4 words (mtr_match_result), or nullptr; 16-byte aligned
+    float* scores;              // n x R floats, or nullptr: the scores hook stores every accumulator and decides nothing
+    uint64_t pose_dims;
+    uint32_t nclips;            // >= 1
+    uint32_t R;                 // 1..2^22
+    uint32_t D;                 // 4..64, a multiple of 4
+    uint32_t flags;
+    uint32_t n;                 // 1..max_instances
+    uint32_t instance_base;     // instance_base + n <= 2^32 - 1
+    float seconds, near, margin;
+};
+void mtr_launch_match(const MatchParams& p, hipStream_t s);

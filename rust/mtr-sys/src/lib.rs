@@ -70,7 +70,7 @@ pub const MTR_OWN_SUPERTILES: u32 = 2;
 pub const MTR_TEXRES_DECODED: u32 = 0;
 pub const MTR_TEXRES_BLOCKS: u32 = 1;
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player, mtr_anim_ctrl, mtr_anim_events, mtr_anim_blend, mtr_anim_spring);
+opaque!(mtr_device, mtr_texture, mtr_model, mtr_batch, mtr_frame, mtr_anim, mtr_anim_masks, mtr_anim_ik, mtr_anim_root, mtr_anim_player, mtr_anim_ctrl, mtr_anim_events, mtr_anim_blend, mtr_anim_spring, mtr_anim_match);
 
 /// animation clips (mtr.h, SPEC.md section 14): one key of one joint, 48 bytes
 pub const MTR_CLIP_LOOP: u32 = 1;
@@ -246,6 +246,32 @@ pub struct mtr_ctrl_state {
     pub t: f32,
     pub fired: u32,
     pub user: u32,
+}
+// motion matching (SPEC.md section 25)
+pub const MTR_MATCH_INTERRUPT: u32 = 1;
+pub const MTR_MATCH_NONE: u32 = 0xFFFF_FFFF;
+pub const MTR_MATCH_MAX_DIMS: usize = 64;
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_match_row {
+    pub clip: u32,
+    pub x: f32,
+    pub bias: f32,
+    pub tags: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_match_filter {
+    pub require: u32,
+    pub exclude: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mtr_match_result {
+    pub row: u32,
+    pub cur: u32,
+    pub score: f32,
+    pub cur_score: f32,
 }
 // animation events (SPEC.md section 22)
 pub const MTR_EVENT_BACKWARD: u32 = 0x8000_0000;
@@ -449,6 +475,16 @@ extern "C" {
                                      dt: f32, cmds_out_dev: *mut mtr_play_cmd, counts_dev: *mut u32, hip_stream: *mut c_void) -> i32;
     pub fn mtr_anim_ctrl_step_host(ctrl: *mut mtr_anim_ctrl, states: *mut mtr_ctrl_state, play: *const mtr_play_state, params: *mut f32, n: usize, dt: f32,
                                    cmds_out: *mut mtr_play_cmd, counts: *mut u32) -> i32;
+    // motion matching (SPEC.md section 25): declarations only
+    pub fn mtr_anim_match_create(dev: *mut mtr_device, nclips: usize, nkeys: *const u32, clip_flags: *const u32, d: usize, pose_dims: u64, flags: u32, seconds: f32,
+                                 near_x: f32, margin: f32, rows: *const mtr_match_row, nrows: usize, features: *const f32, mean: *const f32, scale: *const f32,
+                                 max_instances: usize, out: *mut *mut mtr_anim_match) -> i32;
+    pub fn mtr_anim_match_destroy(m: *mut mtr_anim_match);
+    pub fn mtr_anim_match_search_device(m: *mut mtr_anim_match, play_dev: *const mtr_play_state, query_dev: *const f32, filter_dev: *const mtr_match_filter, n: usize,
+                                        instance_base: u32, cmds_out_dev: *mut mtr_play_cmd, results_dev: *mut mtr_match_result, hip_stream: *mut c_void) -> i32;
+    pub fn mtr_anim_match_search_host(m: *mut mtr_anim_match, play: *const mtr_play_state, query: *const f32, filter: *const mtr_match_filter, n: usize,
+                                      instance_base: u32, cmds_out: *mut mtr_play_cmd, results: *mut mtr_match_result) -> i32;
+    pub fn mtr_anim_match_scores_host(m: *mut mtr_anim_match, play: *const mtr_play_state, query: *const f32, n: usize, out: *mut f32) -> i32;
     // animation events (SPEC.md section 22): declarations only
     pub fn mtr_anim_events_create(dev: *mut mtr_device, nclips: usize, nkeys: *const u32, clip_flags: *const u32, counts: *const u32,
                                   markers: *const mtr_event_marker, max_instances: usize, out: *mut *mut mtr_anim_events) -> i32;
