@@ -16,8 +16,9 @@
 // instances; their creates and destroys traced, every optional argument present and absent, a second stream after a first
 // for each set, the rejected clips of the four clock-set creates with the order their checks fire in, and a last line with
 // the counts of the whole run.
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_HARNESS_OWN_CULL_INSTANCES
+#define MTR_HARNESS_OWN_TRACE
+#include "harness.h"
 
 #define MUST(x) do { if ((x) != MTR_OK) { fprintf(stderr, "line %d: %s failed\n", __LINE__, #x); exit(4); } } while (0)
 
@@ -163,24 +164,11 @@ static std::string spring_str(const AnimSpringParams& p) {
 void mtr_launch_anim_spring(const AnimSpringParams& p, bool tracks, bool fold, uint32_t n, hipStream_t s) {
     launched(anim_name("anim_spring", tracks, fold).c_str(), n, s, spring_str(p));
 }
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
-void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_pack_shard(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_unpack_shards(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, hipStream_t) {}
 void mtr_launch_cull_instances(const CullParams&, hipStream_t) {}
-void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
 
 // ---- calls ----
 static mtr_device* g_dev = nullptr;
 static bool host_hook(hipStream_t s) { return s == g_dev->s_copy; }
-static int g_failed = 0;
 static long g_rejected = 0;
 
 #define CALL(x) do { printf("%s\n", #x); hipStubTrace() = trace; const int32_t rc_ = (x); hipStubTrace() = nullptr; \
@@ -194,14 +182,6 @@ static long g_rejected = 0;
     for (size_t i_ = g0_; i_ < g_dev->garbage.size(); i_++) { const std::string b_ = B(g_dev->garbage[i_].p), e_ = E(g_dev->garbage[i_].ev); \
         printf("    parked %s behind %s\n", b_.c_str(), e_.c_str()); } } while (0)
 
-template <class T>
-static T* dev_copy(const std::vector<T>& v) {  // "device" memory: the stub's is the heap; 16-byte aligned like hipMalloc's
-    const size_t bytes = (v.size() * sizeof(T) + 15) / 16 * 16;
-    T* p = static_cast<T*>(aligned_alloc(16, bytes ? bytes : 16));
-    memset(p, 0, bytes ? bytes : 16);
-    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
 template <class T>
 static T* odd(T* p) { return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + 4); }  // misaligned
 

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <vector>
 
+#include "blob_io.h"
 #include "../../mt_renderer_amd/csrc/anim_blend.h"
 
 static mtr::AnimKey key_at(const float* k) {
@@ -21,14 +22,8 @@ static mtr::AnimKey key_at(const float* k) {
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::fseek(f, 0, SEEK_END);
-    const long size = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    std::vector<uint32_t> blob((size_t)(size + 3) / 4);
-    if (std::fread(blob.data(), 1, (size_t)size, f) != (size_t)size) return 2;
-    std::fclose(f);
+    long size = 0;
+    std::vector<uint32_t> blob = read_words(argv[1], &size);
     const size_t n = blob[0], J = blob[1], L = blob[2];
     const uint32_t* head = blob.data() + 4;
     const float* per = reinterpret_cast<const float*>(head + n * L * 2);
@@ -56,8 +51,6 @@ int main(int argc, char** argv) {
             const float tqs[12] = {r.t.x, r.t.y, r.t.z, 0.0f, r.q.x, r.q.y, r.q.z, r.q.w, r.s.x, r.s.y, r.s.z, 0.0f};
             std::memcpy(&out[(i * J + j) * 12], tqs, sizeof(tqs));
         }
-    FILE* o = std::fopen(argv[2], "wb");
-    if (!o || std::fwrite(out.data(), 4, out.size(), o) != out.size()) return 2;
-    std::fclose(o);
+    write_words(argv[2], out);
     return 0;
 }

@@ -5,24 +5,10 @@
 // names (clamped) and the clip table entry with the first and last key (or descriptor) of the clip it names (clamped), and
 // it writes the last word of the output.  A wrong size or offset on the host side is an ASan report.
 //   usage: anim_layers_host_asan <iterations>
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_RND_SEED 0x13198A2E03707344ull
+#include "harness.h"
 #include "../../mt_renderer_amd/csrc/mtr_files.cpp"
 
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
-static void stub_status(const TileParams& p) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_pack_shard(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_unpack_shards(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, hipStream_t) {}
-void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t i = 0; i < p.ninst; i++) { p.strad[p.count[1]++] = *p.count; p.list[(*p.count)++] = i; } }
-void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
 // the section-14 launchers: the plain animate calls are made here too, between the layered ones
 void mtr_launch_anim(const AnimParams& p, bool, bool fold, uint32_t ninst, hipStream_t) {
     if (!fold) abort();  // no plain sample call is made here
@@ -70,17 +56,6 @@ void mtr_launch_anim_layers(const AnimLayerParams& p, bool tracks, bool fold, ui
     if (fold) check_skeleton(p);
     touch_layers(p, ninst, tracks);
 }
-
-static uint64_t rs = 0x13198A2E03707344ull;
-static uint64_t rnd() {
-    uint64_t z = (rs += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint32_t pick(uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rnd() % (hi - lo + 1)); }
-
-#define EXPECT(call, code) do { const int32_t rc_ = (call); if (rc_ != (code)) { fprintf(stderr, "line %d: %s = %d, expected %d (%s)\n", __LINE__, #call, rc_, (int)(code), mtr_last_error(dev)); return 1; } } while (0)
 
 // a one-clip-per-entry track set with one key per track: exactly sized arrays
 static int32_t make_tracks(mtr_device* dev, uint32_t J, uint32_t nclips, mtr_anim** out) {

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "blob_io.h"
 #include "../../mt_renderer_amd/csrc/anim_tracks.h"
 
 struct Track { uint32_t first, count; float lo[3], step[3]; };
@@ -17,14 +18,8 @@ static_assert(sizeof(Track) == 32, "mtr_anim_track");
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::fseek(f, 0, SEEK_END);
-    const long size = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    std::vector<uint32_t> blob((size_t)(size + 3) / 4);
-    if (std::fread(blob.data(), 1, (size_t)size, f) != (size_t)size) return 2;
-    std::fclose(f);
+    long size = 0;
+    std::vector<uint32_t> blob = read_words(argv[1], &size);
     const uint32_t J = blob[0], C = blob[1], nkeys = blob[2], n = blob[3];
     const uint32_t* clips = blob.data() + 4;
     const Track* tracks = reinterpret_cast<const Track*>(clips + 2 * C);
@@ -57,8 +52,6 @@ int main(int argc, char** argv) {
                 }
         }
     for (uint32_t code = 0; code < 65536u; code++) put_f(mtr::track_snorm16(code));
-    FILE* o = std::fopen(argv[2], "wb");
-    if (!o || std::fwrite(out.data(), 4, out.size(), o) != out.size()) return 2;
-    std::fclose(o);
+    write_words(argv[2], out);
     return 0;
 }

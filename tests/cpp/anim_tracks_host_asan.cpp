@@ -4,24 +4,9 @@
 // (clamped), the first and last key of the uniform set, or the first and last descriptor of the track set and the first
 // and last time and value those descriptors own, and it writes the last word of the output.  A wrong size or offset on
 // the host side is an ASan report.   usage: anim_tracks_host_asan <iterations>
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_RND_SEED 0x243F6A8885A308D3ull
+#include "harness.h"
 #include "../../mt_renderer_amd/csrc/mtr_files.cpp"
-
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
-static void stub_status(const TileParams& p) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_pack_shard(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_unpack_shards(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, hipStream_t) {}
-void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t i = 0; i < p.ninst; i++) { p.strad[p.count[1]++] = *p.count; p.list[(*p.count)++] = i; } }
-void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
 
 static uint64_t g_key_reads = 0, g_track_reads = 0;
 static void touch_uniform(const AnimParams& p, uint32_t ninst) {
@@ -71,17 +56,6 @@ void mtr_launch_anim(const AnimParams& p, bool tracks, bool fold, uint32_t ninst
     if (fold) check_skeleton(p);
     if (tracks) touch_tracks(p, ninst); else touch_uniform(p, ninst);
 }
-
-static uint64_t rs = 0x243F6A8885A308D3ull;
-static uint64_t rnd() {
-    uint64_t z = (rs += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint32_t pick(uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rnd() % (hi - lo + 1)); }
-
-#define EXPECT(call, code) do { const int32_t rc_ = (call); if (rc_ != (code)) { fprintf(stderr, "line %d: %s = %d, expected %d (%s)\n", __LINE__, #call, rc_, (int)(code), mtr_last_error(dev)); return 1; } } while (0)
 
 // a valid random track set: exactly sized arrays, so that one key too many read by the library is an ASan report
 struct Set {

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <vector>
 
+#include "blob_io.h"
 #include <hip/hip_runtime.h>  // the stand-in of tests/cpp/hip_stub
 
 #include "../../mt_renderer_amd/csrc/attach_math.h"
@@ -17,14 +18,8 @@ using namespace mtr;
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::fseek(f, 0, SEEK_END);
-    const long size = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    std::vector<uint32_t> blob((size_t)(size + 3) / 4);
-    if (std::fread(blob.data(), 1, (size_t)size, f) != (size_t)size) return 2;
-    std::fclose(f);
+    long size = 0;
+    std::vector<uint32_t> blob = read_words(argv[1], &size);
     if (blob.size() < 4) return 2;
     const size_t n = blob[0], n_src = blob[1], npal = blob[2];
     if ((long)((4 + n_src * 16 + n_src * npal * 16 + n * MTR_ATTACH_WORDS) * 4) != size || n_src == 0) { std::fprintf(stderr, "blob size\n"); return 2; }
@@ -48,8 +43,6 @@ int main(int argc, char** argv) {
             out[r * 16 + e] = attach_elem(a, O + c * 4);
         }
     }
-    FILE* o = std::fopen(argv[2], "wb");
-    if (!o || std::fwrite(out.data(), 4, out.size(), o) != out.size()) return 2;
-    std::fclose(o);
+    write_words(argv[2], out);
     return 0;
 }

@@ -8,16 +8,12 @@
 //   2. attach, then mtr_batch_destroy(src): the buffer is parked behind the reader's event, no host wait, no free;
 //   3. batch == src, twice;
 //   and every invalid call leaves `cur` and the version ring of both batches untouched.
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_HARNESS_OWN_CULL_INSTANCES
+#include "harness.h"
 
-static int g_failed = 0;
 #define MUST(x) do { if ((x) != MTR_OK) { fprintf(stderr, "line %d: %s failed\n", __LINE__, #x); exit(4); } } while (0)
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "line %d: %s does not hold\n", __LINE__, #c); g_failed++; } } while (0)
 
 // ---- the kernels: only k_attach is launched here ----
-struct Op { std::string op; const void* what; const void* stream; };
-static std::vector<Op> g_ops;
 static AttachParams g_last;
 static int g_attach_launches = 0;
 static float g_sink = 0.0f;
@@ -30,23 +26,9 @@ void mtr_launch_attach(const AttachParams& p, hipStream_t s) {
     if (p.npal) g_sink += p.src_pals[0] + p.src_pals[(size_t)p.n_src * p.npal * 16 - 1];
     p.out[0] = 1.0f;
     p.out[(size_t)p.n * 16 - 1] = 1.0f;
-    g_ops.push_back({"attach", p.out, s});
+    g_ops.push_back({"attach", 0, p.out, s});
 }
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
-void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_pack_shard(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_unpack_shards(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, hipStream_t) {}
 void mtr_launch_cull_instances(const CullParams&, hipStream_t) {}
-void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
-
-static void trace(const char* name, size_t, const void* what, const void* stream) { g_ops.push_back({name, what, stream}); }
 
 // ---- names ----
 struct Named { const char* name; mtr_batch* b; };

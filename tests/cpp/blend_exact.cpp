@@ -11,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "blob_io.h"
 #include <hip/hip_runtime.h>  // the stand-in of tests/cpp/hip_stub
 
 #include "../../mt_renderer_amd/csrc/blend_math.h"
@@ -21,14 +22,8 @@ static uint32_t bits(float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; }
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::fseek(f, 0, SEEK_END);
-    const long size = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    std::vector<uint32_t> blob((size_t)(size + 3) / 4);
-    if (std::fread(blob.data(), 1, (size_t)size, f) != (size_t)size) return 2;
-    std::fclose(f);
+    long size = 0;
+    std::vector<uint32_t> blob = read_words(argv[1], &size);
     if (blob.size() < 12) return 2;
     const size_t n = blob[0], C = blob[1], K = blob[2], T = blob[3], NP = blob[4], nl = blob[7];
     float damp, dt;
@@ -79,8 +74,6 @@ int main(int argc, char** argv) {
             o_shares[i * 3 + s] = bits(fr.share[s]);
         }
     }
-    FILE* o = std::fopen(argv[2], "wb");
-    if (!o || std::fwrite(out.data(), 4, out.size(), o) != out.size()) return 2;
-    std::fclose(o);
+    write_words(argv[2], out);
     return 0;
 }

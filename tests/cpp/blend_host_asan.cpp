@@ -6,13 +6,8 @@
 // made and must launch nothing and leave the states, the layers, the steps and the shares as they were, the error naming the
 // clip, the sample or the triangle; sets are created and destroyed with calls queued.
 //   usage: blend_host_asan <iterations>
-#include "host_all.h"
-using namespace mtr_host;
-
-static int g_failed = 0;
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "line %d: %s does not hold\n", __LINE__, #c); g_failed++; } } while (0)
-#define EXPECT(call, code) do { const int32_t rc_ = (call); if (rc_ != (code)) { fprintf(stderr, "line %d: %s = %d, expected %d (%s)\n", __LINE__, #call, rc_, (int)(code), mtr_last_error(dev)); return 1; } } while (0)
-#define NAMES(word) do { if (!strstr(mtr_last_error(dev), word)) { fprintf(stderr, "line %d: the error must say \"%s\": %s\n", __LINE__, word, mtr_last_error(dev)); return 1; } } while (0)
+#define MTR_RND_SEED 0x13198A2E03707344ull
+#include "harness.h"
 
 static uint64_t g_launches = 0;
 static const void* g_last_stream = nullptr;
@@ -56,46 +51,12 @@ void mtr_launch_blend(const BlendParams& p, hipStream_t s) {
     g_last_stream = s;
     run_rule(p);
 }
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
-static void stub_status(const TileParams& p) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_pack_shard(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_unpack_shards(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, hipStream_t) {}
-void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t i = 0; i < p.ninst; i++) { p.strad[p.count[1]++] = *p.count; p.list[(*p.count)++] = i; } }
-void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
 
-struct Op { std::string op; size_t bytes; const void* what; const void* stream; };
-static std::vector<Op> g_ops;
-static void trace(const char* name, size_t bytes, const void* what, const void* stream) { g_ops.push_back({name, bytes, what, stream}); }
-
-static uint64_t rs = 0x13198A2E03707344ull;
-static uint64_t rnd() {
-    uint64_t z = (rs += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint32_t pick(uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rnd() % (hi - lo + 1)); }
 static float unit() { return (float)(rnd() % 100001) / 100000.0f; }
 static float edge() {
     static const float e[] = {0.0f, -0.0f, 0.3f, 1.5f, 0.99f, -1e-7f, 1e30f, NAN, INFINITY, -INFINITY, -1.0f, 0.05f, 1e-41f, -1e-41f, 0.5f, 1.0f, -0.37f, 3e38f};
     return e[rnd() % (sizeof e / sizeof e[0])];
 }
-template <class T>
-static T* dev_copy(const std::vector<T>& v) {  // "device" memory, 16-byte aligned and exactly sized
-    const size_t bytes = (v.size() * sizeof(T) + 15) / 16 * 16;
-    T* p = static_cast<T*>(aligned_alloc(16, bytes ? bytes : 16));
-    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
-static bool same(const void* a, const void* b, size_t bytes) { return bytes == 0 || memcmp(a, b, bytes) == 0; }
 
 int main(int argc, char** argv) {
     const long iters = argc > 1 ? strtol(argv[1], nullptr, 10) : 40;

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "blob_io.h"
 #include <hip/hip_runtime.h>  // the stand-in of tests/cpp/hip_stub
 
 #include "../../mt_renderer_amd/csrc/ctrl_math.h"
@@ -18,14 +19,8 @@ using namespace mtr;
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::fseek(f, 0, SEEK_END);
-    const long size = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    std::vector<uint32_t> blob((size_t)(size + 3) / 4);
-    if (std::fread(blob.data(), 1, (size_t)size, f) != (size_t)size) return 2;
-    std::fclose(f);
+    long size = 0;
+    std::vector<uint32_t> blob = read_words(argv[1], &size);
     if (blob.size() < 8) return 2;
     const size_t n = blob[0], C = blob[1], S = blob[2], T = blob[3], nany = blob[4], NP = blob[5];
     float dt;
@@ -63,8 +58,6 @@ int main(int argc, char** argv) {
     }
     std::memcpy(out.data() + n * 4, params.data(), n * NP * 4);
     if (T) std::memcpy(o_cmds + n * 4, counts.data(), T * 4);
-    FILE* o = std::fopen(argv[2], "wb");
-    if (!o || std::fwrite(out.data(), 4, out.size(), o) != out.size()) return 2;
-    std::fclose(o);
+    write_words(argv[2], out);
     return 0;
 }

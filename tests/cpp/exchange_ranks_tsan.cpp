@@ -7,17 +7,18 @@
 //   * frames whose bin queues "overflow" (the stub tile launch publishes flag 4 now and then) are re-run by the exchange
 //     thread while the render thread flips parts_disp and the palette of the same model: ThreadSanitizer sees no race.
 // usage: exchange_ranks_tsan <frames>
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_HARNESS_OWN_TILE
+#define MTR_HARNESS_OWN_TILE_VIS
+#define MTR_HARNESS_OWN_PACK_SHARD
+#define MTR_HARNESS_OWN_UNPACK_SHARDS
+#define MTR_HARNESS_OWN_CULL_CHUNKS
+#include "harness.h"
 
 #include <atomic>
 #include <chrono>
 
 static std::atomic<long> g_tile_launches{0};
 static std::atomic<long> g_reruns{0};
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
 static void stub_status(const TileParams& p) {
     uint32_t flags = 0;
     if (p.fb.direct && g_tile_launches.fetch_add(1, std::memory_order_relaxed) % 13 == 5) flags = 4u;  // a bounded bin queue "filled up"
@@ -26,10 +27,6 @@ static void stub_status(const TileParams& p) {
 }
 void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { stub_status(p); }
 void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
 static uint8_t* g_fail_send = nullptr;          // rank 1's send buffer
 static std::atomic<long> g_packs_rank1{0};
 static long g_fail_at = 37;
@@ -38,7 +35,6 @@ void mtr_launch_pack_shard(const uint8_t* color, uint8_t* dst, uint32_t, uint32_
     if (dst == g_fail_send && g_packs_rank1.fetch_add(1) == g_fail_at) hipStubInjectedError() = 719;  // "the launch failed" on this thread
 }
 void mtr_launch_unpack_shards(const uint8_t* g, uint8_t* dst, uint32_t, uint32_t, const uint32_t* src_of_bin, hipStream_t) { dst[0] = g[0] + (uint8_t)src_of_bin[0]; }
-void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t i = 0; i < p.ninst; i++) { p.strad[p.count[1]++] = *p.count; p.list[(*p.count)++] = i; } }
 void mtr_launch_cull_chunks(const ChunkCullParams& p, hipStream_t) { if (p.nchunks && p.ninst) p.work_mask[(size_t)((p.nchunks + 15) / 16) * p.ninst - 1] = 0xFFFF; }
 
 struct Collective {

@@ -3,26 +3,16 @@
 // while the exchange thread packs, "gathers", unpacks and destroys them; frames that never reach the exchange thread are
 // begun and destroyed in between, so the framebuffer pool is touched from both sides.  Any unsynchronised access to
 // shared host state is reported by TSan (exit code 66).          usage: exchange_tsan <frames>
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_HARNESS_OWN_PACK_SHARD
+#define MTR_HARNESS_OWN_UNPACK_SHARDS
+#define MTR_HARNESS_OWN_CULL_CHUNKS
+#include "harness.h"
 
 #include <atomic>
 
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
-// what tile_prologue does on the device: publish the (clean) overflow flags of the frame
-static void stub_status(const TileParams& p) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
 // the copies the real kernels make, so that the send / gathered / destination buffers are really written by this thread
 void mtr_launch_pack_shard(const uint8_t* color, uint8_t* dst, uint32_t, uint32_t, const uint32_t* own_list, uint32_t n, uint32_t, hipStream_t) { dst[0] = color[0] + (n ? (uint8_t)own_list[0] : 0); }
 void mtr_launch_unpack_shards(const uint8_t* g, uint8_t* dst, uint32_t, uint32_t, const uint32_t* src_of_bin, hipStream_t) { dst[0] = g[0] + (uint8_t)src_of_bin[0]; }
-void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t i = 0; i < p.ninst; i++) { p.strad[p.count[1]++] = *p.count; p.list[(*p.count)++] = i; } }
 void mtr_launch_cull_chunks(const ChunkCullParams& p, hipStream_t) { if (p.nchunks && p.ninst) p.work_mask[(size_t)((p.nchunks + 15) / 16) * p.ninst - 1] = 0xFFFF; }  // the last mask of the draw
 
 static std::atomic<long> g_calls{0};

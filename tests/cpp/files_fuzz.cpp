@@ -3,6 +3,8 @@
 // deterministic mutations of the valid files named on the command line.
 // usage: files_fuzz <iterations> model.mod shader.mfx material.mrl texture.tex schedule.sdl archive.arc
 #include "../../mt_renderer_amd/csrc/mtr_files.cpp"
+#define MTR_RND_SEED 0x9E3779B97F4A7C15ull
+#include "rnd.h"
 
 #include <cstdlib>
 #include <fstream>
@@ -33,14 +35,6 @@ int32_t mtr_model_create(mtr_device*, const void*, size_t, const uint16_t*, size
 static std::vector<uint8_t> slurp(const char* p) {
     std::ifstream f(p, std::ios::binary);
     return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() {  // splitmix64
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
 }
 
 static std::vector<uint8_t> mutate(std::vector<uint8_t> a) {

@@ -6,8 +6,15 @@
 // requires every buffer of the FrameBuffers it is handed to be non-null.  The expected logs are written out below.
 // usage: frame_launch_log            every scenario but the allocation failures
 //        frame_launch_log nomem      hipMalloc failing at each allocation of a frame in turn
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_HARNESS_OWN_GEOM
+#define MTR_HARNESS_OWN_SCAN
+#define MTR_HARNESS_OWN_FILL
+#define MTR_HARNESS_OWN_TILE
+#define MTR_HARNESS_OWN_TILE_VIS
+#define MTR_HARNESS_OWN_CULL_INSTANCES
+#define MTR_HARNESS_OWN_CULL_CHUNKS
+#define MTR_HARNESS_OWN_TRACE
+#include "harness.h"
 
 #include <cstdarg>
 
@@ -83,12 +90,6 @@ static void tile_stub(const char* name, const TileParams& p, bool textured) {
 }
 void mtr_launch_tile(const TileParams& p, bool textured, hipStream_t) { tile_stub("tile", p, textured); }
 void mtr_launch_tile_vis(const TileParams& p, bool textured, hipStream_t) { tile_stub("tile_vis", p, textured); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_pack_shard(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_unpack_shards(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, hipStream_t) {}
 void mtr_launch_cull_instances(const CullParams& p, hipStream_t) {
     need(p.boxes, "cull_instances", "boxes"); need(p.list, "cull_instances", "list"); need(p.count, "cull_instances", "count");
     need(p.comp, "cull_instances", "comp"); need(p.work_mask, "cull_instances", "work_mask"); need(p.strad, "cull_instances", "strad");
@@ -147,9 +148,7 @@ static void trace(const char* name, size_t bytes, const void* what, const void* 
 
 // ---- scenes ----
 static const float kClear[4] = {1, 1, 1, 1}, kI[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-static int g_failed = 0;
 #define MUST(x) do { if ((x) != MTR_OK) { fprintf(stderr, "line %d: %s failed\n", __LINE__, #x); exit(4); } } while (0)
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "line %d: %s does not hold\n", __LINE__, #c); g_failed++; } } while (0)
 
 struct Scene {  // one device with a single slot (every frame then runs on slot0), what lives on it, destroyed in order
     mtr_device* d = nullptr;

@@ -4,13 +4,14 @@
 // byte it finds at src_of_bin[b] over bin b, so the gathered image is right exactly when every rank packed its own bins,
 // the group copied each shard to its rank's offset, and the tables agree -- and every copy is bounds-checked by ASan.
 // usage: group_asan <rounds>
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_HARNESS_OWN_TILE
+#define MTR_HARNESS_OWN_TILE_VIS
+#define MTR_HARNESS_OWN_PACK_SHARD
+#define MTR_HARNESS_OWN_UNPACK_SHARDS
+#define MTR_HARNESS_OWN_CULL_CHUNKS
+#include "harness.h"
 #include "../../mt_renderer_amd/csrc/mtr_group.cpp"
 
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
 static long g_tiles = 0, g_reruns = 0;
 static void stub_status(const TileParams& p) {
     uint32_t flags = 0;
@@ -20,10 +21,6 @@ static void stub_status(const TileParams& p) {
 }
 void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { stub_status(p); }
 void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
 static uint8_t bin_byte(uint32_t b) { return (uint8_t)(b * 7u + 1u); }
 void mtr_launch_pack_shard(const uint8_t*, uint8_t* dst, uint32_t, uint32_t, const uint32_t* own_list, uint32_t n, uint32_t stride_bins, hipStream_t) {
     for (uint32_t k = 0; k < stride_bins; k++) memset(dst + (size_t)k * 1024, k < n ? bin_byte(own_list[k]) : 0, 1024);
@@ -36,7 +33,6 @@ void mtr_launch_unpack_shards(const uint8_t* g, uint8_t* dst, uint32_t W, uint32
             for (uint32_t x = b % nbx * 16; x < std::min(W, b % nbx * 16 + 16); x++) memset(dst + ((size_t)y * W + x) * 4, v, 4);
     }
 }
-void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t i = 0; i < p.ninst; i++) { p.strad[p.count[1]++] = *p.count; p.list[(*p.count)++] = i; } }
 void mtr_launch_cull_chunks(const ChunkCullParams& p, hipStream_t) { if (p.nchunks && p.ninst) p.work_mask[(size_t)((p.nchunks + 15) / 16) * p.ninst - 1] = 0xFFFF; }
 
 #define REQ(x) do { if ((x) != MTR_OK) { fprintf(stderr, "%s failed: %s\n", #x, mtr_group_last_error(g)); return 4; } } while (0)

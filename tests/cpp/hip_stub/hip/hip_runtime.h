@@ -1,8 +1,8 @@
-// Stand-in for <hip/hip_runtime.h> used ONLY by the host-side tests of tests/cpp (host_fuzz.cpp, exchange_tsan.cpp,
-// exchange_ranks_tsan.cpp, group_asan.cpp, anim_host_asan.cpp, frame_launch_log.cpp): lets the host side of the library
-// (csrc/host_*.cpp, csrc/mtr_files.cpp, csrc/mtr_group.cpp) be compiled by g++ with AddressSanitizer / UBSan / TSan.
-// "Device memory" is the host heap, so every hipMemcpy the host code issues is bounds-checked by ASan; streams and events
-// are inert tokens.
+// Stand-in for <hip/hip_runtime.h> used ONLY by the CPU programs of tests/cpp: every host-side program of this directory,
+// through harness.h, and every *_exact program that includes a kernel header.  It lets the host side of the library
+// (csrc/host_*.cpp, csrc/mtr_files.cpp, csrc/mtr_group.cpp) be compiled by g++ with AddressSanitizer / UBSan / TSan, and
+// the kernels' plain C++ headers by g++ at all.  "Device memory" is the host heap, so every hipMemcpy the host code issues
+// is bounds-checked by ASan; streams and events are inert tokens.
 #pragma once
 #include <algorithm>
 #include <cstdint>

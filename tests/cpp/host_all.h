@@ -1,5 +1,6 @@
-// The host side of libmtr.so as one translation unit, for the CPU harnesses of this directory: every csrc/host_*.cpp.
-// A file missing here shows up as an undefined symbol when a harness links.
+// The host side of libmtr.so as one translation unit: every csrc/host_*.cpp, as csrc/Makefile picks them up.  Every
+// host-side program of this directory includes it, through harness.h.  tests/test_cpp_harness.py holds this list to the
+// files that exist: a file missing here goes unnoticed by every program that does not call its entry points.
 #pragma once
 #include "../../mt_renderer_amd/csrc/host_device.cpp"
 #include "../../mt_renderer_amd/csrc/host_texture.cpp"
@@ -11,6 +12,7 @@
 #include "../../mt_renderer_amd/csrc/host_events.cpp"
 #include "../../mt_renderer_amd/csrc/host_blend.cpp"
 #include "../../mt_renderer_amd/csrc/host_spring.cpp"
+#include "../../mt_renderer_amd/csrc/host_match.cpp"
 #include "../../mt_renderer_amd/csrc/host_frame.cpp"
 #include "../../mt_renderer_amd/csrc/host_submit.cpp"
 #include "../../mt_renderer_amd/csrc/host_shard.cpp"

@@ -2,43 +2,28 @@
 // HIP runtime (tests/cpp/hip_stub): model / texture / batch creation with random, mostly malformed arguments, frames
 // drawn, submitted, waited and read back.  The kernels are no-ops here; what is exercised is everything the host does
 // with caller-provided sizes, offsets and indices before a kernel may trust them.   usage: host_fuzz <iterations>
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_HARNESS_OWN_ALPHA_MIN
+#define MTR_HARNESS_OWN_BC1_DECODE
+#define MTR_HARNESS_OWN_BC7_DECODE
+#define MTR_HARNESS_OWN_CULL_CHUNKS
+#define MTR_RND_SEED 0x243F6A8885A308D3ull
+#include "harness.h"
 #include "../../mt_renderer_amd/csrc/mtr_files.cpp"
 
-// kernel launchers: inert, except the ones whose output the host reads back
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
-// what tile_prologue does on the device: publish the (clean) overflow flags of the frame
-static void stub_status(const TileParams& p) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { stub_status(p); }
+// the launchers whose output the host reads back, or that read what the host sized
 void mtr_launch_alpha_min(const uint8_t* rgba, size_t npixels, uint32_t* out_min, hipStream_t) {
     uint32_t m = 255;
     for (size_t i = 0; i < npixels; i++) m = std::min<uint32_t>(m, rgba[4 * i + 3]);  // reads every texel: ASan checks the size
     *out_min = m;
 }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
 void mtr_launch_bc1_decode(const uint8_t* b, uint8_t* rgba, uint32_t w, uint32_t h, hipStream_t) {
     memset(rgba, b[(size_t)((w + 3) / 4) * ((h + 3) / 4) * 8 - 1], (size_t)w * h * 4);  // touches the last block byte
 }
 void mtr_launch_bc7_decode(const uint8_t* b, uint8_t* rgba, uint32_t w, uint32_t h, hipStream_t) {
     memset(rgba, b[(size_t)((w + 3) / 4) * ((h + 3) / 4) * 16 - 1], (size_t)w * h * 4);
 }
-void mtr_launch_pack_shard(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_unpack_shards(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, hipStream_t) {}
-void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t i = 0; i < p.ninst; i++) { p.strad[p.count[1]++] = *p.count; p.list[(*p.count)++] = i; } }
 void mtr_launch_cull_chunks(const ChunkCullParams& p, hipStream_t) { if (p.nchunks && p.ninst) p.work_mask[(size_t)((p.nchunks + 15) / 16) * p.ninst - 1] = 0xFFFF; }  // the last mask of the draw
 
-static uint64_t rs = 0x243F6A8885A308D3ull;
-static uint64_t rnd() {
-    uint64_t z = (rs += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint32_t pick(uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rnd() % (hi - lo + 1)); }
 static uint32_t weird() {  // mostly sane, sometimes hostile
     switch (rnd() % 8) {
         case 0: return 0xFFFFFFFFu;

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "blob_io.h"
 #include <hip/hip_runtime.h>  // the stand-in of tests/cpp/hip_stub
 
 #include "../../mt_renderer_amd/csrc/play_math.h"
@@ -20,14 +21,8 @@ static uint32_t bits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::fseek(f, 0, SEEK_END);
-    const long size = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    std::vector<uint32_t> blob((size_t)(size + 3) / 4);
-    if (std::fread(blob.data(), 1, (size_t)size, f) != (size_t)size) return 2;
-    std::fclose(f);
+    long size = 0;
+    std::vector<uint32_t> blob = read_words(argv[1], &size);
     if (blob.size() < 4) return 2;
     const size_t n = blob[0], C = blob[1], m = blob[2];
     float dt;
@@ -54,8 +49,6 @@ int main(int argc, char** argv) {
         o[0] = fr.clip_a; o[1] = fr.clip_b; o[2] = bits(fr.x_a); o[3] = bits(fr.x_b); o[4] = bits(fr.w);
         o[5] = bits(fr.x0_a); o[6] = bits(fr.dx_a); o[7] = bits(fr.x0_b); o[8] = bits(fr.dx_b);
     }
-    FILE* o = std::fopen(argv[2], "wb");
-    if (!o || std::fwrite(out.data(), 4, out.size(), o) != out.size()) return 2;
-    std::fclose(o);
+    write_words(argv[2], out);
     return 0;
 }

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "blob_io.h"
 #include <hip/hip_runtime.h>  // the stand-in of tests/cpp/hip_stub
 
 #include "../../mt_renderer_amd/csrc/root_math.h"
@@ -19,14 +20,8 @@ using namespace mtr;
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::fseek(f, 0, SEEK_END);
-    const long size = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    std::vector<uint32_t> blob((size_t)(size + 3) / 4);
-    if (std::fread(blob.data(), 1, (size_t)size, f) != (size_t)size) return 2;
-    std::fclose(f);
+    long size = 0;
+    std::vector<uint32_t> blob = read_words(argv[1], &size);
     if (blob.size() < 8) return 2;
     const bool tracks = blob[0] != 0;
     const size_t J = blob[1], C = blob[2], joint = blob[3], n = blob[4], S = blob[5], nkeys = blob[6];
@@ -80,8 +75,6 @@ int main(int argc, char** argv) {
             out[(n + inst) * 16 + e] = attach_elem(m, Dc);
         }
     }
-    FILE* o = std::fopen(argv[2], "wb");
-    if (!o || std::fwrite(out.data(), 4, out.size(), o) != out.size()) return 2;
-    std::fclose(o);
+    write_words(argv[2], out);
     return 0;
 }

@@ -7,16 +7,9 @@
 // was; root sets are created and destroyed with calls queued and frames in flight; and a trace hook pins the event order of
 // a root-motion call between an animate call and an attach call on the same batch.
 //   usage: root_host_asan <iterations>
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_RND_SEED 0x13198A2E03707344ull
+#include "harness.h"
 
-static int g_failed = 0;
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "line %d: %s does not hold\n", __LINE__, #c); g_failed++; } } while (0)
-#define EXPECT(call, code) do { const int32_t rc_ = (call); if (rc_ != (code)) { fprintf(stderr, "line %d: %s = %d, expected %d (%s)\n", __LINE__, #call, rc_, (int)(code), mtr_last_error(dev)); return 1; } } while (0)
-#define NAMES(word) do { if (!strstr(mtr_last_error(dev), word)) { fprintf(stderr, "line %d: the error must say \"%s\": %s\n", __LINE__, word, mtr_last_error(dev)); return 1; } } while (0)
-
-struct Op { std::string op; const void* what; const void* stream; };
-static std::vector<Op> g_ops;
 static uint64_t g_root_launches = 0, g_delta_launches = 0, g_step_reads = 0;
 static float g_sink = 0.0f;
 static size_t g_key_words = 0;  // what the trajectory set of the next launch holds behind its clip table (uniform keys)
@@ -39,7 +32,7 @@ static void touch_root(const RootParams& p, bool apply, hipStream_t s) {
     if (apply) g_sink += p.mats_in[0] + p.mats_in[(size_t)p.n * 16 - 1];
     p.out[0] = (float)acc;
     p.out[(size_t)p.n * 16 - 1] = 1.0f;
-    g_ops.push_back({apply ? "root" : "root_deltas", p.out, s});
+    g_ops.push_back({apply ? "root" : "root_deltas", 0, p.out, s});
 }
 void mtr_launch_root(const RootParams& p, hipStream_t s) { g_root_launches++; touch_root(p, true, s); }
 void mtr_launch_root_deltas(const RootParams& p, hipStream_t s) { g_delta_launches++; touch_root(p, false, s); }
@@ -47,38 +40,13 @@ void mtr_launch_attach(const AttachParams& p, hipStream_t s) {
     g_sink += (float)p.recs[0] + p.src_mats[0] + p.src_mats[(size_t)p.n_src * 16 - 1];
     p.out[0] = 1.0f;
     p.out[(size_t)p.n * 16 - 1] = 1.0f;
-    g_ops.push_back({"attach", p.out, s});
+    g_ops.push_back({"attach", 0, p.out, s});
 }
 void mtr_launch_anim(const AnimParams& p, bool, bool fold, uint32_t ninst, hipStream_t s) {
     if (!fold) abort();  // no sample call is made here
     p.pose.out[(size_t)ninst * p.pose.njoints * 16 - 1] = (float)p.states[(size_t)ninst * 6 - 1];
-    g_ops.push_back({"anim", p.pose.out, s});
+    g_ops.push_back({"anim", 0, p.pose.out, s});
 }
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
-static void stub_status(const TileParams& p) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_pack_shard(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_unpack_shards(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, hipStream_t) {}
-void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t i = 0; i < p.ninst; i++) { p.strad[p.count[1]++] = *p.count; p.list[(*p.count)++] = i; } }
-void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
-
-static void trace(const char* name, size_t, const void* what, const void* stream) { g_ops.push_back({name, what, stream}); }
-
-static uint64_t rs = 0x13198A2E03707344ull;
-static uint64_t rnd() {
-    uint64_t z = (rs += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint32_t pick(uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rnd() % (hi - lo + 1)); }
 
 static int32_t make_tracks(mtr_device* dev, uint32_t J, uint32_t nclips, const uint32_t* flags, mtr_anim** out) {
     std::vector<uint32_t> nticks(nclips, 16u);

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "blob_io.h"
 #include <hip/hip_runtime.h>  // the stand-in of tests/cpp/hip_stub: no vector types of floats
 struct float4 {
     float x, y, z, w;
@@ -44,14 +45,8 @@ static void rebuild(const AnimKey& r, float4* loc) {
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::fseek(f, 0, SEEK_END);
-    const long size = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    std::vector<uint32_t> blob((size_t)(size + 3) / 4);
-    if (std::fread(blob.data(), 1, (size_t)size, f) != (size_t)size) return 2;
-    std::fclose(f);
+    long size = 0;
+    std::vector<uint32_t> blob = read_words(argv[1], &size);
     const size_t n = blob[0], J = blob[1], K = blob[2], pw = (J + 3) / 4;
     const bool moved = blob[3] != 0;
     const float dt = f32(blob[4]);
@@ -131,8 +126,6 @@ int main(int argc, char** argv) {
             }
         std::memcpy(&out[i * J * 16], loc.data(), J * 64);
     }
-    FILE* o = std::fopen(argv[2], "wb");
-    if (!o || std::fwrite(out.data(), 4, out.size(), o) != out.size() || std::fwrite(out_states.data(), 4, out_states.size(), o) != out_states.size()) return 2;
-    std::fclose(o);
+    write_words(argv[2], out, out_states);
     return 0;
 }

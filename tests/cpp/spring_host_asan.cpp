@@ -6,8 +6,8 @@
 // spring at a position made of its index and the instance's: a wrong size or offset on the host side is an ASan report, and
 // the states after a call are compared with a second run of the rule.
 //   usage: spring_host_asan <iterations>
-#include "host_all.h"
-using namespace mtr_host;
+#define MTR_RND_SEED 0x13198A2E03707344ull
+#include "harness.h"
 #include "../../mt_renderer_amd/csrc/mtr_files.cpp"
 
 struct float4 {
@@ -19,20 +19,6 @@ static inline float4 make_float4(float x, float y, float z, float w) {
 }
 #include "../../mt_renderer_amd/csrc/spring_math.h"
 
-void mtr_launch_geom(const GeomParams&, hipStream_t) {}
-void mtr_launch_scan(const FrameBuffers&, hipStream_t) {}
-void mtr_launch_fill(const FrameBuffers&, uint32_t, hipStream_t) {}
-static void stub_status(const TileParams& p) { if (p.host_status) __atomic_store_n(p.host_status, 0x80000000u, __ATOMIC_RELEASE); }
-void mtr_launch_tile(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_tile_vis(const TileParams& p, bool, hipStream_t) { stub_status(p); }
-void mtr_launch_alpha_min(const uint8_t*, size_t, uint32_t* out_min, hipStream_t) { *out_min = 255; }
-void mtr_launch_vertex_stage(const GeomParams&, uint32_t, float*, float*, hipStream_t) {}
-void mtr_launch_bc1_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_bc7_decode(const uint8_t*, uint8_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_pack_shard(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, hipStream_t) {}
-void mtr_launch_unpack_shards(const uint8_t*, uint8_t*, uint32_t, uint32_t, const uint32_t*, hipStream_t) {}
-void mtr_launch_cull_instances(const CullParams& p, hipStream_t) { for (uint32_t i = 0; i < p.ninst; i++) { p.strad[p.count[1]++] = *p.count; p.list[(*p.count)++] = i; } }
-void mtr_launch_cull_chunks(const ChunkCullParams&, hipStream_t) {}
 // a spring call makes the checks of the kinds it nests over, so their kernels count as built; the layered call is made
 // here too, between the spring ones
 void mtr_launch_anim(const AnimParams&, bool, bool, uint32_t, hipStream_t) { abort(); }
@@ -110,18 +96,8 @@ static void run_springs(const AnimSpringParams& p, uint32_t ninst, bool tracks, 
 }
 void mtr_launch_anim_spring(const AnimSpringParams& p, bool tracks, bool fold, uint32_t ninst, hipStream_t) { run_springs(p, ninst, tracks, fold); }
 
-static uint64_t rs = 0x13198A2E03707344ull;
-static uint64_t rnd() {
-    uint64_t z = (rs += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint32_t pick(uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rnd() % (hi - lo + 1)); }
 static float unit() { return (float)(rnd() % 2001) / 1000.0f - 1.0f; }
 
-#define EXPECT(call, code) do { const int32_t rc_ = (call); if (rc_ != (code)) { fprintf(stderr, "line %d: %s = %d, expected %d (%s)\n", __LINE__, #call, rc_, (int)(code), mtr_last_error(dev)); return 1; } } while (0)
-#define NAMES(word) do { if (!strstr(mtr_last_error(dev), word)) { fprintf(stderr, "line %d: the error must say \"%s\": %s\n", __LINE__, word, mtr_last_error(dev)); return 1; } } while (0)
 // a rejected call: the code, no launch, the states as they were
 #define REJECT(call) do { const uint64_t l_ = g_launches; EXPECT(call, MTR_E_INVALID); if (g_launches != l_ || memcmp(st.data(), st_before.data(), st.size() * sizeof st[0])) { fprintf(stderr, "line %d: a rejected call launched or changed the states\n", __LINE__); return 1; } rejected++; } while (0)
 

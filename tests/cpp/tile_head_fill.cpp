@@ -16,7 +16,7 @@
 #include "../../mt_renderer_amd/csrc/tile_common.h"
 
 static unsigned long long g_checks = 0, g_bad = 0;
-#define CHECK(cond)                                                                       \
+#define HOLDS(cond)                                                                       \
     do {                                                                                  \
         g_checks++;                                                                       \
         if (!(cond)) { g_bad++; std::fprintf(stderr, "set %d: %s\n", g_set, #cond); }     \
@@ -69,39 +69,39 @@ static void check(const Case& c, bool mutant) {
     // the workgroups of the launch: the rank's bins, eight XCDs, whole runs
     uint32_t grid = (c.own_count + 7) / 8 * 8;
     if (c.xcd_run) grid = (grid / 8 + c.xcd_run - 1) / c.xcd_run * c.xcd_run * 8;
-    CHECK(h.grid == grid);
-    CHECK(h.grid % 8 == 0 && h.grid >= c.own_count && (c.own_count == 0 || c.xcd_run || h.grid - c.own_count < 8));
-    CHECK(h.own_count == p.fb.own.own_count);
-    CHECK(h.own_list == p.fb.own.own_list);
-    CHECK(h.nbx == p.fb.nbx);
-    CHECK(h.nbins == p.fb.nbx * p.fb.nby);
-    CHECK(h.W == p.fb.W);
-    CHECK(h.H == p.fb.H);
-    CHECK(h.direct == p.fb.direct);
-    CHECK(h.qcap == p.fb.qcap);
-    CHECK(h.scap == p.fb.scap);
-    CHECK(h.xcd_run == p.xcd_run);
-    CHECK(h.zero_nwords == p.zero_nwords);
-    CHECK(h.nhint == p.nhint);
-    CHECK(h.entries == p.fb.entries);
-    CHECK(h.bin_fill == p.fb.bin_fill);
-    CHECK(h.bin_start == p.fb.bin_start);
-    CHECK(h.seg_start == p.fb.seg_start);
-    CHECK(h.counters == p.fb.counters);
-    CHECK(h.rec_a == p.fb.rec_a);
-    CHECK(h.zero_next == p.zero_next);
-    CHECK(h.zero_words == p.zero_words);
-    CHECK(h.host_status == p.host_status);
+    HOLDS(h.grid == grid);
+    HOLDS(h.grid % 8 == 0 && h.grid >= c.own_count && (c.own_count == 0 || c.xcd_run || h.grid - c.own_count < 8));
+    HOLDS(h.own_count == p.fb.own.own_count);
+    HOLDS(h.own_list == p.fb.own.own_list);
+    HOLDS(h.nbx == p.fb.nbx);
+    HOLDS(h.nbins == p.fb.nbx * p.fb.nby);
+    HOLDS(h.W == p.fb.W);
+    HOLDS(h.H == p.fb.H);
+    HOLDS(h.direct == p.fb.direct);
+    HOLDS(h.qcap == p.fb.qcap);
+    HOLDS(h.scap == p.fb.scap);
+    HOLDS(h.xcd_run == p.xcd_run);
+    HOLDS(h.zero_nwords == p.zero_nwords);
+    HOLDS(h.nhint == p.nhint);
+    HOLDS(h.entries == p.fb.entries);
+    HOLDS(h.bin_fill == p.fb.bin_fill);
+    HOLDS(h.bin_start == p.fb.bin_start);
+    HOLDS(h.seg_start == p.fb.seg_start);
+    HOLDS(h.counters == p.fb.counters);
+    HOLDS(h.rec_a == p.fb.rec_a);
+    HOLDS(h.zero_next == p.zero_next);
+    HOLDS(h.zero_words == p.zero_words);
+    HOLDS(h.host_status == p.host_status);
     // the divisor words: bin / nbx and bin % nbx for every bin of the frame, i / run and i % run for every blockIdx.x >> 3
     for (uint32_t bin = 0; bin < h.nbins; bin++) {
         const uint32_t by = mtr::udiv_apply(bin, h.nbx_mul, h.nbx_shift);
-        if (by != bin / h.nbx || bin - by * h.nbx != bin % h.nbx) { CHECK(!"bin / nbx"); break; }
+        if (by != bin / h.nbx || bin - by * h.nbx != bin % h.nbx) { HOLDS(!"bin / nbx"); break; }
     }
     g_checks++;
     if (c.xcd_run) {
         for (uint32_t i = 0; i < h.grid / 8; i++) {
             const uint32_t q = mtr::udiv_apply(i, h.run_mul, h.run_shift);
-            if (q != i / c.xcd_run || i - q * c.xcd_run != i % c.xcd_run) { CHECK(!"i / run"); break; }
+            if (q != i / c.xcd_run || i - q * c.xcd_run != i % c.xcd_run) { HOLDS(!"i / run"); break; }
         }
         // ... and block_to_bin's slots with them: every bin of the rank is some workgroup's, once
         unsigned long long sum = 0, want = (unsigned long long)c.own_count * (c.own_count - (c.own_count ? 1 : 0)) / 2, taken = 0;
@@ -110,18 +110,18 @@ static void check(const Case& c, bool mutant) {
             const uint32_t slot = (q * 8 + x) * c.xcd_run + (i - q * c.xcd_run);
             if (slot < c.own_count) { sum += slot; taken++; }
         }
-        CHECK(taken == c.own_count && sum == want);
+        HOLDS(taken == c.own_count && sum == want);
     } else {
-        CHECK(h.run_mul == 0 && h.run_shift == 0);
+        HOLDS(h.run_mul == 0 && h.run_shift == 0);
     }
     // nothing but the head was written
-    CHECK(std::memcmp(&p.fb, &before.fb, sizeof p.fb) == 0);
-    CHECK(std::memcmp(&p.mats, &before.mats, sizeof(TileParams) - offsetof(TileParams, mats)) == 0);
+    HOLDS(std::memcmp(&p.fb, &before.fb, sizeof p.fb) == 0);
+    HOLDS(std::memcmp(&p.mats, &before.mats, sizeof(TileParams) - offsetof(TileParams, mats)) == 0);
     // filling twice, or over another launch's head, gives the same head (the mixed frame's second launch reuses the copy)
     TileParams again = p;
     again.nhint = 0;
     tile_fill_head(again);
-    CHECK(again.head.nhint == 0 && again.head.grid == h.grid && again.head.entries == p.fb.entries);
+    HOLDS(again.head.nhint == 0 && again.head.grid == h.grid && again.head.entries == p.fb.entries);
 }
 
 int main(int argc, char** argv) {

@@ -8,21 +8,17 @@ image is a difference here, not a wrong pose on the GPU."""
 import difflib
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
+
+from tests import cpp_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_anim_call_trace_matches_the_recorded_one(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "anim_call_trace")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "anim_call_trace.cpp"), "-o", exe, "-lz"])
+    exe = cpp_build.build("anim_call_trace", tmp_path, cpp_build.HOST_ASAN)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-6000:]
     # two such lines: where the first recording ended (598 operations, 34 rejected calls), and the whole run's, the last

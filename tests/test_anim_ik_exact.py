@@ -3,8 +3,6 @@ csrc/anim_blend.h's local matrix and csrc/pose_common.h's pose_mul chain, compil
 together as the k_anim_ik kernels put them together and compared bit for bit with the numpy model of section 17: the GPU
 bit-exactness test's rehearsal on a machine without a GPU.  The (T, Q, S) the chains start from come from the model of
 section 16."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -13,18 +11,14 @@ import pytest
 from tests import anim_ik_model as ik
 from tests import anim_layers_model as lm
 from tests import anim_model as am
+from tests import cpp_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("anim_ik_exact") / "anim_ik_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I",
-                           os.path.join(ROOT, "tests", "cpp", "hip_stub"), os.path.join(ROOT, "tests", "cpp", "anim_ik_exact.cpp"), "-o", out])
+    out = cpp_build.build("anim_ik_exact", tmp_path_factory.mktemp("anim_ik_exact"), cpp_build.EXACT, extra=["-Wno-unused-function", "-Wno-unknown-pragmas"])
     return out
 
 

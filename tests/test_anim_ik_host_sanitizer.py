@@ -4,23 +4,14 @@ program whose launchers read the first and last layer and target of every instan
 every chain's first joint: every invalid call and every creation rule of SPEC.md section 17 (the error names the chain, or
 the first joint whose parent differs), both kinds of set with host and device targets, and one batch animated by every kind
 of pose call with frames in flight while IK sets are created and destroyed between them."""
-import os
 import re
-import shutil
 import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import cpp_build
 
 
 def test_anim_ik_host_side_under_asan_ubsan(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "anim_ik_host_asan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "anim_ik_host_asan.cpp"), "-o", exe, "-lz"])
+    exe = cpp_build.build("anim_ik_host_asan", tmp_path, cpp_build.HOST_ASAN)
     r = subprocess.run([exe, "60"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"animated=(\d+) rejected=(\d+) target_reads=(\d+) chain_reads=(\d+) path_reads=(\d+)", r.stdout)

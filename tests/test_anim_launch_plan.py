@@ -9,21 +9,17 @@ decision says no launches nothing and reports nothing, so a dropped term is a di
 import difflib
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
+
+from tests import cpp_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_anim_launch_plan_matches_the_recorded_one(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "anim_launch_plan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "anim_launch_plan.cpp"), "-o", exe])
+    exe = cpp_build.build("anim_launch_plan", tmp_path, cpp_build.HOST_ASAN)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-6000:]
     with open(os.path.join(ROOT, "tests", "golden", "anim_launch_plan.txt")) as f:

@@ -2,8 +2,6 @@
 the layer weight and the two layer steps), compiled by g++ with -ffp-contract=off and compared bit for bit with the numpy
 model of SPEC.md section 16 on the inputs the GPU tests use: the GPU bit-exactness test's rehearsal on a machine without a
 GPU.  The keys and fractions each layer blends come from the models of sections 14 and 15."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,18 +10,14 @@ import pytest
 from tests import anim_layers_model as lm
 from tests import anim_model as am
 from tests import anim_tracks_model as tm
+from tests import cpp_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("anim_layers_exact") / "anim_layers_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"),
-                           os.path.join(ROOT, "tests", "cpp", "anim_layers_exact.cpp"), "-o", out])
+    out = cpp_build.build("anim_layers_exact", tmp_path_factory.mktemp("anim_layers_exact"), cpp_build.EXACT)
     return out
 
 

@@ -3,23 +3,14 @@ csrc/host_anim.cpp, csrc/host_batch.cpp) compiled by g++ with AddressSanitizer a
 as a stand-alone program whose launchers read the first and last layer of every instance and the first and last mask
 weight and clip entry each layer names: every invalid call, both kinds of set with and without masks, and one batch
 animated by all kinds of call with frames in flight while mask sets come and go."""
-import os
 import re
-import shutil
 import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import cpp_build
 
 
 def test_anim_layers_host_side_under_asan_ubsan(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "anim_layers_host_asan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "anim_layers_host_asan.cpp"), "-o", exe, "-lz"])
+    exe = cpp_build.build("anim_layers_host_asan", tmp_path, cpp_build.HOST_ASAN)
     r = subprocess.run([exe, "60"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"animated=(\d+) rejected=(\d+) layer_reads=(\d+) mask_reads=(\d+) clip_reads=(\d+)", r.stdout)

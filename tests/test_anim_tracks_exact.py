@@ -1,25 +1,18 @@
 """CPU: csrc/anim_tracks.h, the source k_anim.hip's track source is made of (position -> r, the key search with (k, k1, a),
 the two key decodes), compiled by g++ with -ffp-contract=off and compared bit for bit with the numpy model of SPEC.md
 section 15 on the inputs the GPU tests use: the GPU bit-exactness test's rehearsal on a machine without a GPU."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from tests import anim_tracks_model as tm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import cpp_build
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("anim_tracks_exact") / "anim_tracks_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"),
-                           os.path.join(ROOT, "tests", "cpp", "anim_tracks_exact.cpp"), "-o", out])
+    out = cpp_build.build("anim_tracks_exact", tmp_path_factory.mktemp("anim_tracks_exact"), cpp_build.EXACT)
     return out
 
 

@@ -2,26 +2,20 @@
 A * O) compiled by g++ with -ffp-contract=off over the HIP stub, put together as k_attach puts it together and compared bit
 for bit with the numpy model on every case of the generator: the GPU bit-exactness test's rehearsal on a machine without a
 GPU.  An element that is NaN in the model must be NaN in the result; payloads are free."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from tests import attach_model as am
+from tests import cpp_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = am.cases()
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("attach_exact") / "attach_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I",
-                           os.path.join(ROOT, "tests", "cpp", "hip_stub"), os.path.join(ROOT, "tests", "cpp", "attach_exact.cpp"), "-o", out])
+    out = cpp_build.build("attach_exact", tmp_path_factory.mktemp("attach_exact"), cpp_build.EXACT, extra=["-Wno-unused-function", "-Wno-unknown-pragmas"])
     return out
 
 

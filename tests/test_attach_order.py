@@ -3,23 +3,14 @@ the stand-in HIP runtime (tests/cpp/hip_stub) built by g++ with AddressSanitizer
 stream waits, launches and event records for an attach followed by two updates of the source, an attach followed by the
 source's destruction, and a batch attached to itself, and that every invalid call leaves `cur` and the version rings
 untouched."""
-import os
 import re
-import shutil
 import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import cpp_build
 
 
 def test_attach_ordering_under_asan_ubsan(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "attach_order")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "attach_order.cpp"), "-o", exe, "-lz"])
+    exe = cpp_build.build("attach_order", tmp_path, cpp_build.HOST_ASAN)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
     m = re.search(r"attach_order: launches=(\d+) failed=(\d+) sink=ok", r.stdout)

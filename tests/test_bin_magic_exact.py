@@ -2,23 +2,16 @@
 `/` and `%`, exhaustively: bin / nbx and bin % nbx for every bins-per-row count and every bin index a frame can have,
 blockIdx.x >> 3 by every run length the host accepts for every block of such a launch, and the pair walks' k / iw.  A
 multiplier one too small must be caught."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "cpp", "bin_magic_exact.cpp")
+from tests import cpp_build
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("bin_magic") / "bin_magic_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-pthread", SRC, "-o", out])
-    return out
+    return cpp_build.build("bin_magic_exact", tmp_path_factory.mktemp("bin_magic"), cpp_build.BARE, extra=["-pthread"])
 
 
 def _run(exe, *args):

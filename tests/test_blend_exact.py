@@ -3,26 +3,20 @@ first triangle that holds the point and the closest-edge fallback of a 2-D space
 g++ with -ffp-contract=off over the HIP stub, put together as k_blend puts it together and compared bit for bit with the numpy
 model on every case of the generator, three chained calls each: the GPU bit-exactness test's rehearsal on a machine without a
 GPU.  A NaN in the model must be a NaN in the result; payloads are free."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from tests import blend_model as bm
+from tests import cpp_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = bm.cases()
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("blend_exact") / "blend_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I",
-                           os.path.join(ROOT, "tests", "cpp", "hip_stub"), os.path.join(ROOT, "tests", "cpp", "blend_exact.cpp"), "-o", out])
+    out = cpp_build.build("blend_exact", tmp_path_factory.mktemp("blend_exact"), cpp_build.EXACT, extra=["-Wno-unused-function", "-Wno-unknown-pragmas"])
     return out
 
 

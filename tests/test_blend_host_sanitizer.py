@@ -5,23 +5,14 @@ words it is handed: every rejected creation and call of SPEC.md section 23 launc
 the steps and the shares as they were (the error names the clip, the sample or the triangle), the valid calls equal a second
 run of the rule on copies -- through the device call on two streams and through the host hook on unaligned memory --, and sets
 are created and destroyed with calls queued."""
-import os
 import re
-import shutil
 import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import cpp_build
 
 
 def test_blend_host_side_under_asan_ubsan(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "blend_host_asan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "blend_host_asan.cpp"), "-o", exe, "-lz"])
+    exe = cpp_build.build("blend_host_asan", tmp_path, cpp_build.HOST_ASAN)
     r = subprocess.run([exe, "40"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"advanced=(\d+) rejected=(\d+) launches=(\d+) failed=(\d+)", r.stdout)

@@ -3,27 +3,21 @@ candidates with their skips, the conditions, the fire and the store) compiled by
 put together as k_ctrl puts it together and compared bit for bit with the numpy model on every step of every case of the
 generator: the GPU bit-exactness test's rehearsal on a machine without a GPU.  A NaN in the model must be a NaN in the result;
 payloads are free."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cpp_build
 from tests import ctrl_model as cm
 from tests import player_model as pm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = cm.cases()
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("ctrl_exact") / "ctrl_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I",
-                           os.path.join(ROOT, "tests", "cpp", "hip_stub"), os.path.join(ROOT, "tests", "cpp", "ctrl_exact.cpp"), "-o", out])
+    out = cpp_build.build("ctrl_exact", tmp_path_factory.mktemp("ctrl_exact"), cpp_build.EXACT, extra=["-Wno-unused-function", "-Wno-unknown-pragmas"])
     return out
 
 

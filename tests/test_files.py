@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from mt_renderer_amd import api, files, scene
+from tests import cpp_build
 from tests import mt_files
 from tests.pixel_scenes import pixel_model
 
@@ -236,10 +237,7 @@ def test_cpp_mirror_reads_the_same_files(tmp_path):
         p = tmp_path / name
         p.write_bytes(data)
         paths.append(str(p))
-    exe = str(tmp_path / "files_demo")
-    lib_dir = os.path.join(ROOT, "mt_renderer_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "files_demo.cpp"), "-o", exe, "-L", lib_dir, "-lmtr", "-Wl,-rpath," + lib_dir])
+    exe = cpp_build.build("files_demo", tmp_path, cpp_build.CLIENT)
     r = subprocess.run([exe] + paths, capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stderr)
     out = r.stdout.splitlines()
@@ -356,10 +354,7 @@ def test_parsers_survive_mutated_files():
 def test_parsers_under_address_sanitizer(tmp_path):
     """The same kind of mutations, 30 000 of them, against an AddressSanitizer + UBSan build of csrc/mtr_files.cpp
     (host-only build with stand-ins for the device entry points; sanitizers cannot run on the GPU box)."""
-    import shutil
     import subprocess
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     md = _model()
     rmodel, rshader2, rmaterial, rtextures = mt_files.files_from_model_data(md)
     joints = [(i, max(i - 1, 0), (0.1 * i, 0.0, 1.0)) for i in range(4)]
@@ -374,9 +369,7 @@ def test_parsers_under_address_sanitizer(tmp_path):
         p = tmp_path / name
         p.write_bytes(data)
         paths.append(str(p))
-    exe = str(tmp_path / "files_fuzz")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "files_fuzz.cpp"), "-o", exe, "-lz"])
+    exe = cpp_build.build("files_fuzz", tmp_path, cpp_build.HOST_ASAN)
     r = subprocess.run([exe, "30000"] + paths, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
     ok, err = [int(t.split("=")[1]) for t in r.stdout.split()]

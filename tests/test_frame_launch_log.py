@@ -4,23 +4,16 @@ and a trace hook that logs the memsets, uploads, waits, event records and stream
 which kernels run in which order for direct / two-pass binning, visibility / mixed / ordered tile kernels, sharded draws,
 overflow re-runs, an empty band, profiling, frames of several draws on one slot (with every draw's share of the culling
 buffers checked) -- are written out in tests/cpp/frame_launch_log.cpp."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import cpp_build
 
 
 @pytest.fixture(scope="module")
 def launch_log_exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("frame_launch_log") / "frame_launch_log")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "frame_launch_log.cpp"), "-o", exe])
+    exe = cpp_build.build("frame_launch_log", tmp_path_factory.mktemp("frame_launch_log"), cpp_build.HOST_ASAN)
     return exe
 
 

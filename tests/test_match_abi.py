@@ -12,6 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import cpp_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "mtr.h")
 NAMES = {"mtr_anim_match_create": 17, "mtr_anim_match_destroy": 1, "mtr_anim_match_search_device": 9, "mtr_anim_match_search_host": 8,
@@ -80,7 +82,7 @@ def test_record_layouts(tmp_path):
     subprocess.check_call(["g++", "-x", "c", "-std=c11", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)])
     cpp = tmp_path / "mirror.cpp"
     cpp.write_text('#include "mtr.hpp"\nint main() { return sizeof(mtr::AnimMatch) != 0 ? 0 : 1; }\n')
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(cpp)])
+    subprocess.check_call(["g++", cpp_build.STD, "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(cpp)])
 
 
 def test_null_handles_are_rejected_without_a_device():

@@ -3,26 +3,20 @@ chain, the order key and the decision) compiled by g++ with -ffp-contract=off ov
 it together and compared bit for bit with the numpy model on every case of the generator, for scores, winners, commands and
 results: the GPU bit-exactness test's rehearsal on a machine without a GPU.  A NaN in the model must be a NaN in the result;
 payloads are free."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cpp_build
 from tests import match_model as mm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = mm.cases()
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("match_exact") / "match_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I",
-                           os.path.join(ROOT, "tests", "cpp", "hip_stub"), os.path.join(ROOT, "tests", "cpp", "match_exact.cpp"), "-o", out])
+    out = cpp_build.build("match_exact", tmp_path_factory.mktemp("match_exact"), cpp_build.EXACT, extra=["-Wno-unused-function", "-Wno-unknown-pragmas"])
     return out
 
 

@@ -2,16 +2,14 @@
 clip, the weight, the records of the frame and the store) compiled by g++ with -ffp-contract=off over the HIP stub, put together
 as k_play puts it together and compared bit for bit with the numpy model on every call of every case of the generator: the GPU
 bit-exactness test's rehearsal on a machine without a GPU.  A NaN in the model must be a NaN in the result; payloads are free."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cpp_build
 from tests import player_model as pm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = pm.cases()
 F32 = np.float32
 FRAME = ("clip_a", "clip_b", "x_a", "x_b", "w", "x0_a", "dx_a", "x0_b", "dx_b")
@@ -19,11 +17,7 @@ FRAME = ("clip_a", "clip_b", "x_a", "x_b", "w", "x0_a", "dx_a", "x0_b", "dx_b")
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("play_exact") / "play_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I",
-                           os.path.join(ROOT, "tests", "cpp", "hip_stub"), os.path.join(ROOT, "tests", "cpp", "play_exact.cpp"), "-o", out])
+    out = cpp_build.build("play_exact", tmp_path_factory.mktemp("play_exact"), cpp_build.EXACT, extra=["-Wno-unused-function", "-Wno-unknown-pragmas"])
     return out
 
 

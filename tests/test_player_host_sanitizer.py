@@ -5,23 +5,14 @@ exactly the words it is handed: every rejected call of SPEC.md section 20 launch
 were (the error names the clip), host commands are staged in the player's own buffer before the call returns, device
 commands are read where they are, a second stream waits for the player's event, the scratch array is clean after every
 call, and players are created and destroyed with advances queued while their command buffer grows."""
-import os
 import re
-import shutil
 import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import cpp_build
 
 
 def test_player_host_side_under_asan_ubsan(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "player_host_asan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "player_host_asan.cpp"), "-o", exe, "-lz"])
+    exe = cpp_build.build("player_host_asan", tmp_path, cpp_build.HOST_ASAN)
     r = subprocess.run([exe, "40"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"advanced=(\d+) rejected=(\d+) launches=(\d+) cmd_launches=(\d+) failed=(\d+)", r.stdout)

@@ -3,26 +3,20 @@ of the trajectory joint from uniform keys and from tracks, delta, composition, t
 with -ffp-contract=off over the HIP stub, put together as k_root puts it together and compared bit for bit with the numpy model
 on every case of the generator: the GPU bit-exactness test's rehearsal on a machine without a GPU.  An element that is NaN in
 the model must be NaN in the result; payloads are free."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cpp_build
 from tests import root_model as rm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = rm.cases()
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("root_exact") / "root_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I",
-                           os.path.join(ROOT, "tests", "cpp", "hip_stub"), os.path.join(ROOT, "tests", "cpp", "root_exact.cpp"), "-o", out])
+    out = cpp_build.build("root_exact", tmp_path_factory.mktemp("root_exact"), cpp_build.EXACT, extra=["-Wno-unused-function", "-Wno-unknown-pragmas"])
     return out
 
 

@@ -5,23 +5,14 @@ everything k_root is handed: every rejected call of SPEC.md section 19 (the erro
 LOOP clip of a trajectory set) leaves the batch's version ring as it was, both kinds of set with host and device steps, root
 sets created and destroyed with calls queued and frames in flight, and the event order of a root-motion call between an
 animate call and an attach call on the same batch."""
-import os
 import re
-import shutil
 import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import cpp_build
 
 
 def test_root_host_side_under_asan_ubsan(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "root_host_asan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "root_host_asan.cpp"), "-o", exe, "-lz"])
+    exe = cpp_build.build("root_host_asan", tmp_path, cpp_build.HOST_ASAN)
     r = subprocess.run([exe, "40"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"moved=(\d+) rejected=(\d+) root_launches=(\d+) delta_launches=(\d+) step_reads=(\d+) failed=(\d+)", r.stdout)

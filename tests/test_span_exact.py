@@ -4,14 +4,12 @@ vertices anywhere, on pixel centres and on bin corners, horizontal and vertical 
 bin and by the viewport, edge values near the class limit).  The row bounds come from an f32 estimate settled by one
 integer evaluation, so the check is repeated with the reciprocal 1 ulp off either way (v_rcp_f32's error bound), and a
 reciprocal 3 % off must be caught."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "cpp", "span_exact.cpp")
+from tests import cpp_build
+
 
 RCP = {
     "exact": "(1.0f/(x))",
@@ -21,12 +19,8 @@ RCP = {
 
 
 def _build(tmp_path, name, rcp):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / f"span_exact_{name}")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", f"-DMTR_SPAN_RCP(x)={rcp}", "-include", "cmath",
-                           SRC, "-o", exe])
-    return exe
+    return cpp_build.build("span_exact", tmp_path, cpp_build.BARE, extra=["-ffp-contract=off", f"-DMTR_SPAN_RCP(x)={rcp}", "-include", "cmath"],
+                           exe=f"span_exact_{name}")
 
 
 @pytest.mark.parametrize("name", sorted(RCP))

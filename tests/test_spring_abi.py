@@ -11,6 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import cpp_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "mtr.h")
 NAMES = {"mtr_anim_spring_create": 6, "mtr_anim_spring_destroy": 1, "mtr_batch_animate_spring_device": 12, "mtr_anim_sample_spring": 13}
@@ -70,7 +72,7 @@ def test_record_layouts(tmp_path):
     # and the C++ mirror compiles
     cpp = tmp_path / "mirror.cpp"
     cpp.write_text('#include "mtr.hpp"\nint main() { return sizeof(mtr::AnimSpring) != 0 ? 0 : 1; }\n')
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(cpp)])
+    subprocess.check_call(["g++", cpp_build.STD, "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(cpp)])
 
 
 def test_null_arguments_are_rejected_without_a_device():

@@ -3,27 +3,21 @@ csrc/pose_common.h's pose_mul chain, compiled by g++ with -ffp-contract=off, put
 them together and compared bit for bit -- local matrices and state records -- with the numpy model of section 24 on the
 generator's cases: the GPU bit-exactness test's rehearsal on a machine without a GPU.  The (T, Q, S) the springs start from
 come from the models of sections 16 and 17."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from tests import anim_ik_model as ik
+from tests import cpp_build
 from tests import spring_model as sm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("spring_exact") / "spring_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I",
-                           os.path.join(ROOT, "tests", "cpp", "hip_stub"), os.path.join(ROOT, "tests", "cpp", "spring_exact.cpp"), "-o", out])
+    out = cpp_build.build("spring_exact", tmp_path_factory.mktemp("spring_exact"), cpp_build.EXACT, extra=["-Wno-unused-function", "-Wno-unknown-pragmas"])
     return out
 
 

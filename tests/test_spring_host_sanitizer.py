@@ -5,23 +5,14 @@ device image and run csrc/spring_math.h on the state words they are handed: ever
 section 24 launches nothing, leaves the states untouched and names the spring (or the joint whose parent differs); valid
 calls on two streams, with and without an IK set, motion and masks, equal a second run of the rule; the host hook works on
 memory one byte off every alignment; spring sets are destroyed with their calls queued and frames in flight."""
-import os
 import re
-import shutil
 import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import cpp_build
 
 
 def test_spring_host_side_under_asan_ubsan(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "spring_host_asan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "spring_host_asan.cpp"), "-o", exe, "-lz"])
+    exe = cpp_build.build("spring_host_asan", tmp_path, cpp_build.HOST_ASAN)
     r = subprocess.run([exe, "60"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"animated=(\d+) rejected=(\d+) launches=(\d+) state_steps=(\d+) path_reads=(\d+)", r.stdout)

@@ -3,24 +3,16 @@ TileParams is what the kernels fetch first and read instead of the fields it mir
 source, the grid must be the whole runs of the launch, the divisor words must still give `/` and `%`, and nothing outside the
 head may change -- over unsharded and sharded parameter sets, own_list null and set, a rank without a bin, xcd_run 0 / 1 /
 16 / 65536, both queue layouts (tests/cpp/tile_head_fill.cpp).  A head with two fields swapped must be caught."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "cpp", "tile_head_fill.cpp")
+from tests import cpp_build
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("tile_head") / "tile_head_fill")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(HERE, "cpp", "hip_stub"), SRC, "-o", out])
-    return out
+    return cpp_build.build("tile_head_fill", tmp_path_factory.mktemp("tile_head"), cpp_build.HOST_ASAN)
 
 
 def _run(exe, *args):

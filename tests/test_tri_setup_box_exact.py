@@ -4,21 +4,13 @@ on the cases tests/test_tri_setup_exact.py draws from tests/cpp/tri_gen.h (same 
 area, rcpA, the z plane and the bbox are tri_setup's bit for bit; the small class's C_i equal tri_edge(C_i, A_i, B_i, ox,
 oy) of tri_setup's -- the rebase the kernel used to do for every staged triangle -- and the int64 edge value at that pixel;
 the 64-bit class's C stays where the whole-wave walk reads it."""
-import os
-import shutil
 import subprocess
 
-import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "cpp", "tri_setup_box_exact.cpp")
+from tests import cpp_build
 
 
 def test_box_setup_matches_rebased_shared_setup(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "tri_setup_box_exact")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", SRC, "-o", exe])
+    exe = cpp_build.build("tri_setup_box_exact", tmp_path, cpp_build.BARE, extra=["-ffp-contract=off"])
     out = subprocess.run([exe, "1000000", "30000", "20261018"], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
     small, large, moved, bad = (int(v) for v in out.stdout.split())

@@ -7,23 +7,15 @@ the bin-relative integers at every covered pixel.
 The small class multiplies with v_mul_i32_i24, which the header's host macro models.  Its widest operand is
 A = 256 * dy, a signed 24-bit value iff |256 * dy| < 2^23 (the positive side), i.e. dy <= 32767.  A class limit L admits
 dy = L, so L = 32768 is the first limit at which A (= 2^23, read back as -2^23) no longer fits: the mutant build."""
-import os
-import shutil
 import subprocess
 
-import pytest
+from tests import cpp_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "cpp", "tri_setup_exact.cpp")
 MUTANT_LIMIT = 32768  # 256 * 32768 = 2^23: one past the largest positive 24-bit operand
 
 
 def _build(tmp_path, name, *defs):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / f"tri_setup_exact_{name}")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", *defs, SRC, "-o", exe])
-    return exe
+    return cpp_build.build("tri_setup_exact", tmp_path, cpp_build.BARE, extra=["-ffp-contract=off", *defs], exe=f"tri_setup_exact_{name}")
 
 
 def test_shared_setup_matches_int64_reference(tmp_path):
