@@ -36,6 +36,7 @@
 // address.
 #include "mtr_internal.h"
 #include "match_math.h"
+#include "match_launch.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -225,31 +226,18 @@ static void match_search_launch(const MatchParams& p, bool share, dim3 grid, uin
 
 }  // namespace mtr
 
-// The shape of the search grid.  share_groups: crowds of up to this many groups of 32 instances run the SHARE layout;
-// target: about this many workgroups, the row slabs making up what the instances leave.  MTR_MATCH_TUNE="share_groups,target"
-// overrides both for timing ablations (tools/bench_match.py), read once.
-struct MatchTune {
-    uint32_t share_groups = 32u, target = 1024u;
-    MatchTune() {
-        const char* e = getenv("MTR_MATCH_TUNE");
-        unsigned a = 0, b = 0;
-        if (e && sscanf(e, "%u,%u", &a, &b) == 2 && b >= 1u && b <= 65535u) { share_groups = a; target = b; }
-    }
-};
-
+// The shape of the search grid and the reading of MTR_MATCH_TUNE="share_groups,target" live in match_launch.h, which the host
+// test compiles too; the variable overrides both numbers for timing ablations (tools/bench_match.py) and for the tests that
+// force a grid shape, and is read once.
 void mtr_launch_match(const MatchParams& p, hipStream_t s) {
     if (p.n == 0 || p.R == 0 || p.nclips == 0) return;
-    static const MatchTune tune;
+    static const MatchTune tune = match_tune_parse(getenv("MTR_MATCH_TUNE"));
     const uint32_t np = (p.n + 31u) & ~31u;
     hipLaunchKernelGGL(mtr::k_match_query, dim3((np + 255u) / 256u), dim3(256), 0, s, p);
-    const uint32_t ngroups = np / 32u, ntiles = (p.R + 31u) / 32u;
-    const bool share = !p.scores && ngroups <= tune.share_groups;
-    const uint32_t gx = share ? ngroups : (ngroups + 3u) / 4u;
-    uint32_t gy = (tune.target + gx - 1u) / gx;
-    if (gy > ntiles) gy = ntiles;
-    const uint32_t tps = (ntiles + gy - 1u) / gy;
-    gy = (ntiles + tps - 1u) / tps;
-    const dim3 grid(gx, gy);
+    const MatchGrid g = match_grid(p.n, p.R, p.scores != nullptr, tune.share_groups, tune.target);
+    const bool share = g.share;
+    const uint32_t tps = g.tiles_per_slab;
+    const dim3 grid(g.gx, g.gy);
     switch (mtr::match_dp(p.D) / 8u) {
     case 1: mtr::match_search_launch<1>(p, share, grid, tps, s); break;
     case 2: mtr::match_search_launch<2>(p, share, grid, tps, s); break;

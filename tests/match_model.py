@@ -225,12 +225,53 @@ def make_rows(R):
 
 
 def dup_pairs(R):
-    """(source, copy) rows whose features and bias are made equal, across tile (32) boundaries, which are also the wave and
-    slab boundaries of the search at these sizes, and at both ends"""
+    """(source, copy) rows whose features and bias are made equal, across tile (32) boundaries and at both ends.  At the
+    generator's sizes (R <= 1025, n <= 257) the default grid gives every slab one tile, so a tile boundary is a slab boundary
+    too, no wave meets a second tile, and only wave 0 of a SHARE workgroup has work: what these pairs join is two registers of
+    one lane or two slabs.  tests/match_grid_cases.py places pairs by the plan of a forced grid for everything else."""
     return [(a, b) for a, b in ((0, 1), (31, 32), (63, 64), (95, 97), (R - 2, R - 1), (31, R - 1)) if 0 <= a < b < R]
 
 
-def make_case(rng, n, R, D, family, idx):
+def pair_bit(k):
+    """the tag bit of duplicated pair k: six below ZERO_BIT, as ever, and from the seventh on above it"""
+    return PAIR_BIT << k if k < 6 else ZERO_BIT << (k - 5)
+
+
+def grid(n, R, scores=False, share_groups=32, target=1024):
+    """the search grid of csrc/match_launch.h for n instances and R rows (tests/test_match_launch_plan.py holds the two
+    together): the layout, the workgroups in x (instance groups) and y (slabs), the tiles of a slab, and the counts it is made of"""
+    ngroups, ntiles = (n + 31) // 32, (R + 31) // 32
+    share = (not scores) and ngroups <= share_groups
+    gx = ngroups if share else (ngroups + 3) // 4
+    gy = min((target + gx - 1) // gx, ntiles)
+    tps = (ntiles + gy - 1) // gy
+    return dict(share=share, gx=gx, gy=(ntiles + tps - 1) // tps, tiles_per_slab=tps, ngroups=ngroups, ntiles=ntiles, n=n, R=R)
+
+
+def wave_tiles(plan, slab):
+    """the tiles [t0, t1) of each wave that walks slab `slab`: four waves and a quarter each under SHARE (a wave may have
+    none), otherwise one entry, every wave of the workgroup walking the whole slab for its own instances"""
+    tps = plan["tiles_per_slab"]
+    t0, t1 = slab * tps, min(slab * tps + tps, plan["ntiles"])
+    if not plan["share"]:
+        return [(t0, t1)]
+    quarter = (tps + 3) // 4
+    return [(t0 + w * quarter, max(t0 + w * quarter, min(t0 + w * quarter + quarter, t1))) for w in range(4)]
+
+
+def owner(row, plan):
+    """(slab, wave, tile, half, register) of a row under a plan: the wave among those the slab's tiles are split over (always 0
+    in the wave-owned layout), and the half-wave and accumulator register of the 32 x 32 result that hold the row: lane l has
+    rows 8 (i >> 2) + 4 (l >> 5) + (i & 3), i = 0..15, of a tile"""
+    tile = row // 32
+    slab = tile // plan["tiles_per_slab"]
+    wave = next(w for w, (t0, t1) in enumerate(wave_tiles(plan, slab)) if t0 <= tile < t1)
+    r = row % 32
+    return slab, wave, tile, (r >> 2) & 1, 4 * (r >> 3) + (r & 3)
+
+
+def make_case(rng, n, R, D, family, idx, pairs=None):
+    """one case; `pairs` is the list of duplicated (source, copy) rows, dup_pairs(R) where none is given"""
     rows = make_rows(R)
     if family == "benign":
         feats, qamp = rng.standard_normal((R, D)).astype(F), 1.0
@@ -260,11 +301,11 @@ def make_case(rng, n, R, D, family, idx):
         raw[5::16] = (-1e-19 * (1.0 + rng.random(raw[5::16].shape))).astype(F)
     # duplicated rows win for the instances whose filter admits them: a bias below every other row's cost
     big = {"benign": 1e3, "cancel": 1e9, "subnormal": 1e-15, "large": 1e37}[family]
-    for k, (a, b) in enumerate(dup_pairs(R)):
+    for k, (a, b) in enumerate(dup_pairs(R) if pairs is None else pairs):
         feats[b] = feats[a]
         rows["bias"][a] = rows["bias"][b] = F(-big * (1.0 + k))
-        rows["tags"][a] |= PAIR_BIT << k
-        rows["tags"][b] |= PAIR_BIT << k
+        rows["tags"][a] |= pair_bit(k)
+        rows["tags"][b] |= pair_bit(k)
     mode = ("all", "none", "mixed")[idx % 3]
     pose = {"all": (1 << D) - 1, "none": 0, "mixed": sum(1 << d for d in range(0, D, 3))}[mode]
     norm = idx % 2 == 1
