@@ -10,14 +10,9 @@ import tempfile
 
 import pytest
 
+from tests.abi_header import declared as _declared, prototypes as _prototypes, return_types as _return_types
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
-
-
-def _declared(hdr=HDR):
-    src = open(hdr).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(mtr_[a-z0-9_]+)\s*\(", src)))
 
 
 def test_library_exports_every_declared_symbol():
@@ -29,6 +24,21 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), f"libmtr.so does not export {n}"
     assert sorted(api.EXPORTED_SYMBOLS) == names
     assert api.lib.mtr_abi_version() == 2
+
+
+def test_every_declared_function_is_bound_with_its_prototype():
+    """every function of include/mtr.h, the ones from before the animation entry points too: the binding gives it the
+    argument count of its prototype and the ctypes class of its declared return type"""
+    from mt_renderer_amd import api
+    protos, returns = _prototypes(), _return_types()
+    assert sorted(protos) == _declared() and sorted(returns) == _declared(), "the header was not parsed"
+    scalars = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "size_t": ctypes.c_size_t, "void": None, "const char *": ctypes.c_char_p}
+    for name, nargs in protos.items():
+        fn = getattr(api.lib, name)
+        ret = returns[name]
+        assert ret in scalars or ret.endswith("*"), (name, ret)
+        assert len(fn.argtypes) == nargs, (name, len(fn.argtypes), nargs)
+        assert fn.restype is scalars.get(ret, ctypes.c_void_p), (name, ret, fn.restype)
 
 
 def test_library_exports_nothing_but_the_declared_abi():

@@ -3,7 +3,6 @@ api.py with the argument count of their prototype; the two structs have their st
 section 14 (tests/anim_model.py), which the GPU tests pin the kernel to, gives the answers the section's rules imply."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
@@ -11,20 +10,11 @@ import numpy as np
 import pytest
 
 from tests import anim_model as am
+from tests.abi_header import prototypes as _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
 NEW = ["mtr_anim_create", "mtr_anim_destroy", "mtr_model_animate", "mtr_batch_animate", "mtr_batch_animate_device", "mtr_anim_sample"]
 F = np.float32
-
-
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
-        args = [a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
-        out[m.group(1)] = len(args)
-    return out
 
 
 def test_anim_prototypes_declared_exported_and_bound():

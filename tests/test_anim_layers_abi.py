@@ -3,25 +3,17 @@ bound by api.py with the argument counts of their prototypes; mtr_anim_layer has
 arguments are rejected without a GPU; the ABI version stays 2."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests.abi_header import prototypes as _prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
 NAMES = {"mtr_anim_masks_create": 5, "mtr_anim_masks_destroy": 1, "mtr_model_animate_layers": 5, "mtr_batch_animate_layers": 5,
          "mtr_batch_animate_layers_device": 6, "mtr_anim_sample_layers": 7}
-
-
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-    return out
 
 
 def test_prototypes_declared_exported_and_bound():

@@ -3,24 +3,16 @@ with the argument count of its prototype; mtr_anim_track has its stated size and
 without a GPU; the ABI version stays 2."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests.abi_header import prototypes as _prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
 NAME = "mtr_anim_create_tracks"
-
-
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-    return out
 
 
 def test_prototype_declared_exported_and_bound():

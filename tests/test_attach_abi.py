@@ -3,25 +3,17 @@ api.py with the argument counts of their prototypes; mtr_attach has its stated s
 the error table of include/mtr.h holds where no GPU is needed; the ABI version stays 2."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests.abi_header import prototypes as _prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
 NAMES = {"mtr_batch_attach": 3, "mtr_batch_attach_device": 4, "mtr_batch_sockets": 5, "mtr_batch_sockets_device": 5,
          "mtr_batch_read_model_mats": 3}
-
-
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-    return out
 
 
 def test_prototypes_declared_exported_and_bound():

@@ -5,24 +5,16 @@ held on the host build by tests/test_ctrl_host_sanitizer.py and on the GPU by te
 the tables of the model's locomotion graph; the ABI version stays 2."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests.abi_header import prototypes as _prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
 NAMES = {"mtr_anim_ctrl_create": 11, "mtr_anim_ctrl_destroy": 1, "mtr_anim_ctrl_step_device": 9, "mtr_anim_ctrl_step_host": 8}
-
-
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-    return out
 
 
 def test_prototypes_declared_exported_and_bound():

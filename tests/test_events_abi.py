@@ -5,24 +5,16 @@ device hold (the rest is held on the host build by tests/test_events_host_saniti
 tests/test_gpu_events.py); anim_events.build sorts stably and decode splits `where`; the ABI version stays 2."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests.abi_header import prototypes as _prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
 NAMES = {"mtr_anim_events_create": 8, "mtr_anim_events_destroy": 1, "mtr_anim_events_collect_device": 10, "mtr_anim_events_collect_host": 9}
-
-
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-    return out
 
 
 def test_prototypes_declared_exported_and_bound():

@@ -5,7 +5,6 @@ table that need no device hold (the rest is held on the host build by tests/test
 tests/test_gpu_match.py); anim_match.py builds rows, normalised features and trajectory features; the ABI version stays 2."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
@@ -13,19 +12,11 @@ import numpy as np
 import pytest
 
 from tests import cpp_build
+from tests.abi_header import prototypes as _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
 NAMES = {"mtr_anim_match_create": 17, "mtr_anim_match_destroy": 1, "mtr_anim_match_search_device": 9, "mtr_anim_match_search_host": 8,
          "mtr_anim_match_scores_host": 5}
-
-
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-    return out
 
 
 def test_prototypes_declared_exported_and_bound():

@@ -4,25 +4,17 @@ in api.PLAY_STATE / api.PLAY_CMD; the constants agree; the error table of includ
 held on the host build by tests/test_player_host_sanitizer.py and on the GPU by tests/test_gpu_player.py); the ABI version stays 2."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests.abi_header import prototypes as _prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
 NAMES = {"mtr_anim_player_create": 7, "mtr_anim_player_destroy": 1, "mtr_anim_player_advance_device": 11, "mtr_anim_player_advance_device_cmds": 11,
          "mtr_anim_player_advance_host": 10}
-
-
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-    return out
 
 
 def test_prototypes_declared_exported_and_bound():

@@ -2,21 +2,12 @@
 by api.py with the argument count of their prototype."""
 import ctypes
 import os
-import re
+
+from tests.abi_header import prototypes as _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
 NEW = ["mtr_model_set_skeleton", "mtr_model_set_pose", "mtr_batch_update", "mtr_batch_set_poses", "mtr_batch_set_poses_device",
        "mtr_batch_read_palettes"]
-
-
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
-        args = [a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
-        out[m.group(1)] = len(args)
-    return out
 
 
 def test_pose_prototypes_declared_exported_and_bound():

@@ -4,7 +4,6 @@ mtr_spring_state have their stated sizes and field offsets; NULL arguments are r
 2; anim_spring.chain builds the records of a strand."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
@@ -12,18 +11,10 @@ import numpy as np
 import pytest
 
 from tests import cpp_build
+from tests.abi_header import prototypes as _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "mtr.h")
 NAMES = {"mtr_anim_spring_create": 6, "mtr_anim_spring_destroy": 1, "mtr_batch_animate_spring_device": 12, "mtr_anim_sample_spring": 13}
-
-
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mtr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-    return out
 
 
 def test_prototypes_declared_exported_and_bound():
