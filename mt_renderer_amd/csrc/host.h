@@ -57,6 +57,7 @@ struct Slot {
     int4* rec_l = nullptr;
     RecB* rec_b = nullptr;
     ChunkInfo* chunk_info = nullptr;
+    uint32_t* defer_list = nullptr;  // chunks k_geom left to k_geom_clip (GeomParams::defer_list); shares chunk_cap
     uint32_t rec_cap = 0, chunk_cap = 0;
     unsigned long long* bin_count = nullptr;
     unsigned long long* bin_fill = nullptr;

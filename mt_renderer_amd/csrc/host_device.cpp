@@ -176,7 +176,7 @@ void mtr_device_destroy(mtr_device* d) {
         if (f.done) (void)hipEventDestroy(f.done);
     }
     for (Slot& sl : d->slots) {
-        void* ptrs[] = {sl.rec_hdr, sl.rec_a, sl.rec_l, sl.rec_b, sl.chunk_info, sl.bin_count, sl.bin_fill,
+        void* ptrs[] = {sl.rec_hdr, sl.rec_a, sl.rec_l, sl.rec_b, sl.chunk_info, sl.defer_list, sl.bin_count, sl.bin_fill,
                         sl.bin_start, sl.seg_start, sl.entries, sl.segs, sl.mats, sl.bin_flag, sl.inst_list, sl.inst_count, sl.work_mask, sl.comp};
         for (void* p : ptrs)
             if (p) (void)hipFree(p);

@@ -15,6 +15,7 @@ struct FrameRun {
     std::vector<uint32_t> inst_off, work_off, comp_off;  // per draw: its share of the slot's culling buffers (prepare_stream)
     uint32_t strad_base = 0;   // the second half of inst_list: the slots of the instances that straddle the rank's border
     uint32_t chunk_base = 0;   // global chunk id of the next draw's first chunk
+    uint32_t clip_seq = 0;     // k_geom_clip launches queued so far (one behind every draw that launches geometry)
     uint32_t nhint = 0;        // batch draws whose culling counters this frame's tile kernel reports to the host (launch sizing)
     uint16_t hint_word[4] = {}, hint_slot[4] = {};
     bool use_vis = false, prof = false;
@@ -81,7 +82,7 @@ int32_t reserve_slot_buffers(mtr_device* d, mtr_frame* f, Slot& sl, const FrameR
     const uint64_t rec_need = r.total_chunks * MTR_CHUNK_SLOTS;
     if (rec_need > 0xFFFFFFF0ull) return fail(d, MTR_E_OVERFLOW, "too many triangles in one frame");
     if ((rc = grow_slot(d, sl, nullptr, nullptr, rec_need, &sl.rec_cap, &sl.rec_hdr, &sl.rec_a, &sl.rec_l, &sl.rec_b))) return rc;
-    if ((rc = grow_slot(d, sl, nullptr, nullptr, r.total_chunks, &sl.chunk_cap, &sl.chunk_info))) return rc;
+    if ((rc = grow_slot(d, sl, nullptr, nullptr, r.total_chunks, &sl.chunk_cap, &sl.chunk_info, &sl.defer_list))) return rc;
     bool grew;  // mtr_frame_read_bin_counts copies from the bin arrays on the public stream
     if ((rc = grow_slot(d, sl, d->stream, &grew, nbins + 1, &sl.bin_cap, &sl.bin_count, &sl.bin_fill, &sl.bin_start, &sl.seg_start, &sl.bin_flag))) return rc;
     if (grew) sl.bin_fill_dirty = true;
@@ -345,6 +346,11 @@ int32_t record_draw(mtr_device* d, mtr_frame* f, Slot& sl, FrameRun& r, size_t d
     // a draw of fewer than ~64 k geometry waves (the headline model: 16 k) overlaps with the neighbouring frames' tile
     // kernels for most of its life: the build that leaves them a wave slot per SIMD (k_geom.hip: GEOM_OCC_SMALL)
     gp.small_draw = ((uint64_t)gp.nchunks * dr.ninst < 65536u) ? 1u : 0u;
+    // the chunks with a triangle to clip go through the frame's deferred list to k_geom_clip, which mtr_launch_geom queues
+    // behind the draw's geometry launches -- for every draw: the host keeps no bound of a skinned vertex's depth that
+    // would prove a draw free of them
+    gp.defer_list = sl.defer_list; gp.defer_cap = sl.chunk_cap; gp.clip_seq = r.clip_seq;
+    if (mtr_geom_has_work(gp)) r.clip_seq++;
     mtr_launch_geom(gp, sg);
     HIPCHK(d, hipGetLastError());
     r.chunk_base += gp.nchunks * dr.ninst;

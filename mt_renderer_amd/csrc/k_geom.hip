@@ -193,7 +193,12 @@ __device__ __forceinline__ uint32_t fetch_index(const GeomParams& P, const DChun
 
 // MODE 0: count pass of the exact two-pass queues; 1: single-pass binning, ordered segments; 2: single-pass binning
 // for frames the visibility-key tile kernel renders (no order kept, no segments)
-template <int MODE>
+// CLIP: the clipper is compiled in (k_geom_clip, k_geom_rest).  Without it (k_geom) a wave that meets a triangle to clip
+// appends its chunk to the frame's deferred list and leaves, before any side effect: k_geom_clip runs the chunk again,
+// whole.  The clipper -- three vertices shaded again with the matrix in 16 registers, Sutherland-Hodgman over poly[8] and
+// tmp[8], the fan in a second pass -- ran for no triangle of the headline frame, and every launch of k_geom paid for it:
+// half of the kernel's code, a private segment of 496 bytes per lane.
+template <int MODE, bool CLIP>
 __device__ __forceinline__ void geom_chunk(const GeomParams& P, uint32_t inst, uint32_t c, const DChunk& ch, const DPrim& pr,
                                            bool skinned, const float* s_M, const float* s_pal, RecHdr* s_hdr, uint32_t* s_slot,
                                            float4* s_pv, uint32_t lane, uint32_t idx) {
@@ -326,10 +331,21 @@ __device__ __forceinline__ void geom_chunk(const GeomParams& P, uint32_t inst, u
 #if MTR_ABL == 5   // no triangle set-up
     tri = tri && ta.X == 0x7ffffff0;
 #endif
+    // a vertex behind the near plane, or one the rasteriser cannot take (w <= 0, beyond the guard band)
+    const bool to_clip = tri && (((f_or >> 2) & OC_ZN) || !(f_and & 2u));
+    if (!CLIP) {
+        if (__ballot(to_clip)) {  // wave-uniform, and nothing has been written yet
+            if (lane == 0) {
+                const uint32_t k = atomicAdd(&P.fb.counters[CTR_DEFER], 1u);
+                if (k < P.defer_cap) P.defer_list[k] = inst * P.nchunks + c;  // always: a chunk is deferred at most once
+            }
+            return;
+        }
+    }
     if (tri) {
-        if (!((f_or >> 2) & OC_ZN) && (f_and & 2u)) {
+        if (!to_clip) {
             if (setup_tri(ta, tb, tc, W, H, mat, pr.cull, r0, &small)) n_out = 1;
-        } else {
+        } else if (CLIP) {
             // near-plane clip (z >= 0) and / or guard-band clip: rare, re-shades the three vertices in clip space
             const uint32_t ia = vid2, ib = odd ? vid : vid1, ic = odd ? vid1 : vid;
             float M[16];
@@ -456,7 +472,7 @@ __device__ __forceinline__ void geom_chunk(const GeomParams& P, uint32_t inst, u
     };
     if (n_out >= 1) put_rec(rank, r0);
     if (n_out == 2) put_rec(rank + 1, r1);
-    if (n_poly) {  // the fan of a guard-clipped polygon: (p0, p_k+1, p_k+2)
+    if (CLIP && n_poly) {  // the fan of a guard-clipped polygon: (p0, p_k+1, p_k+2)
         uint32_t nvalid = 0;
         for (uint32_t k = 0; k + 2u < n_poly; k++) {
             Rec t;
@@ -508,7 +524,10 @@ __device__ __forceinline__ void geom_chunk(const GeomParams& P, uint32_t inst, u
 #define GEOM_OCC_SMALL 7  // a draw that does not fill the GPU (the headline model: 16 k waves) overlaps with the neighbouring
                     // frames' tile kernels for most of its life and does better leaving them a wave slot per SIMD, with the
                     // 72 registers that allows: 0.0485 ms per frame against 0.0509 at 8 and 0.0498 at 6 (three runs each,
-                    // tools/sweep_geom_occ.sh); capping the residency of the 64-register build by LDS gets 0.0498
+                    // tools/sweep_geom_occ.sh); capping the residency of the 64-register build by LDS gets 0.0498.
+                    // Without the clipper neither build spills (0 and 12 bytes of private segment) and they tie: frames in
+                    // flight 0.03995 ms at 7 against 0.04003 at 8, the default command 0.03985 against 0.03917, each inside
+                    // the other's range, no config apart (profiles/clip_defer_ab.txt, call 2).  7 stays
 #endif
 // 256 threads, wave = one chunk (62 strip positions) of one instance.  Unsharded frames (CULL false): grid = (blocks
 // of 4 chunks, instances).  Sharded frames (CULL true): k_cull_chunks has bounded every chunk against the rank's bins
@@ -541,7 +560,7 @@ __global__ __launch_bounds__(256, OCC) void k_geom(GeomParams P) {
         if (has) { ch = P.chunks[c]; pr = P.prims[ch.prim]; idx = fetch_index(P, ch, pr, lane); }
         stage_palette(P, blockIdx.y, s_pal, s_M);  // every thread of the workgroup copies its share
         if (!has) return;
-        geom_chunk<MODE>(P, blockIdx.y, c, ch, pr, pr.skinnable && P.palettes && P.npal, s_M, s_pal, s_hdr[wave], s_slot[wave], s_pv[wave], lane, idx);
+        geom_chunk<MODE, false>(P, blockIdx.y, c, ch, pr, pr.skinnable && P.palettes && P.npal, s_M, s_pal, s_hdr[wave], s_slot[wave], s_pv[wave], lane, idx);
         return;
     }
     // sharded: workgroup g = (group x, quarter q) fastest, then instance slot ii: it takes the q-th four survivors of the 16
@@ -575,7 +594,7 @@ __global__ __launch_bounds__(256, OCC) void k_geom(GeomParams P) {
     if (has) { ch = P.chunks[c]; pr = P.prims[ch.prim]; idx = fetch_index(P, ch, pr, lane); }  // before the barrier, as above
     stage_palette(P, inst, s_pal, s_M);
     if (!has) return;
-    geom_chunk<MODE>(P, inst, c, ch, pr, pr.skinnable && P.palettes && P.npal, s_M, s_pal, s_hdr[wave], s_slot[wave], s_pv[wave], lane, idx);
+    geom_chunk<MODE, false>(P, inst, c, ch, pr, pr.skinnable && P.palettes && P.npal, s_M, s_pal, s_hdr[wave], s_slot[wave], s_pv[wave], lane, idx);
 }
 
 // The instance slots the full-rate launch of k_geom<MODE, true> does not cover (mtr_launch_geom): MTR_GEOM_REST_SPLIT
@@ -608,8 +627,61 @@ __global__ __launch_bounds__(256) void k_geom_rest(GeomParams P) {
             const uint32_t c = x * 16u + (uint32_t)__ffs((int)mm) - 1u;
             const DChunk ch = P.chunks[c];
             const DPrim pr = P.prims[ch.prim];
-            geom_chunk<MODE>(P, inst, c, ch, pr, pr.skinnable && P.palettes && P.npal, s_M, s_pal, s_hdr[wave], s_slot[wave], s_pv[wave], lane,
-                             fetch_index(P, ch, pr, lane));
+            geom_chunk<MODE, true>(P, inst, c, ch, pr, pr.skinnable && P.palettes && P.npal, s_M, s_pal, s_hdr[wave], s_slot[wave], s_pv[wave], lane,
+                                   fetch_index(P, ch, pr, lane));
+        }
+    }
+}
+// The chunks k_geom deferred (geom_chunk: a triangle to clip), run whole with the clipper compiled in.  Launched behind the
+// geometry launches of every draw, so nearly always the list is empty: every workgroup reads the frame's count and the mark
+// its draw starts from (two scalar loads of neighbouring words) and leaves.  Nobody waits for anybody.  The list is the
+// frame's: the count only grows, draw i's launch takes the entries [mark, count) -- its own draw's, the stream orders the
+// draws -- and workgroup 0 leaves the count as the mark of the next launch, in the word that launch reads (the other one
+// of the two: the launch after that one overwrites what this one read).
+// A workgroup takes four consecutive entries, one per wave.  They arrive in the order the waves of k_geom reached the
+// atomic, so they may belong to different instances of a batch: the palette and the matrix are staged once per DISTINCT
+// instance among the four, and the waves of that instance run while the others wait at the next barrier.  A single draw,
+// or neighbouring chunks of one instance, stage once.
+// Like k_geom_rest its own kernel with no register cap: its allocation, private segment included, is its own.
+#ifndef MTR_GEOM_CLIP_GRID
+#define MTR_GEOM_CLIP_GRID 256u  // one workgroup per CU; 1024 (what its registers admit) was measured too: DESIGN.md section 5
+#endif
+template <int MODE>
+__global__ __launch_bounds__(256) void k_geom_clip(GeomParams P) {
+    extern __shared__ __align__(16) float s_pal[];
+    __shared__ RecHdr s_hdr[4][MTR_CHUNK_SLOTS + 4];
+    __shared__ uint32_t s_slot[MODE == 2 ? 4 : 1][128];
+    __shared__ float4 s_pv[4][128];
+    __shared__ float s_M[16];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t n = min(P.fb.counters[CTR_DEFER], P.defer_cap);
+    const uint32_t first = P.fb.counters[CTR_DEFER_MARK + (P.clip_seq & 1u)];
+    if (blockIdx.x == 0 && threadIdx.x == 0) P.fb.counters[CTR_DEFER_MARK + ((P.clip_seq & 1u) ^ 1u)] = n;
+    for (uint32_t base = first + blockIdx.x * 4u; base < n; base += gridDim.x * 4u) {
+        const uint32_t cnt = min(4u, n - base);
+        uint32_t e[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) e[k] = k < cnt ? (uint32_t)__builtin_amdgcn_readfirstlane((int)P.defer_list[base + k]) : 0xFFFFFFFFu;
+        const uint32_t e_mine = wave == 0 ? e[0] : wave == 1 ? e[1] : wave == 2 ? e[2] : e[3];
+        uint32_t done = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            if (k >= cnt || ((done >> k) & 1u)) continue;  // workgroup-uniform
+            const uint32_t inst = e[k] / P.nchunks;
+            if (inst >= P.ninst) continue;  // never: the entries of [mark, count) are this draw's
+            __syncthreads();  // the waves of the instance staged before have read its palette
+            stage_palette(P, inst, s_pal, s_M);
+#pragma unroll
+            for (uint32_t j = k; j < 4; j++)
+                if (j < cnt && e[j] / P.nchunks == inst) done |= 1u << j;
+            if (wave >= k && wave < cnt && e_mine / P.nchunks == inst) {
+                const uint32_t c = e_mine - inst * P.nchunks;
+                const DChunk ch = P.chunks[c];
+                const DPrim pr = P.prims[ch.prim];
+                geom_chunk<MODE, true>(P, inst, c, ch, pr, pr.skinnable && P.palettes && P.npal, s_M, s_pal, s_hdr[wave], s_slot[wave], s_pv[wave], lane,
+                                       fetch_index(P, ch, pr, lane));
+            }
         }
     }
 }
@@ -647,8 +719,15 @@ static void launch_geom(const GeomParams& p, dim3 grid, size_t lds, hipStream_t 
         else hipLaunchKernelGGL((mtr::k_geom<MODE, CULL, GEOM_OCC>), grid, dim3(256), lds, s, p);
     });
 }
+// behind the geometry launches of a draw: the chunks they deferred.  A fixed small grid (one workgroup per CU, fewer for
+// a draw of fewer chunks) that strides over the list; an empty list costs the launch alone
+static void launch_geom_clip(const GeomParams& p, size_t lds, hipStream_t s) {
+    const uint64_t groups = ((uint64_t)p.nchunks * p.ninst + 3u) / 4u;
+    dim3 grid((uint32_t)std::min<uint64_t>(groups, MTR_GEOM_CLIP_GRID));
+    with_geom_mode(p.fb, [&](auto mode) { hipLaunchKernelGGL((mtr::k_geom_clip<decltype(mode)::value>), grid, dim3(256), lds, s, p); });
+}
 void mtr_launch_geom(const GeomParams& p, hipStream_t s) {
-    if (p.nchunks == 0 || p.ninst == 0) return;
+    if (!mtr_geom_has_work(p)) return;
     size_t lds = (size_t)p.npal * 64;
     if (p.work_mask) {
         // sharded: four workgroups per group of 16 chunks and instance slot (what k_cull_chunks kept of them is on the device)
@@ -682,12 +761,14 @@ void mtr_launch_geom(const GeomParams& p, hipStream_t s) {
             dim3 rest((p.ninst - slots) * std::min<uint32_t>(p.work_nx, r.rest_split));
             with_geom_mode(p.fb, [&](auto mode) { hipLaunchKernelGGL((mtr::k_geom_rest<decltype(mode)::value>), rest, dim3(256), lds, s, r); });
         }
+        launch_geom_clip(p, lds, s);
         return;
     }
     uint32_t nblk = (p.nchunks + 3) / 4;
     nblk = (nblk + 7) / 8 * 8;  // whole multiple of 8 for the XCD remap
     dim3 grid(nblk, p.ninst);
     launch_geom<false>(p, grid, lds, s);
+    launch_geom_clip(p, lds, s);
 }
 
 void mtr_launch_vertex_stage(const GeomParams& p, uint32_t prim, float* out_clip, float* out_uv, hipStream_t s) {

@@ -269,7 +269,9 @@ __device__ __forceinline__ uint32_t live_instances(const uint32_t* count, uint32
 // a line serialise in its L2 channel (64 shards packed into two lines cost k_geom 20 us on the headline scene).
 // CTR_OVERFLOW bits: 1 a chunk needed more than MTR_CHUNK_SLOTS records (guard-band clipping fanning many triangles of
 // one chunk), 2 two-pass queue capacity, 4 direct-mode per-bin queue full
-enum { CTR_ENTRIES = 1, CTR_SEGS = 2, CTR_OVERFLOW = 3, CTR_SHARD_BASE = 32, CTR_SHARD_STRIDE = 32, CTR_NSHARDS = 128,
+// [4] chunks deferred to k_geom_clip so far in the frame (k_geom.hip), [5] and [6] how many of them the clip launches of
+// the even / odd draws before this one have taken: draw i's launch reads word 5 + (i & 1) and writes the other one
+enum { CTR_ENTRIES = 1, CTR_SEGS = 2, CTR_OVERFLOW = 3, CTR_DEFER = 4, CTR_DEFER_MARK = 5, CTR_SHARD_BASE = 32, CTR_SHARD_STRIDE = 32, CTR_NSHARDS = 128,
        CTR_REC = 0, CTR_ENT = 1, CTR_SEG = 2, CTR_CULL = 3 /* geometry chunks culled against the ownership map */,
        CTR_NUM = CTR_SHARD_BASE + CTR_NSHARDS * CTR_SHARD_STRIDE };
 #define MTR_CTR(kind, k) (CTR_SHARD_BASE + ((k) & (CTR_NSHARDS - 1)) * CTR_SHARD_STRIDE + (kind))
@@ -352,6 +354,12 @@ struct GeomParams {
     uint32_t chunk_base;      // global chunk id of (instance 0, chunk 0)
     uint32_t mat_base, mat_inst_stride;
     const DMat* mats;         // frame material table (read: is this primitive textured?)
+    // chunks with a triangle to clip (near plane, guard band): k_geom emits nothing for them and appends instance * nchunks +
+    // chunk here, at the index a returning atomic on counters[CTR_DEFER] hands out; k_geom_clip, launched behind the draw's
+    // geometry launches, runs them.  One list per frame, as long as chunk_info (every chunk is deferred at most once).
+    uint32_t* defer_list;
+    uint32_t defer_cap;       // entries the list holds
+    uint32_t clip_seq;        // clip launches of the frame ahead of this draw's: which mark word it reads (CTR_DEFER_MARK)
     FrameBuffers fb;
 };
 
@@ -424,6 +432,10 @@ static inline uint32_t mtr_vis_waves_for(uint32_t forced, uint32_t own_count) {
     if (forced) return forced;
     return own_count <= 1536 ? 8u : own_count <= 4096 ? 4u : 2u;
 }
+
+// whether mtr_launch_geom launches anything for the draw -- and with it a k_geom_clip, which takes and leaves a mark word
+// (CTR_DEFER_MARK): the host numbers the clip launches of a frame (GeomParams::clip_seq) by this same test
+static inline bool mtr_geom_has_work(const GeomParams& p) { return p.nchunks != 0 && p.ninst != 0; }
 
 // launchers (defined in the .hip files, called from host_*.cpp)
 void mtr_launch_geom(const GeomParams& p, hipStream_t s);
